@@ -1,21 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark: env steps/s of the batched lock-step engine (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 A "step" is one lock-step iteration of the hot path over all tables of this rank: legal-move enumeration into the
 per-table list + random-policy action application with auto-reset (game.py:169-181 with envi.py:79-116).
   Every N: 65,536 tables per GPU -- the largest single-GPU table count of BASELINE.json (configs[2], configs[3]; configs[4]
          = 524,288 tables at N = 8), random policy, legal-move list only (the workload of configs[1]).  Weak scaling: every
          GPU owns a range of the global table ids and the timed region is the same at every N (tables are independent: no
-         data-path collective); the N = 1 line is the N > 1 line's per-GPU workload.  The path's one exchange -- packed
-         trajectories gathered to rank 0 over RCCL -- is measured right after the headline region (config.exchange,
-         env_steps_per_s_with_gather, the ranks' own rates and the gather on its own).
-  N = 1 also carries measured legs of the other single-GPU configurations (`configs`), each with the roofline that
-         bounds its dominant kernel: configs[1] as written (4096 tables), the policy-driven stepping launch, configs[2]
-         with the Q-network in the loop, configs[3] against the rule agent, the CSR layout beside the slab layout.
-The K-iteration launch is repeated until at least 50 ms have been timed, whatever K is (a single short launch
-would measure launch latency); `value` and `ms_per_step` are means over all timed iterations.  Rank 0 prints ONE
-JSON line; at N = 1 it also carries short measured legs of the other single-GPU configs (`configs`).
+         data-path collective); the N = 1 line is the N > 1 line's per-GPU workload.
+After W untimed steps exactly K steps are timed (one k_rollout launch: the engine splits only runs beyond 2^20
+iterations); `value` and `ms_per_step` are their mean.  Rank 0 prints ONE JSON line.  --dump-outputs DIR writes what the
+timed steps left for their caller (dump_outputs); the inputs depend only on the arguments (seed 0, K, W, N, --tables).
+--full also measures everything beside the headline, after it:
+  - the roofline of the headline kernel (HIP events around launches of >= 1000 iterations, >= 50 ms summed) and the
+    same loop with packed CSR lists;
+  - N > 1: the path's one exchange -- packed trajectories gathered to rank 0 over RCCL (config.exchange,
+    env_steps_per_s_with_gather, the gather on its own);
+  - N = 1: measured legs of the other single-GPU configurations (`configs`), each with the roofline that bounds its
+    dominant kernel: configs[1] as written (4096 tables), the policy-driven stepping launch, configs[2] with the
+    Q-network in the loop, configs[3] against the rule agent, the stress set; and the CPU baseline (`cpu_baseline`).
 """
 import argparse
 import importlib
@@ -527,6 +530,97 @@ def issue_block(key, units_per_launch, seconds_per_launch):
                     "plain 32-bit, ~4.5 for 64-bit shifts / carry chains / v_mul_lo / v_mbcnt / compares, ~6.3 v_readlane"}
 
 
+DUMP_TABLES = 65536      # --dump-outputs: tables whose state and list sizes are written (a seeded sample beyond that)
+DUMP_LIST_TABLES = 256   # ... and whose legal-move rows are written (<= 512 rows each): <= 55 MB in all
+
+
+def dump_outputs(env, directory, stats):
+    """What the timed rollout leaves its caller, as DIR/<name>.npy (float32, counters float64):
+      state [S,11,16]        the packed state of each dumped table after the last step
+      legal_counts [S]       the list sizes of the last step's pre-step states (rollout_random's slab lists)
+      legal_rows [R,16]      the rows of those lists for a sample of DUMP_LIST_TABLES of the S tables, in table order
+      legal_rows_tables [L]  the indices of that sample
+      stats [6]              plies, episodes, legal_rows, lord_wins, up_wins, down_wins accumulated so far
+    S = every table up to DUMP_TABLES, else a fixed seeded sample of them; the samples depend on T alone."""
+    import numpy as np
+    import torch
+    T = env.T
+    rng = np.random.default_rng(0)
+    pick = np.arange(T) if T <= DUMP_TABLES else np.sort(rng.choice(T, DUMP_TABLES, replace=False))
+    lpick = np.sort(rng.choice(pick, min(len(pick), DUMP_LIST_TABLES), replace=False))
+    sel = torch.from_numpy(pick).to(env.device)
+    lsel = torch.from_numpy(lpick).to(env.device)
+    state = env.state.view(T, -1)[sel].float().view(len(pick), -1, 16).cpu().numpy()
+    counts = env.counts[sel].float().cpu().numpy()
+    lcounts = env.counts[lsel].cpu().numpy()
+    lrows = env.slab_rows()[lsel].cpu().numpy()
+    rows = np.concatenate([lrows[i, :c] for i, c in enumerate(lcounts)]).astype(np.float32)
+    keys = ("plies", "episodes", "legal_rows", "lord_wins", "up_wins", "down_wins")
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in (("state", state), ("legal_counts", counts), ("legal_rows", rows),
+                      ("legal_rows_tables", lpick.astype(np.float64)),
+                      ("stats", np.array([stats[k] for k in keys], np.float64))):
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
+def rollout_extras(env, torch, dev, T, K):
+    """--full: the headline kernel's roofline and the same loop with packed CSR lists, measured after the headline."""
+    # ---- duration of the dominant kernel: launches of KL iterations (at least 1000, a multiple of K: a short launch would
+    # measure its ~25 us ramp-up), two HIP events around every launch on the launching stream, repeated until >= 50 ms of
+    # kernel time are summed
+    KL = K if K >= 1000 else K * math.ceil(1000 / K)
+    sa = env.stats()
+    ms_total, n_launch = 0.0, 0
+    while ms_total < MIN_TIMED_S * 1e3 and n_launch < (1 << 16):
+        ms_total += env.rollout_random_timed(KL)
+        n_launch += 1
+    sb = env.stats()
+    steps_timed = sb["plies"] - sa["plies"]
+    mean_a2 = (sb["legal_rows"] - sa["legal_rows"]) / max(1, steps_timed)
+    # algorithmic bytes per env step, SURVEY.md 8(d): 128 state read + 128 state write + 4 list size/offset + 16*A
+    # legal rows (DESIGN.md 3 states what the kernel really moves)
+    b_step = 260 + 16 * mean_a2
+    dur_launch = ms_total * 1e-3 / n_launch           # mean duration of one KL-iteration launch
+    steps_per_launch = steps_timed / n_launch
+    b_launch = b_step * steps_per_launch
+    pmc_key = "k_rollout_65536" if T >= 32768 and "k_rollout_65536" in (_profile("pmc_traffic.json") or {}) else "k_rollout"
+    traffic, traffic_source = None, None
+    prof = (_profile("pmc_traffic.json") or {}).get(pmc_key, {})
+    if prof.get("hbm_bytes_per_env_step") is not None:
+        traffic = prof["hbm_bytes_per_env_step"] * steps_per_launch
+        traffic_source = ("REPLAYED, not measured in this run: profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
+                          "separate passes, FETCH doubled per the gfx950 note; " + str(prof.get("workload", "")) + ") x this run's env steps per launch")
+    issue = issue_block(pmc_key if pmc_key in (_profile("pmc_kernels.json") or {}) else "k_rollout", steps_per_launch, dur_launch)
+    ach = b_launch / dur_launch / 1e9
+    roofline = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source, "kernel": "k_rollout",
+                "launch_us": dur_launch * 1e6, "launches_timed": n_launch, "env_steps_per_launch": steps_per_launch,
+                "us_per_iteration": dur_launch * 1e6 / KL, "iterations_per_launch": KL,
+                "algorithmic_bytes_per_env_step": b_step,
+                "algorithmic_bytes_per_launch": b_launch,
+                "note": "achieved = ALGORITHMIC bytes (SURVEY 8d) / launch time: a store rate into the write-back "
+                        "L2, not HBM utilisation -- every iteration overwrites the same state rows / list slab, so "
+                        "the HBM counters (traffic) see ~2 B per env step.  The path is instruction-issue bound: "
+                        "see issue",
+                "issue": issue}
+
+    # ---- the same loop with packed CSR lists (one launch per iteration): a number, not the headline
+    sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
+    env.rollout_random_csr(64)
+    sync()
+    dtc, repc = timed_loop(lambda: env.rollout_random_csr(256), sync)
+    csr = {"csr_env_steps_per_s": T * 256 * repc / dtc, "csr_us_per_iteration": dtc / (256 * repc) * 1e6,
+           "csr_staging_GiB": env._staging.numel() / 2**30}
+    env.rollout_random_csr(10, batch=0)
+    dtc, repc = timed_loop(lambda: env.rollout_random_csr(20, batch=0), sync)
+    csr["csr_launch_per_iteration_env_steps_per_s"] = T * 20 * repc / dtc
+    csr["csr_note"] = ("the same loop with packed CSR lists (offsets / rows as ddz_legal writes them: SURVEY 8(d) "
+                       "config 2 'outputs = CSR legal list only') beside the slab layout of `value`: batches of "
+                       "iterations staged by one rollout launch, compacted by two more "
+                       "(ddz_rollout_random_csr_staged); csr_launch_per_iteration: round 3's form")
+    return roofline, csr
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes -- one per GPU,
     `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` -- before this process has imported
@@ -557,21 +651,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--tables", type=int, default=0,
                     help="tables per GPU; default 65536 at every N (the largest single-GPU configuration; configs[4] at N = 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (rank 0's tables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure its roofline, the CSR layout, the trajectory exchange (N > 1), "
+                         "the other configs' legs and the CPU baseline (N = 1)")
     ap.add_argument("--allow-leg-failure", action="store_true",
-                    help="N = 1: report a failing leg in the JSON (`errors`) and exit 0 (default: exit 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full, N = 1: report a failing leg in the JSON (`errors`) and exit 0 (default: exit 4)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the short legs of the other configs")
-    ap.add_argument("--exchange-steps", type=int, default=200, help="N > 1: iterations of the trajectory-gather leg")
-    ap.add_argument("--no-exchange", action="store_true", help="N > 1: skip the trajectory-gather leg")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N = 1: skip the short legs of the other configs")
+    ap.add_argument("--exchange-steps", type=int, default=200, help="--full, N > 1: iterations of the trajectory-gather leg")
+    ap.add_argument("--no-exchange", action="store_true", help="--full, N > 1: skip the trajectory-gather leg")
     ap.add_argument("--allow-exchange-failure", action="store_true",
-                    help="N > 1: report a failing trajectory-gather leg in the JSON and exit 0 (default: exit 3)")
+                    help="--full, N > 1: report a failing trajectory-gather leg in the JSON and exit 0 (default: exit 3)")
     ap.add_argument("--strict-exchange", action="store_true", help="(default behaviour now; kept for old command lines)")
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 on ONE GPU (all ranks on cuda:0, gloo, host-staged gather): control-flow rehearsal only")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus))   # `python bench.py --gpus N` as typed: this process becomes the launcher
 
@@ -609,46 +710,36 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # ---- headline: the K steps, repeated until >= 50 ms are timed (same repeat count on every rank).  The engine runs
-    # any number of lock-step iterations per launch; a launch carries at least 1000 of them (a multiple of K), so that a
-    # small --steps does not turn the figure into a launch-latency measurement (a launch costs ~25 us of ramp-up)
-    KL = K if K >= 1000 else K * math.ceil(1000 / K)   # iterations per launch
+    # ---- headline: exactly the K steps, all in one k_rollout launch (the caller picks K: a short run measures the
+    # launch's ~25 us of ramp-up as well)
     env.rollout_random(W)
-    barrier()
-    t0 = time.perf_counter()
-    env.rollout_random(KL)
-    torch.cuda.synchronize(dev)
-    est = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(est, op=dist.ReduceOp.MIN)
-    RL = int(min(1 << 16, max(1, math.ceil(MIN_TIMED_S / max(float(est.item()), 1e-6)))))   # launches timed
-    R = RL * (KL // K)                                                                      # repeats of the K steps
     s0 = env.stats()  # cumulative counters so far (sync)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(RL):
-        env.rollout_random(KL)
+    env.rollout_random(K)
     barrier()
     dt = time.perf_counter() - t0
-    per_rank = [T * K * R / dt]
+    per_rank = [T * K / dt]
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         mine = tmax.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)                       # every rank's own clock over the same K x R iterations
-        per_rank = [T * K * R / float(x.item()) for x in every]
+        dist.all_gather(every, mine)                       # every rank's own clock over the same K iterations
+        per_rank = [T * K / float(x.item()) for x in every]
         dt = float(tmax.item())
     s1 = env.stats()
     st = {k: s1[k] - s0[k] for k in s1}
     status = env.status()
-    assert st["plies"] == T * K * R and status == 0, (st, status)
+    assert st["plies"] == T * K and status == 0, (st, status)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(env, a.dump_outputs, s1)
 
     # ---- the path's one exchange, measured beside the headline, never inside it: every ply also writes
     # its 32-byte trajectory record and the batch goes to the learner (rank 0) over RCCL in two half-batches; the
     # gather of the first half overlaps the rollout of the second one.
     exchange = None
-    if world > 1 and not a.no_exchange:
+    if a.full and world > 1 and not a.no_exchange:
         try:
             KX = max(2, a.exchange_steps)
             half = KX // 2
@@ -695,7 +786,7 @@ def main():
                 # digest of every gathered record in (iteration, global table) order: the rehearsal test recomputes it
                 # from a single-process rollout of the union of the shards
                 digest = int((x * 31 + (x >> 13) + torch.arange(x.numel(), device=dev) * x).sum().item())
-            exchange = {"steps": KX, "iterations_before": W + KL * (RL + 1), "env_steps_per_s_with_gather": total_tables * KX / dtx,
+            exchange = {"steps": KX, "iterations_before": W + K, "env_steps_per_s_with_gather": total_tables * KX / dtx,
                         "bytes_to_rank0": (world - 1) * KX * T * pkg.TRAJ_PACKED_BYTES, "seconds": dtx, "digest": digest,
                         "gather_only": {"seconds": dtg, "bytes_into_rank0": (world - 1) * (KX - half) * T * pkg.TRAJ_PACKED_BYTES,
                                         "GBps_into_rank0": (world - 1) * (KX - half) * T * pkg.TRAJ_PACKED_BYTES / dtg / 1e9,
@@ -710,51 +801,17 @@ def main():
     mean_a = st["legal_rows"] / max(1, st["plies"])
     leg_errors = []
 
-    # ---- duration of the dominant kernel: all K iterations run inside ONE k_rollout launch; two HIP events around
-    # every launch on the launching stream, repeated until >= 50 ms of kernel time are summed
-    sa = env.stats()
-    ms_total, n_launch = 0.0, 0
-    while ms_total < MIN_TIMED_S * 1e3 and n_launch < (1 << 16):
-        ms_total += env.rollout_random_timed(KL)
-        n_launch += 1
-    sb = env.stats()
-    steps_timed = sb["plies"] - sa["plies"]
-    mean_a2 = (sb["legal_rows"] - sa["legal_rows"]) / max(1, steps_timed)
-    # algorithmic bytes per env step, SURVEY.md 8(d): 128 state read + 128 state write + 4 list size/offset + 16*A
-    # legal rows (DESIGN.md 3 states what the kernel really moves)
-    b_step = 260 + 16 * mean_a2
-    dur_launch = ms_total * 1e-3 / n_launch           # mean duration of one K-iteration launch
-    steps_per_launch = steps_timed / n_launch
-    b_launch = b_step * steps_per_launch
-    dominant = "k_rollout"
-    pmc_key = "k_rollout_65536" if T >= 32768 and "k_rollout_65536" in (_profile("pmc_traffic.json") or {}) else "k_rollout"
-    traffic, traffic_source = None, None
-    prof = (_profile("pmc_traffic.json") or {}).get(pmc_key, {})
-    if prof.get("hbm_bytes_per_env_step") is not None:
-        traffic = prof["hbm_bytes_per_env_step"] * steps_per_launch
-        traffic_source = ("REPLAYED, not measured in this run: profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
-                          "separate passes, FETCH doubled per the gfx950 note; " + str(prof.get("workload", "")) + ") x this run's env steps per launch")
-    issue = issue_block(pmc_key if pmc_key in (_profile("pmc_kernels.json") or {}) else "k_rollout", steps_per_launch, dur_launch)
-    ach = b_launch / dur_launch / 1e9
-
-    # ---- the same loop with packed CSR lists (one launch per iteration): a number, not the headline
-    env.rollout_random_csr(64)
-    torch.cuda.synchronize(dev)
-    dtc, repc = timed_loop(lambda: env.rollout_random_csr(256), lambda: torch.cuda.synchronize(dev))
-    csr_rate = T * 256 * repc / dtc
-    csr_us = dtc / (256 * repc) * 1e6
-    env.rollout_random_csr(10, batch=0)
-    dtc, repc = timed_loop(lambda: env.rollout_random_csr(20, batch=0), lambda: torch.cuda.synchronize(dev))
-    csr_rate_per_launch = T * 20 * repc / dtc
+    roofline = csr = None
+    if a.full:
+        roofline, csr = rollout_extras(env, torch, dev, T, K)
 
     if rank == 0:
         out = {
-            "metric": "env steps/sec (batched tables)", "value": total_tables * K * R / dt,
+            "metric": "env steps/sec (batched tables)", "value": total_tables * K / dt,
             "unit": "env steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": dt / (K * R) * 1e3, "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "timed_steps": K * R, "repeats_of_the_steps_launch": R, "iterations_per_launch": KL, "launches_timed": RL,
-            "timed_seconds": dt,
+            "timed_steps": K, "timed_seconds": dt,
             "config": {"workload": f"{T} tables per GPU, random policy (engine RNG), legal-move list only (no NN), auto-reset: "
                                    "the workload of BASELINE.json configs[1] at the largest single-GPU table count "
                                    "(65,536 per GPU: configs[2] / configs[3]; configs[4] = 8 x 65,536), the same per-GPU "
@@ -762,30 +819,15 @@ def main():
                        "tables_per_gpu": T, "total_tables": total_tables,
                        "mean_legal_moves": round(mean_a, 3), "episodes": st["episodes"],
                        "list_layout": "slab (fixed-stride segment per table)",
-                       "csr_env_steps_per_s": csr_rate, "csr_us_per_iteration": csr_us,
-                       "csr_staging_GiB": env._staging.numel() / 2**30,
-                       "csr_launch_per_iteration_env_steps_per_s": csr_rate_per_launch,
-                       "csr_note": "the same loop with packed CSR lists (offsets / rows as ddz_legal writes them: SURVEY 8(d) "
-                                   "config 2 'outputs = CSR legal list only') beside the slab layout of `value`: batches of "
-                                   "iterations staged by one rollout launch, compacted by two more "
-                                   "(ddz_rollout_random_csr_staged); csr_launch_per_iteration: round 3's form",
-                       "per_rank_env_steps_per_s": per_rank,
-                       "exchange": exchange},
-            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source, "kernel": dominant,
-                         "launch_us": dur_launch * 1e6, "launches_timed": n_launch, "env_steps_per_launch": steps_per_launch,
-                         "us_per_iteration": dur_launch * 1e6 / KL, "iterations_per_launch": KL,
-                         "algorithmic_bytes_per_env_step": b_step,
-                         "algorithmic_bytes_per_launch": b_launch,
-                         "note": "achieved = ALGORITHMIC bytes (SURVEY 8d) / launch time: a store rate into the write-back "
-                                 "L2, not HBM utilisation -- every iteration overwrites the same state rows / list slab, so "
-                                 "the HBM counters (traffic) see ~2 B per env step.  The path is instruction-issue bound: "
-                                 "see issue",
-                         "issue": issue},
+                       "per_rank_env_steps_per_s": per_rank},
         }
+        if a.full:
+            out["config"].update(csr)
+            out["config"]["exchange"] = exchange
+            out["roofline"] = roofline
         if exchange and "env_steps_per_s_with_gather" in exchange:
             out["env_steps_per_s_with_gather"] = exchange["env_steps_per_s_with_gather"]
-        if world == 1 and not a.no_configs:
+        if a.full and world == 1 and not a.no_configs:
             del env                                    # (the legs make their own environments)
             try:
                 out["configs"] = other_config_legs(pkg, torch, dev, leg_errors)
@@ -799,7 +841,7 @@ def main():
                 out["configs"]["stress_plane_rich_leads"] = {"error": repr(ex)[:300]}
                 leg_errors.append({"leg": "stress_plane_rich_leads", "error": repr(ex)[:300]})
                 print(f"[bench] stress leg FAILED: {ex!r}", file=sys.stderr, flush=True)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(T, a.cpu_budget)   # the same workload, a bounded sample
         out["errors"] = leg_errors                      # legs that raised: a non-empty list is a non-zero exit
         print(json.dumps(out), flush=True)

@@ -990,7 +990,7 @@ def test_bench_contract():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "300", "--warmup", "30",
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "300", "--warmup", "30",
                         "--cpu-budget", "1.5"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -1006,12 +1006,13 @@ def test_bench_contract():
     assert j["value"] > 1e8 and abs(j["ms_per_step"] * 1e-3 * j["value"] - 65536) < 16
     r = j["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0 < r["frac"] < 1 and abs(r["achieved"] / r["peak"] - r["frac"]) < 1e-9
-    assert r["kernel"] == "k_rollout" and r["env_steps_per_launch"] == 65536 * j["iterations_per_launch"]
+    assert r["kernel"] == "k_rollout" and r["env_steps_per_launch"] == 65536 * r["iterations_per_launch"]
     assert r["traffic"] is None or "profiles/pmc_traffic.json" in r["traffic_source"]          # replayed inputs say so
     assert "workload" in j["config"] and "model" not in j["config"]
-    # self-sufficient timing: the 300-iteration launch is repeated until >= 50 ms are timed
-    assert j["timed_steps"] == 300 * j["repeats_of_the_steps_launch"] and j["timed_seconds"] >= 0.045
-    assert j["iterations_per_launch"] == 1200   # four times the 300 steps: a launch carries >= 1000 iterations
+    # the headline times exactly the 300 steps asked for; the roofline's own timing is self-sufficient: launches of
+    # >= 1000 iterations repeated until >= 50 ms are timed
+    assert j["timed_steps"] == 300 and abs(j["timed_seconds"] / 300 * 1e3 - j["ms_per_step"]) < 1e-9
+    assert r["iterations_per_launch"] == 1200   # four times the 300 steps: a launch carries >= 1000 iterations
     assert r["launches_timed"] >= 2 and r["launch_us"] * r["launches_timed"] >= 45e3
     # the CSR layout beside the slab layout, at the same table count
     assert j["config"]["csr_env_steps_per_s"] > 1e8 and j["config"]["csr_launch_per_iteration_env_steps_per_s"] > 1e7
@@ -1050,6 +1051,48 @@ def test_bench_contract():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 1e4 and "sample" in c
 
 
+def test_bench_plain_run_times_k_steps_and_dumps_them(pkg, tmp_path):
+    """A plain bench.py run is the headline alone: exactly --steps timed steps, none of --full's figures.  Its
+    --dump-outputs files are the same in two runs and equal an independent rollout of warmup + steps iterations."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    T, K, W = 4096, 50, 7
+    runs = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--tables", str(T), "--steps", str(K),
+                            "--warmup", str(W), "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0]) < 4000
+        runs.append(json.loads(lines[0]))
+    j = runs[0]
+    assert j["steps"] == K and j["timed_steps"] == K and j["warmup"] == W and j["value"] > 0 and j["errors"] == []
+    assert abs(j["ms_per_step"] * 1e-3 * j["value"] - T) < 1e-6 * T
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(j)
+    assert not {"roofline", "configs", "cpu_baseline"} & set(j) and "exchange" not in j["config"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "state.npy" in names
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        assert out[n[:-4]].dtype in (np.float32, np.float64), n
+        assert np.array_equal(out[n[:-4]], np.load(tmp_path / "b" / n)), n
+    env = pkg.BatchedEnv(T, seed=0, device=_dev(), want_ids=False)
+    env.reset()
+    env.rollout_random(W)
+    env.rollout_random(K)
+    assert np.array_equal(out["state"], env.state.view(T, -1, 16).float().cpu().numpy())
+    counts = env.counts.cpu().numpy()
+    assert np.array_equal(out["legal_counts"], counts.astype(np.float32))
+    tabs = out["legal_rows_tables"].astype(np.int64)
+    rows = env.slab_rows().cpu().numpy()
+    assert np.array_equal(out["legal_rows"], np.concatenate([rows[t, :counts[t]] for t in tabs]).astype(np.float32))
+    assert out["stats"][0] == T * (W + K) and out["stats"][1] == env.stats()["episodes"]
+
+
 def test_bench_two_ranks_rehearsal_gathers_the_union(pkg):
     """The N > 1 control flow of bench.py (shard ids, packed trajectory gather to rank 0, two pipelined half-batches)
     executed by two processes on this one GPU (gloo, host-staged: a rehearsal, not a measurement): the records rank 0
@@ -1062,7 +1105,7 @@ def test_bench_two_ranks_rehearsal_gathers_the_union(pkg):
     T, K, W, KX = 512, 40, 10, 30
     env_ = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     # exactly what the driver types: no launcher here -- bench.py starts its two ranks itself (spawn_ranks)
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--rehearse", "--tables", str(T),
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--rehearse", "--tables", str(T),
                         "--steps", str(K), "--warmup", str(W), "--exchange-steps", str(KX)],
                        capture_output=True, text=True, timeout=600, env=env_)
     assert p.returncode == 0, p.stderr[-3000:]

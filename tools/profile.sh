@@ -25,8 +25,8 @@ for pass in "$@"; do
   mkdir -p "$O"
   case $pass in
     bench)
-      python3 bench.py > $O/bench.json 2> $O/bench.err
-      stats $O/bench_stats python3 bench.py --no-cpu-baseline
+      python3 bench.py --full > $O/bench.json 2> $O/bench.err
+      stats $O/bench_stats python3 bench.py --full --no-cpu-baseline
       head -8 $O/bench_stats/p_kernel_stats.csv ;;
     rollout)
       for c in FETCH_SIZE WRITE_SIZE; do pmc $O/pmc_$c $c python3 tools/run_rollout.py 4096 2000; done
