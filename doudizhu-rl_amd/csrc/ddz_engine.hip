@@ -2253,96 +2253,14 @@ __global__ __launch_bounds__(BLOCK) void k_select(const uint8_t* __restrict__ st
 }
 
 // ------------------------------------------------------------------------------------
-// k_q_slab: the per-row stage of the ragged Q forward (game.py:95-104 -> dqn.py:56,67: policy_net(face, actions) over
-// ALL legal actions of a state; net.py:99-101 relu(fc1) -> fc2) over the slab lists, with the first layer factorised
-// per (rank, count) by the host glue (doudizhu-rl_amd/dqn_glue.py FactorisedQ.tables):
-//     q[t][j] = b2 + w2 . relu( sum_{r = 0..14} (U[r][cnt_r][t][:] + Z[r][cnt_r][:]) ),   cnt_r = count of rank r in row j of table t
-// U f32 [15][5][T][256] (per table), Z f32 [15][5][256] (weights only: the action plane through conv_shunzi and fc1; Z[r][0] = 0).
-// One wavefront per table (tpw consecutive tables per wave), lane l owns hidden units 4l..4l+3: the all-zero-count sum
-// once per table (15 coalesced 1-KB reads), then per row three 1-KB reads per rank the action touches, a 4-wide dot and
-// a DPP wave reduction.  The lists are read where ddz_step_slab left them (counts / rows): no CSR, no padding rows, no
-// host sync.
+// The ragged Q forward (game.py:95-104 -> dqn.py:56,67: policy_net(face, actions) over ALL legal actions of a state;
+// net.py:99-101 relu(fc1) -> fc2) over the slab lists, with the first layer factorised per (rank, count): k_q_feat below,
+// the needed-rows form of the rest in ddz_qnet.h.
 constexpr int QH = 256;  // hidden units of fc1 (net.py:147)
-// PACKED (ddz_q_slab_packed): u holds only the (rank, count, table) rows a legal move can use -- rank r's rows start at
-// row0[r], its first T rows are count 0 of tables 0..T-1, the row of (r, c >= 1, t) is pidx[t][QP_OF(r, c)] -- and the
-// per-table term (fc1 bias + the face part of conv_shunzi) comes as its own [T][256] array instead of riding on rank 0.
-constexpr int QP_COLS = 64;  // pidx row: (rank r < 13, count c = 1..4) at 4 r + c - 1, the jokers' count 1 at 52, 53
+constexpr int QP_COLS = 64;  // row_index row: (rank r < 13, count c = 1..4) at 4 r + c - 1, the jokers' count 1 at 52, 53
 __device__ __forceinline__ int qp_col(int r, int c) { return r < 13 ? 4 * r + c - 1 : 52 + (r - 13); }
-struct QRow0 { int64_t v[16]; };  // first packed row of each rank; [15] = the number of rows
-template <bool PACKED>
-__global__ __launch_bounds__(TB, 4) void k_q_slab(const float4* __restrict__ U, const float4* __restrict__ Z, int64_t T, int tpw,
-                                                 const float4* __restrict__ w2, const float* __restrict__ b2,
-                                                 const int32_t* __restrict__ counts, const uint4* __restrict__ rows, int64_t stride,
-                                                 float* __restrict__ q, const int32_t* __restrict__ pidx, QRow0 row0,
-                                                 const float4* __restrict__ tab, int32_t* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int wv = (int)rfl(threadIdx.x >> 6);
-  const int64_t t0 = ((int64_t)blockIdx.x * WPB + wv) * tpw;
-  const int ntab = t0 < T ? (int)(T - t0 < tpw ? T - t0 : tpw) : 0;
-  const float4 w = w2[lane];
-  const float bias = b2[0];
-  const int64_t cstride = T * (QH / 4);  // float4s between the counts of a rank; 5 of them between two ranks
-  for (int i = 0; i < ntab; ++i) {
-    const int64_t t = t0 + i;
-    int n = (int)rfl((uint32_t)counts[t]);
-    if (n < 0 || n > stride) n = 0;
-    const float4* ut = U + (PACKED ? 0 : t * (QH / 4)) + lane;
-    const float4* zl = Z + lane;
-    const uint4* lrow = rows + t * stride;
-    float* qt = q + t * stride;
-    if (n == 0) continue;
-    int32_t myidx = -1;  // PACKED: lane l holds pidx[t][l] (one coalesced 256-byte read per table)
-    if (PACKED) myidx = pidx[t * QP_COLS + lane];
-    // h0 = the sum with every count 0 (the pass): once per table; a row then swaps in the terms of the ranks it touches
-    // (an action touches 1.3 ranks on average)
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (PACKED && tab) h0 = tab[t * (QH / 4) + lane];
-#pragma unroll
-    for (int r = 0; r < 15; ++r) {
-      const float4 v = PACKED ? ut[(row0.v[r] + t) * (QH / 4)] : ut[r * 5 * cstride];
-      h0.x += v.x; h0.y += v.y; h0.z += v.z; h0.w += v.w;
-    }
-    for (int j0 = 0; j0 < n; j0 += 64) {
-      const int m = n - j0 < 64 ? n - j0 : 64;
-      uint4 myrow = make_uint4(0, 0, 0, 0);
-      if (lane < m) myrow = lrow[j0 + lane];  // one coalesced read of up to 64 rows; row jj is handed round by readlane
-      const uint64_t mynib = pack_row(myrow);
-      float res = 0.f;
-      for (int jj = 0; jj < m; ++jj) {
-        const uint64_t nib = rl64(mynib, jj);  // wave-uniform
-        float4 h = h0;
-        for (uint32_t tm = ge_mask(nib, 1); tm; tm &= tm - 1) {  // the ranks the action touches
-          const int r = __builtin_ctz(tm);
-          uint32_t c = (uint32_t)(nib >> (4 * r)) & 15u;
-          c = c > 4u ? 4u : c;
-          if (r >= 13 && c > 1u) c = 1u;  // (a joker exists once; u holds counts 0 and 1 for ranks 13, 14)
-          float4 v, z0;
-          if (PACKED) {
-            // (a count the actor does not hold has no row: such a move is not legal -- read rank r's count-0 row instead
-            // of faulting on a list that does not belong to this state)
-            // a row index at or beyond n_rows (a row_index that does not belong to this u: a stale pack, a caller's
-            // bug) is never dereferenced: count-0 row + status bit 5
-            const int32_t pr = (int32_t)__builtin_amdgcn_readlane(myidx, qp_col(r, (int)c));
-            z0 = ut[(row0.v[r] + t) * (QH / 4)];
-            const bool inside = (uint32_t)pr < (uint32_t)row0.v[15];
-            v = inside ? ut[(int64_t)pr * (QH / 4)] : z0;
-            if (pr >= 0 && !inside && lane == 0) atomicOr(status, 32);
-          } else {
-            v = ut[(r * 5 + (int64_t)c) * cstride]; z0 = ut[r * 5 * cstride];
-          }
-          const float4 zz = zl[(r * 5 + (int)c) * (QH / 4)];
-          h.x += v.x - z0.x + zz.x; h.y += v.y - z0.y + zz.y; h.z += v.z - z0.z + zz.z; h.w += v.w - z0.w + zz.w;
-        }
-        float p = fmaxf(h.x, 0.f) * w.x + fmaxf(h.y, 0.f) * w.y + fmaxf(h.z, 0.f) * w.z + fmaxf(h.w, 0.f) * w.w;
-        p = wave_sum_f32(p);
-        if (lane == jj) res = p + bias;
-      }
-      if (lane < m) qt[j0 + lane] = res;  // coalesced
-    }
-  }
-}
 
-// k_q_feat: the first layer of the same forward per (table, rank, count) -- conv1..conv4 + the (1,4) max-pool of
+// k_q_feat: the first layer of the Q forward per (table, rank, count) -- conv1..conv4 + the (1,4) max-pool of
 // net.py:92-94 (each conv_k is a (1,k) window, stride 4, on a width-4 input: ONE output column per rank; the pool is the
 // max over the four convs) -- evaluated from `face` alone, for every count cnt = 0..4 an action could take of the rank:
 //     Y[r][cnt][t][c] = max_k ( bias_k[c] + sum_{plane, slot < k} W_k[c][plane][slot] * face[t][plane][r][slot] + A[cnt][k][c] )
@@ -2353,12 +2271,10 @@ __global__ __launch_bounds__(TB, 4) void k_q_slab(const float4* __restrict__ U, 
 // count) are one 16-KB run of y.  Written once, read once by the fc1 GEMM: bound by its 5 x 1 KB of stores per pair.  (The torch statement of the same stage -- FactorisedQ.tables(fused=False) --
 // reads and writes the [T, 15, 4, 256] conv output ten times; this kernel never materialises it.)
 constexpr int QF_TILE = 16;  // tables per block
-// PACKED (ddz_q_features_packed): only the rows a legal move can use are written, at the packed positions k_q_slab reads.
-template <int P, bool PACKED>
+template <int P>
 __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, int64_t T, const float* __restrict__ wf,
                                                const float* __restrict__ bias, const float* __restrict__ acnt,
-                                               float* __restrict__ y, int64_t ystride, const int32_t* __restrict__ pidx,
-                                               QRow0 row0) {
+                                               float* __restrict__ y, int64_t ystride) {
   const int c = threadIdx.x;
   // the block's tile of `face` (QF_TILE tables x P x 15 float4: one contiguous piece) goes through LDS: coalesced loads,
   // then wave-uniform (broadcast) LDS reads per (table, rank) pair
@@ -2366,9 +2282,6 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
   const int64_t tb = (int64_t)blockIdx.x * QF_TILE;
   const int nt = (int)(T - tb < QF_TILE ? T - tb : QF_TILE);
   for (int i = threadIdx.x; i < nt * P * 15; i += QH) s_face[i] = face[tb * P * 15 + i];
-  __shared__ __attribute__((aligned(16))) int32_t s_pidx[PACKED ? QF_TILE * QP_COLS : 4];  // PACKED: the tile's rows of pidx (one coalesced 4-KB read)
-  if (PACKED)
-    for (int i = threadIdx.x; i < nt * QP_COLS; i += QH) s_pidx[i] = pidx[tb * QP_COLS + i];
   // this channel's weights: wf [P * 4][4 * 256] (row = plane * 4 + slot, column = k * 256 + c; slots >= k + 1 are zero)
   float w[P][10];
 #pragma unroll
@@ -2391,9 +2304,9 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
   // rank-major over the tile: for a (rank, count) the tile's tables are consecutive rows of y -- QF_TILE KB per run
   for (int r = 0; r < 15; ++r) {
     const int ncnt = r < 13 ? 4 : 1;  // a joker exists once: counts 2..4 of ranks 13, 14 are never read
-    float* dst = y + (PACKED ? row0.v[r] + tb : (int64_t)r * 5 * T + tb) * ystride + c;
+    float* dst = y + ((int64_t)r * 5 * T + tb) * ystride + c;
     // (two tables per trip with the sums as halves of packed-fp32 registers -- v_pk_fma_f32, half the FMA instructions --
-    // measured slower: 0.79 -> 1.30 ms for the packed form at 65,536 tables, 196 VGPRs and ~130 moves to pair the operands)
+    // measured slower: 0.79 -> 1.30 ms for round 3's packed rows at 65,536 tables, 196 VGPRs and ~130 moves to pair the operands)
     for (int ti = 0; ti < nt; ++ti) {
       float s0 = b[0], s1 = b[1], s2 = b[2], s3 = b[3];
 #pragma unroll
@@ -2407,25 +2320,8 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
       // (plain stores: y is read back by the fc1 GEMM right behind this kernel)
       float* d = dst + ti * ystride;
       d[0] = fmaxf(fmaxf(s0, s1), fmaxf(s2, s3));
-      if (PACKED) {
-        // the rows of counts 1..4 of this (table, rank): ONE 16-byte LDS broadcast (columns 4 r .. 4 r + 3; a joker has
-        // one), the tests and the addresses stay in vector registers (the scalar unit was this kernel's second bound:
-        // 60 scalar instructions per (table, rank) against 93 vector ones -- 790 -> 605 us at 65,536 tables)
-        int4 pr4 = make_int4(-1, -1, -1, -1);
-        if (r < 13) pr4 = *(const int4*)&s_pidx[ti * QP_COLS + 4 * r];
-        else pr4.x = s_pidx[ti * QP_COLS + 52 + (r - 13)];
-        const uint32_t ys = (uint32_t)ystride;  // (rows x stride < 2^31: checked by the caller)
-        // (unsigned compares: -1 = not held and anything at or beyond n_rows -- a row_index that does not belong to this
-        // y -- are skipped alike, nothing outside y[:n_rows] is ever written)
-        const uint32_t nr = (uint32_t)row0.v[15];
-        if ((uint32_t)pr4.x < nr) y[(uint32_t)pr4.x * ys + c] = fmaxf(fmaxf(s0 + a[0][0], s1 + a[0][1]), fmaxf(s2 + a[0][2], s3 + a[0][3]));
-        if ((uint32_t)pr4.y < nr) y[(uint32_t)pr4.y * ys + c] = fmaxf(fmaxf(s0 + a[1][0], s1 + a[1][1]), fmaxf(s2 + a[1][2], s3 + a[1][3]));
-        if ((uint32_t)pr4.z < nr) y[(uint32_t)pr4.z * ys + c] = fmaxf(fmaxf(s0 + a[2][0], s1 + a[2][1]), fmaxf(s2 + a[2][2], s3 + a[2][3]));
-        if ((uint32_t)pr4.w < nr) y[(uint32_t)pr4.w * ys + c] = fmaxf(fmaxf(s0 + a[3][0], s1 + a[3][1]), fmaxf(s2 + a[3][2], s3 + a[3][3]));
-      } else {
-        for (int n = 0; n < ncnt; ++n)
-          d[(n + 1) * cs] = fmaxf(fmaxf(s0 + a[n][0], s1 + a[n][1]), fmaxf(s2 + a[n][2], s3 + a[n][3]));
-      }
+      for (int n = 0; n < ncnt; ++n)
+        d[(n + 1) * cs] = fmaxf(fmaxf(s0 + a[n][0], s1 + a[n][1]), fmaxf(s2 + a[n][2], s3 + a[n][3]));
     }
   }
 }
@@ -2841,26 +2737,8 @@ static int launch_auto(int device, AutoArgs& a, hipStream_t st, int kernel = AUT
   return check_launch();
 }
 
-// rank_row0[15] (host): first packed row of each rank, in any order; validated against the table count: every rank owns at
-// least its T count-0 rows, inside [0, n_rows), and no two ranks' count-0 rows overlap
-static bool q_row0(const int64_t* rank_row0, int64_t n_rows, int64_t T, QRow0& out) {
-  if (!rank_row0 || n_rows <= 0 || n_rows > ((int64_t)1 << 31) - 1) return false;
-  for (int r = 0; r < 15; ++r) {
-    out.v[r] = rank_row0[r];
-    if (rank_row0[r] < 0 || rank_row0[r] > n_rows - T) return false;
-    for (int q = 0; q < r; ++q) {
-      const int64_t d = rank_row0[r] > rank_row0[q] ? rank_row0[r] - rank_row0[q] : rank_row0[q] - rank_row0[r];
-      if (d < T) return false;
-    }
-  }
-  out.v[15] = n_rows;
-  return true;
-}
-
-template <bool PACKED>
 static int launch_q_features(int device, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
-                             const float* acnt, float* y, int64_t y_row_stride, const int32_t* pidx, const QRow0& row0,
-                             void* stream) {
+                             const float* acnt, float* y, int64_t y_row_stride, void* stream) {
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(acnt, 4) || !al(y, 4)) return DDZ_EINVAL;
   if (!face || !wf || !bias || !acnt || !y || n_tables <= 0 || y_row_stride < QH) return DDZ_EINVAL;
   if (n_tables > ((int64_t)1 << 30)) return DDZ_ECAP;
@@ -2870,10 +2748,10 @@ static int launch_q_features(int device, const float* face, int64_t n_tables, in
   hipStream_t st = (hipStream_t)stream;
   const float4* f = (const float4*)face;
   switch (planes) {
-    case 4: hipLaunchKernelGGL((k_q_feat<4, PACKED>), grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride, pidx, row0); break;
-    case 6: hipLaunchKernelGGL((k_q_feat<6, PACKED>), grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride, pidx, row0); break;
-    case 7: hipLaunchKernelGGL((k_q_feat<7, PACKED>), grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride, pidx, row0); break;
-    case 9: hipLaunchKernelGGL((k_q_feat<9, PACKED>), grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride, pidx, row0); break;
+    case 4: hipLaunchKernelGGL(k_q_feat<4>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
+    case 6: hipLaunchKernelGGL(k_q_feat<6>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
+    case 7: hipLaunchKernelGGL(k_q_feat<7>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
+    case 9: hipLaunchKernelGGL(k_q_feat<9>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
     default: return DDZ_EINVAL;
   }
   return check_launch();
@@ -3547,54 +3425,7 @@ int ddz_select_slab(ddz_env_t* e, const float* q, const int32_t* counts, int64_t
 
 int ddz_q_features(int device, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                    const float* acnt, float* y, int64_t y_row_stride, void* stream) {
-  return launch_q_features<false>(device, face, n_tables, planes, wf, bias, acnt, y, y_row_stride, nullptr, QRow0{}, stream);
-}
-
-int ddz_q_features_packed(int device, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
-                          const float* acnt, const int32_t* row_index, const int64_t* rank_row0, int64_t n_rows, float* y,
-                          int64_t y_row_stride, void* stream) {
-  QRow0 row0;
-  if (!row_index || !al(row_index, 16) || !q_row0(rank_row0, n_rows, n_tables, row0)) return DDZ_EINVAL;
-  if (y_row_stride > 0 && n_rows > (((int64_t)1 << 31) - 1) / y_row_stride) return DDZ_ECAP;  // k_q_feat indexes y with 32 bits
-  return launch_q_features<true>(device, face, n_tables, planes, wf, bias, acnt, y, y_row_stride, row_index, row0, stream);
-}
-
-int ddz_q_slab(ddz_env_t* e, const float* u, const float* z, int64_t hidden, const float* w2, const float* b2,
-               const int32_t* counts, const int8_t* rows, int64_t stride, float* q, void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!al(u, 16) || !al(z, 16) || !al(w2, 16) || !al(b2, 4) || !al(counts, 4) || !al(rows, 16) || !al(q, 4)) return DDZ_EINVAL;
-  if (!u || !z || !w2 || !b2 || !counts || !rows || !q || hidden != QH || stride < 1) return DDZ_EINVAL;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  // one table per wave up to 16 waves per CU, then consecutive tables per wave (as the stepping kernels)
-  int64_t v = (e->T + 4095) / 4096;
-  const int tpw = (int)(v < 1 ? 1 : v > 8 ? 8 : v);
-  const int64_t per_block = (int64_t)WPB * tpw;
-  hipLaunchKernelGGL(k_q_slab<false>, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
-                     (const float4*)u, (const float4*)z, e->T, tpw, (const float4*)w2, b2, counts, (const uint4*)rows, stride, q,
-                     (const int32_t*)nullptr, QRow0{}, (const float4*)nullptr, e->sc.status);
-  return check_launch();
-}
-
-int ddz_q_slab_packed(ddz_env_t* e, const float* u, const int32_t* row_index, const int64_t* rank_row0, int64_t n_rows,
-                      const float* table_term, const float* z, int64_t hidden, const float* w2, const float* b2,
-                      const int32_t* counts, const int8_t* rows, int64_t stride, float* q, void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!al(u, 16) || !al(z, 16) || !al(w2, 16) || !al(b2, 4) || !al(counts, 4) || !al(rows, 16) || !al(q, 4) || !al(row_index, 4) ||
-      !al(table_term, 16))
-    return DDZ_EINVAL;
-  if (!u || !z || !w2 || !b2 || !counts || !rows || !q || !row_index || hidden != QH || stride < 1) return DDZ_EINVAL;
-  QRow0 row0;
-  if (!q_row0(rank_row0, n_rows, e->T, row0)) return DDZ_EINVAL;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  int64_t v = (e->T + 4095) / 4096;
-  const int tpw = (int)(v < 1 ? 1 : v > 8 ? 8 : v);
-  const int64_t per_block = (int64_t)WPB * tpw;
-  hipLaunchKernelGGL(k_q_slab<true>, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
-                     (const float4*)u, (const float4*)z, e->T, tpw, (const float4*)w2, b2, counts, (const uint4*)rows, stride, q,
-                     row_index, row0, (const float4*)table_term, e->sc.status);
-  return check_launch();
+  return launch_q_features(device, face, n_tables, planes, wf, bias, acnt, y, y_row_stride, stream);
 }
 
 // ---- the "needed rows" form of the ragged Q forward (ddz_qnet.h) ----
@@ -3792,10 +3623,7 @@ int ddz_q_slab_needed(ddz_env_t* e, const float* h0, const float* d, int64_t row
   // (64 tables per block at most: the blocks are the unit the hardware balances over the CUs, the tables inside a block are
   // handed out by an LDS ticket)
   int64_t v = (e->T + 4095) / 4096;
-  int tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
-#ifdef DDZ_QS_TPW_ENV   // (a timing experiment: tables per wave of the row stage from the environment; tools/row_stage_probe.py)
-  if (const char* s_ = getenv("DDZ_QS_TPW")) { const int x = atoi(s_); if (x >= 1 && x <= 8) tpw = x; }
-#endif
+  const int tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
   const int64_t per_block = (int64_t)WPB * tpw;
   hipLaunchKernelGGL(k_q_slab_needed, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
                      (const float4*)h0, (const float4*)d, row_capacity, e->T, tpw, (const float4*)w2, b2, counts,

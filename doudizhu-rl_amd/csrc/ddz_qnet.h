@@ -1,6 +1,6 @@
 // ddz_qnet.h -- the "needed rows" form of the ragged Q forward (BASELINE configs[2]: NetCooperationSimplify inference in the
 // loop; net.py:81-102, dqn.py:50-71, game.py:95-104), device side.  Included by ddz_engine.hip inside its anonymous
-// namespace, after k_q_slab / k_q_feat (it uses QH, QP_COLS, qp_col, pack_row, ge_mask, rl64, rfl, wave_sum_f32).
+// namespace, after k_q_feat (it uses QH, QP_COLS, qp_col, pack_row, ge_mask, rl64, rfl, wave_sum_f32).
 //
 // With the first layer factorised per (table, rank, count) (ddz_engine.hip k_q_feat, dqn_glue.FactorisedQ):
 //     fc1 pre-activation of action j of table t = tab[t] + sum_r W2[r]^T Y[t][r][cnt_jr]          (+ Z[r][cnt_jr], weights only)

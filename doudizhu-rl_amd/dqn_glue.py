@@ -126,8 +126,8 @@ def td_target(transitions, q_next, gamma=0.95):
 # branch, linear end to end, folded in: a per-table vector and a per-(rank, count) vector).  Per iteration:
 #     tables(face)  -> U [15, 5, T, 256]   dense, fixed shapes, plain torch GEMMs (hipBLASLt) -- no ragged dimension
 #     per legal row -> q = fc2(relu(sum_r U[r, cnt_r, t] + Z[r, cnt_r]))   a gather-sum + a 256-dot per row
-# The per-row stage runs over the slab lists in the engine (ddz_q_slab: no CSR, no host sync, no padded rows), or
-# over CSR rows with plain torch ops (q_csr: the reference statement, used by the tests).
+# The loop evaluates the same sum over the NEEDED rows only (FactorisedQ.needed -> ddz_q_slab_needed, over the slab lists:
+# no CSR, no host sync, no padded rows); q_csr is the sum over CSR rows with plain torch ops (the training path, ragged_q).
 import torch.nn as nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
@@ -182,10 +182,6 @@ class FactorisedQ:
     def __init__(self, net, chunk_tables=16384):
         self.net, self.chunk = net, int(chunk_tables)
         self.two_streams = True        # needed(shared="all"): the D chain on a side stream beside the H0 chain
-        # packed form: fifteen fc1 GEMMs over exactly the rows that exist (default), or ONE batched GEMM over segments
-        # padded to the longest (True).  Measured at 65,536 tables: steady state (thousands of iterations in) 4.00 against
-        # 4.23 ms per iteration; a batch of young games (30 iterations in, 16 % padding) 3.75 against 3.60 ms.
-        self.batched_gemm = False
         self.P = net.planes
         self._ver = None
         self._ws = {}
@@ -292,90 +288,6 @@ class FactorisedQ:
                 torch.bmm(Y75[5 * r: 5 * r + 2], self.W2_jok[k], out=U75[5 * r: 5 * r + 2, t0:t1])
             U[0, :, t0:t1] += torch.addmm(self.base, f.reshape(Tc, P * 60), self.Mz_f)
         return U
-
-    # ---- packed form: only the (rank, count, table) rows a legal move can use ----
-    @torch.no_grad()
-    def pack(self, hands):
-        """hands int [T,15] (BatchedEnv.actor_hands: what the acting role holds) -> (row_index int32 [T,64], rank_row0):
-        the layout of ddz_q_features_packed / ddz_q_slab_packed.  A legal move takes at most hands[t][r] cards of rank r,
-        so of the 69 (rank, count) rows of a table only 15 + (cards in hand) are ever read: count 0 of every rank (the
-        first T rows of rank r's segment) and counts 1..hands[t][r] (behind them, in table order).  The segments follow
-        each other without gaps (fifteen GEMMs of different row counts), or -- batched_gemm -- all have the length of the
-        longest, rounded up to 2048 rows (rank_row0[r] = r M; the rows behind a shorter rank's last held count are
-        padding): ONE batched GEMM [15, M, 256] x [15, 256, 256].  rank_row0 = 16 python ints (rank r's first row; [15] =
-        the number of rows); the sizes come from ONE small device -> host copy, the only sync of the packed forward."""
-        T, dev = hands.shape[0], hands.device
-        hc = hands.clamp(0, 4)
-        hc[:, 13:] = hc[:, 13:].clamp(max=1)                           # a joker exists once
-        per_rank = hc.t().contiguous()                                 # [15, T]
-        flat = per_rank.view(-1)
-        excl = (flat.cumsum(0) - flat).view(15, T)                     # ONE 1-D scan: held rows before (r, t), all ranks
-        rel = T + excl - excl[:, :1]                                   # row of (r, t, count 1) inside rank r's segment
-        sizes = [int(x) for x in (T + per_rank.sum(1)).cpu()]          # the sync
-        if self.batched_gemm:
-            # every segment as long as the longest, rounded up to 2048 rows (a coarse grid: the GEMM's shape then repeats
-            # from iteration to iteration)
-            M = (max(sizes) + 2047) // 2048 * 2048
-            host = [r * M for r in range(16)]
-        else:                                                          # fifteen GEMMs over exactly the rows that exist
-            host = [0] * 16
-            for r in range(15):
-                host[r + 1] = host[r] + sizes[r]
-        base = (rel + torch.tensor(host[:15], device=dev)[:, None]).t()   # [T,15]
-        c = torch.arange(4, device=dev)
-        idx = torch.where(c < hc[:, :, None], base[:, :, None] + c, -1).to(torch.int32)   # [T,15,4]
-        row_index = torch.full((T, 64), -1, dtype=torch.int32, device=dev)
-        row_index[:, :52] = idx[:, :13].reshape(T, 52)
-        row_index[:, 52], row_index[:, 53] = idx[:, 13, 0], idx[:, 14, 0]
-        return row_index, host
-
-    @torch.no_grad()
-    def tables_packed(self, face, hands, fused=None):
-        """face f32 [T,P,15,4], hands int [T,15] -> PackedU: the rows of tables() a legal move can use (a third of them
-        at ~10 cards per hand: a third of the fc1 GEMM and of the first layer's stores), one GEMM per rank over that rank's
-        rows (or one batched GEMM over padded segments: batched_gemm), the per-table term on its own.  One host sync (pack).  fused=False (CPU): the same rows
-        gathered from the plain-torch tables() -- the statement the packed kernels are tested against.
-        The result's .u is THIS object's cached workspace, not a copy: the next tables_packed() call on the same
-        FactorisedQ overwrites it (and a batch holding more cards than any before reallocates it) -- consume a PackedU
-        before asking for the next one, or clone .u."""
-        if self._ver != self._versions():
-            self.refresh()
-        T, P, H, H1 = face.shape[0], self.P, self.H, self.H1
-        if tuple(face.shape[1:]) != (P, 15, 4) or tuple(hands.shape) != (T, 15):
-            raise ValueError(f"face must be [T,{P},15,4] and hands [T,15]")
-        if fused is None:
-            fused = face.is_cuda
-        if T * 69 * max(H, H1) >= 1 << 31:
-            raise ValueError(f"tables_packed: {T} tables can need more packed rows than ddz_q_features_packed indexes with 32 "
-                             "bits; call it on slices of at most 120,000 tables (tables() chunks by itself)")
-        row_index, row0 = self.pack(hands)
-        n = row0[15]
-        key = ("packed", face.device)
-        if key not in self._ws or self._ws[key][0].shape[0] < n:
-            cap = max(n, 30 * T) * 9 // 8                              # (grows when a batch holds more cards than any before)
-            self._ws[key] = (torch.zeros((cap, H), dtype=torch.float32, device=face.device),
-                             torch.zeros((cap, H1), dtype=torch.float32, device=face.device))
-        Yc, Uc = self._ws[key]
-        if fused:
-            from .engine import q_features_packed
-            q_features_packed(face.contiguous(), self.Wf, self.bias_f, self.A, row_index, row0, Yc)
-        else:
-            Y = self._first_layer_torch(face)                          # [15,5,T,H]
-            for r in range(15):
-                Yc[row0[r]: row0[r] + T] = Y[r, 0]
-            cols = [(r, c) for r in range(13) for c in range(1, 5)] + [(13, 1), (14, 1)]
-            for k, (r, c) in enumerate(cols):
-                dst = row_index[:, k].long()
-                m = dst >= 0
-                Yc[dst[m]] = Y[r, c][m]
-        if self.batched_gemm:
-            M = row0[1]
-            torch.bmm(Yc[:n].view(15, M, H), self.W2, out=Uc[:n].view(15, M, H1))
-        else:
-            for r in range(15):
-                torch.mm(Yc[row0[r]: row0[r + 1]], self.W2[r], out=Uc[row0[r]: row0[r + 1]])
-        tab = torch.addmm(self.base, face.reshape(T, P * 60), self.Mz_f)
-        return PackedU(Uc, row_index, row0, tab)
 
     # ---- needed form: H0 per table from ONE dense GEMM + D only for the (rank, count) rows some legal move uses ----
     @torch.no_grad()
@@ -578,29 +490,11 @@ class FactorisedQ:
         return torch.stack([(S + self.A[cnt]).amax(dim=1).view(15, T, H) for cnt in range(5)], dim=1)
 
     @torch.no_grad()
-    def q_csr_packed(self, pu, rows, offsets):
-        """q_csr over packed rows (plain torch; the statement ddz_q_slab_packed is tested against)."""
-        T = pu.row_index.shape[0]
-        N = rows.shape[0]
-        pos = torch.arange(N, device=rows.device, dtype=offsets.dtype)
-        seg = torch.searchsorted(offsets[1:].contiguous(), pos, right=True).clamp_(max=T - 1).long()
-        cnt = rows[:, :15].long().clamp_(0, 4)
-        cnt[:, 13:] = cnt[:, 13:].clamp(max=1)
-        r = torch.arange(15, device=rows.device)
-        row0 = torch.tensor(pu.rank_row0[:15], device=rows.device)
-        col = torch.where(r < 13, 4 * r, 52 + (r - 13) - 0)[None, :] + torch.where(r[None, :] < 13, cnt - 1, torch.zeros_like(cnt))
-        held = pu.row_index.long()[seg[:, None], col.clamp(min=0)]
-        zero_row = row0[None, :] + seg[:, None]
-        urow = torch.where((cnt > 0) & (held >= 0), held, zero_row)
-        h = pu.u[urow].sum(1) + pu.table_term[seg]
-        h = h + F.embedding_bag(r[None, :] * 5 + cnt, self.Z.view(-1, self.H1), mode="sum")
-        return F.relu(h) @ self.w2 + self.b2
-
-    @torch.no_grad()
     def q_csr(self, U, rows, offsets):
-        """The per-row stage with plain torch ops over CSR lists (the statement the engine's ddz_q_slab is tested
-        against): rows int8 [N,16] count rows (ddz_legal / ddz_slab_to_csr; rows beyond offsets[T] are padding and get
-        some table's value), offsets int32 [T+1] -> q f32 [N].  No host sync: N is the buffer size."""
+        """The per-row stage with plain torch ops over CSR lists (the training path, ragged_q; the tests' reference for
+        the needed form): U from tables(), rows int8 [N,16] count rows (ddz_legal / ddz_slab_to_csr; rows beyond
+        offsets[T] are padding and get some table's value), offsets int32 [T+1] -> q f32 [N].  No host sync: N is the
+        buffer size."""
         T = U.shape[2]
         N = rows.shape[0]
         pos = torch.arange(N, device=rows.device, dtype=offsets.dtype)
@@ -613,23 +507,10 @@ class FactorisedQ:
         return F.relu(h) @ self.w2 + self.b2
 
     @torch.no_grad()
-    def q_slab(self, env, U, out=None):
-        """The per-row stage over the engine's slab lists (ddz_q_slab): q f32 [T, stride], entries beyond counts[t]
-        untouched.  Feeds env.policy_step_slab / select_slab."""
-        if isinstance(U, NeededU):
-            return env.q_slab_needed(U.h0, U.d, U.row_index, self.w2, self.b2, out=out)
-        if isinstance(U, PackedU):
-            return env.q_slab_packed(U.u, U.row_index, U.rank_row0, U.table_term, self.Z, self.w2, self.b2, out=out)
-        return env.q_slab(U, self.Z, self.w2, self.b2, out=out)
-
-
-class PackedU:
-    """FactorisedQ.tables_packed's result: u f32 [>= n_rows, 256] (fc1's pre-activation contribution of the packed (rank,
-    count, table) rows), row_index int32 [T,64], rank_row0 (16 python ints), table_term f32 [T,256]."""
-    __slots__ = ("u", "row_index", "rank_row0", "table_term")
-
-    def __init__(self, u, row_index, rank_row0, table_term):
-        self.u, self.row_index, self.rank_row0, self.table_term = u, row_index, rank_row0, table_term
+    def q_slab(self, env, nu, out=None):
+        """The per-row stage over the engine's slab lists (ddz_q_slab_needed) from needed()'s NeededU: q f32 [T, stride],
+        entries beyond counts[t] untouched.  Feeds env.policy_step_slab / select_slab."""
+        return env.q_slab_needed(nu.h0, nu.d, nu.row_index, self.w2, self.b2, out=out)
 
 
 class NeededU:
@@ -658,41 +539,33 @@ class PolicyLoop:
     the host:
         face -> Q of every legal move of every table (slab layout) -> ddz_policy_step_slab (epsilon-greedy arg-max + apply +
         next lists + next face, ONE launch).
-    mode "needed" (default): FactorisedQ.needed -- the rows legal moves use, found on the device; the per-rank rows GEMM on
-        the engine's fp32 MFMA kernel (segment sizes stay in device memory), the plain dense GEMM by hipBLASLt (gemm="mfma":
-        by the same MFMA kernel); nothing crosses to the host, every launch is graph-capturable;
-    mode "packed": round 3's form (15 + cards-in-hand rows per table, fifteen library GEMMs, one 128-byte device -> host copy
-        per iteration for their shapes); mode "full": all 69 rows per table, fixed shapes (packed=True / False select these)."""
+    The Q values come from FactorisedQ.needed -- the rows legal moves use, found on the device; the per-rank rows GEMM on
+    the engine's fp32 MFMA kernel (segment sizes stay in device memory), the plain dense GEMM by hipBLASLt (gemm="mfma":
+    by the same MFMA kernel); nothing crosses to the host, every launch is graph-capturable."""
 
-    def __init__(self, env, net, face_variant=3, epsilon=0.0, auto_reset=True, packed=None, mode=None, gemm="torch", shared=None):
+    def __init__(self, env, net, face_variant=3, epsilon=0.0, auto_reset=True, gemm="torch", shared=None):
         from .engine import FACE_PLANES
         if FACE_PLANES[face_variant] != net.planes:
             raise ValueError("the network's input planes do not match the face variant")
-        if mode is None:
-            mode = "needed" if packed is None else ("packed" if packed else "full")
-        if mode not in ("needed", "packed", "full"):
-            raise ValueError("mode must be 'needed', 'packed' or 'full'")
         self.env, self.fq = env, FactorisedQ(net)
         self.variant, self.epsilon, self.auto_reset = int(face_variant), float(epsilon), bool(auto_reset)
-        self.mode, self.gemm = mode, gemm
-        # shared rows (FactorisedQ.needed(shared=True)): the default wherever it applies -- the needed form on
-        # EnvCooperationSimplify faces (variant 3), whose columns ddz_q_shared_rows keys from the environment's state
+        self.gemm = gemm
+        # shared rows (FactorisedQ.needed(shared=True)): the default wherever it applies -- EnvCooperationSimplify faces
+        # (variant 3), whose columns ddz_q_shared_rows keys from the environment's state
         # (True: H0 from shared rows; "all": the needed rows D shared as well -- the default)
-        self.shared = ("all" if (mode == "needed" and int(face_variant) == 3) else False) if shared is None else \
+        self.shared = ("all" if int(face_variant) == 3 else False) if shared is None else \
             ("all" if shared == "all" else bool(shared))
-        if self.shared and (mode != "needed" or int(face_variant) != 3):
-            raise ValueError("shared rows need mode 'needed' and face variant 3")
+        if self.shared and int(face_variant) != 3:
+            raise ValueError("shared rows need face variant 3")
         T = env.T
         self.face = env.observe(self.variant)
-        self.packed = mode == "packed"
-        self.U = torch.zeros((15, 5, T, self.fq.H1), dtype=torch.float32, device=env.device) if mode == "full" else None
         self.q = torch.zeros((T, env.slab_stride), dtype=torch.float32, device=env.device)
         self.choice = torch.empty(T, dtype=torch.int32, device=env.device)
         if not env._slab_fresh:
             env.legal_slab()
 
     def describe(self):
-        if self.mode == "needed" and self.shared:
+        if self.shared:
             return ("ddz_q_need (the (rank, count) rows the legal moves use) + ddz_q_shared_rows (one row per DISTINCT (rank, face "
                     "column) of the batch, direct-addressed, on the device) -> ddz_q_features_rows (first layer of the shared rows) + "
                     "ddz_q_features_needed (dY of the needed rows) -> ddz_q_fc1_rows twice (G = Y x fc1[rank] over the shared rows, "
@@ -700,26 +573,16 @@ class PolicyLoop:
                     "ddz_q_gather_h0 (the fifteen shared rows of every table; no dense K = 3840 GEMM) -> ddz_q_slab_needed -> "
                     "ddz_policy_step_slab(greedy, face): every legal action of every table gets its exact Q value each iteration "
                     "from the current weights; nothing is kept between iterations, nothing crosses to the host")
-        if self.mode == "needed":
-            return ("ddz_q_need (the (rank, count) rows the legal moves use, on the device) -> ddz_q_features_needed (first "
-                    "layer: y0 per table + dY per needed row) -> H0 = tab + y0 x Wd (K = 3840: "
-                    + ("torch.addmm / hipBLASLt" if self.gemm == "torch" else "ddz_q_fc1_dense, the fp32 MFMA kernel k_fc1")
-                    + ") + ddz_q_fc1_rows (D = dY x fc1[rank], k_fc1 with the segment table in device memory)"
-                    + " -> ddz_q_slab_needed -> ddz_policy_step_slab(greedy, face): every legal action of every table gets its Q "
-                    "value each iteration; nothing crosses to the host")
-        if self.mode == "packed":
-            return ("FactorisedQ.tables_packed [ddz_q_features_packed + one torch GEMM per rank over 15 + cards-in-hand rows per "
-                    "table] -> ddz_q_slab_packed -> ddz_policy_step_slab; one 128-byte device -> host copy per iteration")
-        return "FactorisedQ.tables (all 69 (rank, count) rows per table, fixed shapes) -> ddz_q_slab -> ddz_policy_step_slab"
+        return ("ddz_q_need (the (rank, count) rows the legal moves use, on the device) -> ddz_q_features_needed (first "
+                "layer: y0 per table + dY per needed row) -> H0 = tab + y0 x Wd (K = 3840: "
+                + ("torch.addmm / hipBLASLt" if self.gemm == "torch" else "ddz_q_fc1_dense, the fp32 MFMA kernel k_fc1")
+                + ") + ddz_q_fc1_rows (D = dY x fc1[rank], k_fc1 with the segment table in device memory)"
+                + " -> ddz_q_slab_needed -> ddz_policy_step_slab(greedy, face): every legal action of every table gets its Q "
+                "value each iteration; nothing crosses to the host")
 
     def q_values(self):
         """q [T, stride] of the current lists (valid in [:, :counts[t]])"""
-        if self.mode == "needed":
-            return self.fq.q_slab(self.env, self.fq.needed(self.env, self.face, gemm=self.gemm, shared=self.shared), out=self.q)
-        if self.mode == "packed":
-            return self.fq.q_slab(self.env, self.fq.tables_packed(self.face, self.env.actor_hands()), out=self.q)
-        self.fq.tables(self.face, out=self.U)
-        return self.fq.q_slab(self.env, self.U, out=self.q)
+        return self.fq.q_slab(self.env, self.fq.needed(self.env, self.face, gemm=self.gemm, shared=self.shared), out=self.q)
 
     def step(self, traj=None):
         q = self.q_values()
@@ -732,13 +595,11 @@ class PolicyLoop:
             self.step()
 
     def capture(self, n=1):
-        """n lock-step iterations as ONE hipGraph (the needed forms have no host synchronisation and no size-dependent shape):
+        """n lock-step iterations as ONE hipGraph (the loop has no host synchronisation and no size-dependent shape):
         returns the torch.cuda.CUDAGraph; every .replay() runs the n iterations on the state the previous ones left (states,
         faces, choices, q values: bit for bit what n eager step() calls give -- tests/test_gpu_qnet.py).  Call step() a few
         times first (workspaces allocated, libraries warm).  An iteration is ~30 short launches: the replay removes the host's
         share of the gaps between them."""
-        if self.mode != "needed":
-            raise ValueError("only the needed forms are free of host synchronisation")
         dev = self.env.device
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
@@ -751,11 +612,9 @@ class PolicyLoop:
         return g
 
     def profile(self, n=10):
-        """Per-stage device time of n iterations of the needed form (HIP events on the launching stream around every stage)
+        """Per-stage device time of n iterations (HIP events on the launching stream around every stage)
         with each stage's algorithmic FLOP or bytes: {stage: {"us", "kernel", "flop" | "bytes", "note"}}.  Synchronises."""
         from . import engine as E
-        if self.mode != "needed":
-            raise ValueError("profile() describes the needed form")
         env, fq, T, P = self.env, self.fq, self.env.T, self.fq.P
         w = None
         names = ("need", "shared_rows", "features_shared", "features", "table_term", "fc1_dense", "fc1_shared", "gather_h0", "shared_need",
@@ -861,17 +720,16 @@ class PolicyLoop:
         }
 
     def variants(self, timed_loop, sync):
-        """env steps/s of the other forms of the same loop on the same environment (bench.py): the dense GEMM by hipBLASLt,
-        round 3's packed rows, fixed shapes."""
+        """env steps/s of the other forms of the same loop on the same environment (bench.py): H0 from the dense K = 3840
+        GEMM over every table, by hipBLASLt and by k_fc1."""
         out = {}
         T = self.env.T
         other = "mfma" if self.gemm == "torch" else "torch"
-        forms = [("needed_dense_gemm_by_" + ("k_fc1" if other == "mfma" else "hipblaslt"), {"mode": "needed", "gemm": other, "shared": False})]
+        forms = [("needed_dense_gemm_by_" + ("k_fc1" if other == "mfma" else "hipblaslt"), {"gemm": other, "shared": False})]
         if self.shared:   # the dense form of H0 (round 4's first form: one K = 3840 GEMM over every table)
             forms.insert(0, ("needed_dense_gemm_by_" + ("hipblaslt" if self.gemm == "torch" else "k_fc1"),
-                             {"mode": "needed", "gemm": self.gemm, "shared": False}))
-        for name, kw in (*forms,
-                         ("packed_rows_round3", {"mode": "packed"}), ("fixed_shapes", {"mode": "full"})):
+                             {"gemm": self.gemm, "shared": False}))
+        for name, kw in forms:
             loop = PolicyLoop(self.env, self.fq.net, face_variant=self.variant, epsilon=self.epsilon, **kw)
             loop.run(2)
             dt, reps = timed_loop(lambda: loop.run(5), sync, min_s=0.2, max_reps=64)

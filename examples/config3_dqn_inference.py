@@ -25,7 +25,6 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--mode", default="needed", choices=("needed", "packed", "full"))
     ap.add_argument("--gemm", default="torch", choices=("mfma", "torch"), help="the plain dense GEMM: hipBLASLt (default) or the engine's k_fc1")
     ap.add_argument("--dense", action="store_true", help="H0 by the dense K = 3840 GEMM over every table instead of the shared rows")
     ap.add_argument("--stages", action="store_true", help="also print the per-stage device times (HIP events)")
@@ -38,8 +37,7 @@ def main(argv=None):
     T = a.tables
     env = pkg.BatchedEnv(T, seed=0, device=dev)
     env.reset()
-    loop = glue.PolicyLoop(env, net, face_variant=3, epsilon=0.0, mode=a.mode, gemm=a.gemm,
-                           shared=False if (a.dense or a.mode != "needed") else None)
+    loop = glue.PolicyLoop(env, net, face_variant=3, epsilon=0.0, gemm=a.gemm, shared=False if a.dense else None)
     loop.run(2)
     torch.cuda.synchronize()
     s0 = env.stats()
@@ -53,7 +51,7 @@ def main(argv=None):
            "legal_rows_per_table": rows / a.iters / T, "q_evals_per_s": rows / dt, "episodes": s1["episodes"],
            "status": env.status()}
     print(out)
-    if a.stages and a.mode == "needed":
+    if a.stages:
         for k, v in loop.profile(10).items():
             rate = f"{v['flop'] / v['us'] / 1e6:8.1f} TFLOP/s" if v.get("flop") else f"{v['bytes'] / v['us'] / 1e3:8.1f} GB/s"
             print(f"  {k:12s} {v['us']:9.1f} us  {rate}  {v['kernel']}")

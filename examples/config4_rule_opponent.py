@@ -48,7 +48,7 @@ def main():
     @torch.no_grad()
     def lord_ids():
         """the Q-network's greedy move as a canonical action id, for every table (only the lord's tables use it): the
-        ragged forward of dqn_glue (per-rank GEMMs over the rows the actors' hands allow + ddz_q_slab_packed), arg-max by
+        ragged forward of dqn_glue (per-rank GEMMs over the rows the legal moves need + ddz_q_slab_needed), arg-max by
         ddz_select_slab"""
         env.observe(3, out=face)
         q = fq.q_slab(env, fq.needed(env, face, shared="all"), out=qbuf)   # (shared rows: csrc/ddz_qnet.h sections 5-6)

@@ -248,7 +248,7 @@ int ddz_select(ddz_env_t* env, const float* q, const int32_t* offsets, double ep
 int ddz_select_slab(ddz_env_t* env, const float* q, const int32_t* counts, int64_t stride, double epsilon,
                     int32_t* choice, void* stream);
 
-/* First layer of the same forward per (table, rank, count), from `face` alone: conv1..conv4 (net.py:141-144: a (1,k)
+/* First layer of the Q forward below per (table, rank, count), from `face` alone: conv1..conv4 (net.py:141-144: a (1,k)
  * window, stride 4, on the width-4 input = one output column per rank) + the (1,4) max-pool (net.py:93-94 = the max over
  * the four convs), for every count cnt = 0..4 an action could take of that rank (its thermometer, envi.py:139-146, is the
  * action plane net.py:89-90 appends):
@@ -257,51 +257,20 @@ int ddz_select_slab(ddz_env_t* env, const float* q, const int32_t* counts, int64
  * (the two joker ranks r = 13, 14 exist once: only cnt = 0, 1 are written for them).
  * face f32 [T][planes][15][4] (ddz_observe / ddz_policy_step_slab), wf f32 [planes * 4][1024], bias f32 [1024], acnt f32
  * [5][4][256] (weight-only tables, built by FactorisedQ.refresh from the network's conv weights); planes in {4, 6, 7, 9}.
- * The host glue multiplies y by fc1 per rank (a batched GEMM) into the u of ddz_q_slab.  Stateless; fp32.            */
+ * The training glue (dqn_glue.FactorisedQ.tables, ragged_q) multiplies y by fc1 per rank.  Stateless; fp32.          */
 int ddz_q_features(int device_id, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                    const float* acnt, float* y, int64_t y_row_stride, void* stream);
 
-/* The per-row stage of the reference's ragged Q forward -- policy_net(face, actions) over ALL legal actions of a state
- * (game.py:95-104, dqn.py:56,67; net.py:99-101 relu(fc1) -> fc2) -- for every table at once, over the slab lists as
- * ddz_step_slab / ddz_legal_slab left them.  The host glue evaluates the first layer factorised per (rank, count)
- * (doudizhu-rl_amd/dqn_glue.py FactorisedQ.tables: dense per-table GEMMs, no ragged dimension) into
- *   u f32 [15][5][T][hidden]: fc1's pre-activation contribution of rank r when the action takes cnt cards of it (per table),
- *   z f32 [15][5][hidden]:    the same for the action plane's own path through conv_shunzi (weights only; z[r][0] = 0),
- * and this writes q[t * stride + j] = b2[0] + w2 . relu(sum_r (u[r][cnt_r][t][:] + z[r][cnt_r][:])), cnt_r = the count of rank
- * r in row j of table t, for j < counts[t] (entries beyond counts[t] are left alone) -- what ddz_policy_step_slab /
- * ddz_select_slab take.  No CSR, no padded rows, no host sync.  hidden must be 256 (net.py:147); w2 f32 [hidden], b2 f32
- * [1]: DEVICE memory.  fp32 (tests: tolerance 1e-5 against the literal nn.Conv2d evaluation).                     */
-int ddz_q_slab(ddz_env_t* env, const float* u, const float* z, int64_t hidden, const float* w2, const float* b2,
-               const int32_t* counts, const int8_t* rows, int64_t stride, float* q, void* stream);
-
-/* The same two stages over PACKED rows: only the (rank, count, table) triples a legal move of table t can use exist -- count 0
- * of every rank, and count c >= 1 of rank r where the actor holds at least c cards of it (15 + cards-in-hand rows per table
- * instead of 69: a third of the fc1 GEMM).  Layout (built by the host glue from the actors' hands, FactorisedQ.pack):
- *   rank r's rows start at rank_row0[r] (HOST memory, 15 entries read; the ranks' segments in any order, not overlapping,
- *   inside [0, n_rows); rows between segments are padding the glue's batched GEMMs may compute on): the first T rows of a
- *   segment are count 0 of tables 0..T-1, then the held counts in any order;
- *   row_index int32 [T][64] (device): row of (r < 13, c = 1..4) at column 4 r + c - 1, of a joker's count 1 at column 52 /
- *   53; -1 = not held (ddz_q_features_packed skips it; ddz_q_slab_packed reads the count-0 row instead: no legal move of
- *   the table takes that count).  Entries are device data and are never trusted as addresses: one at or beyond n_rows is
- *   treated like -1 by both functions (nothing outside y[:n_rows] / u[:n_rows] is touched) and ddz_q_slab_packed raises
- *   status bit 5.
- * y / u f32 [n_rows][y_row_stride / hidden]; the glue multiplies each rank's rows by that rank's fc1 block (15 GEMMs).
- * table_term f32 [T][hidden] or NULL: the per-table term (fc1 bias + the face part of conv_shunzi), added once per table
- * (the unpacked form carries it on rank 0's rows).  Results equal the unpacked functions' up to the GEMM's summation order. */
-int ddz_q_features_packed(int device_id, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
-                          const float* acnt, const int32_t* row_index, const int64_t* rank_row0, int64_t n_rows, float* y,
-                          int64_t y_row_stride, void* stream);
-int ddz_q_slab_packed(ddz_env_t* env, const float* u, const int32_t* row_index, const int64_t* rank_row0, int64_t n_rows,
-                      const float* table_term, const float* z, int64_t hidden, const float* w2, const float* b2,
-                      const int32_t* counts, const int8_t* rows, int64_t stride, float* q, void* stream);
-
-/* The same forward over NEEDED rows only -- nothing on the host, no host-side sizes (doudizhu-rl_amd/csrc/ddz_qnet.h;
- * BASELINE configs[2]: net.py inference in the loop, game.py:95-104 / dqn.py:56,67 for every table at once):
+/* The reference's ragged Q forward -- policy_net(face, actions) over ALL legal actions of a state (game.py:95-104,
+ * dqn.py:56,67; net.py:99-101 relu(fc1) -> fc2) -- for every table at once, over the slab lists as ddz_step_slab /
+ * ddz_legal_slab left them, with the first layer factorised per (rank, count) and evaluated over NEEDED rows only: nothing
+ * on the host, no host-side sizes (doudizhu-rl_amd/csrc/ddz_qnet.h; BASELINE configs[2]: net.py inference in the loop):
  *   fc1 pre-activation of move j of table t = H0[t] + sum over the ranks r the move touches of D[row(t, r, cnt_jr)]
  *   H0[t] = table_term[t] + sum_r fc1_r^T Y[t][r][0]               one dense GEMM, K = 15 * 256
  *   D[row] = fc1_r^T (Y[t][r][c] - Y[t][r][0]) + z[r][c], c >= 1   only for the (r, c) some LEGAL MOVE of table t takes
  * ddz_q_need: finds those (r, c) from the slab lists (counts / rows as ddz_step_slab left them) and lays their rows out in
- *   fifteen rank segments: row_index int32 [T][64] (columns as above; -1 = not needed) and seg int32 [40] (DEVICE memory:
+ *   fifteen rank segments: row_index int32 [T][64] (the row of (r < 13, c = 1..4) at column 4 r + c - 1, of a joker's count 1
+ *   at column 52 / 53; -1 = not needed) and seg int32 [40] (DEVICE memory:
  *   [r] first row of rank r's segment -- a multiple of the tile, ddz_q_fc1_tile_rows() = 128 --, [15] rows in use, [16 + r] first tile of rank r, [31]
  *   tiles in use, [32] rows needed, [33] 1 if row_capacity was too small -- then status bit 1 is raised and the rows that did
  *   not fit are -1); row_cnt uint8 [row_capacity]: the count c of every needed row (ddz_q_fc1_rows adds z[rank][c]).
@@ -313,10 +282,13 @@ int ddz_q_slab_packed(ddz_env_t* env, const float* u, const int32_t* row_index, 
  *   d[row] = dy[row] x w2[rank of the row] + z[rank][row_cnt[row]] (w2 f32 [15][256][256], input-major; z f32 [15][5][256]: the
  *   action plane's own path through conv_shunzi and fc1, weights only), rows and ranks from seg -- both one launch
  *   of a hand-written fp32 MFMA kernel (v_mfma_f32_32x32x2_f32: exact f32, a k-ordered fmaf chain; no library GEMM).
- * ddz_q_slab_needed: the per-row stage (as ddz_q_slab) from h0 f32 [T][256], d, row_index (a table's needed rows are staged in
- *   LDS once: every move that takes that count of the rank uses the row); a move whose (r, c) has no row
- *   (a list that does not belong to this row_index) contributes nothing for that rank and raises status bit 5.
- * fp32 throughout; results equal ddz_q_slab's up to summation order (tests: 1e-5 against the literal nn.Conv2d network). */
+ * ddz_q_slab_needed: the per-row stage from h0 f32 [T][256], d and row_index: q[t * stride + j] = b2[0] + w2 . relu(fc1
+ *   pre-activation of move j of table t) for j < counts[t] (entries beyond counts[t] are left alone) -- what
+ *   ddz_policy_step_slab / ddz_select_slab take.  hidden must be 256 (net.py:147); w2 f32 [hidden], b2 f32 [1]: DEVICE
+ *   memory.  A table's needed rows are staged in LDS once (every move that takes that count of the rank uses the row); a
+ *   move whose (r, c) has no row (a list that does not belong to this row_index) contributes nothing for that rank and
+ *   raises status bit 5.
+ * fp32 throughout (tests: 1e-5 against the literal nn.Conv2d network). */
 int ddz_q_fc1_tile_rows(void);   /* rows per tile of the fc1 kernel: segment starts and row_capacity are multiples of it */
 int64_t ddz_q_need_scratch_bytes(int64_t n_tables);
 int ddz_q_need(ddz_env_t* env, const int32_t* counts, const int8_t* rows, int64_t stride, int64_t row_capacity, void* scratch,
@@ -440,8 +412,8 @@ int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
 /* device status word: bit0 enumerator/count mismatch, bit1 row capacity overflow,
  * bit2 invalid `last` combo, bit3 a wait of ddz_auto_choose_state's cooperating wavefronts hit its
  * hang guard (never in a working launch; the ids of that launch are not to be trusted), bit4 the sequential
- * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a row_index entry of ddz_q_slab_packed at or
- * beyond n_rows (not dereferenced: the count-0 row was read instead).
+ * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a move of ddz_q_slab_needed whose (rank, count)
+ * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing).
  * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
 /* the same word for the STATELESS rule-agent entry point (ddz_auto_choose has no handle): one per device, bits as above

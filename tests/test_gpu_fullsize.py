@@ -136,10 +136,11 @@ def test_rule_opponent_full_size_with_oracle_slice(pkg, oracle):
     assert s["episodes"] > T // 4 and s["up_wins"] + s["down_wins"] > 2 * s["lord_wins"]
 
 
-def test_q_slab_equals_the_torch_statement_and_the_literal_network(pkg):
-    """ddz_q_slab (per-row stage of the ragged Q forward over the slab lists) == FactorisedQ.q_csr (plain torch ops over
-    the CSR rows of the same lists) == the literal nn.Conv2d evaluation of net.py:81-102 on a sample of rows.
-    Floating point, fp32: tolerance 1e-5 absolute (summation order is the only difference)."""
+def test_q_features_and_q_csr_equal_the_torch_statement_and_the_literal_network(pkg):
+    """The first layer of the ragged Q forward by ddz_q_features (FactorisedQ.tables) == the same stage in plain torch ops,
+    and FactorisedQ.q_csr over the CSR rows of the slab lists (the training path, ragged_q) == the literal nn.Conv2d
+    evaluation of net.py:81-102 on a sample of rows.  Floating point, fp32: tolerance 1e-5 absolute (summation order is
+    the only difference)."""
     import importlib
     glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
     for T, variant in ((3001, 3), (517, 2), (64, 0), (1000, 1)):
@@ -155,15 +156,11 @@ def test_q_slab_equals_the_torch_statement_and_the_literal_network(pkg):
         U = fq.tables(face)                            # first layer by ddz_q_features (one pass over `face`)
         U_torch = fq.tables(face, fused=False)         # ... and the same stage in plain torch ops
         assert torch.allclose(U, U_torch, rtol=1e-5, atol=1e-5), float((U - U_torch).abs().max())
-        q = env.q_slab(U, fq.Z, fq.w2, fq.b2)
         off, rows, _ = env.slab_to_csr(rows_per_table=512)
         qc = fq.q_csr(U, rows, off)
         n = int(off[-1].item())
         counts = env.counts.long()
-        valid = torch.arange(env.slab_stride, device=_dev())[None, :] < counts[:, None]
-        assert int(valid.sum()) == n
-        assert float((q[valid] - qc[:n]).abs().max()) < 1e-5
-        assert bool((q[~valid] == 0).all())            # entries beyond counts[t] are left alone
+        assert int(counts.sum()) == n
         # literal evaluation on every 7th row -- on the CPU (MIOpen would tune a convolution for every new batch size)
         seg = torch.repeat_interleave(torch.arange(T, device=_dev()), counts)
         pick = torch.arange(0, n, 7, device=_dev())
@@ -171,81 +168,7 @@ def test_q_slab_equals_the_torch_statement_and_the_literal_network(pkg):
         with torch.no_grad():
             want = copy.deepcopy(net).cpu()(face[seg[pick]].cpu(), acts.cpu())[:, 0]
         assert float((qc[:n][pick].cpu() - want).abs().max()) < 1e-5
-        # the packed form (ddz_q_features_packed -> one GEMM per rank -> ddz_q_slab_packed): only the (rank, count) rows the
-        # actors' hands allow; the same q (fp32, 1e-5: the GEMMs differ in their row counts only)
-        pu = fq.tables_packed(face, env.actor_hands())
-        nrow = pu.rank_row0[15]
-        held_r = env.actor_hands().sum(0)
-        assert nrow == 15 * T + int(held_r.sum())                       # fifteen exact segments (the default)
-        if T <= 1000:
-            fqc = glue.FactorisedQ(copy.deepcopy(net).cpu())
-            pu_torch = fqc.tables_packed(face.cpu(), env.actor_hands().cpu(), fused=False)
-            assert torch.equal(pu_torch.row_index, pu.row_index.cpu()) and pu_torch.rank_row0 == pu.rank_row0
-            used = torch.zeros(nrow, dtype=torch.bool)                 # the rows that exist: count 0 + the held counts
-            for r in range(15):
-                used[pu.rank_row0[r]: pu.rank_row0[r] + T + int(held_r[r])] = True
-            assert torch.allclose(pu.u[:nrow].cpu()[used], pu_torch.u[:nrow][used], rtol=1e-5, atol=1e-5)
-        qp = fq.q_slab(env, pu)
-        assert float((qp[valid] - q[valid]).abs().max()) < 1e-5
-        assert bool((qp[~valid] == 0).all())
-        fq.batched_gemm = True                                         # ... and ONE batched GEMM over padded segments
-        pub = fq.tables_packed(face, env.actor_hands())
-        assert pub.rank_row0[1] % 2048 == 0 and pub.rank_row0 == [r * pub.rank_row0[1] for r in range(16)]
-        assert float((fq.q_slab(env, pub)[valid] - q[valid]).abs().max()) < 1e-5
-        fq.batched_gemm = False
-        assert float((fq.q_csr_packed(pu, rows, off)[:n] - qc[:n]).abs().max()) < 1e-5
         assert env.status() == 0
-
-
-def test_packed_q_entry_points_reject_a_layout_that_does_not_fit_the_tables(pkg):
-    """ddz_q_features_packed / ddz_q_slab_packed check the host-side segment starts before anything is launched: every
-    rank needs at least its T count-0 rows, the starts must be ordered, the row count must fit int32 -- DDZ_EINVAL, not
-    a fault; and a held-count column of -1 (a count the actor does not hold) reads the rank's count-0 row."""
-    import importlib
-    glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
-    T = 300
-    torch.manual_seed(1)
-    net = glue.QNet(6).to(_dev()).eval()
-    env = pkg.BatchedEnv(T, seed=2, device=_dev())
-    env.reset(); env.rollout_random(7); env.legal_slab()
-    face = env.observe(3)
-    fq = glue.FactorisedQ(net)
-    pu = fq.tables_packed(face, env.actor_hands())
-    good = list(pu.rank_row0)
-    near = list(good)
-    near[3] = near[4] + T - 1                                            # rank 3's count-0 rows would overlap rank 4's
-    for bad in ([0] * 16, near, [g + (1 << 31) for g in good], good[:15] + [max(good[:15]) + T - 1]):
-        with pytest.raises((pkg.DdzError, ValueError)):   # (the host mirror rejects a row count beyond its buffer itself)
-            env.q_slab_packed(pu.u, pu.row_index, bad, pu.table_term, fq.Z, fq.w2, fq.b2)
-    with pytest.raises(pkg.DdzError):
-        pkg.q_features_packed(face, fq.Wf, fq.bias_f, fq.A, pu.row_index, [0] * 16, pu.u)
-    q = fq.q_slab(env, pu).clone()
-    # every held-count column -1: each row's q falls back to the value of the pass (all counts 0) -- no fault, finite
-    none = torch.full_like(pu.row_index, -1)
-    q0 = env.q_slab_packed(pu.u, none, good, pu.table_term, fq.Z, fq.w2, fq.b2)
-    counts = env.counts.long()
-    valid = torch.arange(env.slab_stride, device=_dev())[None, :] < counts[:, None]
-    assert bool(torch.isfinite(q0[valid]).all()) and bool(torch.isfinite(q[valid]).all())
-    assert env.status() == 0
-    # row_index is DEVICE data and is never trusted as an address: entries at or beyond n_rows (a stale pack, a row_index
-    # of other hands) are skipped by ddz_q_features_packed -- nothing outside y[:n_rows] changes, nothing inside either
-    # where no valid row points -- and read as the count-0 row by ddz_q_slab_packed, which raises status bit 5
-    n_rows = good[15]
-    wild = pu.row_index.clone()
-    held = wild >= 0
-    wild[held] = wild[held] + n_rows                                     # every held row now points beyond the buffer
-    wild[0, 0] = 0x7FFFFFF0
-    y = torch.full((n_rows + 4096, 256), 7.0, device=_dev())
-    pkg.q_features_packed(face, fq.Wf, fq.bias_f, fq.A, wild, good, y)
-    torch.cuda.synchronize()
-    written = (y != 7.0).any(1)
-    count0 = torch.zeros(n_rows + 4096, dtype=torch.bool, device=_dev())
-    for r in range(15):
-        count0[good[r]: good[r] + T] = True                              # the T count-0 rows of every rank: always written
-    assert bool((written == count0).all())
-    qw = env.q_slab_packed(pu.u, wild, good, pu.table_term, fq.Z, fq.w2, fq.b2)
-    assert torch.equal(qw[valid], q0[valid])                             # exactly the all-held-columns-absent result
-    assert env.status() & 32
 
 
 def test_policy_loop_with_the_q_network_full_size_with_oracle_slice(pkg, oracle):

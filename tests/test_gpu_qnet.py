@@ -84,9 +84,10 @@ def test_needed_rows_kernels_vs_torch_statement_and_literal_network(pkg, P, vari
         assert float((w["dy"].cpu()[rows_used] - ref.dy[rows_used]).abs().max()) < 2e-6
         assert float((nu.h0.cpu() - ref.h0).abs().max()) < 1e-5
         assert float((nu.d.cpu()[rows_used] - ref.d[rows_used]).abs().max()) < 1e-5
-        q = fq.q_slab(env, nu)
+        q = fq.q_slab(env, nu, out=torch.zeros((T, env.slab_stride), dtype=torch.float32, device=_dev()))
         counts = env.counts.long()
         valid = torch.arange(env.slab_stride, device=_dev())[None, :] < counts[:, None]
+        assert bool((q[~valid] == 0).all())                   # entries beyond counts[t] are left alone
         q_csr = q[valid].cpu()                                # slab order == CSR order
         qt = fqc.q_csr_needed(ref, rows.cpu(), off.cpu())[:n]
         assert q_csr.numel() == n and float((q_csr - qt).abs().max()) < 1e-5
