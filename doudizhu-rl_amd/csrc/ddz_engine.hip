@@ -3519,26 +3519,68 @@ int ddz_q_shared_rows(ddz_env_t* e, void* ws, int64_t ws_bytes, int64_t row_capa
   if (hipMemsetAsync(rep, 0xFF, (size_t)row_capacity * 4, st) != hipSuccess) return DDZ_EHIP;
   const unsigned nb = (unsigned)((e->T * 16 + 255) / 256);
   hipLaunchKernelGGL(k_qs_mark, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, slots, rows);
-  hipLaunchKernelGGL(k_qs_count, dim3(15 * QSH_CPR), dim3(256), 0, st, (const int32_t*)slots, cnt);
-  hipLaunchKernelGGL(k_qs_seg, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity);
-  hipLaunchKernelGGL(k_qs_assign, dim3(15 * QSH_CPR), dim3(256), 0, st, slots, (const int32_t*)base, rep, (int32_t)row_capacity);
-  hipLaunchKernelGGL(k_qs_rows, dim3(nb), dim3(256), 0, st, (const int32_t*)slots, e->T, rows);
+  hipLaunchKernelGGL(k_qs_count<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, (const int32_t*)slots, cnt, QSH_COLS, QSH_CPR);
+  hipLaunchKernelGGL(k_qs_seg<true>, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity, QSH_CPR);
+  hipLaunchKernelGGL(k_qs_assign<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, slots, (const int32_t*)base, rep, (int32_t)row_capacity,
+                     QSH_COLS, QSH_CPR);
+  hipLaunchKernelGGL(k_qs_rows<true>, dim3(nb), dim3(256), 0, st, (const int32_t*)slots, e->T, rows, QSH_KEYS);
+  return check_launch();
+}
+// the hashed row finder (ddz_qnet.h section 5b): EnvComplicated / EnvCooperation faces
+int64_t ddz_q_shared_hash_ws_bytes(int64_t n_tables) {
+  if (n_tables <= 0 || n_tables > ((int64_t)1 << 26)) return DDZ_EINVAL;
+  const int64_t R = qsh_hash_region(n_tables), cpr = R / QSH_CHUNK;
+  return 15 * R * 12 + 2 * 15 * cpr * 4;                        // keys u64 [15 R] | vals i32 [15 R] | cnt [15][cpr] | base [15][cpr]
+}
+int ddz_q_shared_rows_hashed(ddz_env_t* e, int variant, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* rows, int32_t* rep,
+                             int32_t* seg, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (variant != 1 && variant != 2) return DDZ_EINVAL;
+  if (!ws || !rows || !rep || !seg || !al(ws, 16) || !al(rows, 16) || !al(rep, 4) || !al(seg, 4)) return DDZ_EINVAL;
+  if (e->T > ((int64_t)1 << 26) || ws_bytes < ddz_q_shared_hash_ws_bytes(e->T) || row_capacity % FC_M) return DDZ_ECAP;
+  if (row_capacity < e->T * 15 + 15 * FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = qsh_hash_region(e->T), cpr = R / QSH_CHUNK;    // (row_capacity bounds T: 15 R < 2^31)
+  uint64_t* keys = (uint64_t*)ws;
+  int32_t* vals = (int32_t*)(keys + (int64_t)15 * R);
+  int32_t* cnt = vals + (int64_t)15 * R;
+  int32_t* base = cnt + 15 * cpr;
+  if (hipMemsetAsync(keys, 0, (size_t)15 * R * 12, st) != hipSuccess) return DDZ_EHIP;   // keys and values: one clear
+  if (hipMemsetAsync(rep, 0xFF, (size_t)row_capacity * 4, st) != hipSuccess) return DDZ_EHIP;
+  const unsigned nb = (unsigned)((e->T * 16 + 255) / 256);
+  if (variant == 1)
+    hipLaunchKernelGGL(k_qs_hmark<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
+  else
+    hipLaunchKernelGGL(k_qs_hmark<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
+  hipLaunchKernelGGL(k_qs_count<false>, dim3(15 * cpr), dim3(256), 0, st, (const int32_t*)vals, cnt, R, cpr);
+  hipLaunchKernelGGL(k_qs_seg<false>, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity, cpr);
+  hipLaunchKernelGGL(k_qs_assign<false>, dim3(15 * cpr), dim3(256), 0, st, vals, (const int32_t*)base, rep, (int32_t)row_capacity, R, cpr);
+  hipLaunchKernelGGL(k_qs_rows<false>, dim3(nb), dim3(256), 0, st, (const int32_t*)vals, e->T, rows, 15 * R);
   return check_launch();
 }
 int ddz_q_features_rows(int device, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                         const int32_t* rep, const int32_t* seg, float* ys, int64_t ys_ld, int64_t row_capacity, const float* mz, float* g,
                         void* stream) {
   if (!face || !wf || !bias || !rep || !seg || !ys || n_tables <= 0 || ((mz == nullptr) != (g == nullptr))) return DDZ_EINVAL;
-  if (ys_ld != QH && ys_ld != QH + 32) return DDZ_EINVAL;
+  // the faces whose columns ddz_q_shared_rows (6 planes) / ddz_q_shared_rows_hashed (7, 9) key
+  if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
+  if (ys_ld != QH && ys_ld != QH + (4 * planes + 15) / 16 * 16) return DDZ_EINVAL;
   if (!al(mz, 4) || !al(g, 4)) return DDZ_EINVAL;
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(rep, 4) || !al(seg, 4) || !al(ys, 4)) return DDZ_EINVAL;
-  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > (((int64_t)1 << 31) - 1) / (QH + 32) || n_tables > ((int64_t)1 << 26))
+  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > (((int64_t)1 << 31) - 1) / ys_ld || n_tables > ((int64_t)1 << 26))
     return DDZ_ECAP;
-  if (planes != 6) return DDZ_EINVAL;   // EnvCooperationSimplify's six planes: the only face whose columns ddz_q_shared_rows keys
   DeviceGuard gd(device);
   if (!gd.ok) return DDZ_ENODEV;
-  hipLaunchKernelGGL(k_q_feat_rows<6>, dim3((unsigned)(row_capacity / QR_TILE)), dim3(QH), 0, (hipStream_t)stream, (const float4*)face,
-                     n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g);
+  const dim3 grid((unsigned)(row_capacity / QR_TILE)), block(QH);
+  hipStream_t st = (hipStream_t)stream;
+  const float4* f4 = (const float4*)face;
+  switch (planes) {
+    case 6: hipLaunchKernelGGL(k_q_feat_rows<6>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
+    case 7: hipLaunchKernelGGL(k_q_feat_rows<7>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
+    default: hipLaunchKernelGGL(k_q_feat_rows<9>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
+  }
   return check_launch();
 }
 // the needed rows D shared as well (ddz_qnet.h section 6)
@@ -3580,11 +3622,17 @@ int ddz_q_features_drows(int device, const float* face, int64_t n_tables, int pl
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(acnt, 4) || !al(rep, 4) || !al(drep, 4) || !al(dseg, 4) || !al(dy, 4)) return DDZ_EINVAL;
   if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > (((int64_t)1 << 31) - 1) / QH || n_tables > ((int64_t)1 << 26))
     return DDZ_ECAP;
-  if (planes != 6) return DDZ_EINVAL;
+  if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
-  hipLaunchKernelGGL(k_q_feat_drows<6>, dim3((unsigned)(row_capacity / QR_TILE)), dim3(QH), 0, (hipStream_t)stream, (const float4*)face,
-                     n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy);
+  const dim3 grid((unsigned)(row_capacity / QR_TILE)), block(QH);
+  hipStream_t st = (hipStream_t)stream;
+  const float4* f4 = (const float4*)face;
+  switch (planes) {
+    case 6: hipLaunchKernelGGL(k_q_feat_drows<6>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
+    case 7: hipLaunchKernelGGL(k_q_feat_drows<7>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
+    default: hipLaunchKernelGGL(k_q_feat_drows<9>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
+  }
   return check_launch();
 }
 int ddz_q_gather_h0(int device, const float* g, int64_t g_rows, const int32_t* rows, int64_t n_tables, const float* base, float* h0,

@@ -660,13 +660,18 @@ __global__ __launch_bounds__(256) void k_qs_mark(const uint8_t* __restrict__ sta
   slots[key] = (int32_t)idx + 1;
   rows[idx] = key;
 }
-__global__ __launch_bounds__(256) void k_qs_count(const int32_t* __restrict__ slots, int32_t* __restrict__ cnt) {
+// (cols, cpr): slots per rank region and QSH_CHUNK-key chunks per rank -- the region size R and R / QSH_CHUNK of the hashed
+// table (section 5b); DIRECT: the direct-addressed table's QSH_COLS / QSH_CPR (n_slots: QSH_KEYS), folded at compile time
+// (the arguments then carry the same values and are not read)
+template <bool DIRECT>
+__global__ __launch_bounds__(256) void k_qs_count(const int32_t* __restrict__ slots, int32_t* __restrict__ cnt, int cols_, int cpr_) {
+  const int cols = DIRECT ? QSH_COLS : cols_, cpr = DIRECT ? QSH_CPR : cpr_;
   __shared__ int s_n[4];
-  const int r = blockIdx.x / QSH_CPR, ch = blockIdx.x % QSH_CPR;
+  const int r = blockIdx.x / cpr, ch = blockIdx.x % cpr;
   const int k0 = ch * QSH_CHUNK + (int)threadIdx.x * 8;
   int n = 0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) n += (k0 + i < QSH_COLS && slots[r * QSH_COLS + k0 + i] != 0) ? 1 : 0;
+  for (int i = 0; i < 8; ++i) n += (k0 + i < cols && slots[r * cols + k0 + i] != 0) ? 1 : 0;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
   if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = n;
@@ -675,13 +680,15 @@ __global__ __launch_bounds__(256) void k_qs_count(const int32_t* __restrict__ sl
 }
 // one block: rank totals -> seg (the layout k_fc1<true> reads, QN_SEG_WORDS ints), chunk bases.  row_capacity >= 15 T + 15 tiles
 // always suffices (checked on the host), so nothing can overflow; seg[33] stays 0.
+template <bool DIRECT>
 __global__ __launch_bounds__(64) void k_qs_seg(const int32_t* __restrict__ cnt, int32_t* __restrict__ base, int32_t* __restrict__ seg,
-                                               int32_t row_capacity) {
+                                               int32_t row_capacity, int cpr_) {
+  const int cpr = DIRECT ? QSH_CPR : cpr_;
   __shared__ int s_tot[16], s_start[16];
   const int r = threadIdx.x;
   if (r < 15) {
     int n = 0;
-    for (int c = 0; c < QSH_CPR; ++c) n += cnt[r * QSH_CPR + c];
+    for (int c = 0; c < cpr; ++c) n += cnt[r * cpr + c];
     s_tot[r] = n;
   }
   __syncthreads();
@@ -700,17 +707,19 @@ __global__ __launch_bounds__(64) void k_qs_seg(const int32_t* __restrict__ cnt, 
   __syncthreads();
   if (r < 15) {
     int b = s_start[r];
-    for (int c = 0; c < QSH_CPR; ++c) { base[r * QSH_CPR + c] = b; b += cnt[r * QSH_CPR + c]; }
+    for (int c = 0; c < cpr; ++c) { base[r * cpr + c] = b; b += cnt[r * cpr + c]; }
   }
 }
+template <bool DIRECT>
 __global__ __launch_bounds__(256) void k_qs_assign(int32_t* __restrict__ slots, const int32_t* __restrict__ base,
-                                                   int32_t* __restrict__ rep, int32_t row_capacity) {
+                                                   int32_t* __restrict__ rep, int32_t row_capacity, int cols_, int cpr_) {
+  const int cols = DIRECT ? QSH_COLS : cols_, cpr = DIRECT ? QSH_CPR : cpr_;
   __shared__ int s_w[4];
-  const int r = blockIdx.x / QSH_CPR, ch = blockIdx.x % QSH_CPR;
+  const int r = blockIdx.x / cpr, ch = blockIdx.x % cpr;
   const int k0 = ch * QSH_CHUNK + (int)threadIdx.x * 8;
   int v[8], n = 0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = k0 + i < QSH_COLS ? slots[r * QSH_COLS + k0 + i] : 0; n += v[i] != 0; }
+  for (int i = 0; i < 8; ++i) { v[i] = k0 + i < cols ? slots[r * cols + k0 + i] : 0; n += v[i] != 0; }
   // exclusive scan of n over the block: inside the wave by DPP-free shuffles, across the four waves through LDS
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int inc = n;
@@ -723,16 +732,100 @@ __global__ __launch_bounds__(256) void k_qs_assign(int32_t* __restrict__ slots, 
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     if (v[i] != 0) {
-      if (off < row_capacity) { rep[off] = v[i] - 1; slots[r * QSH_COLS + k0 + i] = off + 1; }
-      else slots[r * QSH_COLS + k0 + i] = 0;    // (cannot happen with the documented capacity; never a row beyond it)
+      if (off < row_capacity) { rep[off] = v[i] - 1; slots[r * cols + k0 + i] = off + 1; }
+      else slots[r * cols + k0 + i] = 0;    // (cannot happen with the documented capacity; never a row beyond it)
       ++off;
     }
 }
-__global__ __launch_bounds__(256) void k_qs_rows(const int32_t* __restrict__ slots, int64_t T, int32_t* __restrict__ rows) {
+// rows[t][r] holds the slot of (t, r) (k_qs_mark / k_qs_hmark); n_slots = 15 regions of slots
+template <bool DIRECT>
+__global__ __launch_bounds__(256) void k_qs_rows(const int32_t* __restrict__ slots, int64_t T, int32_t* __restrict__ rows, int n_slots_) {
+  const int n_slots = DIRECT ? QSH_KEYS : n_slots_;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= T * 16) return;
   const int key = rows[idx];
-  if (key >= 0) rows[idx] = (key < QSH_KEYS ? slots[key] : 0) - 1;
+  if (key >= 0) rows[idx] = (key < n_slots ? slots[key] : 0) - 1;
+}
+
+// ---- 5b. the hashed row finder: the same shared rows for the faces of EnvComplicated (variant 1, P = 7: hand, taken, the three
+// history planes, the two prob planes) and EnvCooperation (variant 2, P = 9: + the two recent-handout planes) ----------------
+// The column of rank r is a function of (hand_r, taken_r, h0_r, h1_r, h2_r[, b1_r, b2_r], canonical (n1, n2)) -- h0 / h1 / h2 =
+// the history of (role - 1, role, role + 1), b1 / b2 = the recent handout of (role - 1, role + 1) (k_observe<1> / <2>).  Direct
+// addressing would need 15 x 5^7 x 441 = 517 M slots for variant 2, so the key is hashed instead:
+//   key   rank (4 bits) | the fields saturated at 4 (3 bits each, every field: none is dropped on the strength of a state
+//         invariant such as taken = h0 + h1 + h2 -- a corrupted or imported state must never alias two columns) | ncode (9 bits,
+//         as k_qs_mark's) -- 28 bits for variant 1, 34 for variant 2; the slot stores key + 1 (0 = empty)
+//   table one region of R = max(2048, pow2 >= 2 T) slots per rank: a rank has at most T distinct keys, so the load stays <= 1/2
+//         and a probe always ends; slot = uint64 key word + int32 value (instance + 1, the layout k_qs_count / k_qs_assign /
+//         k_qs_rows read with cols = R, cpr = R / QSH_CHUNK: R is a multiple of QSH_CHUNK, no chunk straddles two ranks)
+//   k_qs_hmark<V>   every (t, r): 64-bit mix of the key, linear probing inside rank r's region, insert by a 64-bit compare-and-
+//         swap on global memory after a plain read of the slot (a fresh deal has ~69 distinct keys for 15 T instances: the
+//         lanes of a wave hit the same few slots, most find their key by the read); the CAS winner writes the value (any
+//         instance with the key, as k_qs_mark); rows[t][r] = the slot
+// then k_qs_count / k_qs_seg / k_qs_assign / k_qs_rows exactly as for the direct table.
+// Determinism: row numbers follow SLOT order, and under collisions the slot a key lands in depends on which insert wins -- rows
+// are not numbered in key order, and the numbering may differ from call to call.  That changes no value: a row's G and D depend
+// only on its column (bit-identical for every representative) and rank, and k_fc1 computes a k-ordered chain per row whatever
+// its tile, so H0, D and q are bit-identical from call to call and between graph replay and eager issue.
+constexpr int qsh_hash_region(int64_t T) {       // R(T); T <= 2^26 (checked on the host)
+  int64_t r = QSH_CHUNK;
+  while (r < 2 * T) r <<= 1;
+  return (int)r;
+}
+__device__ __forceinline__ uint64_t qsh_mix64(uint64_t x) {   // (murmur3's 64-bit finaliser)
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+template <int V>
+__global__ __launch_bounds__(256) void k_qs_hmark(const uint8_t* __restrict__ state, int64_t T, uint64_t* __restrict__ keys,
+                                                  int32_t* __restrict__ vals, int region, int32_t* __restrict__ rows) {
+  static_assert(V == 1 || V == 2, "hashed keys: the faces of EnvComplicated and EnvCooperation");
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * 16) return;
+  const int64_t t = idx >> 4;
+  const int r = (int)(idx & 15);
+  if (r == 15) { rows[idx] = -1; return; }
+  const uint8_t* row = state + t * STATE_ROW_BYTES;
+  int role = row[DDZ_F_META * 16];
+  if (role > 2) role = 0;
+  const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
+  auto c4 = [](int v) { return v > 4 ? 4 : v; };
+  const int hand = c4(row[(DDZ_F_HAND0 + role) * 16 + r]), taken = c4(row[DDZ_F_TAKEN * 16 + r]);
+  uint64_t key = (uint64_t)r;
+  key = key << 3 | (uint64_t)hand;
+  key = key << 3 | (uint64_t)taken;
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + rm1) * 16 + r]);
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + role) * 16 + r]);
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + rp1) * 16 + r]);
+  if (V == 2) {
+    key = key << 3 | (uint64_t)c4(row[(DDZ_F_RECENT0 + rm1) * 16 + r]);
+    key = key << 3 | (uint64_t)c4(row[(DDZ_F_RECENT0 + rp1) * 16 + r]);
+  }
+  int n1 = row[(DDZ_F_HAND0 + rp1) * 16 + 15], n2 = row[(DDZ_F_HAND0 + rm1) * 16 + 15];
+  n1 = n1 > 20 ? 20 : n1; n2 = n2 > 20 ? 20 : n2;
+  {
+    int g = n1, b = n2;
+    while (b) { const int m = g % b; g = b; b = m; }
+    if (g > 1) { n1 /= g; n2 /= g; }
+  }
+  const int ncode = hand + taken >= (r < 13 ? 4 : 1) ? 0 : n1 * 21 + n2;
+  key = (key << 9 | (uint64_t)ncode) + 1;        // (stored word: 0 = empty)
+  const int64_t base = (int64_t)r * region;
+  const uint32_t mask = (uint32_t)region - 1;
+  uint32_t pos = (uint32_t)qsh_mix64(key) & mask;
+  int32_t out = -1;
+  for (int probe = 0; probe < region; ++probe, pos = (pos + 1) & mask) {
+    unsigned long long* p = (unsigned long long*)(keys + base + pos);
+    unsigned long long cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0) {
+      cur = atomicCAS(p, 0ull, (unsigned long long)key);
+      if (cur == 0) vals[base + pos] = (int32_t)idx + 1;     // the insert that won owns the value
+    }
+    if (cur == 0 || cur == key) { out = (int32_t)(base + pos); break; }
+  }
+  rows[idx] = out;                                // (-1 cannot happen at load <= 1/2; k_qs_rows leaves it -1)
 }
 
 // first layer of the distinct rows: ys[row][c] = Y[t][r][0][c] for (t, r) = rep[row] (padding rows of a segment: zeros);
@@ -743,9 +836,10 @@ __global__ __launch_bounds__(QH) void k_q_feat_rows(const float4* __restrict__ f
                                                     const float* __restrict__ bias, const int32_t* __restrict__ rep,
                                                     const int32_t* __restrict__ seg, float* __restrict__ ys, int ys_ld,
                                                     const float* __restrict__ mz, float* __restrict__ g) {
-  // ys_ld > 256 (QS_K = 288): the row's 24 COLUMN values (plane-major, then 8 zeros) are appended behind its 256 first-layer
-  // values -- the table term (linear in the face) then is 24 more rows of the rank's fc1 block: ONE K = 288 GEMM gives
-  // G[row] = Y[row] x fc1[rank] + column x Mz[rank], nothing is accumulated (mz / g: the earlier form, kept).
+  // ys_ld > 256 (256 + ceil16(4 P): 288 for P = 6 / 7, 304 for P = 9): the row's 4 P COLUMN values (plane-major, then zeros)
+  // are appended behind its 256 first-layer values -- the table term (linear in the face) then is 4 P more rows of the rank's
+  // fc1 block: ONE K = ys_ld GEMM gives G[row] = Y[row] x fc1[rank] + column x Mz[rank], nothing is accumulated (mz / g: the
+  // earlier form, kept).
   // mz / g (both or neither): the TABLE TERM folded into the rows -- the face part of conv_shunzi through fc1 is linear in the
   // face, i.e. a sum over the ranks of (column of rank r) x mz[rows p * 60 + 4 r + w] (mz f32 [P * 60][256], the operand of the
   // per-table GEMM [T, 60 P] x [60 P, 256] it replaces): g[row] = that product for the row's column and rank; the rows GEMM

@@ -133,6 +133,9 @@ import torch.nn.functional as F  # noqa: E402
 
 _CONV_CH = 256
 _FC_TILE = None
+# face planes -> face variant of the shared-rows form (FACE_PLANES' values are distinct): EnvCooperationSimplify (direct-addressed
+# row finder), EnvComplicated and EnvCooperation (hashed row finder)
+SHARED_VARIANT = {6: 3, 7: 1, 9: 2}
 
 
 def fc_tile():
@@ -221,10 +224,11 @@ class FactorisedQ:
         W2 = W1y.permute(2, 1, 0).contiguous()                         # [r, c, o]: fc1 per rank
         self.W2 = W2
         # fc1 per rank with the table term's rows appended (the shared-rows form, csrc/ddz_qnet.h section 5): a shared row
-        # carries its 24 column values behind its 256 first-layer values, so [fc1_r ; Mz[:, r] ; 0] (K = 288) gives
-        # Y x fc1_r + column x Mz_r in one product
+        # carries its 4 P column values behind its 256 first-layer values, so [fc1_r ; Mz[:, r] ; 0] (K = 256 + ceil16(4 P):
+        # 288 for P = 6 / 7, 304 for P = 9) gives Y x fc1_r + column x Mz_r in one product
+        pad = (4 * P + 15) // 16 * 16 - 4 * P
         self.W2x = torch.cat([W2, Mz[:P].permute(1, 0, 2, 3).reshape(15, P * 4, H1),
-                              torch.zeros((15, 32 - P * 4, H1), dtype=dt, device=dev)], dim=1).contiguous() if P * 4 <= 32 else None
+                              torch.zeros((15, pad, H1), dtype=dt, device=dev)], dim=1).contiguous()
         self.Wd = W2.reshape(15 * H, H1)                               # the dense GEMM's right operand: K = 15 * 256, rank-major
         # one GEMM batch per (rank, count): ranks 3..2 have counts 0..4 (65 batches), the two jokers counts 0..1
         self.W2_main = W2[:13, None].expand(13, 5, H, H1).reshape(65, H, H1).contiguous()
@@ -298,10 +302,12 @@ class FactorisedQ:
         MFMA kernel (ddz_q_fc1_rows: a library GEMM would need the sizes on the host).  The dense GEMM (a plain
         [T, 3840] x [3840, 256] product) is torch.addmm = hipBLASLt by default (gemm="torch": 148 TFLOP/s in the loop), or
         the same MFMA kernel (gemm="mfma", ddz_q_fc1_dense: 125 TFLOP/s; six geometries measured, tools/fc1_probe.py).
-        shared=True / "all" (faces of EnvCooperationSimplify only, P = 6, and `face` MUST be env's variant-3 face of its
-        current states -- the rows are keyed from env's state): the SHARED-ROWS form (csrc/ddz_qnet.h sections 5-6) -- no dense
-        GEMM: one row per distinct (rank, face column) of the batch (3.6 % of the 15 T columns at 65,536 tables), first layer +
-        ONE k_fc1 rows product over those (K = 288: the table term rides in it), H0[t] = base + the fifteen rows of table t.
+        shared=True / "all" (faces of EnvCooperationSimplify, P = 6; EnvCooperation, P = 9; EnvComplicated, P = 7 -- the face
+        variant follows from P -- and `face` MUST be env's own face of that variant of its current states: the rows are keyed
+        from env's state, not from `face`): the SHARED-ROWS form (csrc/ddz_qnet.h sections 5-6) -- no dense GEMM: one row per
+        distinct (rank, face column) of the batch (3.6 % of the 15 T columns at 65,536 tables for P = 6; the rows are found by
+        direct addressing for P = 6, by a hashed table for P = 7 / 9, section 5b), first layer + ONE k_fc1 rows product over
+        those (K = 256 + ceil16(4 P): the table term rides in it), H0[t] = base + the fifteen rows of table t.
         True: the needed rows D stay per table (their first layer skips the ranks no legal move touches); "all" (PolicyLoop's
         default): D as well once per distinct (shared row, count) -- the returned row_index is then the remapped one -- and the
         D chain runs on a side stream beside the H0 chain (self.two_streams; fork / join by events, no host synchronisation).
@@ -312,8 +318,9 @@ class FactorisedQ:
         if self._ver != self._versions():
             self.refresh()
         T, P, H, H1 = face.shape[0], self.P, self.H, self.H1
-        if shared and P != 6:
-            raise ValueError("shared=True keys the columns of EnvCooperationSimplify's six planes (face variant 3) only")
+        if shared and P not in SHARED_VARIANT:
+            raise ValueError("shared=True keys the columns of the faces of EnvComplicated, EnvCooperation and EnvCooperationSimplify "
+                             "(face variants 1 / 2 / 3: 7 / 9 / 6 planes) only")
         if tuple(face.shape[1:]) != (P, 15, 4) or T != env.T or not face.is_cuda:
             raise ValueError(f"face must be a device tensor [T,{P},15,4] of the environment's tables")
         key = ("needed", face.device, T)
@@ -342,20 +349,24 @@ class FactorisedQ:
         if shared:
             if "srows" not in w:
                 FC_TILE = fc_tile()
-                scap = (min(15 * T, 4134375) + 15 * FC_TILE + FC_TILE - 1) // FC_TILE * FC_TILE   # cannot overflow (ddz_env.h)
+                v = SHARED_VARIANT[P]
+                # distinct (rank, column) pairs: at most 15 T (and the 4,134,375 direct-addressed keys of variant 3): cannot overflow
+                most = min(15 * T, 4134375) if v == 3 else 15 * T
+                scap = (most + 15 * FC_TILE + FC_TILE - 1) // FC_TILE * FC_TILE
                 dev = face.device
-                w.update({"scap": scap, "sws": torch.zeros(E.q_shared_ws_bytes(), dtype=torch.uint8, device=dev),
+                sws = E.q_shared_ws_bytes() if v == 3 else E.q_shared_hash_ws_bytes(T)
+                w.update({"svariant": v, "scap": scap, "sws": torch.zeros(sws, dtype=torch.uint8, device=dev),
                           "srows": torch.full((T, 16), -1, dtype=torch.int32, device=dev),
                           "srep": torch.full((scap,), -1, dtype=torch.int32, device=dev),
                           "sseg": torch.zeros(40, dtype=torch.int32, device=dev),
-                          "ys": torch.zeros((scap, H + 32), dtype=torch.float32, device=dev),
+                          "ys": torch.zeros((scap, E.shared_row_width(P)), dtype=torch.float32, device=dev),
                           "g": torch.zeros((scap, H1), dtype=torch.float32, device=dev)})
                 w["y0"] = None                                                     # (1 GB at 65,536 tables: not needed in this form)
-            env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"])
+            env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"], variant=w["svariant"])
 
             def h0_chain():
                 # G[row] = Y[row] x fc1[rank] + column x Mz[rank] (the table term is linear in the face: folded into the rows --
-                # the column rides behind Y in the row, Mz[rank] behind fc1[rank] in the operand: one K = 288 product)
+                # the column rides behind Y in the row, Mz[rank] behind fc1[rank] in the operand: one K = 288 / 304 product)
                 E.q_features_rows(face, self.Wf, self.bias_f, w["srep"], w["sseg"], w["ys"])
                 E.q_fc1_rows_k(w["ys"], w["sseg"], self.W2x, w["g"])
                 E.q_gather_h0(w["g"], w["srows"], w["h0"], base=self.base)        # H0[t] = base + sum_r G[row(t, r)]
@@ -550,13 +561,13 @@ class PolicyLoop:
         self.env, self.fq = env, FactorisedQ(net)
         self.variant, self.epsilon, self.auto_reset = int(face_variant), float(epsilon), bool(auto_reset)
         self.gemm = gemm
-        # shared rows (FactorisedQ.needed(shared=True)): the default wherever it applies -- EnvCooperationSimplify faces
-        # (variant 3), whose columns ddz_q_shared_rows keys from the environment's state
-        # (True: H0 from shared rows; "all": the needed rows D shared as well -- the default)
+        # shared rows (FactorisedQ.needed(shared=True)): allowed for face variants 1, 2 and 3, whose columns ddz_q_shared_rows /
+        # ddz_q_shared_rows_hashed key from the environment's state; the default for variant 3 (EnvCooperationSimplify) only
+        # (True: H0 from shared rows; "all": the needed rows D shared as well -- variant 3's default)
         self.shared = ("all" if int(face_variant) == 3 else False) if shared is None else \
             ("all" if shared == "all" else bool(shared))
-        if self.shared and int(face_variant) != 3:
-            raise ValueError("shared rows need face variant 3")
+        if self.shared and int(face_variant) not in (1, 2, 3):
+            raise ValueError("shared rows need face variant 1, 2 or 3")
         T = env.T
         self.face = env.observe(self.variant)
         self.q = torch.zeros((T, env.slab_stride), dtype=torch.float32, device=env.device)
@@ -566,8 +577,12 @@ class PolicyLoop:
 
     def describe(self):
         if self.shared:
-            return ("ddz_q_need (the (rank, count) rows the legal moves use) + ddz_q_shared_rows (one row per DISTINCT (rank, face "
-                    "column) of the batch, direct-addressed, on the device) -> ddz_q_features_rows (first layer of the shared rows) + "
+            finder = ("ddz_q_shared_rows (one row per DISTINCT (rank, face column) of the batch, direct-addressed, on the device)"
+                      if self.variant == 3 else
+                      "ddz_q_shared_rows_hashed (one row per DISTINCT (rank, face column) of the batch, found in a hashed table "
+                      "with one open-addressed region per rank, on the device)")
+            return ("ddz_q_need (the (rank, count) rows the legal moves use) + " + finder + " -> ddz_q_features_rows (first layer "
+                    "of the shared rows) + "
                     "ddz_q_features_needed (dY of the needed rows) -> ddz_q_fc1_rows twice (G = Y x fc1[rank] over the shared rows, "
                     "D = dY x fc1[rank] over the needed rows: k_fc1, segment tables in device memory) -> H0 = table term + "
                     "ddz_q_gather_h0 (the fifteen shared rows of every table; no dense K = 3840 GEMM) -> ddz_q_slab_needed -> "
@@ -634,7 +649,8 @@ class PolicyLoop:
         for _ in range(int(n)):
             timed("need", lambda: env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"]))
             if self.shared:
-                timed("shared_rows", lambda: env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"]))
+                timed("shared_rows", lambda: env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"],
+                                                               variant=w["svariant"]))
                 timed("features_shared", lambda: E.q_features_rows(self.face, fq.Wf, fq.bias_f, w["srep"], w["sseg"], w["ys"]))
                 timed("fc1_shared", lambda: E.q_fc1_rows_k(w["ys"], w["sseg"], fq.W2x, w["g"]))
                 timed("gather_h0", lambda: E.q_gather_h0(w["g"], w["srows"], w["h0"], base=fq.base))
@@ -669,18 +685,29 @@ class PolicyLoop:
         H = fq.H
         if self.shared:
             rs, rsp = rows_shared / n, rows_shared_padded / n
+            K = E.shared_row_width(P)
+            region = 2048
+            while region < 2 * T:                                          # the hashed finder's region per rank (ddz_qnet.h 5b)
+                region *= 2
+            nslot = 15 * region
             return {
                 "need": {"us": us["need"], "kernel": "k_q_need_mask + k_q_need_scan + k_q_need_assign", "bytes": mv * 16 + T * (8 + 8 + 256),
                          "note": "list rows read, need sets written and read, row_index written"},
-                "shared_rows": {"us": us["shared_rows"], "kernel": "memset + k_qs_mark + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
-                                "bytes": T * 176 + 3 * 4134375 * 4 + T * 16 * 4 * 3 + rs * 8,
-                                "note": f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
-                                        "state read, the 16.5-MB slot table cleared / counted / assigned, rows [T,16] written"},
-                "features_shared": {"us": us["features_shared"], "kernel": "k_q_feat_rows<6>", "bytes": rs * (P * 16 + (H + 32) * 4),
-                                    "note": "first layer (count 0) of the shared rows + the table term of their columns (linear in the "
-                                            "face: folded into the rows -- no [T, 360] x [360, 256] GEMM per iteration)"},
-                "fc1_shared": {"us": us["fc1_shared"], "kernel": "k_fc1<true>", "flop": 2.0 * rs * (H + 32) * H,
-                               "note": f"G = [Y | column] x [fc1[rank] ; Mz[rank]] (K = 288) over the {rs:.0f} shared rows ({rsp:.0f} with the padding of the fifteen "
+                "shared_rows": ({"us": us["shared_rows"], "kernel": "memset + k_qs_mark + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
+                                 "bytes": T * 176 + 3 * 4134375 * 4 + T * 16 * 4 * 3 + rs * 8,
+                                 "note": f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
+                                         "state read, the 16.5-MB slot table cleared / counted / assigned, rows [T,16] written"}
+                                if self.variant == 3 else
+                                {"us": us["shared_rows"], "kernel": f"memset + k_qs_hmark<{self.variant}> + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
+                                 "bytes": T * 176 + nslot * (12 + 4 + 4) + T * 16 * 4 * 3 + rs * 8,
+                                 "note": f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
+                                         f"state read, the hashed table ({nslot} slots, {nslot * 12 / 1e6:.1f} MB) cleared / probed / counted / "
+                                         "assigned, rows [T,16] written"}),
+                "features_shared": {"us": us["features_shared"], "kernel": f"k_q_feat_rows<{P}>", "bytes": rs * (P * 16 + K * 4),
+                                    "note": f"first layer (count 0) of the shared rows + the table term of their columns (linear in the "
+                                            f"face: folded into the rows -- no [T, {60 * P}] x [{60 * P}, 256] GEMM per iteration)"},
+                "fc1_shared": {"us": us["fc1_shared"], "kernel": "k_fc1<true>", "flop": 2.0 * rs * K * H,
+                               "note": f"G = [Y | column] x [fc1[rank] ; Mz[rank]] (K = {K}) over the {rs:.0f} shared rows ({rsp:.0f} with the padding of the fifteen "
                                        f"segments) -- the dense form of the same term is 2 x {T} x 3840 x 256 = {2.0 * T * 15 * H * H / 1e9:.0f} GFLOP"},
                 "gather_h0": {"us": us["gather_h0"], "kernel": "k_qs_gather", "bytes": T * (64 + 2 * H * 4) + rs * H * 4,
                               "note": f"H0 read and written, rows [T,16] read, every row of G once ({rs * H * 4 / 1e6:.0f} MB: the fifteen "
@@ -689,7 +716,7 @@ class PolicyLoop:
                                     "bytes": T * 64 * 4 * 3 + T * 64 + rs * 16 * 3 + rn * 5, "needed_triples": rows_private / n,
                                     "note": f"one D row per distinct (shared row, count) some table needs: {rn:.0f} rows for the "
                                             f"{rows_private / n:.0f} needed (table, rank, count) triples ({rows_private / n / T:.2f} per table)"},
-                    "features": {"us": us["features"], "kernel": "k_q_feat_drows<6>", "bytes": rn * (P * 16 + H * 4 + 8),
+                    "features": {"us": us["features"], "kernel": f"k_q_feat_drows<{P}>", "bytes": rn * (P * 16 + H * 4 + 8),
                                  "note": "dY of the shared D rows"}} if self.shared == "all" else
                    {"features": {"us": us["features"], "kernel": f"k_q_feat_needed<{P}> (y0 = null)", "bytes": T * P * 240 + rn * H * 4 + T * 256,
                                  "note": "face + row_index read, dY [needed rows, 256] written; ranks no legal move touches are skipped"}}),

@@ -269,15 +269,21 @@ class BatchedEnv:
         check(self.lib.ddz_q_need(self._h, self._pp["counts"], self._pp["rows"], self.slab_stride, int(row_capacity),
                                   _p(scratch), scratch.numel(), _p(row_index), _p(seg), _p(row_cnt), _stream(self.device)))
 
-    def q_shared_rows(self, ws, row_capacity, rows, rep, seg):
-        """ddz_q_shared_rows: one row per DISTINCT (rank, face column) of the CURRENT states (EnvCooperationSimplify faces):
-        rows int32 [T,16] (row of (t, r)), rep int32 [row_capacity] (row -> instance 16 t + r), seg int32 [40] (rank segments);
-        ws uint8 [q_shared_ws_bytes()].  Nothing crosses to the host."""
+    def q_shared_rows(self, ws, row_capacity, rows, rep, seg, variant=3):
+        """ddz_q_shared_rows: one row per DISTINCT (rank, face column) of the CURRENT states for the faces of `variant`:
+        rows int32 [T,16] (row of (t, r)), rep int32 [row_capacity] (row -> instance 16 t + r), seg int32 [40] (rank segments).
+        variant 3 (EnvCooperationSimplify): direct-addressed, ws uint8 [q_shared_ws_bytes()]; variants 1 / 2 (EnvComplicated /
+        EnvCooperation): ddz_q_shared_rows_hashed, ws uint8 [q_shared_hash_ws_bytes(T)], row_capacity >= 15 T + 15 tiles (any
+        other variant: DdzError).  Nothing crosses to the host."""
         if (rows.dtype != torch.int32 or tuple(rows.shape) != (self.T, 16) or not rows.is_contiguous() or rep.dtype != torch.int32
                 or rep.numel() < int(row_capacity) or seg.dtype != torch.int32 or seg.numel() < 40 or ws.dtype != torch.uint8):
             raise ValueError("rows must be int32 [T,16], rep int32 [row_capacity], seg int32 [40], ws uint8")
-        check(self.lib.ddz_q_shared_rows(self._h, _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep), _p(seg),
-                                         _stream(self.device)))
+        if int(variant) == 3:
+            check(self.lib.ddz_q_shared_rows(self._h, _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep), _p(seg),
+                                             _stream(self.device)))
+        else:
+            check(self.lib.ddz_q_shared_rows_hashed(self._h, int(variant), _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep),
+                                                    _p(seg), _stream(self.device)))
 
     def q_shared_need(self, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
         """ddz_q_shared_need: one D row per distinct (shared row, count) some table needs: row_index2 int32 [T,64], drep int32
@@ -626,17 +632,35 @@ def q_shared_ws_bytes():
     return int(_lib.lib().ddz_q_shared_ws_bytes())
 
 
+def q_shared_hash_ws_bytes(n_tables):
+    """workspace of the hashed row finder (BatchedEnv.q_shared_rows with variant 1 / 2) for n_tables tables"""
+    n = int(_lib.lib().ddz_q_shared_hash_ws_bytes(int(n_tables)))
+    if n < 0:
+        raise ValueError("n_tables must be in 1 .. 2^26")
+    return n
+
+
+SHARED_PLANES = (6, 7, 9)    # the faces the shared-rows form keys: EnvCooperationSimplify, EnvComplicated, EnvCooperation
+
+
+def shared_row_width(planes):
+    """ys row width of the shared-rows form: 256 first-layer values + the 4 P column values, padded to a multiple of 16"""
+    return 256 + (4 * int(planes) + 15) // 16 * 16
+
+
 def q_features_rows(face, wf, bias, rep, seg, ys, mz=None, g=None):
     """ddz_q_features_rows: ys f32 [rows,256] = the first layer (count 0) of the face column of every shared row (rep: row ->
-    instance 16 t + r, from BatchedEnv.q_shared_rows); face f32 [T,6,15,4]."""
+    instance 16 t + r, from BatchedEnv.q_shared_rows); face f32 [T,P,15,4], P = 6, 7 or 9; ys [rows, shared_row_width(P)]:
+    + the row's column values behind the 256."""
     L = _lib.lib()
     dev = _require_gpu(face.device)
     T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or tuple(face.shape[1:]) != (6, 15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,6,15,4] tensor (EnvCooperationSimplify)")
+    if face.dtype != torch.float32 or P not in SHARED_PLANES or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
+        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor, P = 6, 7 or 9 (the faces the shared rows key)")
     n = int(ys.shape[0])
-    if ys.dtype != torch.float32 or ys.dim() != 2 or ys.shape[1] not in (256, 288) or not ys.is_contiguous() or ys.device != dev:
-        raise ValueError("ys must be a contiguous float32 [rows,256] (or [rows,288]: + the column values) tensor on the same device")
+    w_ = shared_row_width(P)
+    if ys.dtype != torch.float32 or ys.dim() != 2 or ys.shape[1] not in (256, w_) or not ys.is_contiguous() or ys.device != dev:
+        raise ValueError(f"ys must be a contiguous float32 [rows,256] (or [rows,{w_}]: + the column values) tensor on the same device")
     if rep.dtype != torch.int32 or rep.numel() < n or rep.device != dev or seg.dtype != torch.int32 or seg.numel() < 40 or seg.device != dev:
         raise ValueError("rep must be int32 [rows], seg int32 [40], on the same device")
     for w, k in ((wf, P * 4 * 1024), (bias, 1024)):
@@ -676,12 +700,12 @@ def q_shared_need_ws_bytes(shared_row_capacity):
 
 def q_features_drows(face, wf, bias, acnt, rep, drep, dseg, dy):
     """ddz_q_features_drows: dy f32 [rows,256] = Y[c] - Y[0] of the column of every shared D row (drep: D row -> 4 * shared row
-    + c - 1, rep: shared row -> instance; from BatchedEnv.q_shared_need / q_shared_rows); face f32 [T,6,15,4]."""
+    + c - 1, rep: shared row -> instance; from BatchedEnv.q_shared_need / q_shared_rows); face f32 [T,P,15,4], P = 6, 7 or 9."""
     L = _lib.lib()
     dev = _require_gpu(face.device)
     T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or tuple(face.shape[1:]) != (6, 15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,6,15,4] tensor (EnvCooperationSimplify)")
+    if face.dtype != torch.float32 or P not in SHARED_PLANES or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
+        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor, P = 6, 7 or 9 (the faces the shared rows key)")
     n = int(dy.shape[0])
     if dy.dtype != torch.float32 or dy.dim() != 2 or dy.shape[1] != 256 or not dy.is_contiguous() or dy.device != dev:
         raise ValueError("dy must be a contiguous float32 [rows,256] tensor on the same device")

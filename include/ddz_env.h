@@ -314,8 +314,18 @@ int ddz_q_slab_needed(ddz_env_t* env, const float* h0, const float* d, int64_t r
  *   segments, starts multiples of the tile).  row_capacity: a multiple of the tile, >= min(15 T, 4134375) + 15 tiles (then
  *   nothing can overflow).  ws: ddz_q_shared_ws_bytes() bytes (16.6 MB: one int32 slot per possible (rank, column)), 16-byte
  *   aligned, contents irrelevant on entry.  Row numbers follow the key order: deterministic.
- * ddz_q_features_rows: ys f32 [row_capacity][ys_ld] (ys_ld 256 or 288) = first layer (count 0) of every row's column, read from `face` f32
- *   [T][6][15][4] at rep[row]; padding rows = 0.  planes must be 6.
+ * ddz_q_shared_rows_hashed: the same outputs for the faces of EnvComplicated (variant 1, 7 planes: hand, taken, the three
+ *   history planes, the two prob planes) and EnvCooperation (variant 2, 9 planes: + the two recent-handout planes), whose
+ *   columns are too many to address directly (517 M for variant 2): the key (rank, hand_r, taken_r, the three history counts
+ *   of rank r[, the two recent-handout counts], each saturated at 4, and the canonical (n1, n2) as above) is hashed into an
+ *   open-addressed table with one region per rank (ddz_qnet.h section 5b).  variant must be 1 or 2 (else DDZ_EINVAL).
+ *   row_capacity: a multiple of the tile, >= 15 T + 15 tiles (else DDZ_ECAP).  ws: ddz_q_shared_hash_ws_bytes(T) bytes
+ *   (12 bytes per slot, 15 regions of max(2048, pow2 >= 2 T) slots: 23.6 MB at 65,536 tables), 16-byte aligned, contents
+ *   irrelevant on entry.  Row numbers follow the slot order, which under hash collisions depends on which insert wins: the
+ *   numbering is NOT deterministic, the values computed from it are (a row's G and D depend only on its column and rank).
+ * ddz_q_features_rows: ys f32 [row_capacity][ys_ld] (ys_ld 256, or 256 + ceil16(4 planes): 288 for 6 / 7 planes, 304 for 9) =
+ *   first layer (count 0) of every row's column, read from `face` f32 [T][planes][15][4] at rep[row]; padding rows = 0.  planes
+ *   must be 6, 7 or 9 (the faces whose columns ddz_q_shared_rows / ddz_q_shared_rows_hashed key).
  * ddz_q_gather_h0: h0 f32 [T][256] += sum over r = 0..14 (in this order) of g[rows[t][r]] (g f32 [g_rows][256]; rows < 0 or
  *   >= g_rows contribute nothing).
  * ddz_q_features_needed with y0 = NULL then evaluates only the ranks a legal move takes cards of (dy alone). */
@@ -327,7 +337,7 @@ int ddz_q_slab_needed(ddz_env_t* env, const float* h0, const float* d, int64_t r
  *   row_cnt uint8 [row_capacity] (c of every D row, for ddz_q_fc1_rows' z fold).  row_capacity as ddz_q_need's (distinct
  *   pairs never outnumber the needed triples).  ws: ddz_q_shared_need_ws_bytes(shared_row_capacity) bytes, 16-byte aligned.
  * ddz_q_features_drows: dy f32 [row_capacity][256] = Y[c] - Y[0] of every D row's column (face read at the shared row's
- *   representative rep[]); padding rows = 0.  planes must be 6. */
+ *   representative rep[]); padding rows = 0.  planes must be 6, 7 or 9. */
 int64_t ddz_q_shared_need_ws_bytes(int64_t shared_row_capacity);
 int ddz_q_shared_need(ddz_env_t* env, const int32_t* row_index, const int32_t* rows, const int32_t* sseg,
                       int64_t shared_row_capacity, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* row_index2,
@@ -338,6 +348,9 @@ int ddz_q_features_drows(int device_id, const float* face, int64_t n_tables, int
 int64_t ddz_q_shared_ws_bytes(void);
 int ddz_q_shared_rows(ddz_env_t* env, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* rows, int32_t* rep,
                       int32_t* seg, void* stream);
+int64_t ddz_q_shared_hash_ws_bytes(int64_t n_tables);
+int ddz_q_shared_rows_hashed(ddz_env_t* env, int variant, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* rows,
+                             int32_t* rep, int32_t* seg, void* stream);
 int ddz_q_features_rows(int device_id, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                         const int32_t* rep, const int32_t* seg, float* ys, int64_t ys_ld, int64_t row_capacity, const float* mz,
                         float* g, void* stream);
