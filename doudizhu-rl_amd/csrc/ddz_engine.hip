@@ -3679,6 +3679,199 @@ int ddz_q_slab_needed(ddz_env_t* e, const float* h0, const float* d, int64_t row
   return check_launch();
 }
 
+// per-role networks (ddz_qnet.h section 7): every buffer holds n_nets slot-major partitions of row_capacity rows, seg / dseg
+// n_nets blocks of QN_SEG_WORDS ints in the single-network layout, relative to the slot's partition
+static bool roles_ok(int n_nets) { return n_nets >= 1 && n_nets <= 3; }
+int64_t ddz_q_roles_ws_bytes(int64_t n_tables, int variant, int n_nets) {
+  if (!roles_ok(n_nets) || n_tables <= 0 || n_tables > ((int64_t)1 << 26)) return DDZ_EINVAL;
+  if (variant == 3) return (int64_t)n_nets * QSH_WS_INTS * 4;        // slots [N][15 * QSH_COLS] | cnt [N][15][cpr] | base [N][15][cpr]
+  if (variant != 1 && variant != 2) return DDZ_EINVAL;
+  const int64_t R = qsh_hash_region(n_tables), cpr = R / QSH_CHUNK;
+  return n_nets * (15 * R * 12 + 2 * 15 * cpr * 4);                // keys u64 [N][15 R] | vals i32 [N][15 R] | cnt | base
+}
+int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int n_nets, void* ws, int64_t ws_bytes, int64_t row_capacity,
+                     int32_t* rows, int32_t* rep, int32_t* seg, int8_t* slot, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!roles_ok(n_nets) || !net_of_role || (variant != 1 && variant != 2 && variant != 3)) return DDZ_EINVAL;
+  uint32_t map = 0;
+  bool used[3] = {false, false, false};
+  for (int k = 0; k < 3; ++k) {
+    if (net_of_role[k] < -1 || net_of_role[k] >= n_nets) return DDZ_EINVAL;
+    if (net_of_role[k] >= 0) used[net_of_role[k]] = true;
+    map |= (uint32_t)(net_of_role[k] + 1) << (8 * k);
+  }
+  for (int s = 0; s < n_nets; ++s)
+    if (!used[s]) return DDZ_EINVAL;                                 // (every slot belongs to a role)
+  if (!ws || !rows || !rep || !seg || !slot || !al(ws, 16) || !al(rows, 16) || !al(rep, 4) || !al(seg, 4)) return DDZ_EINVAL;
+  if (e->T > ((int64_t)1 << 26) || ws_bytes < ddz_q_roles_ws_bytes(e->T, variant, n_nets) || row_capacity % FC_M) return DDZ_ECAP;
+  const int64_t most = variant == 3 && e->T * 15 > (int64_t)QSH_KEYS ? (int64_t)QSH_KEYS : e->T * 15;
+  if (row_capacity < most + 15 * FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb = (unsigned)((e->T * 16 + 255) / 256);
+  if (hipMemsetAsync(rep, 0xFF, (size_t)(n_nets * row_capacity) * 4, st) != hipSuccess) return DDZ_EHIP;
+  if (variant == 3) {
+    int32_t* slots = (int32_t*)ws;
+    int32_t* cnt = slots + (int64_t)n_nets * QSH_KEYS;
+    int32_t* base = cnt + n_nets * 15 * QSH_CPR;
+    if (hipMemsetAsync(slots, 0, (size_t)n_nets * QSH_KEYS * 4, st) != hipSuccess) return DDZ_EHIP;
+    hipLaunchKernelGGL(k_qs_mark_roles, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, slots, rows, slot);
+    for (int s = 0; s < n_nets; ++s) {
+      int32_t* sl = slots + (int64_t)s * QSH_KEYS;
+      int32_t *c = cnt + s * 15 * QSH_CPR, *b = base + s * 15 * QSH_CPR;
+      hipLaunchKernelGGL(k_qs_count<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, (const int32_t*)sl, c, QSH_COLS, QSH_CPR);
+      hipLaunchKernelGGL(k_qs_seg<true>, dim3(1), dim3(64), 0, st, (const int32_t*)c, b, seg + s * QN_SEG_WORDS, (int32_t)row_capacity,
+                         QSH_CPR);
+      hipLaunchKernelGGL(k_qs_assign<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, sl, (const int32_t*)b, rep + s * row_capacity,
+                         (int32_t)row_capacity, QSH_COLS, QSH_CPR);
+    }
+    hipLaunchKernelGGL(k_qs_rows_roles, dim3(nb), dim3(256), 0, st, (const int32_t*)slots, e->T, rows, (int64_t)QSH_KEYS, n_nets,
+                       row_capacity);
+  } else {
+    const int R = qsh_hash_region(e->T), cpr = R / QSH_CHUNK;
+    uint64_t* keys = (uint64_t*)ws;
+    int32_t* vals = (int32_t*)(keys + (int64_t)n_nets * 15 * R);
+    int32_t* cnt = vals + (int64_t)n_nets * 15 * R;
+    int32_t* base = cnt + n_nets * 15 * cpr;
+    if (hipMemsetAsync(keys, 0, (size_t)n_nets * 15 * R * 12, st) != hipSuccess) return DDZ_EHIP;   // keys and values: one clear
+    if (variant == 1)
+      hipLaunchKernelGGL(k_qs_hmark_roles<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
+    else
+      hipLaunchKernelGGL(k_qs_hmark_roles<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
+    for (int s = 0; s < n_nets; ++s) {
+      int32_t* v = vals + (int64_t)s * 15 * R;
+      int32_t *c = cnt + s * 15 * cpr, *b = base + s * 15 * cpr;
+      hipLaunchKernelGGL(k_qs_count<false>, dim3(15 * cpr), dim3(256), 0, st, (const int32_t*)v, c, R, cpr);
+      hipLaunchKernelGGL(k_qs_seg<false>, dim3(1), dim3(64), 0, st, (const int32_t*)c, b, seg + s * QN_SEG_WORDS, (int32_t)row_capacity, cpr);
+      hipLaunchKernelGGL(k_qs_assign<false>, dim3(15 * cpr), dim3(256), 0, st, v, (const int32_t*)b, rep + s * row_capacity,
+                         (int32_t)row_capacity, R, cpr);
+    }
+    hipLaunchKernelGGL(k_qs_rows_roles, dim3(nb), dim3(256), 0, st, (const int32_t*)vals, e->T, rows, (int64_t)15 * R, n_nets, row_capacity);
+  }
+  return check_launch();
+}
+int ddz_q_roles_features_rows(int device, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf, const float* bias,
+                              const int32_t* rep, const int32_t* seg, float* ys, int64_t ys_ld, int64_t row_capacity, void* stream) {
+  if (!roles_ok(n_nets) || !face || !wf || !bias || !rep || !seg || !ys || n_tables <= 0) return DDZ_EINVAL;
+  if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
+  if (ys_ld != QH && ys_ld != QH + (4 * planes + 15) / 16 * 16) return DDZ_EINVAL;
+  if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(rep, 4) || !al(seg, 4) || !al(ys, 4)) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / ys_ld || n_tables > ((int64_t)1 << 26))
+    return DDZ_ECAP;
+  for (int s = 0; s < n_nets; ++s) {
+    const int rc = ddz_q_features_rows(device, face, n_tables, planes, wf + (int64_t)s * planes * 4 * 4 * QH, bias + s * 4 * QH,
+                                       rep + s * row_capacity, seg + s * QN_SEG_WORDS, ys + s * row_capacity * ys_ld, ys_ld, row_capacity,
+                                       nullptr, nullptr, stream);
+    if (rc) return rc;
+  }
+  return DDZ_OK;
+}
+int ddz_q_roles_fc1_rows_k(int device, int n_nets, const float* y, int64_t k, const int32_t* seg, const float* w2k, float* g,
+                           int64_t row_capacity, void* stream) {
+  if (!roles_ok(n_nets) || !y || !seg || !w2k || !g) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
+  if (n_nets * row_capacity > (((int64_t)1 << 31) - 1) / (k > QH ? k : QH)) return DDZ_ECAP;
+  for (int s = 0; s < n_nets; ++s) {
+    const int rc = ddz_q_fc1_rows_k(device, y + s * row_capacity * k, k, seg + s * QN_SEG_WORDS, w2k + (int64_t)s * 15 * k * QH,
+                                    g + s * row_capacity * QH, row_capacity, 0, stream);
+    if (rc) return rc;
+  }
+  return DDZ_OK;
+}
+int ddz_q_roles_gather_h0(int device, int n_nets, const float* g, int64_t g_rows, const int32_t* rows, const int8_t* slot, int64_t n_tables,
+                          const float* base, float* h0, void* stream) {
+  if (!roles_ok(n_nets) || !g || !rows || !slot || !base || !h0 || n_tables <= 0 || g_rows <= 0) return DDZ_EINVAL;
+  if (!al(g, 16) || !al(rows, 16) || !al(h0, 16) || !al(base, 16)) return DDZ_EINVAL;
+  DeviceGuard gd(device);
+  if (!gd.ok) return DDZ_ENODEV;
+  hipLaunchKernelGGL(k_qs_gather_roles, dim3((unsigned)((n_tables + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)g, g_rows,
+                     rows, slot, n_nets, n_tables, (float4*)h0, (const float4*)base);
+  return check_launch();
+}
+int64_t ddz_q_roles_need_ws_bytes(int64_t shared_row_capacity, int n_nets) {
+  if (!roles_ok(n_nets)) return DDZ_EINVAL;
+  const int64_t one = ddz_q_shared_need_ws_bytes(shared_row_capacity);
+  return one < 0 ? one : n_nets * one;                             // dslot [N][scap][4] | cnt [N][tiles] | base [N][tiles]
+}
+int ddz_q_roles_need(ddz_env_t* e, int n_nets, const int32_t* row_index, const int32_t* rows, const int32_t* sseg,
+                     int64_t shared_row_capacity, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* row_index2, int32_t* drep,
+                     int32_t* dseg, uint8_t* row_cnt, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!roles_ok(n_nets) || !row_index || !rows || !sseg || !ws || !row_index2 || !drep || !dseg || !row_cnt) return DDZ_EINVAL;
+  if (!al(row_index, 4) || !al(rows, 4) || !al(sseg, 4) || !al(ws, 16) || !al(row_index2, 4) || !al(drep, 4) || !al(dseg, 4)) return DDZ_EINVAL;
+  if (shared_row_capacity <= 0 || shared_row_capacity % FC_M || n_nets * shared_row_capacity > ((int64_t)1 << 28)) return DDZ_ECAP;
+  if (ws_bytes < ddz_q_roles_need_ws_bytes(shared_row_capacity, n_nets)) return DDZ_ECAP;
+  if (row_capacity < 15 * FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t tiles = shared_row_capacity / FC_M, S = n_nets * shared_row_capacity;
+  int32_t* dslot = (int32_t*)ws;
+  int32_t* cnt = dslot + S * 4;
+  int32_t* base = cnt + n_nets * tiles;
+  if (hipMemsetAsync(dslot, 0, (size_t)S * 16, st) != hipSuccess) return DDZ_EHIP;
+  if (hipMemsetAsync(drep, 0xFF, (size_t)(n_nets * row_capacity) * 4, st) != hipSuccess) return DDZ_EHIP;
+  const unsigned nb = (unsigned)((e->T * QP_COLS + 255) / 256);
+  hipLaunchKernelGGL(k_qd_mark, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, dslot, S);   // (rule tables: rows < 0, no mark)
+  for (int s = 0; s < n_nets; ++s) {
+    int32_t* ds = dslot + s * shared_row_capacity * 4;
+    const int32_t* ss = sseg + s * QN_SEG_WORDS;
+    int32_t *c = cnt + s * tiles, *b = base + s * tiles;
+    hipLaunchKernelGGL(k_qd_count, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)ds, ss, c);
+    hipLaunchKernelGGL(k_qd_seg, dim3(1), dim3(64), 0, st, (const int32_t*)c, ss, b, dseg + s * QN_SEG_WORDS, (int32_t)row_capacity,
+                       e->sc.status);
+    hipLaunchKernelGGL(k_qd_assign, dim3((unsigned)tiles), dim3(256), 0, st, ds, ss, (const int32_t*)b, drep + s * row_capacity,
+                       row_cnt + s * row_capacity, (int32_t)row_capacity);
+  }
+  hipLaunchKernelGGL(k_qd_remap_roles, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, (const int32_t*)dslot, shared_row_capacity, n_nets,
+                     row_capacity, row_index2);
+  return check_launch();
+}
+int ddz_q_roles_features_drows(int device, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf, const float* bias,
+                               const float* acnt, const int32_t* rep, int64_t shared_row_capacity, const int32_t* drep, const int32_t* dseg,
+                               float* dy, int64_t row_capacity, void* stream) {
+  if (!roles_ok(n_nets) || !wf || !bias || !acnt || !rep || !drep || !dseg || !dy) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  for (int s = 0; s < n_nets; ++s) {
+    const int rc = ddz_q_features_drows(device, face, n_tables, planes, wf + (int64_t)s * planes * 4 * 4 * QH, bias + s * 4 * QH,
+                                        acnt + s * 5 * 4 * QH, rep + s * shared_row_capacity, shared_row_capacity, drep + s * row_capacity,
+                                        dseg + s * QN_SEG_WORDS, dy + s * row_capacity * QH, row_capacity, stream);
+    if (rc) return rc;
+  }
+  return DDZ_OK;
+}
+int ddz_q_roles_fc1_rows(int device, int n_nets, const float* dy, const int32_t* seg, const uint8_t* row_cnt, const float* w2, const float* z,
+                         float* d, int64_t row_capacity, void* stream) {
+  if (!roles_ok(n_nets) || !dy || !seg || !row_cnt || !w2 || !z || !d) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
+  if (n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  for (int s = 0; s < n_nets; ++s) {
+    const int rc = ddz_q_fc1_rows(device, dy + s * row_capacity * QH, seg + s * QN_SEG_WORDS, row_cnt + s * row_capacity,
+                                  w2 + (int64_t)s * 15 * QH * QH, z + s * 15 * 5 * QH, d + s * row_capacity * QH, row_capacity, stream);
+    if (rc) return rc;
+  }
+  return DDZ_OK;
+}
+int ddz_q_roles_slab(ddz_env_t* e, int n_nets, const int8_t* slot, const float* h0, const float* d, int64_t d_rows, const int32_t* row_index,
+                     int64_t hidden, const float* w2, const float* b2, const int32_t* counts, const int8_t* rows, int64_t stride, float* q,
+                     void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!al(h0, 16) || !al(d, 16) || !al(w2, 16) || !al(b2, 4) || !al(counts, 4) || !al(rows, 16) || !al(q, 4) || !al(row_index, 4))
+    return DDZ_EINVAL;
+  if (!roles_ok(n_nets) || !slot || !h0 || !d || !w2 || !b2 || !counts || !rows || !q || !row_index || hidden != QH || stride < 1 || d_rows < 1)
+    return DDZ_EINVAL;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  int64_t v = (e->T + 4095) / 4096;                                // (the geometry of ddz_q_slab_needed)
+  const int tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
+  const int64_t per_block = (int64_t)WPB * tpw;
+  hipLaunchKernelGGL(k_q_slab_roles, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
+                     (const float4*)h0, (const float4*)d, d_rows, e->T, tpw, (const float4*)w2, b2, slot, counts, (const uint4*)rows,
+                     stride, q, row_index, e->sc.status);
+  return check_launch();
+}
+
 int ddz_action_table(int device, int8_t* rows, void* stream) {
   if (!al(rows, 16)) return DDZ_EINVAL;
   if (!rows) return DDZ_EINVAL;

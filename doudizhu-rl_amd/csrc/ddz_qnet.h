@@ -1083,3 +1083,294 @@ __global__ __launch_bounds__(QH) void k_q_feat_drows(const float4* __restrict__ 
     dy[(row0 + j) * QH + ch] = out;
   }
 }
+
+// ---- 7. per-role networks: the shared rows keyed by (network slot, rank) --------------------------------------------------------
+// The reference's Game (game.py:11-43) gives every role its own network, or the rule agent.  A role map net_of_role[3] (role order
+// 0 up, 1 lord, 2 down) names a network SLOT 0..N-1 (N <= 3, weights stacked slot-major) or -1 (the rule agent); table t belongs
+// to slot tslot[t] = net_of_role[role of its actor] (int8 [T], -1: a rule table).  Every buffer of sections 5-6 is split into
+// N slot-major PARTITIONS of a fixed capacity: slot s owns rows [s * cap, (s + 1) * cap) of the shared rows (cap >= 15 T + 15
+// tiles, or the direct table's keys + 15 tiles) and of the D rows (cap as ddz_q_need's), and its own 40-word segment table
+// seg[s * 40 ..] in TODAY'S LAYOUT, relative to its partition -- a one-slot pass gives exactly the single-network words.  So the
+// count / segment / assign kernels, the first-layer kernels and k_fc1<true> run UNCHANGED once per slot on the slot's
+// partition and weights (the k-ordered MFMA chain of a row does not depend on the slot); the kernels below are the ones that
+// see all tables at once:
+//   k_qs_mark_roles / k_qs_hmark_roles<V>   the finder's key with the slot in front: region slot * 15 + rank; a rule table
+//            inserts nothing and gets rows[t][*] = -1 (then no D row either: k_qd_mark skips rows < 0)
+//   k_qs_rows_roles   rows[t][r] = s * cap + the row the slot's k_qs_assign gave its key
+//   k_qs_gather_roles H0[t] = base[slot] + sum_r G[rows[t][r]] (rank order, as k_qs_gather); rule tables are left alone
+//   k_qd_remap_roles  row_index2[t][col] = s * dcap + the slot's D row of (rows[t][r], c)
+//   k_q_slab_roles    the row stage with the slot's w2 / b2; rule tables are left alone
+// the keys of k_qs_mark / k_qs_hmark: the same expressions, copied -- k_qs_mark and k_qs_hmark<V> calling these helpers compile
+// to different gfx950 code (instruction order), and the single-network kernels keep theirs.  A change to a key goes into both;
+// tests/test_gpu_seat_q.py pins the copies: the variant-3 rows of a one-slot map word for word against k_qs_mark's, the
+// variant-1 / 2 keys against the same CPU restatement that tests/test_gpu_shared_rows_cooperation.py holds k_qs_hmark to
+// the direct-addressed key of instance (t, r < 15): rank r's region, then the column code
+__device__ __forceinline__ int qsh_direct_key(const uint8_t* __restrict__ row, int r) {
+  int role = row[DDZ_F_META * 16];
+  if (role > 2) role = 0;
+  const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
+  auto c4 = [](int v) { return v > 4 ? 4 : v; };   // (a thermometer saturates at 4; never index outside on a corrupted import)
+  const int hand = c4(row[(DDZ_F_HAND0 + role) * 16 + r]), taken = c4(row[DDZ_F_TAKEN * 16 + r]);
+  const int b1 = c4(row[(DDZ_F_RECENT0 + rm1) * 16 + r]), b2 = c4(row[(DDZ_F_RECENT0 + rp1) * 16 + r]);
+  int n1 = row[(DDZ_F_HAND0 + rp1) * 16 + 15], n2 = row[(DDZ_F_HAND0 + rm1) * 16 + 15];
+  n1 = n1 > 20 ? 20 : n1; n2 = n2 > 20 ? 20 : n2;
+  // canonical (n1, n2): the prob planes hold n / (n1 + n2) -- the same float for (2, 4) and (1, 2) (one correctly rounded
+  // division of the same rational) -- and only in the slots known <= j < total: none when hand + taken >= total.  Halves the
+  // distinct rows (measured on the oracle's states: 86,689 -> 43,232 at 65,536 tables).
+  {
+    int g = n1, b = n2;
+    while (b) { const int m = g % b; g = b; b = m; }
+    if (g > 1) { n1 /= g; n2 /= g; }
+  }
+  const int ncode = hand + taken >= (r < 13 ? 4 : 1) ? 0 : n1 * 21 + n2;
+  return r * QSH_COLS + (((hand * 5 + taken) * 5 + b1) * 5 + b2) * 441 + ncode;
+}
+// the stored key word (key + 1) of instance (t, r < 15) of the hashed table
+template <int V>
+__device__ __forceinline__ uint64_t qsh_hash_key(const uint8_t* __restrict__ row, int r) {
+  static_assert(V == 1 || V == 2, "hashed keys: the faces of EnvComplicated and EnvCooperation");
+  int role = row[DDZ_F_META * 16];
+  if (role > 2) role = 0;
+  const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
+  auto c4 = [](int v) { return v > 4 ? 4 : v; };
+  const int hand = c4(row[(DDZ_F_HAND0 + role) * 16 + r]), taken = c4(row[DDZ_F_TAKEN * 16 + r]);
+  uint64_t key = (uint64_t)r;
+  key = key << 3 | (uint64_t)hand;
+  key = key << 3 | (uint64_t)taken;
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + rm1) * 16 + r]);
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + role) * 16 + r]);
+  key = key << 3 | (uint64_t)c4(row[(DDZ_F_HIST0 + rp1) * 16 + r]);
+  if (V == 2) {
+    key = key << 3 | (uint64_t)c4(row[(DDZ_F_RECENT0 + rm1) * 16 + r]);
+    key = key << 3 | (uint64_t)c4(row[(DDZ_F_RECENT0 + rp1) * 16 + r]);
+  }
+  int n1 = row[(DDZ_F_HAND0 + rp1) * 16 + 15], n2 = row[(DDZ_F_HAND0 + rm1) * 16 + 15];
+  n1 = n1 > 20 ? 20 : n1; n2 = n2 > 20 ? 20 : n2;
+  {
+    int g = n1, b = n2;
+    while (b) { const int m = g % b; g = b; b = m; }
+    if (g > 1) { n1 /= g; n2 /= g; }
+  }
+  const int ncode = hand + taken >= (r < 13 ? 4 : 1) ? 0 : n1 * 21 + n2;
+  return (key << 9 | (uint64_t)ncode) + 1;        // (stored word: 0 = empty)
+}
+// insert / find `key` in the region of `region` slots at keys + base: the slot (absolute), -1 if the region is full
+__device__ __forceinline__ int32_t qsh_probe(uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int64_t base, int region,
+                                             uint64_t key, int32_t val) {
+  const uint32_t mask = (uint32_t)region - 1;
+  uint32_t pos = (uint32_t)qsh_mix64(key) & mask;
+  int32_t out = -1;
+  for (int probe = 0; probe < region; ++probe, pos = (pos + 1) & mask) {
+    unsigned long long* p = (unsigned long long*)(keys + base + pos);
+    unsigned long long cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0) {
+      cur = atomicCAS(p, 0ull, (unsigned long long)key);
+      if (cur == 0) vals[base + pos] = val;         // the insert that won owns the value
+    }
+    if (cur == 0 || cur == key) { out = (int32_t)(base + pos); break; }
+  }
+  return out;
+}
+__device__ __forceinline__ int qsh_slot_of(const uint8_t* __restrict__ row, uint32_t map) {   // map: byte k = slot of role k + 1
+  int role = row[DDZ_F_META * 16];
+  if (role > 2) role = 0;
+  return (int)((map >> (8 * role)) & 0xFFu) - 1;
+}
+__global__ __launch_bounds__(256) void k_qs_mark_roles(const uint8_t* __restrict__ state, int64_t T, uint32_t map,
+                                                       int32_t* __restrict__ slots, int32_t* __restrict__ rows,
+                                                       int8_t* __restrict__ tslot) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * 16) return;
+  const int64_t t = idx >> 4;
+  const int r = (int)(idx & 15);
+  const uint8_t* row = state + t * STATE_ROW_BYTES;
+  const int sl = qsh_slot_of(row, map);
+  if (r == 15) { rows[idx] = -1; tslot[t] = (int8_t)sl; return; }
+  if (sl < 0) { rows[idx] = -1; return; }
+  const int key = sl * QSH_KEYS + qsh_direct_key(row, r);
+  slots[key] = (int32_t)idx + 1;
+  rows[idx] = key;
+}
+template <int V>
+__global__ __launch_bounds__(256) void k_qs_hmark_roles(const uint8_t* __restrict__ state, int64_t T, uint32_t map,
+                                                        uint64_t* __restrict__ keys, int32_t* __restrict__ vals, int region,
+                                                        int32_t* __restrict__ rows, int8_t* __restrict__ tslot) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * 16) return;
+  const int64_t t = idx >> 4;
+  const int r = (int)(idx & 15);
+  const uint8_t* row = state + t * STATE_ROW_BYTES;
+  const int sl = qsh_slot_of(row, map);
+  if (r == 15) { rows[idx] = -1; tslot[t] = (int8_t)sl; return; }
+  if (sl < 0) { rows[idx] = -1; return; }
+  rows[idx] = qsh_probe(keys, vals, (int64_t)(sl * 15 + r) * region, region, qsh_hash_key<V>(row, r), (int32_t)idx + 1);
+}
+// rows[t][r] holds the slot's key index (any slot: slot s's keys are [s * n_keys, (s + 1) * n_keys)) -> the absolute shared row
+__global__ __launch_bounds__(256) void k_qs_rows_roles(const int32_t* __restrict__ slots, int64_t T, int32_t* __restrict__ rows,
+                                                       int64_t n_keys, int n_nets, int64_t cap) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * 16) return;
+  const int key = rows[idx];
+  if (key < 0) return;
+  const int sl = (int)((uint32_t)key / (uint32_t)n_keys);       // (32-bit division: n_nets * n_keys < 2^31)
+  const int v = sl < n_nets ? slots[key] : 0;
+  rows[idx] = v > 0 ? (int32_t)(sl * cap + v - 1) : -1;
+}
+__global__ __launch_bounds__(256) void k_qs_gather_roles(const float4* __restrict__ G, int64_t g_rows, const int32_t* __restrict__ rows,
+                                                         const int8_t* __restrict__ tslot, int n_nets, int64_t T, float4* __restrict__ h0,
+                                                         const float4* __restrict__ base) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int sl = tslot[t];
+  if (sl < 0 || sl >= n_nets) return;
+  const int mine = lane < 16 ? rows[t * 16 + lane] : -1;
+  float4 acc = base[sl * 64 + lane];
+  float4 g[15];
+#pragma unroll
+  for (int r = 0; r < 15; ++r) {
+    const int row = __builtin_amdgcn_readlane(mine, r);
+    g[r] = (row >= 0 && row < g_rows) ? G[(int64_t)row * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int r = 0; r < 15; ++r) { acc.x += g[r].x; acc.y += g[r].y; acc.z += g[r].z; acc.w += g[r].w; }
+  h0[t * 64 + lane] = acc;
+}
+// dslot [N * scap][4] holds the slot-relative D row + 1 (the slot's k_qd_assign); shared row s belongs to slot s / scap
+__global__ __launch_bounds__(256) void k_qd_remap_roles(const int32_t* __restrict__ row_index, const int32_t* __restrict__ rows, int64_t T,
+                                                        const int32_t* __restrict__ dslot, int64_t scap, int n_nets, int64_t dcap,
+                                                        int32_t* __restrict__ row_index2) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * QP_COLS) return;
+  const int col = (int)(idx & (QP_COLS - 1));
+  int out = -1;
+  if (col < 54 && row_index[idx] >= 0) {
+    int r, c;
+    qd_col(col, r, c);
+    const int s = rows[(idx >> 6) * 16 + r];
+    if (s >= 0 && s < scap * n_nets) {
+      const int v = dslot[(int64_t)s * 4 + c - 1];
+      if (v > 0) out = (int)((int64_t)((uint32_t)s / (uint32_t)scap) * dcap + v - 1);   // (32-bit division: s < 2^31)
+    }
+  }
+  row_index2[idx] = out;
+}
+// k_q_slab_needed (section 4) with per-slot weights: w2 f32 [N][256] and b2 f32 [N] stacked per network slot, tslot int8 [T]
+// the slot of every table; a table with tslot < 0 (played by the rule agent) is skipped: its q entries are left alone, no
+// status bit.  (A copy rather than a shared template: k_q_slab_needed as an instance of a template body compiles to different
+// code -- register allocation and the scheduling of its b2 load -- and the single-network kernel keeps its code object.  A change
+// to the row stage goes into both; tests/test_gpu_seat_q.py holds this copy's q bit for bit to k_q_slab_needed's.)
+__global__ __launch_bounds__(TB, 4) void k_q_slab_roles(const float4* __restrict__ H0, const float4* __restrict__ D, int64_t d_rows,
+                                                       int64_t T, int tpw, const float4* __restrict__ w2,
+                                                       const float* __restrict__ b2, const int8_t* __restrict__ tslot,
+                                                       const int32_t* __restrict__ counts, const uint4* __restrict__ rows,
+                                                       int64_t stride, float* __restrict__ q, const int32_t* __restrict__ pidx,
+                                                       int32_t* __restrict__ status) {
+  __shared__ float4 s_cache[WPB][QS_ROWS][QH / 4];
+  __shared__ float4 s_big[QS_BIG][QH / 4];
+  __shared__ int32_t s_heavy[WPB * 8];   // tables of this block left to the whole block (tpw <= 8)
+  __shared__ uint32_t s_nheavy, s_next;
+  const int lane = threadIdx.x & 63, l16 = lane & 15;
+  const int wv = (int)rfl(threadIdx.x >> 6);
+  if (threadIdx.x == 0) { s_nheavy = 0; s_next = WPB; }
+  __syncthreads();
+  const int64_t tb = (int64_t)blockIdx.x * WPB * tpw;    // the block's first table
+  const int nblk_tab = tb < T ? (int)(T - tb < (int64_t)WPB * tpw ? T - tb : (int64_t)WPB * tpw) : 0;   // ... and how many it has
+  float4 (*cache)[QH / 4] = s_cache[wv];
+  float4 w[4];
+  float bias = 0.f;
+  int sl_w = -1;                                         // the slot whose w2 / b2 are in w / bias
+  // ---- phase 1: the block's tables are handed out one by one (an LDS ticket: a table costs between one memory round trip
+  // and dozens -- with a fixed share per wave, half of the wave-slots of the launch stood idle behind the unluckiest wave of
+  // every block).  A HEAVY table -- more needed rows than the wave's cache holds, or a long list: a fresh deal's 20-card
+  // lead has ~20 rows and 70 .. 400 moves -- is left to phase 2.  The next table's list size and row_index travel while the
+  // current table is evaluated.
+  int cur = wv < nblk_tab ? wv : -1;                     // the first WPB tables need no ticket
+  int n_next = cur >= 0 ? counts[tb + cur] : 0;
+  int sl_next = cur >= 0 ? tslot[tb + cur] : -1;       // (the slot travels with the list size)
+  int32_t idx_next = cur >= 0 ? pidx[(tb + cur) * QP_COLS + lane] : -1;
+  while (cur >= 0) {
+    const int64_t t = tb + cur;
+    int n = (int)rfl((uint32_t)n_next);
+    const int sl = (int)rfl((uint32_t)sl_next);
+    const int32_t myidx = idx_next;                     // lane L holds column L of the table's row_index
+    {
+      uint32_t nx = 0;
+      if (lane == 0) nx = atomicAdd(&s_next, 1u);
+      nx = rfl(nx);
+      cur = nx < (uint32_t)nblk_tab ? (int)nx : -1;
+      if (cur >= 0) { n_next = counts[tb + cur]; idx_next = pidx[(tb + cur) * QP_COLS + lane]; sl_next = tslot[tb + cur]; }
+    }
+    if (n < 0 || n > stride) n = 0;
+    if (n == 0) continue;
+    if (sl < 0) continue;
+    const bool mine = (uint32_t)myidx < (uint32_t)d_rows;
+    const uint64_t needm = __ballot(mine);              // the table's needed columns (with a valid row)
+    if (__popcll(needm) > QS_ROWS || n > QS_HEAVY_MOVES) {
+      if (lane == 0) s_heavy[atomicAdd(&s_nheavy, 1u)] = (int32_t)(t - tb);
+      continue;
+    }
+    // stage the needed rows: slot s = the s-th set column.  ALL loads are issued before the first one is stored (a
+    // load-store pair per trip would cost a memory round trip per row)
+    {
+      if (sl != sl_w) {                                  // (reloaded only when the slot changes)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = w2[sl * (QH / 4) + l16 + 16 * k];
+        bias = b2[sl];
+        sl_w = sl;
+      }
+    }
+    float4 h0[4];
+    {
+      uint64_t m = needm;
+      float4 tmp[QS_ROWS];
+#pragma unroll
+      for (int s_ = 0; s_ < QS_ROWS; ++s_) {
+        const bool on = m != 0;                           // wave-uniform
+        const int col = on ? __builtin_ctzll(m) : 0;
+        const int32_t pr = (int32_t)__builtin_amdgcn_readlane(myidx, col);
+        tmp[s_] = on ? D[(int64_t)pr * (QH / 4) + lane] : make_float4(0.f, 0.f, 0.f, 0.f);   // one coalesced 1-KB read
+        m &= m - 1;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) h0[k] = H0[t * (QH / 4) + l16 + 16 * k];
+      __builtin_amdgcn_wave_barrier();                  // (the previous table's reads of the cache are done: same wave, in order)
+#pragma unroll
+      for (int s_ = 0; s_ < QS_ROWS; ++s_) cache[s_][lane] = tmp[s_];
+      __builtin_amdgcn_wave_barrier();
+    }
+    q_slab_moves(D, rows + t * stride, q + t * stride, n, 0, 4, myidx, needm, h0, w, bias, cache, QS_ROWS, lane, status);
+  }
+  __syncthreads();
+  // ---- phase 2: the block's heavy tables, one after the other, by ALL its waves: the rows staged once in the block's cache
+  // (wave w loads rows w, w + 16), wave w evaluates moves 4 w .. 4 w + 3, then + 64, ...
+  const int nheavy = (int)s_nheavy;                      // (block-uniform)
+  for (int hi = 0; hi < nheavy; ++hi) {
+    const int64_t t = tb + s_heavy[hi];
+    int n = counts[t];
+    if (n < 0 || n > stride) n = 0;
+    const int32_t myidx = pidx[t * QP_COLS + lane];
+    const bool mine = (uint32_t)myidx < (uint32_t)d_rows;
+    const uint64_t needm = __ballot(mine);
+    {                                                    // (a heavy table is a network table: phase 1 skipped the others)
+      const int sl = tslot[t];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = w2[sl * (QH / 4) + l16 + 16 * k];
+      bias = b2[sl];
+    }
+    for (int s_ = wv; s_ < QS_BIG; s_ += WPB) {          // the s-th set column, if there is one
+      uint64_t m = needm;
+      for (int k = 0; k < s_ && m; ++k) m &= m - 1;
+      if (m) {
+        const int32_t pr = (int32_t)__builtin_amdgcn_readlane(myidx, __builtin_ctzll(m));
+        s_big[s_][lane] = D[(int64_t)pr * (QH / 4) + lane];
+      }
+    }
+    float4 h0[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h0[k] = H0[t * (QH / 4) + l16 + 16 * k];
+    __syncthreads();
+    q_slab_moves(D, rows + t * stride, q + t * stride, n, 4 * wv, 4 * WPB, myidx, needm, h0, w, bias, s_big, QS_BIG, lane, status);
+    __syncthreads();                                     // (the cache is free for the next heavy table)
+  }
+}

@@ -765,6 +765,268 @@ class PolicyLoop:
         return out
 
 
+ROLE_ORDER = ("up", "lord", "down")      # the engine's role ids 0, 1, 2
+
+
+def role_slots(nets, face_variant):
+    """{"lord" | "down" | "up": QNet | None} (missing keys: None) -> (slot networks, net_of_role [3] in role order up, lord, down:
+    a slot or -1 = the rule agent).  Equal network objects share one slot; slots are numbered in role order.  Raises ValueError
+    for an unknown role, a map without a network, face variant 0 or one the shared rows do not key, and planes that differ
+    between the networks or from the variant.  Pure Python: no device is touched."""
+    from .engine import FACE_PLANES
+    unknown = set(nets) - set(ROLE_ORDER)
+    if unknown:
+        raise ValueError(f"unknown role(s) {sorted(unknown)}: the roles are lord, down and up")
+    v = int(face_variant)
+    if v not in (1, 2, 3):
+        raise ValueError("per-role networks need face variant 1, 2 or 3 (the faces the shared rows key; variant 0 has none)")
+    slots, net_of_role = [], []
+    for role in ROLE_ORDER:
+        net = nets.get(role)
+        if net is None:
+            net_of_role.append(-1)
+            continue
+        for s, other in enumerate(slots):
+            if other is net:
+                net_of_role.append(s)
+                break
+        else:
+            net_of_role.append(len(slots))
+            slots.append(net)
+    if not slots:
+        raise ValueError("the role map has no network (an all-rule game is BatchedEnv.step_auto(0b111))")
+    if len({int(n.planes) for n in slots}) != 1:
+        raise ValueError("the networks' input planes differ: all roles share one face variant")
+    if int(slots[0].planes) != FACE_PLANES[v]:
+        raise ValueError(f"the networks take {slots[0].planes} planes, face variant {v} has {FACE_PLANES[v]}")
+    return slots, net_of_role
+
+
+class RoleQ:
+    """The multi-network counterpart of FactorisedQ's shared-rows form (needed(shared="all")): one network per role, or the rule
+    agent (Game, game.py:11-43).  One pass over the tables whose actor has a network: the shared rows keyed by (network slot,
+    rank, column) (csrc/ddz_qnet.h section 7), the per-slot GEMMs on the slot's weights, H0 / D / q of a table from its own
+    network -- bit for bit what FactorisedQ(net of the table's role).needed(env, face, shared="all") + q_slab give.  Tables played
+    by the rule agent take no part (their q entries are left alone).  The stacked weight tables are rebuilt when a parameter
+    version of any network moves."""
+
+    def __init__(self, nets, face_variant):
+        self.nets, self.net_of_role = role_slots(nets, face_variant)
+        self.variant, self.N = int(face_variant), len(self.nets)
+        self.fqs = [FactorisedQ(n) for n in self.nets]
+        self.P = self.fqs[0].P
+        self._ws = {}
+        self._stack()
+
+    def _versions(self):
+        return tuple(fq._versions() for fq in self.fqs)
+
+    @torch.no_grad()
+    def _stack(self):
+        for fq in self.fqs:
+            if fq._ver != fq._versions():
+                fq.refresh()
+        st = lambda name: torch.stack([getattr(fq, name) for fq in self.fqs]).contiguous()  # noqa: E731
+        self.Wf, self.bias_f, self.A, self.W2x, self.W2, self.Z = (st(k) for k in ("Wf", "bias_f", "A", "W2x", "W2", "Z"))
+        self.base, self.w2, self.b2 = st("base"), st("w2"), torch.cat([fq.b2.view(1) for fq in self.fqs]).contiguous()
+        self._ver = self._versions()
+
+    def _workspace(self, env, face):
+        from . import engine as E
+        T, dev, N, H = env.T, face.device, self.N, _CONV_CH
+        key = (dev, T)
+        if key not in self._ws:
+            self._ws.clear()
+            tile = fc_tile()
+            cap = (20 * T + 15 * tile + tile - 1) // tile * tile                  # D rows per slot: ddz_q_need's capacity
+            most = min(15 * T, 4134375) if self.variant == 3 else 15 * T
+            scap = (most + 15 * tile + tile - 1) // tile * tile                   # shared rows per slot
+            z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+            self._ws[key] = {
+                "cap": cap, "scap": scap,
+                "scratch": z(E.q_need_scratch_bytes(T), dt=torch.uint8), "row_index": z(T, 64, dt=torch.int32),
+                "seg": z(40, dt=torch.int32), "row_cnt": z(cap, dt=torch.uint8),
+                "sws": z(E.q_roles_ws_bytes(T, self.variant, N), dt=torch.uint8), "srows": z(T, 16, dt=torch.int32),
+                "srep": z(N * scap, dt=torch.int32), "sseg": z(N, 40, dt=torch.int32), "slot": z(T, dt=torch.int8),
+                "ys": z(N * scap, E.shared_row_width(self.P)), "g": z(N * scap, H), "h0": z(T, H),
+                "dws": z(E.q_roles_need_ws_bytes(scap, N), dt=torch.uint8), "row_index2": z(T, 64, dt=torch.int32),
+                "drep": z(N * cap, dt=torch.int32), "dseg": z(N, 40, dt=torch.int32), "drow_cnt": z(N * cap, dt=torch.uint8),
+                "dy": z(N * cap, H), "d": z(N * cap, H),
+                "side": torch.cuda.Stream(dev), "fork0": torch.cuda.Event(), "fork": torch.cuda.Event(), "join": torch.cuda.Event()}
+        return self._ws[key]
+
+    @torch.no_grad()
+    def needed(self, env, face):
+        """face f32 [T,P,15,4]: env's own face of the variant of its CURRENT states -> RolesU (h0, d, row_index, seg, slot; device,
+        aliases this object's workspace).  As FactorisedQ.needed(shared="all"): the need sets and the D chain on a side stream
+        beside the finder and the H0 chain (fork / join by events), nothing crosses to the host, every launch is capturable."""
+        from . import engine as E
+        if self._ver != self._versions():
+            self._stack()
+        T, P, N = face.shape[0], self.P, self.N
+        if tuple(face.shape[1:]) != (P, 15, 4) or T != env.T or not face.is_cuda:
+            raise ValueError(f"face must be a device tensor [T,{P},15,4] of the environment's tables")
+        w = self._workspace(env, face)
+        cur = torch.cuda.current_stream(face.device)
+        w["fork0"].record(cur)
+        w["side"].wait_event(w["fork0"])
+        with torch.cuda.stream(w["side"]):
+            env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"])
+        env.q_roles_rows(self.variant, self.net_of_role, N, w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"], w["slot"])
+        w["fork"].record(cur)
+        w["side"].wait_event(w["fork"])
+        with torch.cuda.stream(w["side"]):
+            env.q_roles_need(N, w["row_index"], w["srows"], w["sseg"], w["scap"], w["dws"], w["cap"], w["row_index2"], w["drep"],
+                             w["dseg"], w["drow_cnt"])
+            E.q_roles_features_drows(face, N, self.Wf, self.bias_f, self.A, w["srep"], w["scap"], w["drep"], w["dseg"], w["dy"], w["cap"])
+            E.q_roles_fc1_rows(N, w["dy"], w["dseg"], w["drow_cnt"], self.W2, self.Z, w["d"], w["cap"])
+            w["join"].record(w["side"])
+        E.q_roles_features_rows(face, N, self.Wf, self.bias_f, w["srep"], w["sseg"], w["ys"], w["scap"])
+        E.q_roles_fc1_rows_k(N, w["ys"], w["sseg"], self.W2x, w["g"], w["scap"])
+        E.q_roles_gather_h0(N, w["g"], w["srows"], w["slot"], self.base, w["h0"])   # H0[t] = base[slot] + sum_r G[row(t, r)]
+        cur.wait_event(w["join"])
+        return RolesU(w["h0"], w["d"], w["row_index2"], w["dseg"], w["slot"])
+
+    @torch.no_grad()
+    def q_slab(self, env, nu, out):
+        """ddz_q_roles_slab: q f32 [T, stride] of every legal move of every network table (rule tables' entries left alone)."""
+        return env.q_roles_slab(self.N, nu.slot, nu.h0, nu.d, nu.row_index, self.w2, self.b2, out)
+
+
+class RolesU:
+    """RoleQ.needed's result: NeededU's fields (seg: int32 [N,40] of the D rows, one block per slot) + slot int8 [T] (-1: rule)."""
+    __slots__ = ("h0", "d", "row_index", "seg", "slot")
+
+    def __init__(self, h0, d, row_index, seg, slot):
+        self.h0, self.d, self.row_index, self.seg, self.slot = h0, d, row_index, seg, slot
+
+
+class SeatLoop:
+    """game.py:95-106 for T tables with a network or the rule agent per role, one lock-step iteration per step():
+        act():   RoleQ's pass over the network tables -> greedy choice (ddz_select_slab) and, with epsilon per role, the
+                 epsilon-greedy choice (trained roles explore, game.py:95-104) -> the rule agent's move for the roles mapped to
+                 None (auto_choose) -> one action id per table
+        apply(): one step of every table (step_slab(STEP_IDS), re-deal of finished tables) and the next face.
+    Between act() and apply() a training driver reads face (the face the network tables chose on), choice / greedy (indices
+    into the slab lists; valid for network tables, slot >= 0) and ids (what every table plays): TransitionAssembler.before_step
+    takes them.  Nothing crosses to the host; capture(n) records n iterations as one graph."""
+
+    def __init__(self, env, nets, face_variant, epsilon=0.0, auto_reset=True):
+        self.rq = RoleQ(nets, face_variant)
+        if isinstance(epsilon, dict):
+            bad = set(epsilon) - set(ROLE_ORDER)
+            if bad:
+                raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
+            eps = [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
+        else:
+            eps = [float(epsilon)] * 3
+        self.env, self.variant, self.auto_reset = env, int(face_variant), bool(auto_reset)
+        nr = self.rq.net_of_role
+        self.eps = [e if nr[k] >= 0 else 0.0 for k, e in enumerate(eps)]
+        self.auto_roles = sum(1 << k for k in range(3) if nr[k] < 0)
+        T, dev = env.T, env.device
+        self.face = env.observe(self.variant)
+        self.q = torch.full((T, env.slab_stride), float("nan"), dtype=torch.float32, device=dev)
+        self.greedy = torch.empty(T, dtype=torch.int32, device=dev)
+        self.choice = self.greedy if not any(self.eps) else torch.empty(T, dtype=torch.int32, device=dev)
+        self._eps_of_role = torch.tensor(self.eps, dtype=torch.float32, device=dev)
+        self._auto = torch.empty(T, dtype=torch.int32, device=dev)
+        self.ids = torch.empty(T, dtype=torch.int32, device=dev)
+        self.slot = None
+        if not env._slab_fresh:
+            env.legal_slab()
+
+    def q_values(self):
+        """q [T, stride] of the current lists for the network tables (valid in [t, :counts[t]] where slot[t] >= 0)"""
+        nu = self.rq.needed(self.env, self.face)
+        self.slot = nu.slot
+        return self.rq.q_slab(self.env, nu, self.q)
+
+    def act(self):
+        env = self.env
+        q = self.q_values()
+        env.select_slab(q, 0.0, out=self.greedy)
+        if self.choice is not self.greedy:
+            self.choice.copy_(self.greedy)
+            role_eps = self._eps_of_role[env.role.long()]
+            for e in sorted(set(e for e in self.eps if e > 0)):
+                self.choice.copy_(torch.where(role_eps == e, env.select_slab(q, e), self.choice))
+        net_ids = env.slab_ids().gather(1, self.choice.clamp(min=0).long()[:, None])[:, 0]
+        if self.auto_roles:
+            env.auto_choose(self.auto_roles, out=self._auto)
+            self.ids.copy_(torch.where(self.slot >= 0, net_ids, self._auto))
+        else:
+            self.ids.copy_(net_ids)
+        return self.ids
+
+    def apply(self, traj=None):
+        from .engine import STEP_IDS
+        done, r, illegal = self.env.step_slab(self.ids, STEP_IDS, auto_reset=self.auto_reset, traj=traj)
+        self.env.observe(self.variant, out=self.face)
+        return done, r, illegal
+
+    def step(self, traj=None):
+        self.act()
+        return self.apply(traj)
+
+    def run(self, n):
+        for _ in range(int(n)):
+            self.step()
+
+    def capture(self, n=1):
+        """n lock-step iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first)."""
+        return PolicyLoop.capture(self, n)
+
+
+def _compete_net(x, face_variant, device, cache):
+    """a compete() role entry: None, a QNet, or the path of a reference state dict (loaded weights_only)"""
+    if x is None or isinstance(x, nn.Module):
+        return x
+    from . import metrics
+    from .engine import FACE_PLANES
+    path = str(x)
+    if path not in cache:
+        sd = metrics.load_state_dict(abspath=path)
+        net = QNet(int(sd["conv1.weight"].shape[1]) - 1 if "conv1.weight" in sd else FACE_PLANES[int(face_variant)])
+        net.load_state_dict(sd)
+        cache[path] = net.to(device).eval()
+    return cache[path]
+
+
+@torch.no_grad()
+def compete(face_variant, nets, total, tables=4096, seed=0, book=None, device="cuda:0", check_every=8):
+    """Game.compete (game.py:240-290) on the batched engine: greedy networks (QNet, or the path of a reference state dict) and the
+    rule agent (None) per role, lock-step iterations over `tables` tables until at least `total` episodes have finished (checked
+    every `check_every` iterations: one host sync each).  Returns {"lord", "down", "up": wins, "episodes", "iterations"} from
+    BatchedEnv.stats() deltas (the wins sum to the episodes); with `book` (metrics.WinRateBook) the same stats feed it."""
+    from .engine import BatchedEnv
+    cache = {}
+    nets = {r: _compete_net(v, face_variant, device, cache) for r, v in nets.items()}
+    env = BatchedEnv(int(tables), seed=int(seed), device=device)
+    env.reset()
+    env.legal_slab()
+    if all(v is None for v in nets.values()) and not (set(nets) - set(ROLE_ORDER)):
+        step = lambda: env.step_auto(0b111, slab=True)     # noqa: E731   (the rule agent on every seat)
+    else:
+        step = SeatLoop(env, nets, face_variant, 0.0).step
+    s0 = env.stats()
+    if book is not None:
+        book.update(s0)
+    it = 0
+    while True:
+        for _ in range(int(check_every)):
+            step()
+        it += int(check_every)
+        s1 = env.stats()
+        if s1["episodes"] - s0["episodes"] >= int(total):
+            break
+    if book is not None:
+        book.update(s1)
+    env.close()
+    return {"lord": s1["lord_wins"] - s0["lord_wins"], "down": s1["down_wins"] - s0["down_wins"],
+            "up": s1["up_wins"] - s0["up_wins"], "episodes": s1["episodes"] - s0["episodes"], "iterations": it}
+
+
 class Replay:
     """Ring buffer of transitions on the device (dqn.py:11,22-23: deque(maxlen=REPLAY_SIZE) of tuples)."""
 

@@ -314,6 +314,51 @@ class BatchedEnv:
                                          self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
         return out
 
+    # ---- per-role networks in one shared-rows forward (csrc/ddz_qnet.h section 7; dqn_glue.RoleQ) ----
+    def q_roles_rows(self, variant, net_of_role, n_nets, ws, row_capacity, rows, rep, seg, slot):
+        """ddz_q_roles_rows: the shared rows keyed by (network slot, rank, column) for the role map net_of_role (3 ints, role order
+        up, lord, down: a slot 0 .. n_nets - 1 or -1 = the rule agent): rows int32 [T,16] (absolute rows; -1 for rule tables), rep
+        int32 [n_nets * row_capacity], seg int32 [n_nets, 40] (per slot, relative to its partition of row_capacity rows), slot
+        int8 [T] (-1 = rule table).  ws uint8 [q_roles_ws_bytes(T, variant, n_nets)]."""
+        N = int(n_nets)
+        if (rows.dtype != torch.int32 or tuple(rows.shape) != (self.T, 16) or not rows.is_contiguous() or rep.dtype != torch.int32
+                or rep.numel() < N * int(row_capacity) or seg.dtype != torch.int32 or seg.numel() < 40 * N or ws.dtype != torch.uint8
+                or slot.dtype != torch.int8 or slot.numel() != self.T):
+            raise ValueError("rows must be int32 [T,16], rep int32 [n_nets * row_capacity], seg int32 [n_nets,40], slot int8 [T], ws uint8")
+        m = (C.c_int32 * 3)(*[int(x) for x in net_of_role])
+        check(self.lib.ddz_q_roles_rows(self._h, int(variant), m, N, _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep), _p(seg),
+                                        _p(slot), _stream(self.device)))
+
+    def q_roles_need(self, n_nets, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
+        """ddz_q_roles_need: q_shared_need over the slots of q_roles_rows (per-slot capacities; rule tables get no D row)."""
+        N = int(n_nets)
+        for x, shp in ((row_index, (self.T, 64)), (row_index2, (self.T, 64)), (rows, (self.T, 16))):
+            if x.dtype != torch.int32 or tuple(x.shape) != shp or not x.is_contiguous():
+                raise ValueError("row_index / row_index2 must be int32 [T,64], rows int32 [T,16]")
+        if (drep.dtype != torch.int32 or drep.numel() < N * int(row_capacity) or row_cnt.dtype != torch.uint8
+                or row_cnt.numel() < N * int(row_capacity) or dseg.dtype != torch.int32 or dseg.numel() < 40 * N
+                or sseg.dtype != torch.int32 or sseg.numel() < 40 * N or ws.dtype != torch.uint8):
+            raise ValueError("drep int32 / row_cnt uint8 [n_nets * row_capacity], dseg / sseg int32 [n_nets,40], ws uint8")
+        check(self.lib.ddz_q_roles_need(self._h, N, _p(row_index), _p(rows), _p(sseg), int(shared_row_capacity), _p(ws), ws.numel(),
+                                        int(row_capacity), _p(row_index2), _p(drep), _p(dseg), _p(row_cnt), _stream(self.device)))
+
+    def q_roles_slab(self, n_nets, slot, h0, d, row_index, w2, b2, out):
+        """ddz_q_roles_slab: q_slab_needed with the weights of each table's slot (w2 f32 [n_nets,256], b2 f32 [n_nets]); every
+        entry of a rule table (slot < 0) is left alone."""
+        if not self._slab_fresh:
+            self.legal_slab()
+        H = int(h0.shape[-1])
+        for x, shp in ((h0, (self.T, H)), (d, (d.shape[0], H))):
+            if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != self.device:
+                raise ValueError("h0 must be float32 [T,hidden], d float32 [rows,hidden], contiguous, on the engine's device")
+        if out.dtype != torch.float32 or out.numel() != self.T * self.slab_stride or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [T, stride] tensor")
+        if slot.dtype != torch.int8 or slot.numel() != self.T or w2.numel() != int(n_nets) * H or b2.numel() != int(n_nets):
+            raise ValueError("slot must be int8 [T], w2 float32 [n_nets,hidden], b2 float32 [n_nets]")
+        check(self.lib.ddz_q_roles_slab(self._h, int(n_nets), _p(slot), _p(h0), _p(d), int(d.shape[0]), _p(row_index), H, _p(w2), _p(b2),
+                                        self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
+        return out
+
     def legal_onehot(self):
         """valid_actions(tensor=True) for all tables: f32 [sum A,15,4] (one host sync)."""
         self._need_legal()
@@ -737,6 +782,85 @@ def q_gather_h0(g, rows, h0, base=None):
         raise ValueError("base must be a contiguous float32 [256] tensor on the same device")
     check(L.ddz_q_gather_h0(dev.index, _p(g), int(g.shape[0]), _p(rows), T, _p(base), _p(h0), _stream(dev)))
     return h0
+
+
+def q_roles_ws_bytes(n_tables, variant, n_nets):
+    """workspace of BatchedEnv.q_roles_rows: n_nets times the single-network finder's"""
+    n = int(_lib.lib().ddz_q_roles_ws_bytes(int(n_tables), int(variant), int(n_nets)))
+    if n < 0:
+        raise ValueError("n_tables in 1 .. 2^26, variant 1, 2 or 3, n_nets 1 .. 3")
+    return n
+
+
+def q_roles_need_ws_bytes(shared_row_capacity, n_nets):
+    n = int(_lib.lib().ddz_q_roles_need_ws_bytes(int(shared_row_capacity), int(n_nets)))
+    if n < 0:
+        raise ValueError("the shared row capacity must be a positive multiple of the fc1 tile, n_nets 1 .. 3")
+    return n
+
+
+def _roles_dev(*xs):
+    dev = _require_gpu(xs[0].device)
+    for x in xs:
+        if x.device != dev or not x.is_contiguous():
+            raise ValueError("contiguous tensors on one device")
+    return dev
+
+
+def q_roles_features_rows(face, n_nets, wf, bias, rep, seg, ys, row_capacity):
+    """ddz_q_roles_features_rows: q_features_rows on every slot's partition of ys [n_nets * row_capacity, shared_row_width(P)]
+    with the slot's wf [n_nets, P*4, 1024] / bias [n_nets, 1024]."""
+    dev = _roles_dev(face, wf, bias, rep, seg, ys)
+    T, P, N = int(face.shape[0]), int(face.shape[1]), int(n_nets)
+    if (face.dtype != torch.float32 or P not in SHARED_PLANES or ys.dtype != torch.float32 or ys.shape[0] < N * int(row_capacity)
+            or wf.numel() != N * P * 4 * 1024 or bias.numel() != N * 1024):
+        raise ValueError("face f32 [T,P,15,4] (P = 6, 7, 9), ys f32 [n_nets * row_capacity, width], wf [n_nets,P*4,1024], bias [n_nets,1024]")
+    check(_lib.lib().ddz_q_roles_features_rows(dev.index, _p(face), T, P, N, _p(wf), _p(bias), _p(rep), _p(seg), _p(ys), int(ys.shape[1]),
+                                               int(row_capacity), _stream(dev)))
+    return ys
+
+
+def q_roles_fc1_rows_k(n_nets, y, seg, w2k, g, row_capacity):
+    """ddz_q_roles_fc1_rows_k: g[row] = y[row] @ w2k[slot][rank of the row] on every slot's partition; w2k f32 [n_nets,15,k,256]."""
+    dev = _roles_dev(y, seg, w2k, g)
+    N, k = int(n_nets), int(y.shape[1])
+    if y.shape[0] < N * int(row_capacity) or g.shape[0] < N * int(row_capacity) or w2k.numel() != N * 15 * k * 256:
+        raise ValueError("y [n_nets * row_capacity, k], g [n_nets * row_capacity, 256], w2k [n_nets,15,k,256]")
+    check(_lib.lib().ddz_q_roles_fc1_rows_k(dev.index, N, _p(y), k, _p(seg), _p(w2k), _p(g), int(row_capacity), _stream(dev)))
+    return g
+
+
+def q_roles_gather_h0(n_nets, g, rows, slot, base, h0):
+    """ddz_q_roles_gather_h0: h0[t] = base[slot[t]] + sum_r g[rows[t, r]] (rank order); rule tables (slot < 0) left alone."""
+    dev = _roles_dev(g, rows, slot, base, h0)
+    T = int(h0.shape[0])
+    if tuple(rows.shape) != (T, 16) or slot.dtype != torch.int8 or slot.numel() != T or base.numel() != int(n_nets) * 256:
+        raise ValueError("rows int32 [T,16], slot int8 [T], base f32 [n_nets,256]")
+    check(_lib.lib().ddz_q_roles_gather_h0(dev.index, int(n_nets), _p(g), int(g.shape[0]), _p(rows), _p(slot), T, _p(base), _p(h0),
+                                           _stream(dev)))
+    return h0
+
+
+def q_roles_features_drows(face, n_nets, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy, row_capacity):
+    """ddz_q_roles_features_drows: q_features_drows on every slot's partition (acnt f32 [n_nets,5,4,256])."""
+    dev = _roles_dev(face, wf, bias, acnt, rep, drep, dseg, dy)
+    T, P, N = int(face.shape[0]), int(face.shape[1]), int(n_nets)
+    if dy.shape[0] < N * int(row_capacity) or acnt.numel() != N * 5 * 4 * 256 or rep.numel() < N * int(shared_row_capacity):
+        raise ValueError("dy [n_nets * row_capacity, 256], acnt [n_nets,5,4,256], rep [n_nets * shared_row_capacity]")
+    check(_lib.lib().ddz_q_roles_features_drows(dev.index, _p(face), T, P, N, _p(wf), _p(bias), _p(acnt), _p(rep), int(shared_row_capacity),
+                                                _p(drep), _p(dseg), _p(dy), int(row_capacity), _stream(dev)))
+    return dy
+
+
+def q_roles_fc1_rows(n_nets, dy, seg, row_cnt, w2, z, d, row_capacity):
+    """ddz_q_roles_fc1_rows: d[row] = dy[row] @ w2[slot][rank] + z[slot][rank][row_cnt[row]] on every slot's partition."""
+    dev = _roles_dev(dy, seg, row_cnt, w2, z, d)
+    N = int(n_nets)
+    if w2.numel() != N * 15 * 256 * 256 or z.numel() != N * 75 * 256 or d.shape[0] < N * int(row_capacity):
+        raise ValueError("w2 [n_nets,15,256,256], z [n_nets,15,5,256], dy / d [n_nets * row_capacity, 256]")
+    check(_lib.lib().ddz_q_roles_fc1_rows(dev.index, N, _p(dy), _p(seg), _p(row_cnt), _p(w2), _p(z), _p(d), int(row_capacity),
+                                          _stream(dev)))
+    return d
 
 
 def action_table(device="cuda:0", native_joker_kickers=False):

@@ -366,6 +366,62 @@ int ddz_q_gather_h0(int device_id, const float* g, int64_t g_rows, const int32_t
 int ddz_q_fc1_rows_k(int device_id, const float* y, int64_t k, const int32_t* seg, const float* w2k, float* g,
                      int64_t row_capacity, int accumulate, void* stream);
 
+/* Per-role networks in ONE shared-rows forward (ddz_qnet.h section 7; the reference's Game gives every role its own network or
+ * the rule agent, game.py:11-43,95-106).  net_of_role int32 [3] (host; role order 0 up, 1 lord, 2 down): a network slot 0 ..
+ * n_nets - 1 per role, or -1 = the rule agent; every slot names at least one role (else DDZ_EINVAL); 1 <= n_nets <= 3.  The
+ * weights are stacked slot-major, one face variant for all slots.  Every row buffer holds n_nets slot-major PARTITIONS of
+ * row_capacity rows (slot s: rows [s * row_capacity, (s + 1) * row_capacity)); seg / dseg int32 [n_nets][40] hold one segment
+ * table per slot in ddz_q_need's layout, RELATIVE to the slot's partition (a one-slot map writes exactly the single-network
+ * words).  A table whose actor's role maps to -1 (a RULE table) takes no part: no shared row, no D row, q left alone.
+ * ddz_q_roles_rows: ddz_q_shared_rows (variant 3) / ddz_q_shared_rows_hashed (1, 2) keyed by (slot, rank, column): rows int32
+ *   [T][16] (ABSOLUTE shared row of (t, r); -1 for column 15 and for every column of a rule table), rep int32 [n_nets *
+ *   row_capacity] (-1 = padding), seg, slot int8 [T] (the slot of every table, -1 = rule table).  row_capacity per slot as
+ *   ddz_q_shared_rows' (variant 3) / ddz_q_shared_rows_hashed's (1, 2) and n_nets * row_capacity * 256 < 2^31 (else
+ *   DDZ_ECAP).  ws: ddz_q_roles_ws_bytes(T, variant, n_nets) bytes = n_nets times the single-network workspace (16.5 MB /
+ *   23.6 MB at 65,536 tables per slot, all of it cleared every call), 16-byte aligned.  Deterministic row numbers for variant
+ *   3, not for 1 / 2 (as the single-network finders).
+ * ddz_q_roles_features_rows / ddz_q_roles_fc1_rows_k: ddz_q_features_rows (no mz / g) / ddz_q_fc1_rows_k (no accumulate) on
+ *   every slot's partition with the slot's weights: wf f32 [n_nets][planes * 4][1024], bias [n_nets][1024], ys f32 [n_nets *
+ *   row_capacity][ys_ld], w2k f32 [n_nets][15][k][256], g f32 [n_nets * row_capacity][256].
+ * ddz_q_roles_gather_h0: h0[t] = base[slot[t]] + sum over r = 0..14 (in this order) of g[rows[t][r]] (base f32 [n_nets][256]);
+ *   rule tables' h0 rows are left alone.
+ * ddz_q_roles_need: ddz_q_shared_need over the slots: row_index (ddz_q_need's, all tables), rows / sseg (ddz_q_roles_rows'),
+ *   shared_row_capacity (ddz_q_roles_rows' row_capacity) -> row_index2 int32 [T][64] (ABSOLUTE D rows; -1 for every column of a
+ *   rule table), drep / row_cnt [n_nets * row_capacity] (drep slot-relative: 4 * the slot's shared row + c - 1), dseg.
+ *   row_capacity per slot as ddz_q_need's; ws: ddz_q_roles_need_ws_bytes(shared_row_capacity, n_nets) bytes.  Status bit 1
+ *   as ddz_q_shared_need.
+ * ddz_q_roles_features_drows / ddz_q_roles_fc1_rows: ddz_q_features_drows / ddz_q_fc1_rows on every slot's partition: acnt f32
+ *   [n_nets][5][4][256], w2 f32 [n_nets][15][256][256], z f32 [n_nets][15][5][256], dy / d f32 [n_nets * row_capacity][256].
+ * ddz_q_roles_slab: ddz_q_slab_needed with the weights of the table's slot, w2 f32 [n_nets][256], b2 f32 [n_nets] (device); d
+ *   has d_rows rows.  Every q entry of a rule table is left alone and such a table raises no status bit; status bit 5 as
+ *   ddz_q_slab_needed for the others.
+ * Nothing crosses to the host; every launch can be captured (n_nets launches of the per-slot kernels per call).
+ * Cost of the fixed partitions: every buffer is n_nets times the single-network one (ys, g, dy and d: about 4.9 GB per slot at
+ * 65,536 tables for 9 planes, so 14.7 GB for three networks), and every call clears n_nets times the single-network regions
+ * (finder workspace, rep, the D chain's slots and drep: 48.6 MB per slot at 65,536 tables for variants 1 / 2, 41.5 MB for 3). */
+int64_t ddz_q_roles_ws_bytes(int64_t n_tables, int variant, int n_nets);
+int ddz_q_roles_rows(ddz_env_t* env, int variant, const int32_t* net_of_role, int n_nets, void* ws, int64_t ws_bytes,
+                     int64_t row_capacity, int32_t* rows, int32_t* rep, int32_t* seg, int8_t* slot, void* stream);
+int ddz_q_roles_features_rows(int device_id, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf,
+                              const float* bias, const int32_t* rep, const int32_t* seg, float* ys, int64_t ys_ld,
+                              int64_t row_capacity, void* stream);
+int ddz_q_roles_fc1_rows_k(int device_id, int n_nets, const float* y, int64_t k, const int32_t* seg, const float* w2k, float* g,
+                           int64_t row_capacity, void* stream);
+int ddz_q_roles_gather_h0(int device_id, int n_nets, const float* g, int64_t g_rows, const int32_t* rows, const int8_t* slot,
+                          int64_t n_tables, const float* base, float* h0, void* stream);
+int64_t ddz_q_roles_need_ws_bytes(int64_t shared_row_capacity, int n_nets);
+int ddz_q_roles_need(ddz_env_t* env, int n_nets, const int32_t* row_index, const int32_t* rows, const int32_t* sseg,
+                     int64_t shared_row_capacity, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* row_index2,
+                     int32_t* drep, int32_t* dseg, uint8_t* row_cnt, void* stream);
+int ddz_q_roles_features_drows(int device_id, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf,
+                               const float* bias, const float* acnt, const int32_t* rep, int64_t shared_row_capacity,
+                               const int32_t* drep, const int32_t* dseg, float* dy, int64_t row_capacity, void* stream);
+int ddz_q_roles_fc1_rows(int device_id, int n_nets, const float* dy, const int32_t* seg, const uint8_t* row_cnt, const float* w2,
+                         const float* z, float* d, int64_t row_capacity, void* stream);
+int ddz_q_roles_slab(ddz_env_t* env, int n_nets, const int8_t* slot, const float* h0, const float* d, int64_t d_rows,
+                     const int32_t* row_index, int64_t hidden, const float* w2, const float* b2, const int32_t* counts,
+                     const int8_t* rows, int64_t stride, float* q, void* stream);
+
 /* The canonical action table: rows[ddz_num_actions()][16] = int8 counts[15] + category of action id
  * (rule_based/utils/card.py:34-159 order), device memory. */
 int ddz_action_table(int device_id, int8_t* rows, void* stream);
@@ -425,7 +481,8 @@ int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
 /* device status word: bit0 enumerator/count mismatch, bit1 row capacity overflow,
  * bit2 invalid `last` combo, bit3 a wait of ddz_auto_choose_state's cooperating wavefronts hit its
  * hang guard (never in a working launch; the ids of that launch are not to be trusted), bit4 the sequential
- * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a move of ddz_q_slab_needed whose (rank, count)
+ * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a move of ddz_q_slab_needed (or of a network table of
+ * ddz_q_roles_slab) whose (rank, count)
  * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing).
  * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
