@@ -128,6 +128,8 @@ def td_target(transitions, q_next, gamma=0.95):
 #     per legal row -> q = fc2(relu(sum_r U[r, cnt_r, t] + Z[r, cnt_r]))   a gather-sum + a 256-dot per row
 # The loop evaluates the same sum over the NEEDED rows only (FactorisedQ.needed -> ddz_q_slab_needed, over the slab lists:
 # no CSR, no host sync, no padded rows); q_csr is the sum over CSR rows with plain torch ops (the training path, ragged_q).
+import contextlib  # noqa: E402
+
 import torch.nn as nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
@@ -146,6 +148,30 @@ def fc_tile():
         from . import _lib
         _FC_TILE = int(_lib.lib().ddz_q_fc1_tile_rows())
     return _FC_TILE
+
+
+def _run_stage(name, fn):
+    fn()
+
+
+def _beside(w, fork, two):
+    """The fork of the Q forward's side stream: a context whose launches go to w["side"], behind all the current stream holds so
+    far (event w[fork]: recorded on the current stream, the side stream waits) and beside what it issues next; _join ends it.
+    By events: no host synchronisation, capturable in a hipGraph.  two=False: no context at all -- everything on the current
+    stream."""
+    if not two:
+        return contextlib.nullcontext()
+    side = w["side"]
+    w[fork].record(torch.cuda.current_stream(side.device))
+    side.wait_event(w[fork])
+    return torch.cuda.stream(side)
+
+
+def _join(w, two):
+    """the current stream waits for what _beside put on the side stream"""
+    if two:
+        w["join"].record(w["side"])
+        torch.cuda.current_stream(w["side"].device).wait_event(w["join"])
 
 
 class QNet(nn.Module):
@@ -293,9 +319,42 @@ class FactorisedQ:
             U[0, :, t0:t1] += torch.addmm(self.base, f.reshape(Tc, P * 60), self.Mz_f)
         return U
 
+    def _needed_workspace(self, dev, T, shared):
+        """needed()'s buffers for T tables, the tiers the form takes all made before its first launch: the needed rows (every form),
+        the shared rows (shared), the shared D rows with the side stream and its events ("all"), y0 (the dense form only: 1 GB at
+        65,536 tables)."""
+        from . import engine as E
+        P, H, H1 = self.P, self.H, self.H1
+        w = self._ws.setdefault(("needed", dev, T), {})
+        tile = fc_tile()
+        padded = lambda rows: (rows + 15 * tile + tile - 1) // tile * tile   # noqa: E731  (fifteen tile-aligned rank segments)
+        z = lambda *shape, dt=torch.float32, fill=0: torch.full(shape, fill, dtype=dt, device=dev)   # noqa: E731
+        if "cap" not in w:
+            cap = padded(20 * T)                                             # a move takes at most what the actor holds: <= 20 cards
+            w.update({"cap": cap, "y0": None, "dy": z(cap, H), "d": z(cap, H1), "h0": z(T, H1),
+                      "row_index": z(T, 64, dt=torch.int32, fill=-1), "seg": z(40, dt=torch.int32), "row_cnt": z(cap, dt=torch.uint8),
+                      "scratch": z(E.q_need_scratch_bytes(T), dt=torch.uint8)})
+        if shared and "srows" not in w:
+            v = SHARED_VARIANT[P]
+            # distinct (rank, column) pairs: at most 15 T (and the 4,134,375 direct-addressed keys of variant 3): cannot overflow
+            scap = padded(min(15 * T, 4134375) if v == 3 else 15 * T)
+            sws = E.q_shared_ws_bytes() if v == 3 else E.q_shared_hash_ws_bytes(T)
+            w.update({"svariant": v, "scap": scap, "sws": z(sws, dt=torch.uint8), "srows": z(T, 16, dt=torch.int32, fill=-1),
+                      "srep": z(scap, dt=torch.int32, fill=-1), "sseg": z(40, dt=torch.int32),
+                      "ys": z(scap, E.shared_row_width(P)), "g": z(scap, H1),
+                      "y0": None})                                           # (a dense call's y0 is not needed in this form)
+        if shared == "all" and "dws" not in w:
+            w.update({"dws": z(E.q_shared_need_ws_bytes(w["scap"]), dt=torch.uint8), "row_index2": z(T, 64, dt=torch.int32, fill=-1),
+                      "drep": z(w["cap"], dt=torch.int32, fill=-1), "dseg": z(40, dt=torch.int32), "drow_cnt": z(w["cap"], dt=torch.uint8),
+                      "side": torch.cuda.Stream(dev), "fork0": torch.cuda.Event(), "fork": torch.cuda.Event(),
+                      "join": torch.cuda.Event()})
+        if not shared and w["y0"] is None:
+            w["y0"] = z(T, 15 * H)
+        return w
+
     # ---- needed form: H0 per table from ONE dense GEMM + D only for the (rank, count) rows some legal move uses ----
     @torch.no_grad()
-    def needed(self, env, face, gemm="torch", shared=False):
+    def needed(self, env, face, gemm="torch", shared=False, hook=None):
         """face f32 [T,P,15,4] of env's CURRENT states (its slab lists are read on the device) -> NeededU: h0 f32 [T,256],
         d f32 [rows,256], row_index int32 [T,64], seg int32 [40] (device).  Nothing crosses to the host; every launch is
         graph-capturable.  The rows GEMM (D = dY x fc1[rank], segment sizes in device memory) is always the engine's fp32
@@ -313,110 +372,55 @@ class FactorisedQ:
         D chain runs on a side stream beside the H0 chain (self.two_streams; fork / join by events, no host synchronisation).
         Exact per call from the current weights and states (nothing is cached between calls); same values up to fp32 summation
         order in H0 (tests: 1e-5; D and q bit for bit between True and "all").
+        hook(name, fn): every stage is issued as hook(stage name, the callable that launches it) -- PolicyLoop.profile's timer; the
+        call then keeps every stage on the current stream (events around work of another stream time nothing), same values.
         The result aliases this object's workspace: consume it before the next call."""
         from . import engine as E
         if self._ver != self._versions():
             self.refresh()
-        T, P, H, H1 = face.shape[0], self.P, self.H, self.H1
+        T, P = face.shape[0], self.P
         if shared and P not in SHARED_VARIANT:
             raise ValueError("shared=True keys the columns of the faces of EnvComplicated, EnvCooperation and EnvCooperationSimplify "
                              "(face variants 1 / 2 / 3: 7 / 9 / 6 planes) only")
         if tuple(face.shape[1:]) != (P, 15, 4) or T != env.T or not face.is_cuda:
             raise ValueError(f"face must be a device tensor [T,{P},15,4] of the environment's tables")
-        key = ("needed", face.device, T)
-        if key not in self._ws:
-            FC_TILE = fc_tile()
-            cap = (20 * T + 15 * FC_TILE + FC_TILE - 1) // FC_TILE * FC_TILE   # a move takes at most what the actor holds: <= 20 cards
-            dev = face.device
-            self._ws[key] = {"cap": cap, "y0": None,
-                             "dy": torch.zeros((cap, H), dtype=torch.float32, device=dev),
-                             "d": torch.zeros((cap, H1), dtype=torch.float32, device=dev),
-                             "h0": torch.zeros((T, H1), dtype=torch.float32, device=dev),
-                             "row_index": torch.full((T, 64), -1, dtype=torch.int32, device=dev),
-                             "seg": torch.zeros(40, dtype=torch.int32, device=dev),
-                             "row_cnt": torch.zeros(cap, dtype=torch.uint8, device=dev),
-                             "scratch": torch.zeros(E.q_need_scratch_bytes(T), dtype=torch.uint8, device=dev)}
-        w = self._ws[key]
-        early = shared == "all" and self.two_streams and "side" in w     # the need sets on the side stream, beside the shared rows
-        if early:
-            cur = torch.cuda.current_stream(face.device)
-            w["fork0"].record(cur)
-            w["side"].wait_event(w["fork0"])
-            with torch.cuda.stream(w["side"]):
-                env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"])
-        else:
-            env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"])
-        if shared:
-            if "srows" not in w:
-                FC_TILE = fc_tile()
-                v = SHARED_VARIANT[P]
-                # distinct (rank, column) pairs: at most 15 T (and the 4,134,375 direct-addressed keys of variant 3): cannot overflow
-                most = min(15 * T, 4134375) if v == 3 else 15 * T
-                scap = (most + 15 * FC_TILE + FC_TILE - 1) // FC_TILE * FC_TILE
-                dev = face.device
-                sws = E.q_shared_ws_bytes() if v == 3 else E.q_shared_hash_ws_bytes(T)
-                w.update({"svariant": v, "scap": scap, "sws": torch.zeros(sws, dtype=torch.uint8, device=dev),
-                          "srows": torch.full((T, 16), -1, dtype=torch.int32, device=dev),
-                          "srep": torch.full((scap,), -1, dtype=torch.int32, device=dev),
-                          "sseg": torch.zeros(40, dtype=torch.int32, device=dev),
-                          "ys": torch.zeros((scap, E.shared_row_width(P)), dtype=torch.float32, device=dev),
-                          "g": torch.zeros((scap, H1), dtype=torch.float32, device=dev)})
-                w["y0"] = None                                                     # (1 GB at 65,536 tables: not needed in this form)
-            env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"], variant=w["svariant"])
-
-            def h0_chain():
-                # G[row] = Y[row] x fc1[rank] + column x Mz[rank] (the table term is linear in the face: folded into the rows --
-                # the column rides behind Y in the row, Mz[rank] behind fc1[rank] in the operand: one K = 288 / 304 product)
-                E.q_features_rows(face, self.Wf, self.bias_f, w["srep"], w["sseg"], w["ys"])
-                E.q_fc1_rows_k(w["ys"], w["sseg"], self.W2x, w["g"])
-                E.q_gather_h0(w["g"], w["srows"], w["h0"], base=self.base)        # H0[t] = base + sum_r G[row(t, r)]
-
-            if shared == "all":      # the needed rows shared as well: one D row per distinct (shared row, count) (section 6)
-                if "dws" not in w:
-                    dev = face.device
-                    w.update({"dws": torch.zeros(E.q_shared_need_ws_bytes(w["scap"]), dtype=torch.uint8, device=dev),
-                              "row_index2": torch.full((T, 64), -1, dtype=torch.int32, device=dev),
-                              "drep": torch.full((w["cap"],), -1, dtype=torch.int32, device=dev),
-                              "dseg": torch.zeros(40, dtype=torch.int32, device=dev),
-                              "drow_cnt": torch.zeros(w["cap"], dtype=torch.uint8, device=dev),
-                              "side": torch.cuda.Stream(dev), "fork0": torch.cuda.Event(), "fork": torch.cuda.Event(),
-                              "join": torch.cuda.Event()})
-                # The H0 chain (first layer of the rows -> G -> gather) and the D chain (D rows -> dY -> D) share only their
-                # inputs: both GEMMs are a few hundred tiles -- one or two rounds over the 256 CUs, the launch as long as its
-                # last round -- and the bookkeeping kernels are latency-bound, so the D chain runs on a SIDE STREAM beside the
-                # H0 chain (fork / join by events: no host synchronisation, capturable in a hipGraph).
-                cur = torch.cuda.current_stream(face.device)
-                two = self.two_streams
-                if two:
-                    w["fork"].record(cur)
-                    w["side"].wait_event(w["fork"])
-                with torch.cuda.stream(w["side"] if two else cur):
-                    env.q_shared_need(w["row_index"], w["srows"], w["sseg"], w["scap"], w["dws"], w["cap"], w["row_index2"], w["drep"],
-                                      w["dseg"], w["drow_cnt"])
-                    E.q_features_drows(face, self.Wf, self.bias_f, self.A, w["srep"], w["drep"], w["dseg"], w["dy"])
-                    E.q_fc1_rows(w["dy"], w["dseg"], w["drow_cnt"], self.W2, self.Z, w["d"])
-                    if two:
-                        w["join"].record(w["side"])
-                h0_chain()
-                if two:
-                    cur.wait_event(w["join"])
-                return NeededU(w["h0"], w["d"], w["row_index2"], w["dseg"])
-            h0_chain()
-            E.q_features_needed(face, self.Wf, self.bias_f, self.A, w["row_index"], None, w["dy"])
-            E.q_fc1_rows(w["dy"], w["seg"], w["row_cnt"], self.W2, self.Z, w["d"])
-            return NeededU(w["h0"], w["d"], w["row_index"], w["seg"])
-        if w["y0"] is None:
-            w["y0"] = torch.zeros((T, 15 * H), dtype=torch.float32, device=face.device)
-        E.q_features_needed(face, self.Wf, self.bias_f, self.A, w["row_index"], w["y0"], w["dy"])
-        torch.addmm(self.base, face.view(T, P * 60), self.Mz_f, out=w["h0"])      # the per-table term (K = 60 P: small)
-        if gemm == "mfma":
-            E.q_fc1_dense(w["y0"], self.Wd, w["h0"])
-        elif gemm == "torch":
-            w["h0"].addmm_(w["y0"], self.Wd)
-        else:
+        if not shared and gemm not in ("mfma", "torch"):
             raise ValueError("gemm must be 'mfma' or 'torch'")
-        E.q_fc1_rows(w["dy"], w["seg"], w["row_cnt"], self.W2, self.Z, w["d"])     # D = dY x fc1[rank] + Z[rank][count]
-        return NeededU(w["h0"], w["d"], w["row_index"], w["seg"])
+        w = self._needed_workspace(face.device, T, shared)
+        run = hook or _run_stage
+        all_ = shared == "all"
+        two = all_ and self.two_streams and hook is None
+        Wf, bf, A = self.Wf, self.bias_f, self.A
+        # the needed rows: per table, or ("all") one D row per distinct (shared row, count) (section 6) -- row_index remapped
+        ri, sg, rc = (w["row_index2"], w["dseg"], w["drow_cnt"]) if all_ else (w["row_index"], w["seg"], w["row_cnt"])
+        with _beside(w, "fork0", two):                                   # the need sets beside the shared rows
+            run("need", lambda: env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"]))
+        if shared:
+            run("shared_rows", lambda: env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"], variant=w["svariant"]))
+        else:
+            run("features", lambda: E.q_features_needed(face, Wf, bf, A, ri, w["y0"], w["dy"]))
+            run("table_term", lambda: torch.addmm(self.base, face.view(T, P * 60), self.Mz_f, out=w["h0"]))   # (K = 60 P: small)
+            run("fc1_dense", (lambda: E.q_fc1_dense(w["y0"], self.Wd, w["h0"])) if gemm == "mfma" else
+                (lambda: w["h0"].addmm_(w["y0"], self.Wd)))
+        # The H0 chain (first layer of the rows -> G -> gather) and the D chain (D rows -> dY -> D) share only their inputs: both
+        # GEMMs are a few hundred tiles -- one or two rounds over the 256 CUs, the launch as long as its last round -- and the
+        # bookkeeping kernels are latency-bound, so the D chain runs on a SIDE STREAM beside the H0 chain.
+        with _beside(w, "fork", two):
+            if all_:
+                run("shared_need", lambda: env.q_shared_need(w["row_index"], w["srows"], w["sseg"], w["scap"], w["dws"], w["cap"], ri,
+                                                             w["drep"], sg, rc))
+                run("features", lambda: E.q_features_drows(face, Wf, bf, A, w["srep"], w["drep"], sg, w["dy"]))
+            elif shared:
+                run("features", lambda: E.q_features_needed(face, Wf, bf, A, ri, None, w["dy"]))
+            run("fc1_rows", lambda: E.q_fc1_rows(w["dy"], sg, rc, self.W2, self.Z, w["d"]))   # D = dY x fc1[rank] + Z[rank][count]
+        if shared:
+            # G[row] = Y[row] x fc1[rank] + column x Mz[rank] (the table term is linear in the face: folded into the rows -- the
+            # column rides behind Y in the row, Mz[rank] behind fc1[rank] in the operand: one K = 288 / 304 product)
+            run("features_shared", lambda: E.q_features_rows(face, Wf, bf, w["srep"], w["sseg"], w["ys"]))
+            run("fc1_shared", lambda: E.q_fc1_rows_k(w["ys"], w["sseg"], self.W2x, w["g"]))
+            run("gather_h0", lambda: E.q_gather_h0(w["g"], w["srows"], w["h0"], base=self.base))   # H0[t] = base + sum_r G[row(t, r)]
+        _join(w, two)
+        return NeededU(w["h0"], w["d"], ri, sg)
 
     @staticmethod
     def need_sets(rows, offsets, T):
@@ -627,14 +631,13 @@ class PolicyLoop:
         return g
 
     def profile(self, n=10):
-        """Per-stage device time of n iterations (HIP events on the launching stream around every stage)
-        with each stage's algorithmic FLOP or bytes: {stage: {"us", "kernel", "flop" | "bytes", "note"}}.  Synchronises."""
-        from . import engine as E
-        env, fq, T, P = self.env, self.fq, self.env.T, self.fq.P
-        w = None
-        names = ("need", "shared_rows", "features_shared", "features", "table_term", "fc1_dense", "fc1_shared", "gather_h0", "shared_need",
-                 "fc1_rows", "row_stage", "env_step")
-        ev = {k: [] for k in names}
+        """Per-stage device time of n iterations: FactorisedQ.needed itself, issued through its stage hook with HIP events on the
+        launching stream around every stage, then the row stage and the step; with each stage's algorithmic FLOP or bytes:
+        {stage: {"us", "kernel", "flop" | "bytes", "note"}}.  Synchronises."""
+        from .engine import shared_row_width
+        env, fq, T, P, H = self.env, self.fq, self.env.T, self.fq.P, self.fq.H
+        shared, all_ = bool(self.shared), self.shared == "all"
+        ev = {}
         rows_needed = rows_padded = moves = rows_shared = rows_shared_padded = rows_private = 0
 
         def timed(name, fn):
@@ -642,109 +645,78 @@ class PolicyLoop:
             a.record()
             fn()
             b.record()
-            ev[name].append((a, b))
+            ev.setdefault(name, []).append((a, b))
 
         self.q_values()                                                   # (workspace exists)
         w = fq._ws[("needed", self.face.device, T)]
         for _ in range(int(n)):
-            timed("need", lambda: env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"]))
-            if self.shared:
-                timed("shared_rows", lambda: env.q_shared_rows(w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"],
-                                                               variant=w["svariant"]))
-                timed("features_shared", lambda: E.q_features_rows(self.face, fq.Wf, fq.bias_f, w["srep"], w["sseg"], w["ys"]))
-                timed("fc1_shared", lambda: E.q_fc1_rows_k(w["ys"], w["sseg"], fq.W2x, w["g"]))
-                timed("gather_h0", lambda: E.q_gather_h0(w["g"], w["srows"], w["h0"], base=fq.base))
-                if self.shared == "all":
-                    timed("shared_need", lambda: env.q_shared_need(w["row_index"], w["srows"], w["sseg"], w["scap"], w["dws"], w["cap"],
-                                                                   w["row_index2"], w["drep"], w["dseg"], w["drow_cnt"]))
-                    timed("features", lambda: E.q_features_drows(self.face, fq.Wf, fq.bias_f, fq.A, w["srep"], w["drep"], w["dseg"], w["dy"]))
-                else:
-                    timed("features", lambda: E.q_features_needed(self.face, fq.Wf, fq.bias_f, fq.A, w["row_index"], None, w["dy"]))
+            nu = fq.needed(env, self.face, gemm=self.gemm, shared=self.shared, hook=timed)
+            timed("row_stage", lambda: fq.q_slab(env, nu, out=self.q))
+            seg = nu.seg.cpu()
+            rows_needed += int(seg[32]); rows_padded += int(seg[15]); moves += int(env.counts.sum())
+            if shared:
                 sseg = w["sseg"].cpu()
                 rows_shared += int(sseg[32]); rows_shared_padded += int(sseg[15])
-            else:
-                timed("features", lambda: E.q_features_needed(self.face, fq.Wf, fq.bias_f, fq.A, w["row_index"], w["y0"], w["dy"]))
-                timed("table_term", lambda: torch.addmm(fq.base, self.face.view(T, P * 60), fq.Mz_f, out=w["h0"]))
-                if self.gemm == "mfma":
-                    timed("fc1_dense", lambda: E.q_fc1_dense(w["y0"], fq.Wd, w["h0"]))
-                else:
-                    timed("fc1_dense", lambda: w["h0"].addmm_(w["y0"], fq.Wd))
-            all_ = self.shared == "all"
-            sg, rc, ri = (w["dseg"], w["drow_cnt"], w["row_index2"]) if all_ else (w["seg"], w["row_cnt"], w["row_index"])
-            timed("fc1_rows", lambda: E.q_fc1_rows(w["dy"], sg, rc, fq.W2, fq.Z, w["d"]))
-            timed("row_stage", lambda: env.q_slab_needed(w["h0"], w["d"], ri, fq.w2, fq.b2, out=self.q))
-            seg = sg.cpu()
             if all_:
                 rows_private += int(w["seg"].cpu()[32])
-            rows_needed += int(seg[32]); rows_padded += int(seg[15]); moves += int(env.counts.sum())
             timed("env_step", lambda: env.policy_step_slab(self.q, self.epsilon, face_variant=self.variant, face_out=self.face,
                                                            choice_out=self.choice, auto_reset=self.auto_reset))
         torch.cuda.synchronize(env.device)
-        us = {k: sum(a.elapsed_time(b) for a, b in v) * 1e3 / len(v) for k, v in ev.items() if v}
         rn, rp, mv = rows_needed / n, rows_padded / n, moves / n
-        H = fq.H
-        if self.shared:
-            rs, rsp = rows_shared / n, rows_shared_padded / n
-            K = E.shared_row_width(P)
-            region = 2048
-            while region < 2 * T:                                          # the hashed finder's region per rank (ddz_qnet.h 5b)
-                region *= 2
-            nslot = 15 * region
-            return {
-                "need": {"us": us["need"], "kernel": "k_q_need_mask + k_q_need_scan + k_q_need_assign", "bytes": mv * 16 + T * (8 + 8 + 256),
-                         "note": "list rows read, need sets written and read, row_index written"},
-                "shared_rows": ({"us": us["shared_rows"], "kernel": "memset + k_qs_mark + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
-                                 "bytes": T * 176 + 3 * 4134375 * 4 + T * 16 * 4 * 3 + rs * 8,
-                                 "note": f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
-                                         "state read, the 16.5-MB slot table cleared / counted / assigned, rows [T,16] written"}
-                                if self.variant == 3 else
-                                {"us": us["shared_rows"], "kernel": f"memset + k_qs_hmark<{self.variant}> + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
-                                 "bytes": T * 176 + nslot * (12 + 4 + 4) + T * 16 * 4 * 3 + rs * 8,
-                                 "note": f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
-                                         f"state read, the hashed table ({nslot} slots, {nslot * 12 / 1e6:.1f} MB) cleared / probed / counted / "
-                                         "assigned, rows [T,16] written"}),
-                "features_shared": {"us": us["features_shared"], "kernel": f"k_q_feat_rows<{P}>", "bytes": rs * (P * 16 + K * 4),
-                                    "note": f"first layer (count 0) of the shared rows + the table term of their columns (linear in the "
-                                            f"face: folded into the rows -- no [T, {60 * P}] x [{60 * P}, 256] GEMM per iteration)"},
-                "fc1_shared": {"us": us["fc1_shared"], "kernel": "k_fc1<true>", "flop": 2.0 * rs * K * H,
-                               "note": f"G = [Y | column] x [fc1[rank] ; Mz[rank]] (K = {K}) over the {rs:.0f} shared rows ({rsp:.0f} with the padding of the fifteen "
-                                       f"segments) -- the dense form of the same term is 2 x {T} x 3840 x 256 = {2.0 * T * 15 * H * H / 1e9:.0f} GFLOP"},
-                "gather_h0": {"us": us["gather_h0"], "kernel": "k_qs_gather", "bytes": T * (64 + 2 * H * 4) + rs * H * 4,
-                              "note": f"H0 read and written, rows [T,16] read, every row of G once ({rs * H * 4 / 1e6:.0f} MB: the fifteen "
-                                      f"1-KB reads per table -- {T * 15 * H * 4 / 1e9:.2f} GB -- are served by L2 / MALL)"},
-                **({"shared_need": {"us": us["shared_need"], "kernel": "memset + k_qd_mark + k_qd_count + k_qd_seg + k_qd_assign + k_qd_remap",
-                                    "bytes": T * 64 * 4 * 3 + T * 64 + rs * 16 * 3 + rn * 5, "needed_triples": rows_private / n,
-                                    "note": f"one D row per distinct (shared row, count) some table needs: {rn:.0f} rows for the "
-                                            f"{rows_private / n:.0f} needed (table, rank, count) triples ({rows_private / n / T:.2f} per table)"},
-                    "features": {"us": us["features"], "kernel": f"k_q_feat_drows<{P}>", "bytes": rn * (P * 16 + H * 4 + 8),
-                                 "note": "dY of the shared D rows"}} if self.shared == "all" else
-                   {"features": {"us": us["features"], "kernel": f"k_q_feat_needed<{P}> (y0 = null)", "bytes": T * P * 240 + rn * H * 4 + T * 256,
-                                 "note": "face + row_index read, dY [needed rows, 256] written; ranks no legal move touches are skipped"}}),
-                "fc1_rows": {"us": us["fc1_rows"], "kernel": "k_fc1<true>", "flop": 2.0 * rn * H * H,
-                             "note": f"D = dY x fc1[rank]: {rn:.0f} rows per iteration ({rn / T:.2f} per table), {rp:.0f} computed "
-                                     "with the padding of the fifteen tile-aligned segments; FLOP of the rows"},
-                "row_stage": {"us": us["row_stage"], "kernel": "k_q_slab_needed", "bytes": T * H * 4 + rn * H * 4 + mv * 20,
-                              "note": "H0 + the D rows + the list rows read, q written"},
-                "env_step": {"us": us["env_step"], "kernel": "k_slab<4,true>", "bytes": T * (2 * 176 + P * 240 + 8) + mv * 24,
-                             "note": "arg-max over q, apply, new lists, new face"},
-            }
-        return {
-            "need": {"us": us["need"], "kernel": "k_q_need_mask + k_q_need_scan + k_q_need_assign", "bytes": mv * 16 + T * (8 + 8 + 256),
+        rs, rsp, priv = rows_shared / n, rows_shared_padded / n, rows_private / n
+        K = shared_row_width(P)
+        region = 2048
+        while region < 2 * T:                                              # the hashed finder's region per rank (ddz_qnet.h 5b)
+            region *= 2
+        nslot = 15 * region
+        distinct = f"one row per distinct (rank, face column): {rs:.0f} of the {15 * T} columns ({rs / (15 * T):.3f}); "
+        nd = "" if shared else "needed "
+        # one description per stage, in the order of the report; the stages that ran select theirs
+        stages = {
+            "need": {"kernel": "k_q_need_mask + k_q_need_scan + k_q_need_assign", "bytes": mv * 16 + T * (8 + 8 + 256),
                      "note": "list rows read, need sets written and read, row_index written"},
-            "features": {"us": us["features"], "kernel": f"k_q_feat_needed<{P}>", "bytes": T * P * 240 + T * 15 * H * 4 + rn * H * 4 + T * 256,
-                         "note": "face + row_index read, y0 [T, 3840] + dY [needed rows, 256] written"},
-            "table_term": {"us": us["table_term"], "kernel": "torch.addmm (hipBLASLt)", "flop": 2.0 * T * P * 60 * H,
+            "shared_rows": ({"kernel": "memset + k_qs_mark + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
+                             "bytes": T * 176 + 3 * 4134375 * 4 + T * 16 * 4 * 3 + rs * 8,
+                             "note": distinct + "state read, the 16.5-MB slot table cleared / counted / assigned, rows [T,16] written"}
+                            if self.variant == 3 else
+                            {"kernel": f"memset + k_qs_hmark<{self.variant}> + k_qs_count + k_qs_seg + k_qs_assign + k_qs_rows",
+                             "bytes": T * 176 + nslot * (12 + 4 + 4) + T * 16 * 4 * 3 + rs * 8,
+                             "note": distinct + f"state read, the hashed table ({nslot} slots, {nslot * 12 / 1e6:.1f} MB) cleared / probed / "
+                                     "counted / assigned, rows [T,16] written"}),
+            "features_shared": {"kernel": f"k_q_feat_rows<{P}>", "bytes": rs * (P * 16 + K * 4),
+                                "note": f"first layer (count 0) of the shared rows + the table term of their columns (linear in the "
+                                        f"face: folded into the rows -- no [T, {60 * P}] x [{60 * P}, 256] GEMM per iteration)"},
+            "fc1_shared": {"kernel": "k_fc1<true>", "flop": 2.0 * rs * K * H,
+                           "note": f"G = [Y | column] x [fc1[rank] ; Mz[rank]] (K = {K}) over the {rs:.0f} shared rows ({rsp:.0f} with the padding of the fifteen "
+                                   f"segments) -- the dense form of the same term is 2 x {T} x 3840 x 256 = {2.0 * T * 15 * H * H / 1e9:.0f} GFLOP"},
+            "gather_h0": {"kernel": "k_qs_gather", "bytes": T * (64 + 2 * H * 4) + rs * H * 4,
+                          "note": f"H0 read and written, rows [T,16] read, every row of G once ({rs * H * 4 / 1e6:.0f} MB: the fifteen "
+                                  f"1-KB reads per table -- {T * 15 * H * 4 / 1e9:.2f} GB -- are served by L2 / MALL)"},
+            "shared_need": {"kernel": "memset + k_qd_mark + k_qd_count + k_qd_seg + k_qd_assign + k_qd_remap",
+                            "bytes": T * 64 * 4 * 3 + T * 64 + rs * 16 * 3 + rn * 5, "needed_triples": priv,
+                            "note": f"one D row per distinct (shared row, count) some table needs: {rn:.0f} rows for the "
+                                    f"{priv:.0f} needed (table, rank, count) triples ({priv / T:.2f} per table)"},
+            "features": ({"kernel": f"k_q_feat_drows<{P}>", "bytes": rn * (P * 16 + H * 4 + 8), "note": "dY of the shared D rows"}
+                         if all_ else
+                         {"kernel": f"k_q_feat_needed<{P}> (y0 = null)", "bytes": T * P * 240 + rn * H * 4 + T * 256,
+                          "note": "face + row_index read, dY [needed rows, 256] written; ranks no legal move touches are skipped"}
+                         if shared else
+                         {"kernel": f"k_q_feat_needed<{P}>", "bytes": T * P * 240 + T * 15 * H * 4 + rn * H * 4 + T * 256,
+                          "note": "face + row_index read, y0 [T, 3840] + dY [needed rows, 256] written"}),
+            "table_term": {"kernel": "torch.addmm (hipBLASLt)", "flop": 2.0 * T * P * 60 * H,
                            "note": "fc1 bias + the face part of conv_shunzi: [T, 60 P] x [60 P, 256]"},
-            "fc1_dense": {"us": us["fc1_dense"], "kernel": "k_fc1<false>" if self.gemm == "mfma" else "torch.addmm (hipBLASLt)",
+            "fc1_dense": {"kernel": "k_fc1<false>" if self.gemm == "mfma" else "torch.addmm (hipBLASLt)",
                           "flop": 2.0 * T * 15 * H * H, "note": "H0 += y0 [T, 3840] x Wd [3840, 256]"},
-            "fc1_rows": {"us": us["fc1_rows"], "kernel": "k_fc1<true>", "flop": 2.0 * rn * H * H,
-                         "note": f"D = dY x fc1[rank]: {rn:.0f} needed rows per iteration ({rn / T:.2f} per table), {rp:.0f} computed "
-                                 "with the padding of the fifteen tile-aligned (256-row) segments; FLOP of the needed rows"},
-            "row_stage": {"us": us["row_stage"], "kernel": "k_q_slab_needed", "bytes": T * H * 4 + rn * H * 4 + mv * 20,
-                          "note": "H0 + the needed D rows + the list rows read, q written"},
-            "env_step": {"us": us["env_step"], "kernel": "k_slab<4,true>", "bytes": T * (2 * 176 + P * 240 + 8) + mv * 24,
+            "fc1_rows": {"kernel": "k_fc1<true>", "flop": 2.0 * rn * H * H,
+                         "note": f"D = dY x fc1[rank]: {rn:.0f} {nd}rows per iteration ({rn / T:.2f} per table), {rp:.0f} computed "
+                                 f"with the padding of the fifteen tile-aligned {'' if shared else '(256-row) '}segments; FLOP of the {nd}rows"},
+            "row_stage": {"kernel": "k_q_slab_needed", "bytes": T * H * 4 + rn * H * 4 + mv * 20,
+                          "note": f"H0 + the {nd}D rows + the list rows read, q written"},
+            "env_step": {"kernel": "k_slab<4,true>", "bytes": T * (2 * 176 + P * 240 + 8) + mv * 24,
                          "note": "arg-max over q, apply, new lists, new face"},
         }
+        us = {k: sum(a.elapsed_time(b) for a, b in v) * 1e3 / len(v) for k, v in ev.items()}
+        return {k: {"us": us[k], **d} for k, d in stages.items() if k in us}
 
     def variants(self, timed_loop, sync):
         """env steps/s of the other forms of the same loop on the same environment (bench.py): H0 from the dense K = 3840
@@ -867,24 +839,18 @@ class RoleQ:
         if tuple(face.shape[1:]) != (P, 15, 4) or T != env.T or not face.is_cuda:
             raise ValueError(f"face must be a device tensor [T,{P},15,4] of the environment's tables")
         w = self._workspace(env, face)
-        cur = torch.cuda.current_stream(face.device)
-        w["fork0"].record(cur)
-        w["side"].wait_event(w["fork0"])
-        with torch.cuda.stream(w["side"]):
+        with _beside(w, "fork0", True):
             env.q_need(w["cap"], w["scratch"], w["row_index"], w["seg"], w["row_cnt"])
         env.q_roles_rows(self.variant, self.net_of_role, N, w["sws"], w["scap"], w["srows"], w["srep"], w["sseg"], w["slot"])
-        w["fork"].record(cur)
-        w["side"].wait_event(w["fork"])
-        with torch.cuda.stream(w["side"]):
+        with _beside(w, "fork", True):
             env.q_roles_need(N, w["row_index"], w["srows"], w["sseg"], w["scap"], w["dws"], w["cap"], w["row_index2"], w["drep"],
                              w["dseg"], w["drow_cnt"])
             E.q_roles_features_drows(face, N, self.Wf, self.bias_f, self.A, w["srep"], w["scap"], w["drep"], w["dseg"], w["dy"], w["cap"])
             E.q_roles_fc1_rows(N, w["dy"], w["dseg"], w["drow_cnt"], self.W2, self.Z, w["d"], w["cap"])
-            w["join"].record(w["side"])
         E.q_roles_features_rows(face, N, self.Wf, self.bias_f, w["srep"], w["sseg"], w["ys"], w["scap"])
         E.q_roles_fc1_rows_k(N, w["ys"], w["sseg"], self.W2x, w["g"], w["scap"])
         E.q_roles_gather_h0(N, w["g"], w["srows"], w["slot"], self.base, w["h0"])   # H0[t] = base[slot] + sum_r G[row(t, r)]
-        cur.wait_event(w["join"])
+        _join(w, True)
         return RolesU(w["h0"], w["d"], w["row_index2"], w["dseg"], w["slot"])
 
     @torch.no_grad()
