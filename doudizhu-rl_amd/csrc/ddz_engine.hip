@@ -955,7 +955,8 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
 // block barrier after the prologue.  One wavefront per table:
 //   scan once, staging nib|category of every legal move in the wave's LDS list (its length
 //   is the list size, known before the pick) -> flush the list as coalesced 16-byte rows
-//   -> pick by engine RNG from the staged list -> apply / terminal / deal -> store state.
+//   -> pick by engine RNG from the staged list -> apply / terminal / deal, all on the PACKED table (nibble rows);
+//   the state rows are rebuilt and stored once per table and launch, after its last iteration.
 struct RolloutArgs {
   uint8_t* state;
   int64_t T;
@@ -1014,13 +1015,19 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     const int64_t t = t0 + i;
     stamps.mark(0);  // prologue (or previous table's tail)
     uint4* trow = (uint4*)(a.state + t * STATE_ROW_BYTES);
-    uint4 R = Rnext;  // lane f < 11 holds row f of the table for the whole launch
+    const uint4 R = Rnext;  // lane f < 11 holds row f of the table: decoded below, dead afterwards
     if (i + 1 < ntab && lane < DDZ_NFIELDS) Rnext = ((const uint4*)(a.state + (t + 1) * STATE_ROW_BYTES))[lane];
     const uint64_t gid = a.gid_base + (uint64_t)t;
-    // decode once; afterwards the table's scalars are carried across the iterations
-    const uint64_t P = pack_row(R);
+    // decode once; afterwards the table is carried PACKED across the iterations and its rows are rebuilt and stored once,
+    // after the last one (nothing can read the state between the iterations of a launch):
+    //   P, aux   lane f < 10: row f as 15 nibbles and its byte 15 (cards left / category / whatever a foreign state holds).
+    //            The hand lanes of P go stale: the hands are carried as hc / hn / hp and put back by role at the end.
+    //   the meta row as scalars: role, ply, episode, my_hi (bytes 6..7) and mw (bytes 12..15)
+    uint64_t P = pack_row(R);
+    uint32_t aux = R.w >> 24;
     const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META), mz = rl(R.z, DDZ_F_META);
     const uint32_t my_hi = my & 0xFFFF0000u;
+    uint32_t mw = rl(R.w, DDZ_F_META);
     int role = mx & 0xFF;
     if (role > 2) role = 0;
     const bool active = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF);  // dealt and not done
@@ -1035,8 +1042,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     {
       const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
       const uint64_t n1 = rl64(P, DDZ_F_RECENT0 + rm1), n2 = rl64(P, DDZ_F_RECENT0 + rp1);
-      if (n1) trick = info_of_row(n1, (int)(rl(R.w, DDZ_F_RECENT0 + rm1) >> 24));
-      else if (n2) { trick = info_of_row(n2, (int)(rl(R.w, DDZ_F_RECENT0 + rp1) >> 24)); passes = 1; }
+      if (n1) trick = info_of_row(n1, (int)rl(aux, DDZ_F_RECENT0 + rm1));
+      else if (n2) { trick = info_of_row(n2, (int)rl(aux, DDZ_F_RECENT0 + rp1)); passes = 1; }
     }
     // engine RNG draws for 64 consecutive plies at once: lane j holds the draw of ply dbase + j
     uint32_t draws = 0, dnext = 64;  // lane dnext holds the next draw; 64 = refill
@@ -1057,6 +1064,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       }
       continue;
     }
+    int idle = 0;  // iterations that applied no ply (n <= 0: only behind the STAGE_CAP guard)
     for (int it = (int)a.n_iters; it > 0; --it) {
       uint4 tr0 = make_uint4(0, 0, 0, 0);
       uint4 tr1 = make_uint4((uint32_t)role, ply << 16, episode, 0xFFFFFFFFu);
@@ -1076,7 +1084,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       const uint32_t draw = rl(draws, (int)dnext);
       stamps.mark(1);  // per-iteration setup: frozen check, draw refresh, hand/info select
       int n = 0, idx = -1;
-      uint4 c = make_uint4(0, 0, 0, 0);  // the chosen row, same value in every lane
+      uint4 c = make_uint4(0, 0, 0, 0);  // TRAJ: the chosen row for the record, same value in every lane
       uint64_t snib = 0;                  // ... as a nib, its category and value | len << 8
       uint32_t scat = 0, svlv = 0, ncards = 0;  // ... and its number of cards
       const int lc0 = (int)(info & 0xFF);
@@ -1114,20 +1122,10 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83 (n >= 1: pass)
         const int src = __builtin_ctz((uint32_t)__ballot(pre == idx) & okm);
         const int sr = (src < 16 ? src - 1 : src - 16) & 15;
-#ifndef DDZ_ROLLOUT_PICK_SCALAR
-        c = make_uint4(rl(row.x, src), rl(row.y, src), rl(row.z, src), rl(row.w, src));
-#endif
+        if (TRAJ) c = make_uint4(rl(row.x, src), rl(row.y, src), rl(row.z, src), rl(row.w, src));
         if (src == 0) { snib = 0; scat = EMPTY; svlv = 1u << 8; }
         else if (src == 29) { snib = (1ull << 52) | (1ull << 56); scat = BIGBANG; svlv = 100u | (1u << 8); ncards = 2; }
         else { scat = src < 16 ? (uint32_t)lc0 : (uint32_t)QUADRIC; snib = (uint64_t)scat << (4 * sr); svlv = (uint32_t)sr | (1u << 8); ncards = scat; }
-#ifdef DDZ_ROLLOUT_PICK_SCALAR
-        {  // the chosen row from the chosen lane's number, scalar arithmetic instead of four v_readlane: measured SLOWER (3.78
-           // against 4.06 G env steps/s at 65,536 tables: the CU's scalar unit is the busier one); kept for the record
-          const uint32_t cp = (src == 0 || src == 29) ? 0u : scat, dvs = cp << (8 * (sr & 3)), wq = (uint32_t)sr >> 2;
-          c = make_uint4(wq == 0 ? dvs : 0u, wq == 1 ? dvs : 0u, wq == 2 ? dvs : 0u,
-                         (wq == 3 ? dvs : 0u) | (cp << 24) | (src == 29 ? (0x00010100u | ((uint32_t)BIGBANG << 24)) : 0u));
-        }
-#endif
         stamps.mark(5);  // fast path: list + pick
       } else {
         const Out o{nullptr, nullptr, 0, 0, stage, svl, sid};
@@ -1152,7 +1150,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           const uint64_t e = stage[idx];           // LDS broadcast read
           const uint64_t anib = e & 0x0FFFFFFFFFFFFFFFull;
           const uint32_t acat = (uint32_t)(e >> 60);
-          c = unpack_row(anib, acat);
+          if (TRAJ) c = unpack_row(anib, acat);
           snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
           scat = rfl(acat);
           svlv = rfl((uint32_t)svl[idx]);
@@ -1163,23 +1161,20 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       tr1.y |= (uint32_t)n & 0xFFFF;
       if (n <= 0) {
         tr1.x |= 2u << 24;
+        idle += 1;
       } else {
-        if (snib) {  // a pass (half of all plies) moves no card: only recent_handout and the turn change
-          const uint32_t cw3 = c.w & 0x00FFFFFFu;
-          if (lane == DDZ_F_HAND0 + role) {  // envi.py:39-43, byte-wise (no borrow crosses a byte)
-            R.x -= c.x; R.y -= c.y; R.z -= c.z; R.w -= cw3 + (ncards << 24);
-          } else if (lane == DDZ_F_HIST0 + role || lane == DDZ_F_TAKEN) {
-            R.x += c.x; R.y += c.y; R.z += c.z; R.w += cw3;
-          }
+        {  // envi.py:39-43 on the packed rows, as lane masks (a pass adds zeros; no nibble carries: counts <= 4, jokers <= 1)
+          const int d = lane - role;
+          const uint64_t add = (d == DDZ_F_HIST0 || lane == DDZ_F_TAKEN) ? snib : 0ull;  // history[role], taken
+          P = d == DDZ_F_RECENT0 ? snib : P + add;                                       // recent_handout[role]
+          aux = d == DDZ_F_RECENT0 ? scat : d == DDZ_F_HAND0 ? aux - ncards : aux;       // ... its category; cards left
         }
-        if (lane == DDZ_F_RECENT0 + role) R = c;
         stamps.mark(6);  // row updates
         // carried scalars
         const uint64_t hnew = hand - snib;
         if (snib) { trick = scat | (svlv << 8); passes = 0; } else { passes += 1; }
         const bool won = hnew == 0;
         const uint32_t o_reward = won ? (role == 1 ? 0xFFu : 1u) : 0u;  // rule_play.py:14
-        s_ply += 1;
         tr0 = c;
         tr1.x |= (uint32_t)won << 8 | o_reward << 16;
         tr1.w = (uint32_t)idx;
@@ -1202,23 +1197,31 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           deal_wave_lds(gid, episode, dk0, dk1, lane, stage, h0, h1, h2);  // (the staging list is idle between two lists)
 #endif
           hc = h1; hn = h2; hp = h0;  // the lord (role 1) moves first, then down (2), then up (0)
-          R = lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-              : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, episode, 0) : make_uint4(0, 0, 0, 0);
+          P = 0;  // (the hands: hc / hn / hp)
+          aux = lane == 1 ? 20u : lane < 3 ? 17u : 0u;
+          mw = 0;
           role = 1; ply = 0; trick = mk_info(EMPTY, 0, 1); passes = 0; dnext = 64;
         } else {
           role = role == 2 ? 0 : role + 1;  // lord -> down -> up, game.py:173-181
           hc = hn; hn = hp; hp = hnew;
-          if (lane == DDZ_F_META) { R.x = (uint32_t)role | (0xFFu << 16); R.y = my_hi | (ply & 0xFFFF); }  // z = episode, w: unchanged
         }
         stamps.mark(8);  // deal / turn change
-        if (lane < DDZ_NFIELDS) trow[lane] = R;  // one coalesced 176-byte store
-        stamps.mark(9);  // state store
       }
       if (TRAJ && lane < 2) tj[lane] = sel4(lane == 0, tr0, tr1);
       if (TRAJ) tj += 2 * a.T;
-      stamps.mark(4);  // pick + apply + deal + state/trajectory stores
+      stamps.mark(4);  // pick + apply + deal + trajectory store
       __builtin_amdgcn_wave_barrier();  // the staging list is reused by the next iteration / table
     }
+    s_ply += (int)a.n_iters - idle;
+    if (idle < (int)a.n_iters) {  // the rows after the last applied ply: the hands back by role, the meta row from its scalars
+      const int rp1 = role == 2 ? 0 : role + 1, rm1 = role == 0 ? 2 : role - 1;
+      const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
+      uint4 Rf = unpack_row(Pf, aux);
+      // a deal leaves ply = 0 and the fresh bytes 6..7; every other ply keeps the table's own (my_hi)
+      if (lane == DDZ_F_META) Rf = make_uint4((uint32_t)role | (0xFFu << 16), ply == 0 ? 1u << 16 : my_hi | (ply & 0xFFFF), episode, mw);
+      if (lane < DDZ_NFIELDS) trow[lane] = Rf;  // one coalesced 176-byte store per table and launch
+    }
+    stamps.mark(9);  // state store
   }
   stamps.store(t0, lane == 0 && ntab > 0);
   if (ntab > 0 && lane == 0) {  // each wave owns its statistics slot: no atomics, no barrier

@@ -52,7 +52,10 @@ extern "C" {
  *   6..8  recent_handout of the role, zeros for a pass (envi.py:43); byte 15 = category
  *   9     taken: all cards played (envi.py:40)
  *   10    meta: [0] role to move, [1] done, [2] winner (0xFF running), [3] i8 last r,
- *               [4..5] u16 ply, [6] dealt, [8..11] u32 episode                          */
+ *               [4..5] u16 ply, [6] dealt, [8..11] u32 episode
+ * A count byte (bytes 0..14 of rows 0..9) is at most 15.  The rollouts carry the table as nibbles: of a larger
+ * count byte in an imported state they see, and write back, the low four bits only.  Byte 15 of every row is
+ * kept exactly.                                                                              */
 enum { DDZ_F_HAND0 = 0, DDZ_F_HIST0 = 3, DDZ_F_RECENT0 = 6, DDZ_F_TAKEN = 9, DDZ_F_META = 10 };
 
 /* step modes */
@@ -195,10 +198,11 @@ int ddz_get_moves_slab(int device_id, const int8_t* hands, const int8_t* lasts, 
  * envi.py:79-85): n_iters iterations of {legal list, step_random(auto_reset)} in ONE kernel
  * launch.  The lists are written in the SLAB layout: table t owns
  * rows[t * stride .. t * stride + counts[t]) (ascending canonical id, same rows as
- * ddz_legal), so no table depends on another: a wavefront keeps its table's rows in
- * registers across the iterations and stores the list, the state and the trajectory
- * record of EVERY iteration (each iteration overwrites the table's slab; after the call
- * counts/rows hold the lists of the last pre-step states).
+ * ddz_legal), so no table depends on another: a wavefront keeps its table in registers
+ * across the iterations and stores the list and the trajectory record of EVERY iteration
+ * (each iteration overwrites the table's slab; after the call counts/rows hold the lists
+ * of the last pre-step states).  The state is stored ONCE, after the last iteration:
+ * nothing can read it between the iterations of a launch.
  *   counts int32[T]; rows int8[T * stride][16]; ids int32[T * stride] or NULL;
  *   stride >= 512 covers every list of a <= 20-card hand (497 is the maximum);
  *   stats (device, int64[8], may be NULL) accumulates {plies, finished episodes, total legal

@@ -1,6 +1,8 @@
 """A/B of engine builds: for every shared library given (default: the product build), the random rollout (k_rollout) at 4096 and
 65,536 tables and step_slab(RANDOM) (k_slab) at 65,536, one child process per library.
-  python tools/lib_ab_probe.py [lib.so ...]"""
+  python tools/lib_ab_probe.py [--iters N] [lib.so ...]
+--iters: iterations per timed launch at 65,536 tables (default 1000).  Name a library several times (parent change parent
+change ...) for alternating samples: every child prints the best of its five launches."""
 import importlib
 import os
 import subprocess
@@ -10,6 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 if __name__ == "__main__":
+    ITERS = 1000
+    if len(sys.argv) > 2 and sys.argv[1] == "--iters":
+        ITERS = int(sys.argv[2])
+        del sys.argv[1:3]
     if len(sys.argv) > 2 and sys.argv[1] == "--child":
         import torch
         if sys.argv[2] != "product":
@@ -20,7 +26,7 @@ if __name__ == "__main__":
             env = pkg.BatchedEnv(T, seed=0, want_ids=False)
             env.reset(); env.rollout_random(300)
             torch.cuda.synchronize()
-            n = 4000 if T == 4096 else 1000
+            n = 4000 if T == 4096 else ITERS
             best = min(env.rollout_random_timed(n) for _ in range(5))
             out.append(f"rollout {T}: {best * 1e3 / n:7.3f} us = {T * n / best / 1e6:5.2f} G/s")
             if T == 65536:
@@ -56,4 +62,5 @@ if __name__ == "__main__":
         print(f"{os.path.basename(sys.argv[2]):28s} " + "; ".join(out), flush=True)
     else:
         for lib in (sys.argv[1:] or ["product"]):
-            subprocess.call([sys.executable, os.path.abspath(__file__), "--child", lib if lib == "product" else os.path.abspath(lib)])
+            subprocess.call([sys.executable, os.path.abspath(__file__), "--iters", str(ITERS), "--child",
+                             lib if lib == "product" else os.path.abspath(lib)])

@@ -18,8 +18,9 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 P1="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_ANY"
 P2="SQ_WAVES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_WR"
-stats() { d=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o p -- "$@" > "$d.log" 2>&1; }
-pmc() { d=$1; c=$2; shift 2; rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$d" -o p -- "$@" > "$d.log" 2>&1; }
+# every profiled run under its own time limit; `set -e` ends the script at the first run that fails or is cut off
+stats() { d=$1; shift; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o p -- "$@" > "$d.log" 2>&1; }
+pmc() { d=$1; c=$2; shift 2; timeout -k 10 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$d" -o p -- "$@" > "$d.log" 2>&1; }
 for pass in "$@"; do
   O=gpurun_out/prof/$pass
   mkdir -p "$O"
@@ -33,7 +34,8 @@ for pass in "$@"; do
       pmc $O/pmc_mix "$P1" python3 tools/run_rollout.py 4096 20000
       # the headline configuration (65,536 tables): the same three passes
       for c in FETCH_SIZE WRITE_SIZE; do pmc $O/big_pmc_$c $c python3 tools/run_rollout.py 65536 500; done
-      pmc $O/big_pmc_mix "$P1" python3 tools/run_rollout.py 65536 2000 ;;
+      pmc $O/big_pmc_mix "$P1" python3 tools/run_rollout.py 65536 2000
+      stats $O/big_stats python3 tools/run_rollout.py 65536 2000 ;;
     slab)
       for T in 65536 4096; do
         for m in random fused; do
