@@ -261,6 +261,7 @@ int ddz_select_slab(ddz_env_t* env, const float* q, const int32_t* counts, int64
  * (the two joker ranks r = 13, 14 exist once: only cnt = 0, 1 are written for them).
  * face f32 [T][planes][15][4] (ddz_observe / ddz_policy_step_slab), wf f32 [planes * 4][1024], bias f32 [1024], acnt f32
  * [5][4][256] (weight-only tables, built by FactorisedQ.refresh from the network's conv weights); planes in {4, 6, 7, 9}.
+ * acnt[0] (count 0: an empty thermometer, all zeros) is NOT READ by any first-layer kernel: count 0 adds nothing.
  * The training glue (dqn_glue.FactorisedQ.tables, ragged_q) multiplies y by fc1 per rank.  Stateless; fp32.          */
 int ddz_q_features(int device_id, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                    const float* acnt, float* y, int64_t y_row_stride, void* stream);
@@ -292,7 +293,10 @@ int ddz_q_features(int device_id, const float* face, int64_t n_tables, int plane
  *   memory.  A table's needed rows are staged in LDS once (every move that takes that count of the rank uses the row); a
  *   move whose (r, c) has no row (a list that does not belong to this row_index) contributes nothing for that rank and
  *   raises status bit 5.
- * fp32 throughout (tests: 1e-5 against the literal nn.Conv2d network). */
+ * fp32 throughout (tests: 1e-5 against the literal nn.Conv2d network; and every kernel of this forward alone, EXACTLY,
+ * on integer / dyadic operands whose partial sums fp32 represents -- equal to an fp64 statement of the formulas above
+ * whatever the summation order -- and within gamma_n * sum |terms| of it on random operands:
+ * tests/test_gpu_q_kernels.py against tests/q_reference.py, the whole forward on an integer network included). */
 int ddz_q_fc1_tile_rows(void);   /* rows per tile of the fc1 kernel: segment starts and row_capacity are multiples of it */
 int64_t ddz_q_need_scratch_bytes(int64_t n_tables);
 int ddz_q_need(ddz_env_t* env, const int32_t* counts, const int8_t* rows, int64_t stride, int64_t row_capacity, void* scratch,
