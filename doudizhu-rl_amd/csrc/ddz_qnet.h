@@ -620,7 +620,13 @@ __global__ __launch_bounds__(TB, 4) void k_q_slab_needed(const float4* __restric
 // Every table still gets its exact H0 every iteration from the current weights -- nothing is cached across calls; what is
 // removed is the recomputation of identical subexpressions (equal to the dense form up to fp32 summation order: fifteen K = 256
 // chains added in rank order instead of one K = 3840 chain; tests: 1e-5).
-// Rows are found by direct addressing: slot[key], key = rank * QSH_COLS + column code (4,134,375 int32 slots, 16.5 MB):
+// Rows are found by direct addressing: slot[key], key = rank * QSH_COLS + column code (4,134,375 int32 slots, 16.5 MB).
+// DOMAIN (of this key and of the hashed one of section 5b, which carries the same ncode): the two opponents' card counts (byte
+// 15 of their hand rows) are saturated at 20 -- the table has 21 x 21 codes for (n1, n2).  Equal keys <=> equal columns holds
+// for card counts <= 20 (every state play reaches: a hand holds at most 20 cards; count bytes above 4 and role bytes above 2
+// are inside the domain: they read as 4 / role 0 in k_observe too).  Beyond it the row is still inside its rank's segment, but
+// is shared with the tables of the saturated key ((25, 5) reads as (20, 5): 0.8333333f and 0.8f in k_observe's face) and
+// carries the column of whichever instance won the slot.
 //   k_qs_mark   every (table, rank) writes its instance number into its slot (any winner: equal keys <=> equal columns)
 //   k_qs_count / k_qs_seg / k_qs_assign   occupied slots per 2048-key chunk -> rank segments (starts multiples of the GEMM tile)
 //               and chunk bases -> row number of every occupied slot in KEY ORDER (deterministic), rep[row] = an instance
@@ -753,8 +759,9 @@ __global__ __launch_bounds__(256) void k_qs_rows(const int32_t* __restrict__ slo
 // the history of (role - 1, role, role + 1), b1 / b2 = the recent handout of (role - 1, role + 1) (k_observe<1> / <2>).  Direct
 // addressing would need 15 x 5^7 x 441 = 517 M slots for variant 2, so the key is hashed instead:
 //   key   rank (4 bits) | the fields saturated at 4 (3 bits each, every field: none is dropped on the strength of a state
-//         invariant such as taken = h0 + h1 + h2 -- a corrupted or imported state must never alias two columns) | ncode (9 bits,
-//         as k_qs_mark's) -- 28 bits for variant 1, 34 for variant 2; the slot stores key + 1 (0 = empty)
+//         invariant such as taken = h0 + h1 + h2 -- inside the DOMAIN of section 5, card counts <= 20, a corrupted or imported
+//         state never aliases two columns) | ncode (9 bits, as k_qs_mark's, card counts saturated at 20: beyond 20 two columns
+//         can share a row as in the direct table) -- 28 bits for variant 1, 34 for variant 2; the slot stores key + 1 (0 = empty)
 //   table one region of R = max(2048, pow2 >= 2 T) slots per rank: a rank has at most T distinct keys, so the load stays <= 1/2
 //         and a probe always ends; slot = uint64 key word + int32 value (instance + 1, the layout k_qs_count / k_qs_assign /
 //         k_qs_rows read with cols = R, cpr = R / QSH_CHUNK: R is a multiple of QSH_CHUNK, no chunk straddles two ranks)

@@ -322,11 +322,18 @@ int ddz_q_slab_needed(ddz_env_t* env, const float* h0, const float* d, int64_t r
  *   segments, starts multiples of the tile).  row_capacity: a multiple of the tile, >= min(15 T, 4134375) + 15 tiles (then
  *   nothing can overflow).  ws: ddz_q_shared_ws_bytes() bytes (16.6 MB: one int32 slot per possible (rank, column)), 16-byte
  *   aligned, contents irrelevant on entry.  Row numbers follow the key order: deterministic.
+ *   DOMAIN: byte 15 of a hand row (the cards left) <= 20, as in every state play reaches.  The table has 21 x 21 codes for
+ *   (n1, n2), so a larger byte is read as 20: the row is still inside its rank's segment and nothing is indexed outside, but
+ *   it is shared with the tables of the saturated key, and whichever instance becomes rep[row] lends ALL of them its column
+ *   ((25, 5) shares the row of (20, 5): 0.8 and 0.8333333 in ddz_observe's face, one of the two in the row).  Count bytes
+ *   above 4 and a role byte above 2 are inside the domain (they read as 4 / role 0, as in ddz_observe).
  * ddz_q_shared_rows_hashed: the same outputs for the faces of EnvComplicated (variant 1, 7 planes: hand, taken, the three
  *   history planes, the two prob planes) and EnvCooperation (variant 2, 9 planes: + the two recent-handout planes), whose
  *   columns are too many to address directly (517 M for variant 2): the key (rank, hand_r, taken_r, the three history counts
  *   of rank r[, the two recent-handout counts], each saturated at 4, and the canonical (n1, n2) as above) is hashed into an
- *   open-addressed table with one region per rank (ddz_qnet.h section 5b).  variant must be 1 or 2 (else DDZ_EINVAL).
+ *   open-addressed table with one region per rank (ddz_qnet.h section 5b).  The same DOMAIN as ddz_q_shared_rows: cards left
+ *   <= 20; a larger byte is read as 20 and the row is shared with the saturated key's tables.  variant must be 1 or 2 (else
+ *   DDZ_EINVAL).
  *   row_capacity: a multiple of the tile, >= 15 T + 15 tiles (else DDZ_ECAP).  ws: ddz_q_shared_hash_ws_bytes(T) bytes
  *   (12 bytes per slot, 15 regions of max(2048, pow2 >= 2 T) slots: 23.6 MB at 65,536 tables), 16-byte aligned, contents
  *   irrelevant on entry.  Row numbers follow the slot order, which under hash collisions depends on which insert wins: the
@@ -387,7 +394,8 @@ int ddz_q_fc1_rows_k(int device_id, const float* y, int64_t k, const int32_t* se
  *   ddz_q_shared_rows' (variant 3) / ddz_q_shared_rows_hashed's (1, 2) and n_nets * row_capacity * 256 < 2^31 (else
  *   DDZ_ECAP).  ws: ddz_q_roles_ws_bytes(T, variant, n_nets) bytes = n_nets times the single-network workspace (16.5 MB /
  *   23.6 MB at 65,536 tables per slot, all of it cleared every call), 16-byte aligned.  Deterministic row numbers for variant
- *   3, not for 1 / 2 (as the single-network finders).
+ *   3, not for 1 / 2 (as the single-network finders).  Every variant has ddz_q_shared_rows' DOMAIN (cards left <= 20; beyond
+ *   it a row may be another table's column of the same slot and rank).
  * ddz_q_roles_features_rows / ddz_q_roles_fc1_rows_k: ddz_q_features_rows (no mz / g) / ddz_q_fc1_rows_k (no accumulate) on
  *   every slot's partition with the slot's weights: wf f32 [n_nets][planes * 4][1024], bias [n_nets][1024], ys f32 [n_nets *
  *   row_capacity][ys_ld], w2k f32 [n_nets][15][k][256], g f32 [n_nets * row_capacity][256].
