@@ -2274,6 +2274,15 @@ __device__ __forceinline__ int qp_col(int r, int c) { return r < 13 ? 4 * r + c 
 // count) are one 16-KB run of y.  Written once, read once by the fc1 GEMM: bound by its 5 x 1 KB of stores per pair.  (The torch statement of the same stage -- FactorisedQ.tables(fused=False) --
 // reads and writes the [T, 15, 4, 256] conv output ten times; this kernel never materialises it.)
 constexpr int QF_TILE = 16;  // tables per block
+// One plane's share of the four conv sums: w = the plane's ten weights of this channel (conv_k's k slots, k = 1..4, in a row),
+// x = the plane's four slots of one (table, rank).  THE statement of the first layer: every first-layer kernel (k_q_feat,
+// k_q_feat_needed, k_q_feat_rows, k_q_feat_drows) adds its planes through it, in plane order, so their Y agree bit for bit.
+__device__ __forceinline__ void q_feat_plane(const float (&w)[10], float4 x, float& s0, float& s1, float& s2, float& s3) {
+  s0 += w[0] * x.x;
+  s1 += w[1] * x.x + w[2] * x.y;
+  s2 += w[3] * x.x + w[4] * x.y + w[5] * x.z;
+  s3 += w[6] * x.x + w[7] * x.y + w[8] * x.z + w[9] * x.w;
+}
 template <int P>
 __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, int64_t T, const float* __restrict__ wf,
                                                const float* __restrict__ bias, const float* __restrict__ acnt,
@@ -2315,10 +2324,7 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
 #pragma unroll
       for (int p = 0; p < P; ++p) {
         const float4 x = s_face[(ti * P + p) * 15 + r];  // wave-uniform address: an LDS broadcast
-        s0 += w[p][0] * x.x;
-        s1 += w[p][1] * x.x + w[p][2] * x.y;
-        s2 += w[p][3] * x.x + w[p][4] * x.y + w[p][5] * x.z;
-        s3 += w[p][6] * x.x + w[p][7] * x.y + w[p][8] * x.z + w[p][9] * x.w;
+        q_feat_plane(w[p], x, s0, s1, s2, s3);
       }
       // (plain stores: y is read back by the fc1 GEMM right behind this kernel)
       float* d = dst + ti * ystride;
@@ -2758,6 +2764,34 @@ static int launch_q_features(int device, const float* face, int64_t n_tables, in
     default: return DDZ_EINVAL;
   }
   return check_launch();
+}
+
+// ---- host chains of the Q forward that more than one entry point issues (ddz_qnet.h sections 4-7) ----
+// rows of `ld` floats that a 32-bit element index still reaches: the bound on every row capacity
+constexpr int64_t q_row_limit(int64_t ld = QH) { return (((int64_t)1 << 31) - 1) / ld; }
+// the row finder's count -> segments -> assign over ONE partition: 15 regions of `cols` slots, cnt / base [15][cpr]
+template <bool DIRECT>
+static void launch_qs_number(hipStream_t st, int32_t* slots, int32_t* cnt, int32_t* base, int cols, int cpr, int32_t* seg, int32_t* rep,
+                             int64_t row_capacity) {
+  hipLaunchKernelGGL(k_qs_count<DIRECT>, dim3(15 * cpr), dim3(256), 0, st, (const int32_t*)slots, cnt, cols, cpr);
+  hipLaunchKernelGGL(k_qs_seg<DIRECT>, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity, cpr);
+  hipLaunchKernelGGL(k_qs_assign<DIRECT>, dim3(15 * cpr), dim3(256), 0, st, slots, (const int32_t*)base, rep, (int32_t)row_capacity, cols, cpr);
+}
+// the same for the D rows of ONE partition: `tiles` tiles of shared rows, cnt / base [tiles]
+static void launch_qd_number(hipStream_t st, int32_t* dslot, const int32_t* sseg, int32_t* cnt, int32_t* base, int64_t tiles, int32_t* dseg,
+                             int32_t* drep, uint8_t* row_cnt, int64_t row_capacity, int32_t* status) {
+  hipLaunchKernelGGL(k_qd_count, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)dslot, sseg, cnt);
+  hipLaunchKernelGGL(k_qd_seg, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, sseg, base, dseg, (int32_t)row_capacity, status);
+  hipLaunchKernelGGL(k_qd_assign, dim3((unsigned)tiles), dim3(256), 0, st, dslot, sseg, (const int32_t*)base, drep, row_cnt,
+                     (int32_t)row_capacity);
+}
+// the row stage's geometry (k_q_slab_needed / k_q_slab_roles): tables per wave, and the grid.  64 tables per block at most: the
+// blocks are the unit the hardware balances over the CUs, the tables inside a block are handed out by an LDS ticket
+static dim3 q_slab_grid(int64_t T, int& tpw) {
+  const int64_t v = (T + 4095) / 4096;
+  tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
+  const int64_t per_block = (int64_t)WPB * tpw;
+  return dim3((unsigned)((T + per_block - 1) / per_block));
 }
 
 static void fill_round_penalty(AutoArgs& a) {
@@ -3445,7 +3479,7 @@ int ddz_q_need(ddz_env_t* e, const int32_t* counts, const int8_t* rows, int64_t 
   if (!good(e)) return DDZ_EHANDLE;
   if (!counts || !rows || !scratch || !row_index || !seg || !row_cnt || stride < 1) return DDZ_EINVAL;
   if (!al(counts, 4) || !al(rows, 16) || !al(scratch, 256) || !al(row_index, 16) || !al(seg, 4)) return DDZ_EINVAL;
-  if (row_capacity < 15 * FC_M || row_capacity % FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_EINVAL;
+  if (row_capacity < 15 * FC_M || row_capacity % FC_M || row_capacity > q_row_limit()) return DDZ_EINVAL;
   if (scratch_bytes < ddz_q_need_scratch_bytes(e->T)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
@@ -3464,7 +3498,7 @@ int ddz_q_features_needed(int device, const float* face, int64_t n_tables, int p
                           const float* acnt, const int32_t* row_index, float* y0, float* dy, int64_t row_capacity, void* stream) {
   if (!face || !wf || !bias || !acnt || !row_index || !dy || n_tables <= 0) return DDZ_EINVAL;   // (y0 may be null: section 5)
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(acnt, 4) || !al(row_index, 16) || !al(y0, 4) || !al(dy, 4)) return DDZ_EINVAL;
-  if (row_capacity < 1 || row_capacity > (((int64_t)1 << 31) - 1) / QH || n_tables > ((int64_t)1 << 30)) return DDZ_ECAP;
+  if (row_capacity < 1 || row_capacity > q_row_limit() || n_tables > ((int64_t)1 << 30)) return DDZ_ECAP;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
   const dim3 grid((unsigned)((n_tables + QF_TILE - 1) / QF_TILE)), block(QH);
@@ -3495,7 +3529,7 @@ int ddz_q_fc1_rows(int device, const float* dy, const int32_t* seg, const uint8_
                    int64_t row_capacity, void* stream) {
   if (!dy || !seg || !w2 || !d || ((z == nullptr) != (row_cnt == nullptr))) return DDZ_EINVAL;   // (z and row_cnt both null: no fold)
   if (!al(dy, 16) || !al(w2, 16) || !al(d, 4) || !al(seg, 4) || !al(z, 4)) return DDZ_EINVAL;
-  if (row_capacity < FC_M || row_capacity % FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M || row_capacity > q_row_limit()) return DDZ_EINVAL;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
   hipLaunchKernelGGL(k_fc1<true>, dim3((unsigned)(row_capacity / FC_M)), dim3(FC_THREADS), 0, (hipStream_t)stream, dy, (int64_t)QH, w2, d,
@@ -3511,7 +3545,7 @@ int ddz_q_shared_rows(ddz_env_t* e, void* ws, int64_t ws_bytes, int64_t row_capa
   if (!ws || !rows || !rep || !seg || !al(ws, 16) || !al(rows, 16) || !al(rep, 4) || !al(seg, 4)) return DDZ_EINVAL;
   if (ws_bytes < ddz_q_shared_ws_bytes() || row_capacity % FC_M || e->T > ((int64_t)1 << 26)) return DDZ_ECAP;
   const int64_t most = e->T * 15 < (int64_t)QSH_KEYS ? e->T * 15 : (int64_t)QSH_KEYS;   // distinct (rank, column) pairs at most
-  if (row_capacity < most + 15 * FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < most + 15 * FC_M || row_capacity > q_row_limit()) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   hipStream_t st = (hipStream_t)stream;
@@ -3522,10 +3556,7 @@ int ddz_q_shared_rows(ddz_env_t* e, void* ws, int64_t ws_bytes, int64_t row_capa
   if (hipMemsetAsync(rep, 0xFF, (size_t)row_capacity * 4, st) != hipSuccess) return DDZ_EHIP;
   const unsigned nb = (unsigned)((e->T * 16 + 255) / 256);
   hipLaunchKernelGGL(k_qs_mark, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, slots, rows);
-  hipLaunchKernelGGL(k_qs_count<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, (const int32_t*)slots, cnt, QSH_COLS, QSH_CPR);
-  hipLaunchKernelGGL(k_qs_seg<true>, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity, QSH_CPR);
-  hipLaunchKernelGGL(k_qs_assign<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, slots, (const int32_t*)base, rep, (int32_t)row_capacity,
-                     QSH_COLS, QSH_CPR);
+  launch_qs_number<true>(st, slots, cnt, base, QSH_COLS, QSH_CPR, seg, rep, row_capacity);
   hipLaunchKernelGGL(k_qs_rows<true>, dim3(nb), dim3(256), 0, st, (const int32_t*)slots, e->T, rows, QSH_KEYS);
   return check_launch();
 }
@@ -3541,7 +3572,7 @@ int ddz_q_shared_rows_hashed(ddz_env_t* e, int variant, void* ws, int64_t ws_byt
   if (variant != 1 && variant != 2) return DDZ_EINVAL;
   if (!ws || !rows || !rep || !seg || !al(ws, 16) || !al(rows, 16) || !al(rep, 4) || !al(seg, 4)) return DDZ_EINVAL;
   if (e->T > ((int64_t)1 << 26) || ws_bytes < ddz_q_shared_hash_ws_bytes(e->T) || row_capacity % FC_M) return DDZ_ECAP;
-  if (row_capacity < e->T * 15 + 15 * FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < e->T * 15 + 15 * FC_M || row_capacity > q_row_limit()) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   hipStream_t st = (hipStream_t)stream;
@@ -3557,9 +3588,7 @@ int ddz_q_shared_rows_hashed(ddz_env_t* e, int variant, void* ws, int64_t ws_byt
     hipLaunchKernelGGL(k_qs_hmark<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
   else
     hipLaunchKernelGGL(k_qs_hmark<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
-  hipLaunchKernelGGL(k_qs_count<false>, dim3(15 * cpr), dim3(256), 0, st, (const int32_t*)vals, cnt, R, cpr);
-  hipLaunchKernelGGL(k_qs_seg<false>, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, base, seg, (int32_t)row_capacity, cpr);
-  hipLaunchKernelGGL(k_qs_assign<false>, dim3(15 * cpr), dim3(256), 0, st, vals, (const int32_t*)base, rep, (int32_t)row_capacity, R, cpr);
+  launch_qs_number<false>(st, vals, cnt, base, R, cpr, seg, rep, row_capacity);
   hipLaunchKernelGGL(k_qs_rows<false>, dim3(nb), dim3(256), 0, st, (const int32_t*)vals, e->T, rows, 15 * R);
   return check_launch();
 }
@@ -3572,7 +3601,7 @@ int ddz_q_features_rows(int device, const float* face, int64_t n_tables, int pla
   if (ys_ld != QH && ys_ld != QH + (4 * planes + 15) / 16 * 16) return DDZ_EINVAL;
   if (!al(mz, 4) || !al(g, 4)) return DDZ_EINVAL;
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(rep, 4) || !al(seg, 4) || !al(ys, 4)) return DDZ_EINVAL;
-  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > (((int64_t)1 << 31) - 1) / ys_ld || n_tables > ((int64_t)1 << 26))
+  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > q_row_limit(ys_ld) || n_tables > ((int64_t)1 << 26))
     return DDZ_ECAP;
   DeviceGuard gd(device);
   if (!gd.ok) return DDZ_ENODEV;
@@ -3599,7 +3628,7 @@ int ddz_q_shared_need(ddz_env_t* e, const int32_t* row_index, const int32_t* row
   if (!al(row_index, 4) || !al(rows, 4) || !al(sseg, 4) || !al(ws, 16) || !al(row_index2, 4) || !al(drep, 4) || !al(dseg, 4)) return DDZ_EINVAL;
   if (shared_row_capacity <= 0 || shared_row_capacity % FC_M || shared_row_capacity > ((int64_t)1 << 28)) return DDZ_ECAP;
   if (ws_bytes < ddz_q_shared_need_ws_bytes(shared_row_capacity)) return DDZ_ECAP;
-  if (row_capacity < 15 * FC_M || row_capacity % FC_M || row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < 15 * FC_M || row_capacity % FC_M || row_capacity > q_row_limit()) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   hipStream_t st = (hipStream_t)stream;
@@ -3611,10 +3640,7 @@ int ddz_q_shared_need(ddz_env_t* e, const int32_t* row_index, const int32_t* row
   if (hipMemsetAsync(drep, 0xFF, (size_t)row_capacity * 4, st) != hipSuccess) return DDZ_EHIP;
   const unsigned nb = (unsigned)((e->T * QP_COLS + 255) / 256);
   hipLaunchKernelGGL(k_qd_mark, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, dslot, shared_row_capacity);
-  hipLaunchKernelGGL(k_qd_count, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)dslot, sseg, cnt);
-  hipLaunchKernelGGL(k_qd_seg, dim3(1), dim3(64), 0, st, (const int32_t*)cnt, sseg, base, dseg, (int32_t)row_capacity, e->sc.status);
-  hipLaunchKernelGGL(k_qd_assign, dim3((unsigned)tiles), dim3(256), 0, st, dslot, sseg, (const int32_t*)base, drep, row_cnt,
-                     (int32_t)row_capacity);
+  launch_qd_number(st, dslot, sseg, cnt, base, tiles, dseg, drep, row_cnt, row_capacity, e->sc.status);
   hipLaunchKernelGGL(k_qd_remap, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, (const int32_t*)dslot, shared_row_capacity, row_index2);
   return check_launch();
 }
@@ -3623,7 +3649,7 @@ int ddz_q_features_drows(int device, const float* face, int64_t n_tables, int pl
                          float* dy, int64_t row_capacity, void* stream) {
   if (!face || !wf || !bias || !acnt || !rep || !drep || !dseg || !dy || n_tables <= 0 || shared_row_capacity <= 0) return DDZ_EINVAL;
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(acnt, 4) || !al(rep, 4) || !al(drep, 4) || !al(dseg, 4) || !al(dy, 4)) return DDZ_EINVAL;
-  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > (((int64_t)1 << 31) - 1) / QH || n_tables > ((int64_t)1 << 26))
+  if (row_capacity < QR_TILE || row_capacity % QR_TILE || row_capacity > q_row_limit() || n_tables > ((int64_t)1 << 26))
     return DDZ_ECAP;
   if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
   DeviceGuard g(device);
@@ -3654,7 +3680,7 @@ int ddz_q_fc1_rows_k(int device, const float* y, int64_t k, const int32_t* seg, 
   if (!y || !seg || !w2k || !g) return DDZ_EINVAL;
   if (!al(y, 16) || !al(w2k, 16) || !al(g, 4) || !al(seg, 4)) return DDZ_EINVAL;
   if (k < FC_K || k % FC_K || k > 4096) return DDZ_EINVAL;
-  if (row_capacity < FC_M || row_capacity % FC_M || row_capacity > (((int64_t)1 << 31) - 1) / k) return DDZ_EINVAL;
+  if (row_capacity < FC_M || row_capacity % FC_M || row_capacity > q_row_limit(k)) return DDZ_EINVAL;
   DeviceGuard gd(device);
   if (!gd.ok) return DDZ_ENODEV;
   hipLaunchKernelGGL(k_fc1<true>, dim3((unsigned)(row_capacity / FC_M)), dim3(FC_THREADS), 0, (hipStream_t)stream, y, k, w2k, g,
@@ -3671,12 +3697,9 @@ int ddz_q_slab_needed(ddz_env_t* e, const float* h0, const float* d, int64_t row
   if (!h0 || !d || !w2 || !b2 || !counts || !rows || !q || !row_index || hidden != QH || stride < 1 || row_capacity < 1) return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
-  // (64 tables per block at most: the blocks are the unit the hardware balances over the CUs, the tables inside a block are
-  // handed out by an LDS ticket)
-  int64_t v = (e->T + 4095) / 4096;
-  const int tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
-  const int64_t per_block = (int64_t)WPB * tpw;
-  hipLaunchKernelGGL(k_q_slab_needed, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
+  int tpw;
+  const dim3 grid = q_slab_grid(e->T, tpw);
+  hipLaunchKernelGGL(k_q_slab_needed, grid, dim3(TB), 0, (hipStream_t)stream,
                      (const float4*)h0, (const float4*)d, row_capacity, e->T, tpw, (const float4*)w2, b2, counts,
                      (const uint4*)rows, stride, q, row_index, e->sc.status);
   return check_launch();
@@ -3708,7 +3731,7 @@ int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int 
   if (!ws || !rows || !rep || !seg || !slot || !al(ws, 16) || !al(rows, 16) || !al(rep, 4) || !al(seg, 4)) return DDZ_EINVAL;
   if (e->T > ((int64_t)1 << 26) || ws_bytes < ddz_q_roles_ws_bytes(e->T, variant, n_nets) || row_capacity % FC_M) return DDZ_ECAP;
   const int64_t most = variant == 3 && e->T * 15 > (int64_t)QSH_KEYS ? (int64_t)QSH_KEYS : e->T * 15;
-  if (row_capacity < most + 15 * FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < most + 15 * FC_M || n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   hipStream_t st = (hipStream_t)stream;
@@ -3720,15 +3743,9 @@ int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int 
     int32_t* base = cnt + n_nets * 15 * QSH_CPR;
     if (hipMemsetAsync(slots, 0, (size_t)n_nets * QSH_KEYS * 4, st) != hipSuccess) return DDZ_EHIP;
     hipLaunchKernelGGL(k_qs_mark_roles, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, slots, rows, slot);
-    for (int s = 0; s < n_nets; ++s) {
-      int32_t* sl = slots + (int64_t)s * QSH_KEYS;
-      int32_t *c = cnt + s * 15 * QSH_CPR, *b = base + s * 15 * QSH_CPR;
-      hipLaunchKernelGGL(k_qs_count<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, (const int32_t*)sl, c, QSH_COLS, QSH_CPR);
-      hipLaunchKernelGGL(k_qs_seg<true>, dim3(1), dim3(64), 0, st, (const int32_t*)c, b, seg + s * QN_SEG_WORDS, (int32_t)row_capacity,
-                         QSH_CPR);
-      hipLaunchKernelGGL(k_qs_assign<true>, dim3(15 * QSH_CPR), dim3(256), 0, st, sl, (const int32_t*)b, rep + s * row_capacity,
-                         (int32_t)row_capacity, QSH_COLS, QSH_CPR);
-    }
+    for (int s = 0; s < n_nets; ++s)
+      launch_qs_number<true>(st, slots + (int64_t)s * QSH_KEYS, cnt + s * 15 * QSH_CPR, base + s * 15 * QSH_CPR, QSH_COLS, QSH_CPR,
+                             seg + s * QN_SEG_WORDS, rep + s * row_capacity, row_capacity);
     hipLaunchKernelGGL(k_qs_rows_roles, dim3(nb), dim3(256), 0, st, (const int32_t*)slots, e->T, rows, (int64_t)QSH_KEYS, n_nets,
                        row_capacity);
   } else {
@@ -3742,14 +3759,9 @@ int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int 
       hipLaunchKernelGGL(k_qs_hmark_roles<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
     else
       hipLaunchKernelGGL(k_qs_hmark_roles<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
-    for (int s = 0; s < n_nets; ++s) {
-      int32_t* v = vals + (int64_t)s * 15 * R;
-      int32_t *c = cnt + s * 15 * cpr, *b = base + s * 15 * cpr;
-      hipLaunchKernelGGL(k_qs_count<false>, dim3(15 * cpr), dim3(256), 0, st, (const int32_t*)v, c, R, cpr);
-      hipLaunchKernelGGL(k_qs_seg<false>, dim3(1), dim3(64), 0, st, (const int32_t*)c, b, seg + s * QN_SEG_WORDS, (int32_t)row_capacity, cpr);
-      hipLaunchKernelGGL(k_qs_assign<false>, dim3(15 * cpr), dim3(256), 0, st, v, (const int32_t*)b, rep + s * row_capacity,
-                         (int32_t)row_capacity, R, cpr);
-    }
+    for (int s = 0; s < n_nets; ++s)
+      launch_qs_number<false>(st, vals + (int64_t)s * 15 * R, cnt + s * 15 * cpr, base + s * 15 * cpr, R, cpr, seg + s * QN_SEG_WORDS,
+                              rep + s * row_capacity, row_capacity);
     hipLaunchKernelGGL(k_qs_rows_roles, dim3(nb), dim3(256), 0, st, (const int32_t*)vals, e->T, rows, (int64_t)15 * R, n_nets, row_capacity);
   }
   return check_launch();
@@ -3760,7 +3772,7 @@ int ddz_q_roles_features_rows(int device, const float* face, int64_t n_tables, i
   if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
   if (ys_ld != QH && ys_ld != QH + (4 * planes + 15) / 16 * 16) return DDZ_EINVAL;
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(rep, 4) || !al(seg, 4) || !al(ys, 4)) return DDZ_EINVAL;
-  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / ys_ld || n_tables > ((int64_t)1 << 26))
+  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > q_row_limit(ys_ld) || n_tables > ((int64_t)1 << 26))
     return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
     const int rc = ddz_q_features_rows(device, face, n_tables, planes, wf + (int64_t)s * planes * 4 * 4 * QH, bias + s * 4 * QH,
@@ -3774,7 +3786,7 @@ int ddz_q_roles_fc1_rows_k(int device, int n_nets, const float* y, int64_t k, co
                            int64_t row_capacity, void* stream) {
   if (!roles_ok(n_nets) || !y || !seg || !w2k || !g) return DDZ_EINVAL;
   if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
-  if (n_nets * row_capacity > (((int64_t)1 << 31) - 1) / (k > QH ? k : QH)) return DDZ_ECAP;
+  if (n_nets * row_capacity > q_row_limit(k > QH ? k : QH)) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
     const int rc = ddz_q_fc1_rows_k(device, y + s * row_capacity * k, k, seg + s * QN_SEG_WORDS, w2k + (int64_t)s * 15 * k * QH,
                                     g + s * row_capacity * QH, row_capacity, 0, stream);
@@ -3805,7 +3817,7 @@ int ddz_q_roles_need(ddz_env_t* e, int n_nets, const int32_t* row_index, const i
   if (!al(row_index, 4) || !al(rows, 4) || !al(sseg, 4) || !al(ws, 16) || !al(row_index2, 4) || !al(drep, 4) || !al(dseg, 4)) return DDZ_EINVAL;
   if (shared_row_capacity <= 0 || shared_row_capacity % FC_M || n_nets * shared_row_capacity > ((int64_t)1 << 28)) return DDZ_ECAP;
   if (ws_bytes < ddz_q_roles_need_ws_bytes(shared_row_capacity, n_nets)) return DDZ_ECAP;
-  if (row_capacity < 15 * FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < 15 * FC_M || row_capacity % FC_M || n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   hipStream_t st = (hipStream_t)stream;
@@ -3817,16 +3829,9 @@ int ddz_q_roles_need(ddz_env_t* e, int n_nets, const int32_t* row_index, const i
   if (hipMemsetAsync(drep, 0xFF, (size_t)(n_nets * row_capacity) * 4, st) != hipSuccess) return DDZ_EHIP;
   const unsigned nb = (unsigned)((e->T * QP_COLS + 255) / 256);
   hipLaunchKernelGGL(k_qd_mark, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, dslot, S);   // (rule tables: rows < 0, no mark)
-  for (int s = 0; s < n_nets; ++s) {
-    int32_t* ds = dslot + s * shared_row_capacity * 4;
-    const int32_t* ss = sseg + s * QN_SEG_WORDS;
-    int32_t *c = cnt + s * tiles, *b = base + s * tiles;
-    hipLaunchKernelGGL(k_qd_count, dim3((unsigned)tiles), dim3(256), 0, st, (const int32_t*)ds, ss, c);
-    hipLaunchKernelGGL(k_qd_seg, dim3(1), dim3(64), 0, st, (const int32_t*)c, ss, b, dseg + s * QN_SEG_WORDS, (int32_t)row_capacity,
-                       e->sc.status);
-    hipLaunchKernelGGL(k_qd_assign, dim3((unsigned)tiles), dim3(256), 0, st, ds, ss, (const int32_t*)b, drep + s * row_capacity,
-                       row_cnt + s * row_capacity, (int32_t)row_capacity);
-  }
+  for (int s = 0; s < n_nets; ++s)
+    launch_qd_number(st, dslot + s * shared_row_capacity * 4, sseg + s * QN_SEG_WORDS, cnt + s * tiles, base + s * tiles, tiles,
+                     dseg + s * QN_SEG_WORDS, drep + s * row_capacity, row_cnt + s * row_capacity, row_capacity, e->sc.status);
   hipLaunchKernelGGL(k_qd_remap_roles, dim3(nb), dim3(256), 0, st, row_index, rows, e->T, (const int32_t*)dslot, shared_row_capacity, n_nets,
                      row_capacity, row_index2);
   return check_launch();
@@ -3835,7 +3840,7 @@ int ddz_q_roles_features_drows(int device, const float* face, int64_t n_tables, 
                                const float* acnt, const int32_t* rep, int64_t shared_row_capacity, const int32_t* drep, const int32_t* dseg,
                                float* dy, int64_t row_capacity, void* stream) {
   if (!roles_ok(n_nets) || !wf || !bias || !acnt || !rep || !drep || !dseg || !dy) return DDZ_EINVAL;
-  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
     const int rc = ddz_q_features_drows(device, face, n_tables, planes, wf + (int64_t)s * planes * 4 * 4 * QH, bias + s * 4 * QH,
                                         acnt + s * 5 * 4 * QH, rep + s * shared_row_capacity, shared_row_capacity, drep + s * row_capacity,
@@ -3848,7 +3853,7 @@ int ddz_q_roles_fc1_rows(int device, int n_nets, const float* dy, const int32_t*
                          float* d, int64_t row_capacity, void* stream) {
   if (!roles_ok(n_nets) || !dy || !seg || !row_cnt || !w2 || !z || !d) return DDZ_EINVAL;
   if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
-  if (n_nets * row_capacity > (((int64_t)1 << 31) - 1) / QH) return DDZ_ECAP;
+  if (n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
     const int rc = ddz_q_fc1_rows(device, dy + s * row_capacity * QH, seg + s * QN_SEG_WORDS, row_cnt + s * row_capacity,
                                   w2 + (int64_t)s * 15 * QH * QH, z + s * 15 * 5 * QH, d + s * row_capacity * QH, row_capacity, stream);
@@ -3866,10 +3871,9 @@ int ddz_q_roles_slab(ddz_env_t* e, int n_nets, const int8_t* slot, const float* 
     return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
-  int64_t v = (e->T + 4095) / 4096;                                // (the geometry of ddz_q_slab_needed)
-  const int tpw = (int)(v < 1 ? 1 : v > 4 ? 4 : v);
-  const int64_t per_block = (int64_t)WPB * tpw;
-  hipLaunchKernelGGL(k_q_slab_roles, dim3((unsigned)((e->T + per_block - 1) / per_block)), dim3(TB), 0, (hipStream_t)stream,
+  int tpw;
+  const dim3 grid = q_slab_grid(e->T, tpw);
+  hipLaunchKernelGGL(k_q_slab_roles, grid, dim3(TB), 0, (hipStream_t)stream,
                      (const float4*)h0, (const float4*)d, d_rows, e->T, tpw, (const float4*)w2, b2, slot, counts, (const uint4*)rows,
                      stride, q, row_index, e->sc.status);
   return check_launch();

@@ -273,10 +273,7 @@ __global__ __launch_bounds__(QH) void k_q_feat_needed(   // ((QH, 5): 96 VGPRs +
 #pragma unroll
       for (int p = 0; p < P; ++p) {
         const float4 x = s_face[(ti * P + p) * 15 + r];
-        s0 += w[p][0] * x.x;
-        s1 += w[p][1] * x.x + w[p][2] * x.y;
-        s2 += w[p][3] * x.x + w[p][4] * x.y + w[p][5] * x.z;
-        s3 += w[p][6] * x.x + w[p][7] * x.y + w[p][8] * x.z + w[p][9] * x.w;
+        q_feat_plane(w[p], x, s0, s1, s2, s3);
       }
       const float v0 = fmaxf(fmaxf(s0, s1), fmaxf(s2, s3));
       if (y0) d0[r * QH] = v0;
@@ -889,12 +886,9 @@ __global__ __launch_bounds__(QH) void k_q_feat_rows(const float4* __restrict__ f
   for (int j = 0; j < QR_TILE; ++j) {
     float s0 = b[0], s1 = b[1], s2 = b[2], s3 = b[3];
 #pragma unroll
-    for (int p = 0; p < P; ++p) {   // (the same expression, in the same order, as k_q_feat_needed: bit-identical Y)
+    for (int p = 0; p < P; ++p) {   // (q_feat_plane in plane order, as every first-layer kernel: bit-identical Y)
       const float4 x = s_col[j * P + p];
-      s0 += w[p][0] * x.x;
-      s1 += w[p][1] * x.x + w[p][2] * x.y;
-      s2 += w[p][3] * x.x + w[p][4] * x.y + w[p][5] * x.z;
-      s3 += w[p][6] * x.x + w[p][7] * x.y + w[p][8] * x.z + w[p][9] * x.w;
+      q_feat_plane(w[p], x, s0, s1, s2, s3);
     }
     ys[(row0 + j) * ys_ld + c] = s_ok[j] ? fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)) : 0.f;
     if (c < ys_ld - QH) ys[(row0 + j) * ys_ld + QH + c] = c < 4 * P ? ((const float*)&s_col[j * P])[c] : 0.f;   // (zeros where !ok)
@@ -1073,12 +1067,9 @@ __global__ __launch_bounds__(QH) void k_q_feat_drows(const float4* __restrict__ 
   for (int j = 0; j < QR_TILE; ++j) {
     float s0 = b[0], s1 = b[1], s2 = b[2], s3 = b[3];
 #pragma unroll
-    for (int p = 0; p < P; ++p) {   // (the expression and order of k_q_feat_needed: bit-identical dY)
+    for (int p = 0; p < P; ++p) {   // (q_feat_plane in plane order, as every first-layer kernel: bit-identical dY)
       const float4 x = s_col[j * P + p];
-      s0 += w[p][0] * x.x;
-      s1 += w[p][1] * x.x + w[p][2] * x.y;
-      s2 += w[p][3] * x.x + w[p][4] * x.y + w[p][5] * x.z;
-      s3 += w[p][6] * x.x + w[p][7] * x.y + w[p][8] * x.z + w[p][9] * x.w;
+      q_feat_plane(w[p], x, s0, s1, s2, s3);
     }
     const float v0 = fmaxf(fmaxf(s0, s1), fmaxf(s2, s3));
     const int c = s_c[j];                      // (block-uniform)

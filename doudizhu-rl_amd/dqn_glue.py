@@ -150,6 +150,15 @@ def fc_tile():
     return _FC_TILE
 
 
+def row_capacities(T, variant, tile=None):
+    """(cap, scap) for T tables, per network slot: the capacity of the needed rows D (a move takes at most what the actor holds:
+    <= 20 T rows) and of the shared rows (<= 15 T distinct (rank, column) pairs, and the 4,134,375 direct-addressed keys of face
+    variant 3), each with the padding of fifteen tile-aligned rank segments and rounded to the tile: neither can overflow."""
+    tile = fc_tile() if tile is None else tile
+    padded = lambda rows: (rows + 15 * tile + tile - 1) // tile * tile   # noqa: E731
+    return padded(20 * T), padded(min(15 * T, 4134375) if variant == 3 else 15 * T)
+
+
 def _run_stage(name, fn):
     fn()
 
@@ -326,18 +335,14 @@ class FactorisedQ:
         from . import engine as E
         P, H, H1 = self.P, self.H, self.H1
         w = self._ws.setdefault(("needed", dev, T), {})
-        tile = fc_tile()
-        padded = lambda rows: (rows + 15 * tile + tile - 1) // tile * tile   # noqa: E731  (fifteen tile-aligned rank segments)
+        cap, scap = row_capacities(T, SHARED_VARIANT.get(P))
         z = lambda *shape, dt=torch.float32, fill=0: torch.full(shape, fill, dtype=dt, device=dev)   # noqa: E731
         if "cap" not in w:
-            cap = padded(20 * T)                                             # a move takes at most what the actor holds: <= 20 cards
             w.update({"cap": cap, "y0": None, "dy": z(cap, H), "d": z(cap, H1), "h0": z(T, H1),
                       "row_index": z(T, 64, dt=torch.int32, fill=-1), "seg": z(40, dt=torch.int32), "row_cnt": z(cap, dt=torch.uint8),
                       "scratch": z(E.q_need_scratch_bytes(T), dt=torch.uint8)})
         if shared and "srows" not in w:
             v = SHARED_VARIANT[P]
-            # distinct (rank, column) pairs: at most 15 T (and the 4,134,375 direct-addressed keys of variant 3): cannot overflow
-            scap = padded(min(15 * T, 4134375) if v == 3 else 15 * T)
             sws = E.q_shared_ws_bytes() if v == 3 else E.q_shared_hash_ws_bytes(T)
             w.update({"svariant": v, "scap": scap, "sws": z(sws, dt=torch.uint8), "srows": z(T, 16, dt=torch.int32, fill=-1),
                       "srep": z(scap, dt=torch.int32, fill=-1), "sseg": z(40, dt=torch.int32),
@@ -809,10 +814,7 @@ class RoleQ:
         key = (dev, T)
         if key not in self._ws:
             self._ws.clear()
-            tile = fc_tile()
-            cap = (20 * T + 15 * tile + tile - 1) // tile * tile                  # D rows per slot: ddz_q_need's capacity
-            most = min(15 * T, 4134375) if self.variant == 3 else 15 * T
-            scap = (most + 15 * tile + tile - 1) // tile * tile                   # shared rows per slot
+            cap, scap = row_capacities(T, self.variant)                            # per slot
             z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
             self._ws[key] = {
                 "cap": cap, "scap": scap,

@@ -285,31 +285,49 @@ class BatchedEnv:
             check(self.lib.ddz_q_shared_rows_hashed(self._h, int(variant), _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep),
                                                     _p(seg), _stream(self.device)))
 
-    def q_shared_need(self, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
-        """ddz_q_shared_need: one D row per distinct (shared row, count) some table needs: row_index2 int32 [T,64], drep int32
-        [row_capacity], dseg int32 [40], row_cnt uint8 [row_capacity] from q_need's row_index and q_shared_rows' rows / sseg."""
+    def _check_q_need(self, n_nets, row_index, rows, sseg, ws, row_capacity, row_index2, drep, dseg, row_cnt):
+        """the argument checks of q_shared_need (n_nets None: one partition) and q_roles_need (n_nets slot-major partitions of
+        row_capacity rows, a segment table each); returns the number of partitions"""
+        N = 1 if n_nets is None else int(n_nets)
         for x, shp in ((row_index, (self.T, 64)), (row_index2, (self.T, 64)), (rows, (self.T, 16))):
             if x.dtype != torch.int32 or tuple(x.shape) != shp or not x.is_contiguous():
                 raise ValueError("row_index / row_index2 must be int32 [T,64], rows int32 [T,16]")
-        if (drep.dtype != torch.int32 or drep.numel() < int(row_capacity) or row_cnt.dtype != torch.uint8 or row_cnt.numel() < int(row_capacity)
-                or dseg.dtype != torch.int32 or dseg.numel() < 40 or sseg.dtype != torch.int32 or sseg.numel() < 40 or ws.dtype != torch.uint8):
-            raise ValueError("drep int32 [row_capacity], row_cnt uint8 [row_capacity], dseg / sseg int32 [40], ws uint8")
+        if (drep.dtype != torch.int32 or drep.numel() < N * int(row_capacity) or row_cnt.dtype != torch.uint8
+                or row_cnt.numel() < N * int(row_capacity) or dseg.dtype != torch.int32 or dseg.numel() < 40 * N
+                or sseg.dtype != torch.int32 or sseg.numel() < 40 * N or ws.dtype != torch.uint8):
+            raise ValueError("drep int32 [row_capacity], row_cnt uint8 [row_capacity], dseg / sseg int32 [40], ws uint8" if n_nets is None
+                             else "drep int32 / row_cnt uint8 [n_nets * row_capacity], dseg / sseg int32 [n_nets,40], ws uint8")
+        return N
+
+    def q_shared_need(self, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
+        """ddz_q_shared_need: one D row per distinct (shared row, count) some table needs: row_index2 int32 [T,64], drep int32
+        [row_capacity], dseg int32 [40], row_cnt uint8 [row_capacity] from q_need's row_index and q_shared_rows' rows / sseg."""
+        self._check_q_need(None, row_index, rows, sseg, ws, row_capacity, row_index2, drep, dseg, row_cnt)
         check(self.lib.ddz_q_shared_need(self._h, _p(row_index), _p(rows), _p(sseg), int(shared_row_capacity), _p(ws), ws.numel(),
                                          int(row_capacity), _p(row_index2), _p(drep), _p(dseg), _p(row_cnt), _stream(self.device)))
 
-    def q_slab_needed(self, h0, d, row_index, w2, b2, out=None):
-        """ddz_q_slab_needed: q f32 [T, stride] of every legal move from h0 f32 [T,256], d f32 [rows,256] (with z folded in by
-        q_fc1_rows), row_index."""
+    def _check_q_slab(self, n_nets, h0, d, out, slot=None, w2=None, b2=None):
+        """the argument checks of q_slab_needed (n_nets None: `out` may be None and is then made) and q_roles_slab (+ the per-slot
+        operands), behind a fresh legal_slab(); returns (hidden, out)"""
         if not self._slab_fresh:
             self.legal_slab()
         H = int(h0.shape[-1])
         for x, shp in ((h0, (self.T, H)), (d, (d.shape[0], H))):
             if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != self.device:
                 raise ValueError("h0 must be float32 [T,hidden], d float32 [rows,hidden], contiguous, on the engine's device")
-        if out is None:
+        if out is None and n_nets is None:
             out = torch.zeros((self.T, self.slab_stride), dtype=torch.float32, device=self.device)
         elif out.dtype != torch.float32 or out.numel() != self.T * self.slab_stride or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 [T, stride] tensor")
+        if n_nets is not None and (slot.dtype != torch.int8 or slot.numel() != self.T or w2.numel() != int(n_nets) * H
+                                   or b2.numel() != int(n_nets)):
+            raise ValueError("slot must be int8 [T], w2 float32 [n_nets,hidden], b2 float32 [n_nets]")
+        return H, out
+
+    def q_slab_needed(self, h0, d, row_index, w2, b2, out=None):
+        """ddz_q_slab_needed: q f32 [T, stride] of every legal move from h0 f32 [T,256], d f32 [rows,256] (with z folded in by
+        q_fc1_rows), row_index."""
+        H, out = self._check_q_slab(None, h0, d, out)
         check(self.lib.ddz_q_slab_needed(self._h, _p(h0), _p(d), int(d.shape[0]), _p(row_index), H, _p(w2), _p(b2),
                                          self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
         return out
@@ -331,30 +349,14 @@ class BatchedEnv:
 
     def q_roles_need(self, n_nets, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
         """ddz_q_roles_need: q_shared_need over the slots of q_roles_rows (per-slot capacities; rule tables get no D row)."""
-        N = int(n_nets)
-        for x, shp in ((row_index, (self.T, 64)), (row_index2, (self.T, 64)), (rows, (self.T, 16))):
-            if x.dtype != torch.int32 or tuple(x.shape) != shp or not x.is_contiguous():
-                raise ValueError("row_index / row_index2 must be int32 [T,64], rows int32 [T,16]")
-        if (drep.dtype != torch.int32 or drep.numel() < N * int(row_capacity) or row_cnt.dtype != torch.uint8
-                or row_cnt.numel() < N * int(row_capacity) or dseg.dtype != torch.int32 or dseg.numel() < 40 * N
-                or sseg.dtype != torch.int32 or sseg.numel() < 40 * N or ws.dtype != torch.uint8):
-            raise ValueError("drep int32 / row_cnt uint8 [n_nets * row_capacity], dseg / sseg int32 [n_nets,40], ws uint8")
+        N = self._check_q_need(n_nets, row_index, rows, sseg, ws, row_capacity, row_index2, drep, dseg, row_cnt)
         check(self.lib.ddz_q_roles_need(self._h, N, _p(row_index), _p(rows), _p(sseg), int(shared_row_capacity), _p(ws), ws.numel(),
                                         int(row_capacity), _p(row_index2), _p(drep), _p(dseg), _p(row_cnt), _stream(self.device)))
 
     def q_roles_slab(self, n_nets, slot, h0, d, row_index, w2, b2, out):
         """ddz_q_roles_slab: q_slab_needed with the weights of each table's slot (w2 f32 [n_nets,256], b2 f32 [n_nets]); every
         entry of a rule table (slot < 0) is left alone."""
-        if not self._slab_fresh:
-            self.legal_slab()
-        H = int(h0.shape[-1])
-        for x, shp in ((h0, (self.T, H)), (d, (d.shape[0], H))):
-            if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != self.device:
-                raise ValueError("h0 must be float32 [T,hidden], d float32 [rows,hidden], contiguous, on the engine's device")
-        if out.dtype != torch.float32 or out.numel() != self.T * self.slab_stride or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [T, stride] tensor")
-        if slot.dtype != torch.int8 or slot.numel() != self.T or w2.numel() != int(n_nets) * H or b2.numel() != int(n_nets):
-            raise ValueError("slot must be int8 [T], w2 float32 [n_nets,hidden], b2 float32 [n_nets]")
+        H, out = self._check_q_slab(n_nets, h0, d, out, slot, w2, b2)
         check(self.lib.ddz_q_roles_slab(self._h, int(n_nets), _p(slot), _p(h0), _p(d), int(d.shape[0]), _p(row_index), H, _p(w2), _p(b2),
                                         self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
         return out

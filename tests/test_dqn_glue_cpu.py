@@ -339,3 +339,22 @@ def test_shared_row_key_determines_the_face_column(oracle):
             b = c.tobytes()
             assert seen.setdefault(k, b) == b                            # one key, one column -- across tables AND states
     assert len(seen) > 2000                                              # (and the states were varied enough to mean something)
+
+
+def test_row_capacities():
+    """dqn_glue.row_capacities, the one statement of the needed-rows capacity `cap` (20 T rows) and the shared-rows capacity
+    `scap` (15 T rows; variant 3: at most the 4,134,375 direct-addressed keys), each plus fifteen tile paddings and rounded to
+    the tile -- against the two formulas written out, with the tile as a parameter (no device).  The key count binds only
+    above T = 275,625 (15 T > 4,134,375): 2^19 tables are there for that."""
+    glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
+    for tile in (128, 64):
+        for T in (1, 37, 4096, 65536, 1 << 19):
+            for v in (1, 2, 3):
+                most = min(15 * T, 4134375) if v == 3 else 15 * T
+                want = ((20 * T + 15 * tile + tile - 1) // tile * tile, (most + 15 * tile + tile - 1) // tile * tile)
+                got = glue.row_capacities(T, v, tile)
+                assert got == want and all(x % tile == 0 for x in got), (tile, T, v, got, want)
+    assert glue.row_capacities(1, 3, 128) == (2048, 2048)                    # 20 + 1,920 -> 16 tiles; 15 + 1,920 -> 16 tiles
+    assert glue.row_capacities(37, 1, 128) == (2688, 2560)                   # 740 + 1,920 = 2,660; 555 + 1,920 = 2,475
+    assert glue.row_capacities(65536, 3, 128) == (1312640, 984960) == glue.row_capacities(65536, 2, 128)
+    assert glue.row_capacities(1 << 19, 3, 128)[1] == 4136320 < glue.row_capacities(1 << 19, 2, 128)[1]   # 4,134,375 + 1,920 -> 32,315 tiles
