@@ -3,8 +3,9 @@
 // Kernel map (reference paths relative to /root/reference):
 //   k_rollout THE DOMINANT KERNEL (ddz_rollout_random): one wavefront per table, all lock-step iterations of a
 //             random-policy rollout (game.py:169-181 with envi.py:79-85) inside one launch, state in registers,
-//             lists in fixed-stride slabs; arithmetic fast path for follows of singles / pairs / triples, planner
-//             + LDS staging list for the rest (see the comment at the kernel).
+//             lists in fixed-stride slabs; every list starts with one closed-form round built from the hand's rank masks
+//             (nine plies in ten: that round is the whole list), planner + LDS staging list for the tail of the rest
+//             (see the comment at the kernel).
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
 //             or slab lists with F_SLAB = apply + enumerate in the same launch):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
@@ -387,7 +388,9 @@ __device__ __forceinline__ int scan_combos(int list, int count, int idb, uint64_
 // (wave-uniform, scalar); ranges are visited in ascending id order.  Everything a range
 // admits too generously is rejected per id by scan_ids, so the planner only has to be a
 // superset -- and cheap.
-template <int EM, bool IDS, bool LEAD, class HT>
+// BASE = false: without the first range (ids 1..54 of a lead; pass and the bombs, ids 0 and 42..54, of a follow): a caller
+// that has already written that round in closed form (k_rollout) gets the rest of the list, counted and staged from index 0.
+template <int EM, bool IDS, bool LEAD, class HT, bool BASE = true>
 __device__ __forceinline__ int plan_scan_t(uint64_t hand, const Follow& f, const HT& hot, int lane, const Out& o, Pick& pk) {
   // PRUNE: skip kicker blocks / ranges that cannot hold a legal move (fewer kicker ranks in the hand than kickers needed).
   // Measured A/B (profiles/r03_notes.md): -16 % on lists of plane-rich hands (the stress leg, the tail of k_slab), but +3 %
@@ -403,10 +406,12 @@ __device__ __forceinline__ int plan_scan_t(uint64_t hand, const Follow& f, const
   int n = 0;
   auto scan = [&](int id0, int count) { n = scan_ids<EM, IDS, LEAD>(id0, count, hot, hand8, f, lane, o, n, pk); };
   if (!LEAD && f.lc == BIGBANG) {  // nothing beats the rocket: pass only (card.py:312-313)
-    scan(0, 1);
+    if (BASE) scan(0, 1);
     return n;
   }
-  if (LEAD) scan(1, 54); else scan(0, 55);  // [pass,] singles, pairs, triples, bombs
+  if (BASE) {
+    if (LEAD) scan(1, 54); else scan(0, 55);  // [pass,] singles, pairs, triples, bombs
+  }
   const uint32_t above = LEAD ? M15 : gt_mask(f.lv);
   if (LEAD || f.lc == THREE_ONE || f.lc == THREE_TWO) {  // mains m..M of card.py:69-82
     const uint32_t mains = m3 & above;
@@ -949,13 +954,125 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
+// Closed-form scan rounds: lists (or first rounds of lists) that are a function of the hand's rank masks alone.  One lane
+// per candidate; a candidate is `copies` cards of one rank, or the rocket; its 16-byte row is built arithmetically (no
+// record table, no LDS) and stored at rows[pos0 + legal lanes below it]: ascending canonical id in both layouts.
+//   follow layout (FastLanes): lanes 0 pass | 1..15 group of rank lane-1 | 16..28 bomb of rank lane-16 | 29 rocket
+//   lead layout   (LeadLanes): lanes 0..14 singles | 15..27 pairs | 28..40 triples | 41..53 bombs | 54 rocket (id = 1 + lane)
+// per-lane constants of the follow layout (VGPRs; opaque so that they are not rebuilt from spilled lane masks)
+struct FastLanes {
+  static constexpr bool WIDE = false;
+  int rr;
+  uint32_t bit, sh, w0, w1, w2, w3, grp, c4, rk;
+};
+__device__ __forceinline__ FastLanes fast_lanes(int lane) {
+  FastLanes f;
+  f.rr = (lane < 16 ? lane - 1 : lane - 16) & 15;
+  f.bit = lane < 32 ? 1u << lane : 0u;
+  f.sh = 8u * (uint32_t)(f.rr & 3);
+  f.w0 = (f.rr >> 2) == 0 ? ~0u : 0u; f.w1 = (f.rr >> 2) == 1 ? ~0u : 0u;
+  f.w2 = (f.rr >> 2) == 2 ? ~0u : 0u; f.w3 = (f.rr >> 2) == 3 ? ~0u : 0u;
+  f.grp = (lane >= 1 && lane < 16) ? ~0u : 0u;
+  f.c4 = (lane >= 16 && lane < 29) ? 4u : 0u;
+  f.rk = lane == 29 ? (0x00010100u | ((uint32_t)BIGBANG << 24)) : 0u;
+  asm volatile("" : "+v"(f.bit), "+v"(f.sh), "+v"(f.w0), "+v"(f.w1), "+v"(f.w2), "+v"(f.w3), "+v"(f.grp), "+v"(f.c4), "+v"(f.rk));
+  return f;
+}
+// the lead layout, computed from the lane where it is used (a lead is a quarter of the plies: not worth held registers)
+struct LeadLanes {
+  static constexpr bool WIDE = true;
+  int rr;
+  uint32_t copies, sh, w0, w1, w2, w3, rk;
+};
+__device__ __forceinline__ LeadLanes lead_lanes(int lane) {
+  LeadLanes f;
+  const int g = (lane >= 15) + (lane >= 28) + (lane >= 41);   // group size - 1
+  f.rr = lane < 54 ? lane - (g ? 2 + 13 * g : 0) : 0;
+  f.copies = lane < 54 ? (uint32_t)g + 1u : 0u;
+  f.sh = 8u * (uint32_t)(f.rr & 3);
+  f.w0 = (f.rr >> 2) == 0 ? ~0u : 0u; f.w1 = (f.rr >> 2) == 1 ? ~0u : 0u;
+  f.w2 = (f.rr >> 2) == 2 ? ~0u : 0u; f.w3 = (f.rr >> 2) == 3 ? ~0u : 0u;
+  f.rk = lane == 54 ? (0x00010100u | ((uint32_t)BIGBANG << 24)) : 0u;
+  return f;
+}
+// the number of legal lanes below this one = the lane's position in the round
+__device__ __forceinline__ int round_pre(uint32_t okm) { return (int)__builtin_amdgcn_mbcnt_lo(okm, 0u); }
+__device__ __forceinline__ int round_pre(uint64_t okm) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(okm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)okm, 0u));
+}
+// one round: `okm` = the legal lanes (a 32-bit mask in the follow layout, 64 bits in the lead layout), `copies` = this
+// lane's group size (= its category; 0 for pass and the rocket).  Stores the legal rows (+ ids), leaves the lane's row and
+// its position in the round to the caller (round_pick) and returns the number of legal lanes.
+template <bool IDS, class L, class M>
+__device__ __forceinline__ int round_emit(M okm, const L& ln, uint32_t copies, int id, uint4* rows, int32_t* ids, int64_t pos0,
+                                          uint4& row, int& pre) {
+  static_assert(L::WIDE == (sizeof(M) == 8), "the lead layout has 55 lanes");
+  int n;
+  bool ok;
+  pre = round_pre(okm);
+  if constexpr (L::WIDE) {
+    n = __builtin_popcountll(okm);
+    ok = ((okm >> (threadIdx.x & 63)) & 1ull) != 0;
+  } else {
+    n = __builtin_popcount(okm);
+    ok = (okm & ln.bit) != 0;
+  }
+  const uint32_t dv = copies << ln.sh;
+  row = make_uint4(dv & ln.w0, dv & ln.w1, dv & ln.w2, (dv & ln.w3) | (copies << 24) | ln.rk);
+  if (ok) {
+    rows[pos0 + pre] = row;
+    if (IDS) ids[pos0 + pre] = id;
+  }
+  return n;
+}
+// the lane that holds entry `idx` of the round (0 <= idx < popcount(okm)); `pre` = round_pre(okm)
+template <bool WIDE, class M>
+__device__ __forceinline__ int round_src(M okm, int pre, int idx) {
+  if constexpr (WIDE) return __builtin_ctzll(__ballot(pre == idx) & okm);
+  else return __builtin_ctz((uint32_t)__ballot(pre == idx) & okm);
+}
+// the entry of source lane `src`: its nib, category, value | len << 8 and number of cards, scalar arithmetic on the lane
+// number alone.  `gsz` = the group size of the follow layout's lanes 1..15.
+template <bool WIDE>
+__device__ __forceinline__ void round_entry(int src, uint32_t gsz, uint64_t& snib, uint32_t& scat, uint32_t& svlv, uint32_t& ncards) {
+  if (src == (WIDE ? 54 : 29)) {
+    snib = (1ull << 52) | (1ull << 56); scat = BIGBANG; svlv = 100u | (1u << 8); ncards = 2;
+  } else if (!WIDE && src == 0) {
+    snib = 0; scat = EMPTY; svlv = 1u << 8; ncards = 0;
+  } else {
+    int sr;
+    if constexpr (WIDE) {
+      const int g = (src >= 15) + (src >= 28) + (src >= 41);
+      sr = src - (g ? 2 + 13 * g : 0);
+      scat = (uint32_t)g + 1u;
+    } else {
+      sr = (src < 16 ? src - 1 : src - 16) & 15;
+      scat = src < 16 ? gsz : (uint32_t)QUADRIC;
+    }
+    snib = (uint64_t)scat << (4 * sr); svlv = (uint32_t)sr | (1u << 8); ncards = scat;
+  }
+}
+// the pick from a round that is the whole list: round_entry of the lane that holds `idx`; TRAJ: also its row, the same
+// value in every lane (four v_readlane: measured faster than scalar arithmetic, profiles/r04_notes.md)
+template <bool TRAJ, bool WIDE, class M>
+__device__ __forceinline__ void round_pick(M okm, int pre, const uint4& row, int idx, uint32_t gsz, uint4& c, uint64_t& snib,
+                                           uint32_t& scat, uint32_t& svlv, uint32_t& ncards) {
+  const int src = round_src<WIDE>(okm, pre, idx);
+  if (TRAJ) c = make_uint4(rl(row.x, src), rl(row.y, src), rl(row.z, src), rl(row.w, src));
+  round_entry<WIDE>(src, gsz, snib, scat, svlv, ncards);
+}
+
+// ------------------------------------------------------------------------------------
 // k_rollout: the random-policy lock-step iteration (game.py:169-181 with envi.py:79-85) with
 // NO dependency between tables: every table owns a fixed-stride slab of the list buffer
 // (rows[t * stride ...], counts[t]), so there is no cross-table scan, no count pass and no
 // block barrier after the prologue.  One wavefront per table:
-//   scan once, staging nib|category of every legal move in the wave's LDS list (its length
-//   is the list size, known before the pick) -> flush the list as coalesced 16-byte rows
-//   -> pick by engine RNG from the staged list -> apply / terminal / deal, all on the PACKED table (nibble rows);
+//   one closed-form round (round_emit: rows built arithmetically from the rank masks, stored straight into the slab) --
+//   the whole list of a follow of a single / pair / triple, of a lead from a hand without a triple, a run of five singles
+//   or of three pairs, and of a follow of any other category the hand cannot answer in kind; otherwise the planner stages
+//   nib|category of the tail in the wave's LDS list (the list size is known before the pick) -> flush of the tail as
+//   coalesced 16-byte rows behind the round's -> pick by engine RNG from the round or the staged tail -> apply / terminal /
+//   deal, all on the PACKED table (nibble rows);
 //   the state rows are rebuilt and stored once per table and launch, after its last iteration.
 struct RolloutArgs {
   uint8_t* state;
@@ -1001,16 +1118,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
   uint16_t* sid = s_sid[IDS ? wv : 0];
   int s_ply = 0;
   int64_t s_rows = 0;
-  // per-lane constants of the fast path (VGPRs; opaque so that they are not rebuilt from spilled lane masks)
-  const int f_rr = (lane < 16 ? lane - 1 : lane - 16) & 15;
-  uint32_t f_bit = lane < 32 ? 1u << lane : 0u;                     // this lane's bit in a 32-bit candidate mask
-  uint32_t f_sh = 8u * (uint32_t)(f_rr & 3);                         // byte position of the rank in its row word
-  uint32_t f_w0 = (f_rr >> 2) == 0 ? ~0u : 0u, f_w1 = (f_rr >> 2) == 1 ? ~0u : 0u;
-  uint32_t f_w2 = (f_rr >> 2) == 2 ? ~0u : 0u, f_w3 = (f_rr >> 2) == 3 ? ~0u : 0u;
-  uint32_t f_grp = (lane >= 1 && lane < 16) ? ~0u : 0u;             // lanes 1..15: a group of the led size
-  uint32_t f_c4 = (lane >= 16 && lane < 29) ? 4u : 0u;              // lanes 16..28: a bomb
-  uint32_t f_rk = lane == 29 ? (0x00010100u | ((uint32_t)BIGBANG << 24)) : 0u;  // lane 29: the rocket row
-  asm volatile("" : "+v"(f_bit), "+v"(f_sh), "+v"(f_w0), "+v"(f_w1), "+v"(f_w2), "+v"(f_w3), "+v"(f_grp), "+v"(f_c4), "+v"(f_rk));
+  const FastLanes fl = fast_lanes(lane);  // per-lane constants of the follow layout's closed-form round
   for (int i = 0; i < ntab; ++i) {
     const int64_t t = t0 + i;
     stamps.mark(0);  // prologue (or previous table's tail)
@@ -1064,7 +1172,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       }
       continue;
     }
-    int idle = 0;  // iterations that applied no ply (n <= 0: only behind the STAGE_CAP guard)
+    int idle = 0;  // iterations that applied no ply (n <= 0: an empty imported hand, or behind the STAGE_CAP guard)
     for (int it = (int)a.n_iters; it > 0; --it) {
       uint4 tr0 = make_uint4(0, 0, 0, 0);
       uint4 tr1 = make_uint4((uint32_t)role, ply << 16, episode, 0xFFFFFFFFu);
@@ -1088,75 +1196,125 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       uint64_t snib = 0;                  // ... as a nib, its category and value | len << 8
       uint32_t scat = 0, svlv = 0, ncards = 0;  // ... and its number of cards
       const int lc0 = (int)(info & 0xFF);
+      // Every list begins with one closed-form round (round_emit): rows built arithmetically and stored straight into the
+      // slab, no record table, no staging.  Whether the list has a TAIL beyond that round is decided on the hand's rank
+      // masks (wave-uniform, scalar): a superset test -- where it says "no tail" the planner would find nothing either.
+      const int cntr = lane < 15 ? (int)((hand >> (4 * (lane & 15))) & 15) : 0;
+      uint4 row = make_uint4(0, 0, 0, 0);  // this lane's row of the round and its position in it (round_emit)
+      int pre = 0;
+      // no tail (nine plies in ten): the round is the list, the pick comes from the round (n0 >= 1)
+      auto whole = [&](int n0) {
+        n = n0;
+        *cnt_p = n;  // every lane stores the same word: no exec-mask change
+        s_rows += n;
+        idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83
+      };
+      const int fid = !IDS ? 0 : lane == 0 ? 0 : lane < 16 ? (lc0 == SINGLE ? 1 : lc0 == DOUBLE ? 16 : lc0 == TRIPLE ? 29 : 42) + fl.rr
+                                 : lane < 29 ? 42 + fl.rr : ID_BIGBANG;   // the follow layout's canonical ids
       if (lc0 != EMPTY && lc0 <= TRIPLE) {
-        // Two thirds of all plies follow a single, a pair or a triple.  Their
-        // legal list is pass + the higher groups of the same size + bombs + rocket
-        // (card.py:307-325): one lane per candidate, rows built arithmetically and stored
-        // straight into the slab; no record table, no staging.
-        //   lanes: 0 pass | 1..15 group of rank lane-1 | 16..28 bomb of rank lane-16 | 29 rocket
+        // Two thirds of all plies follow a single, a pair or a triple.  Their legal list is pass + the higher groups of the
+        // same size + bombs + rocket (card.py:307-325): never a tail.
         const int lv0 = (int)((info >> 8) & 0xFF);
-        const int cntr = lane < 15 ? (int)((hand >> (4 * (lane & 15))) & 15) : 0;
         const uint32_t mlc = (uint32_t)__ballot(cntr >= lc0) & (lc0 == SINGLE ? M15 : M13);
         const uint32_t mq = (uint32_t)__ballot(cntr >= 4) & M13;
         const bool rocket = ((uint32_t)__ballot(cntr >= 1) & JOKERS) == JOKERS;
-        const uint32_t ab = gt_mask(lv0);
-        const uint32_t cand = mlc & ab;
-        const uint32_t bombs = mq;
-        const int rr = f_rr;
         // the candidate mask is scalar: bit 0 pass | 1..15 groups | 16..28 bombs | 29 rocket
-        const uint32_t okm = 1u | (cand << 1) | (bombs << 16) | (rocket ? 1u << 29 : 0u);
-        const bool ok = (okm & f_bit) != 0;
-        n = __builtin_popcount(okm);
-        const int pre = (int)__builtin_amdgcn_mbcnt_lo(okm, 0u);
-        const uint32_t copies = ((uint32_t)lc0 & f_grp) | f_c4;  // category == group size here
-        const uint32_t dv = copies << f_sh;
-        const uint4 row = make_uint4(dv & f_w0, dv & f_w1, dv & f_w2, (dv & f_w3) | (copies << 24) | f_rk);
-        if (ok) {
-          a.rows[base + pre] = row;
-          if (IDS) a.ids[base + pre] = lane == 0 ? 0 : lane < 16 ? (lc0 == SINGLE ? 1 : lc0 == DOUBLE ? 16 : lc0 == TRIPLE ? 29 : 42) + rr
-                                      : lane < 29 ? 42 + rr : ID_BIGBANG;
-        }
-        *cnt_p = n;  // every lane stores the same word: no exec-mask change
-        s_rows += n;
-        stamps.mark(5);
-        idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83 (n >= 1: pass)
-        const int src = __builtin_ctz((uint32_t)__ballot(pre == idx) & okm);
-        const int sr = (src < 16 ? src - 1 : src - 16) & 15;
-        if (TRAJ) c = make_uint4(rl(row.x, src), rl(row.y, src), rl(row.z, src), rl(row.w, src));
-        if (src == 0) { snib = 0; scat = EMPTY; svlv = 1u << 8; }
-        else if (src == 29) { snib = (1ull << 52) | (1ull << 56); scat = BIGBANG; svlv = 100u | (1u << 8); ncards = 2; }
-        else { scat = src < 16 ? (uint32_t)lc0 : (uint32_t)QUADRIC; snib = (uint64_t)scat << (4 * sr); svlv = (uint32_t)sr | (1u << 8); ncards = scat; }
-        stamps.mark(5);  // fast path: list + pick
+        const uint32_t okm = 1u | ((mlc & gt_mask(lv0)) << 1) | (mq << 16) | (rocket ? 1u << 29 : 0u);
+        const uint32_t copies = ((uint32_t)lc0 & fl.grp) | fl.c4;  // category == group size here
+        whole(round_emit<IDS>(okm, fl, copies, fid, a.rows, a.ids, base, row, pre));
+        round_pick<TRAJ, false>(okm, pre, row, idx, (uint32_t)lc0, c, snib, scat, svlv, ncards);
+        stamps.mark(5);  // follow of a single / pair / triple: list + pick
       } else {
-        const Out o{nullptr, nullptr, 0, 0, stage, svl, sid};
-        Pick pk{-1, 0, 0, 0, 0};
-        n = plan_scan<EM_STAGE, IDS>(hand, info, hot, lane, o, pk);
-        __builtin_amdgcn_wave_barrier();
-        if (n > STAGE_CAP || n > a.stride) {  // cannot happen for a <= 20-card hand; never index past the slab
-          if (lane == 0) atomicOr(a.status, 2);
-          n = 0;
+        const uint32_t m1 = (uint32_t)__ballot(cntr >= 1) & M15, m2 = (uint32_t)__ballot(cntr >= 2) & M13;
+        const uint32_t m3 = (uint32_t)__ballot(cntr >= 3) & M13, m4 = (uint32_t)__ballot(cntr >= 4) & M13;
+        const bool jokers = (m1 & JOKERS) == JOKERS;
+        const bool lead = lc0 == EMPTY;
+        uint64_t okm;  // the legal lanes of the round: 55 lanes of the lead layout, 30 of the follow layout
+        bool tail;
+        int n0;
+        if (lead) {
+          // A lead: singles, pairs, triples and bombs (ids 1..54) are legal <=> the rank is held often enough.  Everything
+          // else of the action space needs a triple (3+1, 3+2, planes, triple chains; four-takes: m4 is a subset of m3), a
+          // run of five singles or a run of three pairs; without those the list ends with the rocket, lane 54.  (An empty
+          // hand, m1 == 0, goes the planner's way to its empty list.)
+          tail = m3 != 0 || run_starts(m1 & M12, 5) != 0 || run_starts(m2 & M12, 3) != 0 || m1 == 0;
+          okm = (uint64_t)m1 | (uint64_t)m2 << 15 | (uint64_t)m3 << 28 | (uint64_t)m4 << 41 |
+                (jokers && !tail ? 1ull << 54 : 0ull);   // (with a tail the rocket is the planner's: id order)
+          int ln = lane;
+          asm volatile("" : "+v"(ln));  // opaque: the lane constants are computed here, not hoisted and held
+          const LeadLanes ll = lead_lanes(ln);
+          n0 = round_emit<IDS>(okm, ll, ll.copies, ln < 54 ? 1 + ln : ID_BIGBANG, a.rows, a.ids, base, row, pre);
+        } else {
+          // A follow of any other category: pass + bombs + rocket, unless the hand may hold a higher combination of the
+          // category itself (value above lv; chains and planes: a run of the led length).  A bomb is followed by the higher
+          // bombs (the group lanes, bomb lanes off) and the rocket, the rocket by pass alone (card.py:307-325).
+          const int lv0 = (int)((info >> 8) & 0xFF), ll0 = (int)((info >> 16) & 0xFF);
+          const uint32_t ab = gt_mask(lv0);
+          uint32_t cand = 0, bombs = m4, may = 0;
+          bool rocket = jokers;
+          if (lc0 == QUADRIC) { cand = m4 & ab; bombs = 0; }
+          else if (lc0 == BIGBANG) { bombs = 0; rocket = false; }
+          else if (lc0 == THREE_ONE || lc0 == THREE_TWO) may = m3 & ab;
+          else if (lc0 == SINGLE_LINE) may = run_starts(m1 & M12, ll0) & ab;
+          else if (lc0 == DOUBLE_LINE) may = run_starts(m2 & M12, ll0) & ab;
+          else if (lc0 == TRIPLE_LINE || lc0 == THREE_ONE_LINE || lc0 == THREE_TWO_LINE) may = run_starts(m3 & M12, ll0) & ab;
+          else if (lc0 == FOUR_TAKE_ONE || lc0 == FOUR_TAKE_TWO) may = m4 & ab;
+          tail = may != 0 || m1 == 0;   // (an empty hand: the planner's empty list)
+          // with a tail only pass and the bombs (ids 0, 42..54) come direct: the rocket's id lies inside the planner's part
+          const uint32_t okf = m1 == 0 ? 0u : 1u | (cand << 1) | (bombs << 16) | (rocket && !tail ? 1u << 29 : 0u);
+          const uint32_t copies = ((uint32_t)lc0 & fl.grp) | fl.c4;  // (group lanes: only legal after a bomb, lc0 == 4)
+          n0 = round_emit<IDS>(okf, fl, copies, fid, a.rows, a.ids, base, row, pre);
+          okm = okf;
         }
-        stamps.mark(2);  // scan (planner + rounds + staging)
-        *cnt_p = n;
-        s_rows += n;
-        for (int j = lane; j < n; j += 64) {  // flush: coalesced 16-byte rows
-          const uint64_t e = stage[j];
-          a.rows[base + j] = unpack_row(e & 0x0FFFFFFFFFFFFFFFull, (uint32_t)(e >> 60));
-          if (IDS) a.ids[base + j] = sid[j];
+        if (!tail) {
+          whole(n0);
+          if (lead) round_pick<TRAJ, true>(okm, pre, row, idx, 0u, c, snib, scat, svlv, ncards);
+          else round_pick<TRAJ, false>((uint32_t)okm, pre, row, idx, (uint32_t)lc0, c, snib, scat, svlv, ncards);
+          stamps.mark(11);  // closed-form lead / follow of another category: list + pick
+        } else {
+          // a tail: the planner without its first range stages the rest of the list (nib | category, value | len) in the
+          // wave's LDS list from index 0; the flush puts it behind the round's rows; the pick takes whichever part holds
+          // its index
+          const Out o{nullptr, nullptr, 0, 0, stage, svl, sid};
+          Pick pk{-1, 0, 0, 0, 0};
+          const Follow f = follow_of(info);
+          const int n1 = lead ? plan_scan_t<EM_STAGE, IDS, true, HotTabT<false>, false>(hand, f, hot, lane, o, pk)
+                              : plan_scan_t<EM_STAGE, IDS, false, HotTabT<false>, false>(hand, f, hot, lane, o, pk);
+          __builtin_amdgcn_wave_barrier();
+          n = n0 + n1;
+          if (n > STAGE_CAP || n > a.stride) {  // cannot happen for a <= 20-card hand; never index past the slab
+            if (lane == 0) atomicOr(a.status, 2);
+            n = 0;
+          }
+          stamps.mark(2);  // hybrid: closed-form round + planner + scan rounds + staging
+          *cnt_p = n;
+          s_rows += n;
+          const int64_t tbase = base + n0;
+          for (int j = lane; j < n - n0; j += 64) {  // flush: coalesced 16-byte rows
+            const uint64_t e = stage[j];
+            a.rows[tbase + j] = unpack_row(e & 0x0FFFFFFFFFFFFFFFull, (uint32_t)(e >> 60));
+            if (IDS) a.ids[tbase + j] = sid[j];
+          }
+          stamps.mark(3);  // hybrid: flush rows
+          if (n > 0) {
+            idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83
+            if (idx < n0) {  // from the round: by lane number (its positions are rebuilt here, not held across the planner)
+              if (lead) round_entry<true>(round_src<true>(okm, round_pre(okm), idx), 0u, snib, scat, svlv, ncards);
+              else round_entry<false>(round_src<false>((uint32_t)okm, round_pre((uint32_t)okm), idx), (uint32_t)lc0, snib, scat, svlv, ncards);
+              if (TRAJ) c = unpack_row(snib, scat);
+            } else {
+              const uint64_t e = stage[idx - n0];      // LDS broadcast read
+              const uint64_t anib = e & 0x0FFFFFFFFFFFFFFFull;
+              const uint32_t acat = (uint32_t)(e >> 60);
+              if (TRAJ) c = unpack_row(anib, acat);
+              snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
+              scat = rfl(acat);
+              svlv = rfl((uint32_t)svl[idx - n0]);
+              ncards = (uint32_t)nib_sum(snib);
+            }
+          }
+          stamps.mark(10);  // hybrid: pick
         }
-        stamps.mark(3);  // flush rows
-        if (n > 0) {
-          idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83
-          const uint64_t e = stage[idx];           // LDS broadcast read
-          const uint64_t anib = e & 0x0FFFFFFFFFFFFFFFull;
-          const uint32_t acat = (uint32_t)(e >> 60);
-          if (TRAJ) c = unpack_row(anib, acat);
-          snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
-          scat = rfl(acat);
-          svlv = rfl((uint32_t)svl[idx]);
-          ncards = (uint32_t)nib_sum(snib);
-        }
-        stamps.mark(10);  // generic pick
       }
       tr1.y |= (uint32_t)n & 0xFFFF;
       if (n <= 0) {
@@ -1209,7 +1367,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       }
       if (TRAJ && lane < 2) tj[lane] = sel4(lane == 0, tr0, tr1);
       if (TRAJ) tj += 2 * a.T;
-      stamps.mark(4);  // pick + apply + deal + trajectory store
+      stamps.mark(4);  // record store + end of iteration
       __builtin_amdgcn_wave_barrier();  // the staging list is reused by the next iteration / table
     }
     s_ply += (int)a.n_iters - idle;
@@ -1277,25 +1435,6 @@ struct SlabArgs {
   int lpt;              // tpw >= 2: deals + lists of a block's tables go through a block work list, most expensive first
 };
 constexpr int STEP_Q = 4;  // internal mode of k_slab: sel = f32 q[T][stride]
-
-// per-lane constants of the arithmetic follow list: lanes 0 pass | 1..15 group of rank lane-1 | 16..28 bomb | 29 rocket
-struct FastLanes {
-  int rr;
-  uint32_t bit, sh, w0, w1, w2, w3, grp, c4, rk;
-};
-__device__ __forceinline__ FastLanes fast_lanes(int lane) {
-  FastLanes f;
-  f.rr = (lane < 16 ? lane - 1 : lane - 16) & 15;
-  f.bit = lane < 32 ? 1u << lane : 0u;
-  f.sh = 8u * (uint32_t)(f.rr & 3);
-  f.w0 = (f.rr >> 2) == 0 ? ~0u : 0u; f.w1 = (f.rr >> 2) == 1 ? ~0u : 0u;
-  f.w2 = (f.rr >> 2) == 2 ? ~0u : 0u; f.w3 = (f.rr >> 2) == 3 ? ~0u : 0u;
-  f.grp = (lane >= 1 && lane < 16) ? ~0u : 0u;
-  f.c4 = (lane >= 16 && lane < 29) ? 4u : 0u;
-  f.rk = lane == 29 ? (0x00010100u | ((uint32_t)BIGBANG << 24)) : 0u;
-  asm volatile("" : "+v"(f.bit), "+v"(f.sh), "+v"(f.w0), "+v"(f.w1), "+v"(f.w2), "+v"(f.w3), "+v"(f.grp), "+v"(f.c4), "+v"(f.rk));
-  return f;
-}
 
 // the legal list of (hand, info) into the table's slab rows[base ...], ascending canonical id; returns its size
 template <bool IDS, class HT>

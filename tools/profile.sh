@@ -11,7 +11,8 @@
 #              HBM counters (separate passes), per-stage HIP-event times
 #   secondary  k_observe<0..3>, k_mask, k_moves*: kernel stats + HBM counters
 #   probe      tools/valu_issue_probe.hip (VALU issue rates) + tools/dpp_probe.hip (DPP scan / reduction vs ds_bpermute)
-#   stamps     -DDDZ_STAMP builds: where k_slab's and k_auto2's waves spend their cycles (tools/stamp_slab.py, stamp_auto.py)
+#   stamps     -DDDZ_STAMP builds: where k_slab's, k_auto2's and k_rollout's waves spend their cycles (tools/stamp_slab.py,
+#              stamp_auto.py, stamp_rollout.py)
 # tools/collect_r04.py turns the raw output into the summaries tracked under profiles/ (tools/README.md maps each file).
 set -e
 cd /tmp && export TMPDIR=/tmp
@@ -73,7 +74,8 @@ for pass in "$@"; do
     stamps)
       python3 tools/stamp_slab.py 65536,4096 random > $O/stamp_slab.txt 2>&1
       python3 tools/stamp_auto.py 16384 > $O/stamp_auto.txt 2>&1
-      cat $O/stamp_slab.txt $O/stamp_auto.txt ;;
+      timeout -k 10 600 python3 tools/stamp_rollout.py 65536,4096 > $O/stamp_rollout.txt 2>&1
+      cat $O/stamp_slab.txt $O/stamp_auto.txt $O/stamp_rollout.txt ;;
     *) echo "unknown pass $pass"; exit 2 ;;
   esac
   echo "pass $pass done"
