@@ -38,6 +38,14 @@ SYMBOLS = {
     "ddz_slab_to_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_observe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ddz_observe_states": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "ddz_tr_ws_bytes": (C.c_int64, [C.c_int64]),
+    "ddz_tr_ring_bytes": (C.c_int64, [C.c_int64]),
+    "ddz_tr_ring_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "ddz_tr_before": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ddz_tr_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "ddz_state_prob": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_rows_to_onehot": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_observe_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -2519,18 +2519,10 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_stats(Scratch sc, int64_t nslo
 // VARIANT is a template parameter: the divisions by P * 15 and by 15 are by constants (a 64-bit runtime
 // division per 16-byte store made the first version instruction-bound at half the HBM write rate) and the
 // plane kinds are immediates.
-template <int VARIANT>
-__global__ __launch_bounds__(BLOCK) void k_observe(const uint8_t* __restrict__ state, int64_t T,
-                                                   float4* __restrict__ out) {
-  constexpr int P = VARIANT == 0 ? 4 : VARIANT == 1 ? 7 : VARIANT == 2 ? 9 : 6;
-  // kinds of the planes, 4 bits each, plane 0 in the low nibble
-  constexpr uint64_t KINDS = VARIANT == 0 ? 0x8710ull : VARIANT == 1 ? 0x8743210ull
-                           : VARIANT == 2 ? 0x876543210ull : 0x876510ull;
-  const int64_t idx = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (idx >= T * (P * 15)) return;
-  int64_t t;
-  int rem;
-  if (T * (P * 15) <= 0x7FFFFFFFll) {  // wave-uniform: 32-bit index arithmetic
+// idx of a [n][P][15] grid -> (item, plane * 15 + rank)
+template <int P>
+__device__ __forceinline__ void face_split(int64_t idx, int64_t n, int64_t& t, int& rem) {
+  if (n * (P * 15) <= 0x7FFFFFFFll) {  // wave-uniform: 32-bit index arithmetic
     const uint32_t i32 = (uint32_t)idx, t32 = i32 / (uint32_t)(P * 15);
     t = t32;
     rem = (int)(i32 - t32 * (uint32_t)(P * 15));
@@ -2538,8 +2530,16 @@ __global__ __launch_bounds__(BLOCK) void k_observe(const uint8_t* __restrict__ s
     t = idx / (P * 15);
     rem = (int)(idx - t * (P * 15));
   }
+}
+
+// the four slots of (plane rem / 15, rank rem % 15) of the face of one 176-byte state row: THE statement of `face`
+// (k_observe over an environment's tables, k_observe_states over the rows of a replay batch)
+template <int VARIANT>
+__device__ __forceinline__ float4 face_cell(const uint8_t* __restrict__ row, int rem) {
+  // kinds of the planes, 4 bits each, plane 0 in the low nibble
+  constexpr uint64_t KINDS = VARIANT == 0 ? 0x8710ull : VARIANT == 1 ? 0x8743210ull
+                           : VARIANT == 2 ? 0x876543210ull : 0x876510ull;
   const int p = rem / 15, i = rem - p * 15;
-  const uint8_t* row = state + t * STATE_ROW_BYTES;
   auto byte = [&](int f, int k) { return (int)row[f * 16 + k]; };
   int role = byte(DDZ_F_META, 0);
   if (role > 2) role = 0;
@@ -2559,7 +2559,19 @@ __global__ __launch_bounds__(BLOCK) void k_observe(const uint8_t* __restrict__ s
     auto slot = [&](int j) { return (j >= known && j < total) ? fr : 0.f; };
     v = make_float4(slot(0), slot(1), slot(2), slot(3));
   }
-  store_stream(&out[idx], v);
+  return v;
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(BLOCK) void k_observe(const uint8_t* __restrict__ state, int64_t T,
+                                                   float4* __restrict__ out) {
+  constexpr int P = VARIANT == 0 ? 4 : VARIANT == 1 ? 7 : VARIANT == 2 ? 9 : 6;
+  const int64_t idx = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (idx >= T * (P * 15)) return;
+  int64_t t;
+  int rem;
+  face_split<P>(idx, T, t, rem);
+  store_stream(&out[idx], face_cell<VARIANT>(state + t * STATE_ROW_BYTES, rem));
 }
 
 // get_state_prob_manual(known60, size1, size2) (server/core.py:26-33; native in the reference, prob planes spec v1):
@@ -2590,6 +2602,8 @@ __global__ __launch_bounds__(BLOCK) void k_onehot(const uint8_t* __restrict__ ro
   const int c = rows[r * 16 + (idx - r * 15)];
   store_stream(&out[idx], make_float4(c > 0 ? 1.f : 0.f, c > 1 ? 1.f : 0.f, c > 2 ? 1.f : 0.f, c > 3 ? 1.f : 0.f));
 }
+
+#include "ddz_replay.h"
 
 // ------------------------------------------------------------------------------------
 // action table export and the compact trajectory record.
@@ -3183,6 +3197,94 @@ int ddz_observe_actions(ddz_env_t* e, int variant, float* face, const int8_t* ro
   const int rc = ddz_observe(e, variant, face, stream);
   if (rc != DDZ_OK || n == 0) return rc;
   return ddz_rows_to_onehot(e->device, rows, n, onehot, stream);
+}
+
+int ddz_observe_states(int device, const uint8_t* states, const int64_t* index, int64_t n, int variant, float* face, void* stream) {
+  if (!al(states, 16) || !al(index, 8) || !al(face, 16)) return DDZ_EINVAL;
+  const int P = ddz_face_planes(variant);
+  if (P < 0 || n < 0 || (n > 0 && (!states || !face))) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+  const int64_t m = n * P * 15;
+  const dim3 grid((unsigned)((m + BLOCK - 1) / BLOCK)), block(BLOCK);
+  switch (variant) {
+    case 0: hipLaunchKernelGGL(k_observe_states<0>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
+    case 1: hipLaunchKernelGGL(k_observe_states<1>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
+    case 2: hipLaunchKernelGGL(k_observe_states<2>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
+    default: hipLaunchKernelGGL(k_observe_states<3>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
+  }
+  return check_launch();
+}
+
+int64_t ddz_tr_ws_bytes(int64_t T) { return T <= 0 || T > ((int64_t)1 << 30) ? DDZ_EINVAL : tr_ws_layout(T).bytes; }
+int64_t ddz_tr_ring_bytes(int64_t capacity) {
+  return capacity <= 0 || capacity > ((int64_t)1 << 30) ? DDZ_EINVAL : tr_ring_layout(capacity, nullptr);
+}
+int ddz_tr_ring_layout(int64_t capacity, int64_t* offsets) {
+  if (!offsets || ddz_tr_ring_bytes(capacity) < 0) return DDZ_EINVAL;
+  tr_ring_layout(capacity, offsets);
+  return DDZ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the checks ddz_tr_before and ddz_tr_after share; binds the rings (a null ring: that role records nothing)
+int tr_args(const ddz_env* e, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity, int need,
+            TrRings* out) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!ws || !rings || !al(ws, 16) || ws_bytes < ddz_tr_ws_bytes(e->T)) return DDZ_EINVAL;
+  const int64_t rb = ddz_tr_ring_bytes(capacity);
+  if (rb < 0 || ring_bytes < rb) return DDZ_EINVAL;
+  out->cap = capacity;
+  for (int k = 0; k < 3; ++k) {
+    if (!al(rings[k], 16) || (((need >> k) & 1) && !rings[k])) return DDZ_EINVAL;
+    out->r[k] = tr_ring_bind(rings[k], capacity);
+  }
+  return DDZ_OK;
+}
+
+template <bool AFTER>
+int tr_launch(ddz_env* e, void* ws, const TrRings& rings, const uint8_t* gate, int trained, const int32_t* chosen,
+              const int32_t* greedy, const int8_t* r, TrAfter af, hipStream_t st) {
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const TrWsLayout l = tr_ws_layout(e->T);
+  const TrWs w = tr_bind(ws, l);
+  const uint8_t* state = (const uint8_t*)e->state;
+  hipLaunchKernelGGL((k_tr_mark<AFTER>), dim3((unsigned)l.nb), dim3(TR_BT), 0, st, state, e->T, w, gate, trained);
+  int rc = check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, w, l.nb, rings);
+  rc = check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_tr_emit<AFTER>), dim3((unsigned)((e->T * 16 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, e->T, w,
+                     rings, chosen, greedy, r, af);
+  return check_launch();
+}
+}  // namespace
+
+extern "C" {
+
+int ddz_tr_before(ddz_env_t* e, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity,
+                  const int32_t* chosen, const int32_t* greedy, const uint8_t* active, int trained_roles, void* stream) {
+  TrRings rg;
+  const int rc = tr_args(e, ws, ws_bytes, rings, ring_bytes, capacity, trained_roles & 7, &rg);
+  if (rc) return rc;
+  if (!chosen || !greedy || !al(chosen, 4) || !al(greedy, 4) || (trained_roles & ~7)) return DDZ_EINVAL;
+  return tr_launch<false>(e, ws, rg, active, trained_roles, chosen, greedy, nullptr, TrAfter{}, (hipStream_t)stream);
+}
+
+int ddz_tr_after(ddz_env_t* e, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity,
+                 const uint8_t* done, const int8_t* r, const float* reward, int replicate_reference_quirk, void* stream) {
+  TrRings rg;
+  const int rc = tr_args(e, ws, ws_bytes, rings, ring_bytes, capacity, 0, &rg);
+  if (rc) return rc;
+  if (!done || !r || !reward) return DDZ_EINVAL;
+  const TrAfter af{{reward[0], reward[1], reward[2]}, replicate_reference_quirk ? 1 : 0};
+  return tr_launch<true>(e, ws, rg, done, 0, nullptr, nullptr, r, af, (hipStream_t)stream);
 }
 
 int ddz_state_prob(int device, const uint8_t* known60, const int32_t* sizes, int64_t n, float* out, void* stream) {

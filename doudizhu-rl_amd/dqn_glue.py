@@ -927,6 +927,24 @@ class SeatLoop:
             self.ids.copy_(net_ids)
         return self.ids
 
+    def set_epsilon(self, epsilon):
+        """new exploration rates (a float for every network role, or {"lord" | "down" | "up": float}) for the next act(); a host
+        value, as in __init__: a captured graph keeps the rates it was captured with"""
+        if isinstance(epsilon, dict):
+            bad = set(epsilon) - set(ROLE_ORDER)
+            if bad:
+                raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
+            eps = [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
+        else:
+            eps = [float(epsilon)] * 3
+        nr = self.rq.net_of_role
+        self.eps = [e if nr[k] >= 0 else 0.0 for k, e in enumerate(eps)]
+        self._eps_of_role.copy_(torch.tensor(self.eps, dtype=torch.float32))
+        if any(self.eps) and self.choice is self.greedy:
+            self.choice = torch.empty(self.env.T, dtype=torch.int32, device=self.env.device)
+        elif not any(self.eps):
+            self.choice = self.greedy
+
     def apply(self, traj=None):
         from .engine import STEP_IDS
         done, r, illegal = self.env.step_slab(self.ids, STEP_IDS, auto_reset=self.auto_reset, traj=traj)
@@ -1042,3 +1060,257 @@ def td_step(policy, target, optimizer, batch, gamma=0.95):
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+# ------------------------------------------------------------------------------------------------
+# The same bookkeeping on the device (csrc/ddz_replay.h): TransitionAssembler + one Replay per role as three launches per call,
+# transitions kept packed (two 176-byte state rows, two action ids, reward, done, table) and decoded into faces / thermometers
+# when a batch is drawn.  TransitionAssembler and Replay above stay as the statement the recorder is tested against.
+REPLAY_SIZE, BATCH_SIZE, GAMMA, UPDATE_TARGET_EVERY, LEARNING_RATE = 20000, 256, 0.95, 20, 1e-4   # config.py:8-14, dqn.py:19
+
+
+def _role_id(role):
+    if isinstance(role, str):
+        if role not in ROLE_ORDER:
+            raise ValueError("role must be up / lord / down (or its id 0 / 1 / 2)")
+        return ROLE_ORDER.index(role)
+    if int(role) not in (0, 1, 2):
+        raise ValueError("role must be up / lord / down (or its id 0 / 1 / 2)")
+    return int(role)
+
+
+class TransitionRecorder:
+    """TransitionAssembler + one Replay per role (dqn.py:14) on the device, for env's tables: before() / after() around the
+    step of a lock-step iteration (ddz_tr_before / ddz_tr_after: same semantics as before_step / after_step, the `fresh` rule,
+    trained_roles, the active mask and replicate_reference_quirk included), nothing on the host, capturable.  A role's ring
+    holds `capacity` packed transitions (369 bytes each: any face variant is rebuilt from them, bit for bit, by decode());
+    the transition with sequence number s is entry s % capacity, in the order Replay.push would have stored the same calls
+    (per call: ascending table).  trained_roles: (up, lord, down); only they get a ring."""
+
+    def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), replicate_reference_quirk=False):
+        from . import engine as E
+        self.device = E._require_gpu(env.device)          # (DdzError without a GPU, as BatchedEnv)
+        rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
+        self.env, self.T, self.capacity = env, int(env.T), int(capacity)
+        if self.capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.reward = [float(rd.get(r) or 0.0) for r in ROLE_ORDER]
+        self.trained = tuple(bool(x) for x in trained_roles)
+        if len(self.trained) != 3:
+            raise ValueError("trained_roles: (up, lord, down)")
+        self.trained_mask = sum(1 << k for k in range(3) if self.trained[k])
+        self.quirk = bool(replicate_reference_quirk)
+        dev = self.device
+        self.ws = torch.zeros(E.tr_ws_bytes(self.T), dtype=torch.uint8, device=dev)
+        nbytes, off = E.tr_ring_bytes(self.capacity), E.tr_ring_layout(self.capacity)
+        self.rings = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) if t else None for t in self.trained]
+        cap = self.capacity
+
+        def views(ring):
+            f = lambda name, n, dt: ring[off[name]: off[name] + n].view(dt)   # noqa: E731
+            return {"count": f("count", 8, torch.int64), "s0": f("s0", cap * 176, torch.uint8).view(cap, 176),
+                    "s1": f("s1", cap * 176, torch.uint8).view(cap, 176), "a0": f("a0", cap * 4, torch.int32),
+                    "a1": f("a1", cap * 4, torch.int32), "reward": f("reward", cap * 4, torch.float32),
+                    "table": f("table", cap * 4, torch.int32), "done": f("done", cap, torch.uint8)}
+        self.fields = [None if r is None else views(r) for r in self.rings]
+        self._rows = E.action_table(dev, env.native_joker_kickers)       # [n_actions, 16] int8: id -> count row
+        self.known = [0, 0, 0]                                           # host-known lower bounds of the counts (note_counts)
+
+    @property
+    def ws_bytes_per_table(self):
+        return self.ws.numel() / self.T
+
+    def before(self, chosen_ids, greedy_ids, active=None):
+        """before the step: chosen_ids / greedy_ids int32 [T] canonical ids of what every table plays and of its greedy action
+        (a1 of the closing transition), active u8 / bool [T] the tables that move by a network (None: all)"""
+        self.env.tr_before(self.ws, self.rings, self.capacity, chosen_ids, greedy_ids, active, self.trained_mask)
+
+    def after(self, done, r):
+        """after step(auto_reset=False), before the re-deal: done u8 [T], r i8 [T] as the step returned them"""
+        self.env.tr_after(self.ws, self.rings, self.capacity, done, r, self.reward, self.quirk)
+
+    def _ring(self, role):
+        f = self.fields[_role_id(role)]
+        if f is None:
+            raise ValueError(f"role {role!r} is not trained: it has no ring")
+        return f
+
+    def count(self, role):
+        """transitions ever written into the role's ring: a 0-dim int64 DEVICE tensor (a view: it moves with the recorder)"""
+        return self._ring(role)["count"][0]
+
+    def note_counts(self):
+        """ONE host sync: reads the three counts into `known` (the host-known minimum sample() checks); returns them"""
+        c = torch.stack([f["count"][0] if f is not None else torch.zeros((), dtype=torch.int64, device=self.device)
+                         for f in self.fields]).tolist()
+        self.known = [int(x) for x in c]
+        return self.known
+
+    def decode(self, role, index, variant):
+        """the dict Replay.sample returns -- s0, s1 f32 [n,P,15,4], a0, a1 f32 [n,15,4], reward f32 [n], done bool [n] -- of
+        the ring entries index (int64 [n] device tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
+        from . import engine as E
+        f = self._ring(role)
+        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
+        na = self._rows.shape[0]
+        thermo = lambda ids: E.rows_to_onehot(self._rows[ids[index].clamp(0, na - 1).long()])   # noqa: E731
+        return {"s0": E.observe_states(f["s0"], index, variant), "a0": thermo(f["a0"]),
+                "s1": E.observe_states(f["s1"], index, variant), "a1": thermo(f["a1"]),
+                "reward": f["reward"][index], "done": f["done"][index].bool()}
+
+    def sample(self, role, k, variant, at_least=None):
+        """k entries drawn uniformly (with replacement, as Replay.sample) from the role's min(count, capacity) live entries, the
+        indices drawn ON THE DEVICE from the device count: no .item().  Whether the ring holds anything is the caller's
+        knowledge: at_least (default: known[role], which note_counts() refreshes at the caller's own sync points) is a
+        host-known lower bound of the count, and 0 is an argument error."""
+        rid = _role_id(role)
+        f = self._ring(role)
+        lo = self.known[rid] if at_least is None else int(at_least)
+        if lo <= 0:
+            raise ValueError("sample() needs a host-known positive lower bound of the ring's count (note_counts(), or at_least=)")
+        n = f["count"][0].clamp(min=1, max=self.capacity)
+        idx = (torch.rand(int(k), dtype=torch.float64, device=self.device) * n.double()).long().minimum(n - 1)
+        return self.decode(role, idx, variant)
+
+
+class TrainLoop:
+    """One iteration of Game.train's inner loop (game.py:90-167) for T tables, nothing on the host: SeatLoop.act() ->
+    recorder.before on the network tables -> step_slab(STEP_IDS, no auto-reset) -> recorder.after -> re-deal of the finished
+    tables -> the next lists and faces.  nets / epsilon as SeatLoop's; train_dict {"lord" | "down" | "up": bool} (default:
+    every role with a network trains): a network role that does not train plays greedy and records nothing (game.py:95-104).
+    capture(n) records n iterations as one graph at the epsilon of the moment."""
+
+    def __init__(self, env, nets, face_variant, capacity=REPLAY_SIZE, epsilon=0.0, train_dict=None, reward_dict=None,
+                 replicate_reference_quirk=False):
+        self.seat = SeatLoop(env, nets, face_variant, 0.0, auto_reset=False)
+        nr = self.seat.rq.net_of_role
+        td = {r: True for r in ROLE_ORDER} if train_dict is None else train_dict
+        bad = set(td) - set(ROLE_ORDER)
+        if bad:
+            raise ValueError(f"unknown role(s) {sorted(bad)} in train_dict")
+        self.trained = tuple(nr[k] >= 0 and bool(td.get(r)) for k, r in enumerate(ROLE_ORDER))
+        self.env, self.variant = env, int(face_variant)
+        self.rec = TransitionRecorder(env, capacity, reward_dict, self.trained, replicate_reference_quirk)
+        self.set_epsilon(epsilon)
+        self._greedy_ids = torch.empty(env.T, dtype=torch.int32, device=env.device)
+        self._active = torch.empty(env.T, dtype=torch.uint8, device=env.device)
+
+    def set_epsilon(self, epsilon):
+        """exploration of the TRAINED roles (a float, or a dict per role)"""
+        eps = dict(epsilon) if isinstance(epsilon, dict) else {r: float(epsilon) for r in ROLE_ORDER}
+        self.seat.set_epsilon({r: (e if self.trained[ROLE_ORDER.index(r)] else 0.0) for r, e in eps.items()})
+
+    @property
+    def face(self):
+        return self.seat.face
+
+    def step(self):
+        from .engine import STEP_IDS
+        s, env = self.seat, self.env
+        ids = s.act()
+        self._greedy_ids.copy_(env.slab_ids().gather(1, s.greedy.clamp(min=0).long()[:, None])[:, 0])
+        self._active.copy_(s.slot >= 0)
+        self.rec.before(ids, self._greedy_ids, self._active)
+        done, r, illegal = env.step_slab(ids, STEP_IDS, auto_reset=False)
+        self.rec.after(done, r)
+        env.reset(mask=done)
+        env.legal_slab()
+        env.observe(self.variant, out=s.face)
+        return done, r, illegal
+
+    def run(self, n):
+        for _ in range(int(n)):
+            self.step()
+
+    def capture(self, n=1):
+        """n iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first)."""
+        return PolicyLoop.capture(self, n)
+
+
+def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, tables=4096, seed=0, log_every=100,
+          model_every=1000, book=None, model_dir=None, win_dir=None, device="cuda:0", check_every=8, capacity=REPLAY_SIZE,
+          begin=None, log=None):
+    """Game.train (game.py:183-238) on the batched engine, the counterpart of compete(): nets {"lord" | "down" | "up": QNet |
+    None (the rule agent)}, train_dict which network roles keep training (default: all of them), reward_dict as REWARD_DICT.
+    Lock-step iterations of TrainLoop over `tables` tables until `episodes` episodes have finished; every iteration each
+    trained role whose ring holds BATCH_SIZE entries takes one td_step on a batch sampled on the device (dqn.py:24-48: Adam
+    1e-4, a target network per role).  The host looks at the device every `check_every` iterations only (env.stats() and the
+    ring counts: the one sync): there it moves epsilon (epsilon_schedule of the episodes so far), copies policy -> target
+    every UPDATE_TARGET_EVERY episodes (dqn.py:73-80), writes the log line every log_every and the checkpoints
+    <begin>_<role>_<episode> every model_every episodes (game.py:209-232; metrics.checkpoint_name / save_state_dict under
+    model_dir, the win rates under win_dir) -- `episode` being the multiple of the interval that was crossed, since the tables
+    finish episodes in bulk.  The policy networks learn in train() mode (dropout on, dqn.py:41), the targets are evaluated
+    without dropout.  Returns {"lord", "down", "up": wins, "episodes", "iterations", "loss": {role: last loss | None},
+    "checkpoints": [paths]}."""
+    import copy
+    import time
+    from . import metrics
+    from .engine import BatchedEnv
+    nets = {r: v for r, v in nets.items()}
+    for r, v in nets.items():
+        if v is not None:
+            nets[r] = v.to(device)
+    env = BatchedEnv(int(tables), seed=int(seed), device=device)
+    env.reset()
+    env.legal_slab()
+    loop = TrainLoop(env, nets, face_variant, capacity=capacity, epsilon=epsilon_schedule(0), train_dict=train_dict,
+                     reward_dict=reward_dict)
+    roles = [r for k, r in enumerate(ROLE_ORDER) if loop.trained[k]]
+    if not roles:
+        env.close()
+        raise ValueError("No agent need train.")                     # game.py:184-188
+    policy = {r: nets[r] for r in roles}
+    target, opt = {}, {}
+    for r in roles:                                                  # (roles that share a network object share the learner)
+        same = [o for o in target if policy[o] is policy[r]]
+        target[r] = target[same[0]] if same else copy.deepcopy(policy[r]).eval()
+        opt[r] = opt[same[0]] if same else torch.optim.Adam(policy[r].parameters(), LEARNING_RATE)
+        policy[r].train()
+    book = book if book is not None else metrics.WinRateBook(begin)
+    begin = begin or book.begin
+    s0 = env.stats()
+    book.update(s0)
+    loss = {r: None for r in roles}
+    paths, it, eps_done, eps_logged, t_log = [], 0, 0, 0, time.time()
+    ready = {r: False for r in roles}
+    while True:
+        for _ in range(int(check_every)):
+            loop.step()
+            for r in roles:
+                if ready[r]:
+                    loss[r] = td_step(policy[r], target[r], opt[r], loop.rec.sample(r, BATCH_SIZE, face_variant), GAMMA)
+        it += int(check_every)
+        s1 = env.stats()                                             # the host sync of the interval
+        known = loop.rec.note_counts()
+        for r in roles:
+            ready[r] = known[ROLE_ORDER.index(r)] >= BATCH_SIZE
+        book.update(s1)
+        prev, eps_done = eps_done, s1["episodes"] - s0["episodes"]
+        for r in roles:
+            if loss[r] is not None:
+                book.add_loss(r, float(loss[r]))
+        if eps_done // UPDATE_TARGET_EVERY > prev // UPDATE_TARGET_EVERY:
+            for r in roles:
+                target[r].load_state_dict(policy[r].state_dict())
+        if eps_done // int(log_every) > prev // int(log_every):
+            msg = book.log_message(eps_done - eps_logged, time.time() - t_log)
+            eps_logged = eps_done
+            if log is not None:
+                log(msg)
+            book.close_interval(win_dir)
+            t_log = time.time()
+        if model_dir is not None and eps_done // int(model_every) > prev // int(model_every):
+            mark = eps_done // int(model_every) * int(model_every)
+            for r in metrics.ROLES:
+                if nets.get(r) is not None:
+                    paths.append(metrics.save_state_dict(nets[r], model_dir, metrics.checkpoint_name(begin, r, mark)))
+        if eps_done >= int(episodes):
+            break
+        loop.set_epsilon(epsilon_schedule(eps_done))
+    for r in roles:
+        policy[r].eval()
+    env.close()
+    out = {"lord": s1["lord_wins"] - s0["lord_wins"], "down": s1["down_wins"] - s0["down_wins"],
+           "up": s1["up_wins"] - s0["up_wins"], "episodes": eps_done, "iterations": it,
+           "loss": {r: (None if v is None else float(v)) for r, v in loss.items()}, "checkpoints": paths}
+    return out

@@ -229,6 +229,57 @@ class BatchedEnv:
         check(self.lib.ddz_observe(self._h, int(variant), _p(out), _stream(self.device)))
         return out
 
+    # ---- the transition recorder (csrc/ddz_replay.h; dqn_glue.TransitionRecorder) ----
+    def _check_tr(self, ws, rings, capacity, need):
+        if ws.dtype != torch.uint8 or ws.device != self.device or not ws.is_contiguous() or ws.numel() < tr_ws_bytes(self.T):
+            raise ValueError("ws must be a contiguous uint8 device tensor of tr_ws_bytes(T) bytes")
+        if len(rings) != 3:
+            raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
+        nbytes = tr_ring_bytes(capacity)
+        for k, ring in enumerate(rings):
+            if ring is None:
+                if (need >> k) & 1:
+                    raise ValueError("a trained role needs a ring")
+            elif ring.dtype != torch.uint8 or ring.device != self.device or not ring.is_contiguous() or ring.numel() != nbytes:
+                raise ValueError("a ring must be a contiguous uint8 device tensor of tr_ring_bytes(capacity) bytes")
+        return (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rings]), nbytes
+
+    def _ids_arg(self, x, name):
+        if x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous() or x.numel() != self.T:
+            raise ValueError(f"{name} must be a contiguous int32 [T] device tensor")
+        return x
+
+    def _u8_arg(self, x, name, dtype=torch.uint8):
+        if x.dtype == torch.bool and dtype == torch.uint8:
+            x = x.to(torch.uint8)
+        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or x.numel() != self.T:
+            raise ValueError(f"{name} must be a contiguous {dtype} [T] device tensor")
+        return x
+
+    def tr_before(self, ws, rings, capacity, chosen, greedy, active=None, trained_roles=0b111):
+        """ddz_tr_before: close and open transitions on the CURRENT states (call it before the step).  chosen / greedy int32 [T]
+        canonical action ids, active u8 / bool [T] or None (all tables), trained_roles: bit r = role r.  No host sync."""
+        trained_roles = int(trained_roles)
+        if trained_roles & ~7:
+            raise ValueError("trained_roles is a mask of the role bits 0 (up), 1 (lord), 2 (down)")
+        ptrs, nbytes = self._check_tr(ws, rings, capacity, trained_roles)
+        chosen, greedy = self._ids_arg(chosen, "chosen"), self._ids_arg(greedy, "greedy")
+        if active is not None:
+            active = self._u8_arg(active, "active")
+        check(self.lib.ddz_tr_before(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(chosen), _p(greedy), _p(active),
+                                     trained_roles, _stream(self.device)))
+
+    def tr_after(self, ws, rings, capacity, done, r, reward, replicate_reference_quirk=False):
+        """ddz_tr_after: the terminal transitions of the finished tables (call it after step(auto_reset=False), before the
+        re-deal).  done u8 [T], r i8 [T] as the step wrote them, reward: three floats in role order up, lord, down."""
+        ptrs, nbytes = self._check_tr(ws, rings, capacity, 0)
+        done, r = self._u8_arg(done, "done"), self._u8_arg(r, "r", torch.int8)
+        if len(reward) != 3:
+            raise ValueError("reward: three floats in role order up, lord, down")
+        check(self.lib.ddz_tr_after(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(done), _p(r),
+                                    (C.c_float * 3)(*[float(x) for x in reward]), int(bool(replicate_reference_quirk)),
+                                    _stream(self.device)))
+
     def select(self, q, epsilon=0.0, out=None):
         """greedy / epsilon-greedy choice per table from per-row values q (f32, CSR order of
         the current legal list; dqn.py:50-71).  Returns int32[T] indices for step(STEP_CHOICE)."""
@@ -581,6 +632,60 @@ def rows_to_onehot(rows):
     if n:
         check(L.ddz_rows_to_onehot(dev.index, _p(rows), n, _p(out), _stream(dev)))
     return out
+
+
+def observe_states(states, index=None, variant=3, out=None):
+    """ddz_observe_states: `face` f32 [n,P,15,4] of the packed state rows states[index] (states uint8 [m,176] or [m,11,16] on
+    the device; index int64 [n] device tensor whose entries the CALLER keeps inside [0, m), or None = every row in order):
+    BatchedEnv.observe's expression, bit for bit, on rows that are not an environment's.  No host sync."""
+    dev = _require_gpu(states.device)
+    P = FACE_PLANES[variant]
+    if states.dtype != torch.uint8 or not states.is_contiguous() or states.numel() % (NFIELDS * ROW):
+        raise ValueError("states must be a contiguous uint8 tensor of 176-byte rows")
+    m = states.numel() // (NFIELDS * ROW)
+    if index is None:
+        n = m
+    else:
+        if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous() or index.dim() != 1:
+            raise ValueError("index must be a contiguous int64 [n] tensor on the states' device")
+        n = index.numel()
+        if n and m == 0:
+            raise ValueError("index into an empty states tensor")
+    if out is None:
+        out = torch.empty((n, P, 15, 4), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or out.numel() != n * P * 60 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 [n,{P},15,4] tensor")
+    if n:
+        check(_lib.lib().ddz_observe_states(dev.index, _p(states), _p(index), n, int(variant), _p(out), _stream(dev)))
+    return out
+
+
+def tr_ws_bytes(n_tables):
+    """bytes of the transition recorder's workspace for n_tables tables (ddz_tr_ws_bytes; zero-filled by the caller)"""
+    n = int(_lib.lib().ddz_tr_ws_bytes(int(n_tables)))
+    if n < 0:
+        raise ValueError("n_tables must be in 1 .. 2^30")
+    return n
+
+
+def tr_ring_bytes(capacity):
+    """bytes of one role's ring of `capacity` packed transitions (ddz_tr_ring_bytes; zero-filled by the caller)"""
+    n = int(_lib.lib().ddz_tr_ring_bytes(int(capacity)))
+    if n < 0:
+        raise ValueError("capacity must be in 1 .. 2^30")
+    return n
+
+
+TR_RING_FIELDS = ("count", "s0", "s1", "a0", "a1", "reward", "table", "done")
+
+
+def tr_ring_layout(capacity):
+    """{field: byte offset} of a ring (ddz_tr_ring_layout): count int64, s0 / s1 u8 [capacity,176], a0 / a1 int32, reward f32,
+    table int32, done u8"""
+    off = (C.c_int64 * 8)()
+    if _lib.lib().ddz_tr_ring_layout(int(capacity), off) != 0:
+        raise ValueError("capacity must be in 1 .. 2^30")
+    return dict(zip(TR_RING_FIELDS, [int(x) for x in off]))
 
 
 def state_prob(known60, size1, size2, device="cuda:0"):

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Game.train (game.py:183-238; the set-up of the reference's train.py:8-31) on the batched engine: EnvCooperation faces, a
+NetCooperation-shaped QNet per trained role, the rule agent for the others; dqn_glue.train -- TrainLoop (SeatLoop's acting, the
+device-side transition recorder and packed replay rings of csrc/ddz_replay.h; nothing on the host inside an iteration) + one
+autograd td_step per trained role per iteration.  Hyper-parameters are the reference's (config.py:8-14).  Prints the
+reference's progress lines, the total wins and the checkpoints written.
+
+  python examples/train.py [--lord-vs-rule] [--tables 4096] [--episodes 20000] [--log-every 5000] [--model-every 10000]
+                           [--model-dir models] [--win-dir outs/win_rates]
+
+Default: lord, down and up all train (three networks).  --lord-vs-rule: the reference's train.py as it stands -- the lord trains
+against the rule-based farmers (reward_dict {'lord': 100}).
+"""
+import argparse
+import importlib
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FACE_VARIANT = 2   # EnvCooperation (envi.py:182-198), 9 planes: NetCooperation's input (net.py)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lord-vs-rule", action="store_true")
+    ap.add_argument("--tables", type=int, default=4096)
+    ap.add_argument("--episodes", type=int, default=20000)
+    ap.add_argument("--log-every", type=int, default=5000)
+    ap.add_argument("--model-every", type=int, default=10000)
+    ap.add_argument("--model-dir", default=None)
+    ap.add_argument("--win-dir", default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
+    metrics = importlib.import_module("doudizhu-rl_amd.metrics")
+    engine = importlib.import_module("doudizhu-rl_amd.engine")
+    roles = ("lord",) if a.lord_vs_rule else ("lord", "down", "up")
+    nets, train_dict, reward_dict = {}, {}, dict(glue.REWARD_DICT)
+    for k, role in enumerate(("lord", "down", "up")):
+        torch.manual_seed(a.seed * 3 + k)
+        nets[role] = glue.QNet(engine.FACE_PLANES[FACE_VARIANT]) if role in roles else None
+        train_dict[role] = role in roles
+        print("{}: {} based model.{}".format(role, "AI" if role in roles else "Rule",
+                                             " Without pretrained model. Continue training." if role in roles else ""))
+    book = metrics.WinRateBook()
+    t0 = time.perf_counter()
+    res = glue.train(FACE_VARIANT, nets, a.episodes, train_dict=train_dict, reward_dict=reward_dict, tables=a.tables,
+                     seed=a.seed, log_every=a.log_every, model_every=a.model_every, book=book, model_dir=a.model_dir,
+                     win_dir=a.win_dir, log=lambda m: print(m, end=""))
+    dt = time.perf_counter() - t0
+    eps = max(1, res["episodes"])
+    print("Total wins: lord {} ({:.2%}), down {} ({:.2%}), up {} ({:.2%}) over {} episodes".format(
+        res["lord"], res["lord"] / eps, res["down"], res["down"] / eps, res["up"], res["up"] / eps, res["episodes"]))
+    print("last loss: " + ", ".join(f"{r} {v:.3f}" if v is not None else f"{r} -" for r, v in res["loss"].items()))
+    for p in res["checkpoints"]:
+        print("saved", p)
+    print(f"tables={a.tables} iterations={res['iterations']}: {dt / max(1, res['iterations']) * 1e3:.2f} ms/iteration "
+          f"(wall clock, td_step and first-call allocation included)")
+
+
+if __name__ == "__main__":
+    main()

@@ -167,6 +167,48 @@ int ddz_observe(ddz_env_t* env, int variant, float* face, void* stream);
  * face only).  The N = 1 `Env` view's per-ply call; the two launches are the ones of the separate entry points.        */
 int ddz_observe_actions(ddz_env_t* env, int variant, float* face, const int8_t* rows, int64_t n, float* onehot, void* stream);
 
+/* ddz_observe on state rows that are not an environment's (handle-free): face f32 [n][P][15][4] of the 176-byte rows
+ * states[index[i]] (index int64[n], DEVICE memory; NULL = identity), the same expression, bit for bit.  What rebuilds the
+ * s0 / s1 faces of a replay batch from the packed rings below.  Every index must name a row of `states` (the caller's
+ * bound: the library does not know how many rows there are); a negative one reads row 0.                             */
+int ddz_observe_states(int device_id, const uint8_t* states, const int64_t* index, int64_t n, int variant, float* face,
+                       void* stream);
+
+/* The learner's half of Game.train on the device (game.py:90-167, dqn.py:21-48; doudizhu-rl_amd/csrc/ddz_replay.h): the
+ * bookkeeping of dqn_glue.TransitionAssembler + one Replay per role (dqn.py:14), with a transition kept PACKED as two state
+ * rows, two canonical action ids, reward, done and the table (369 bytes; the faces are a function of the rows:
+ * ddz_observe_states).  Nothing crosses to the host, every launch goes to `stream`, the counts stay in device memory; both
+ * calls can be captured in a graph.
+ *   ws: the recorder's state, ddz_tr_ws_bytes(T) bytes (a multiple of 256; 548 bytes per table + a little), 16-byte
+ *     aligned, ZERO-FILLED by the caller before the first call (= nothing pending, every table fresh).
+ *   rings: HOST array of three device pointers in role order (0 up, 1 lord, 2 down), each a ring of `capacity` entries:
+ *     ddz_tr_ring_bytes(capacity) bytes (ring_bytes = the size of each), 16-byte aligned, zero-filled; NULL = that role
+ *     records nothing (a role named in trained_roles must have one).  Fields at the byte offsets ddz_tr_ring_layout writes
+ *     into offsets[8] (HOST): count int64 (total ever written), s0 u8[capacity][176], s1, a0 int32[capacity], a1, reward
+ *     f32[capacity], table int32[capacity], done u8[capacity].  The transition with sequence number s is entry s % capacity.
+ *   ddz_tr_before (TransitionAssembler.before_step; call it BEFORE the step, on the states the actors chose on): for every
+ *     table that is active (active u8[T], NULL = all) and whose actor's role is in trained_roles (bit r = role r): if the
+ *     role's slot is pending and the table is not fresh (a ply of its episode was played), the role's ring gets (s0, a0 of
+ *     the slot, reward 0, s1 = the state now, a1 = greedy[t], done 0); then the slot takes (the state now, chosen[t]) and
+ *     is pending.  Every active table stops being fresh.  chosen / greedy: int32[T] canonical action ids.
+ *   ddz_tr_after (TransitionAssembler.after_step; call it AFTER the step, before the re-deal: no auto-reset): for every table
+ *     with done[t] != 0, every pending role's ring gets (s0, a0 of its slot, +reward[role] if its side won, else
+ *     -reward[role]; s1 = the state now, a1 = 0 = the pass, whose thermometer is the all-zero a1 of game.py:123; done 1).
+ *     r i8[T] as ddz_step writes it (< 0: the lord won; the two farmers are one side); reward: HOST float[3] in role order.
+ *     The table's pending bits are cleared unless replicate_reference_quirk (game.py never clears *_s0 / *_a0: the first
+ *     feedback of down and up in the next episode then closes a transition across the re-deal), and it is fresh again.
+ *   Order: emit g of a call into a ring, g = the number of lower-numbered tables that emit into that ring in this call (a
+ *     scan over the tables, no atomics), gets sequence number count + g.  A call that emits E > capacity into one ring writes
+ *     the last `capacity` of them only, at count .. count + capacity - 1, and count moves by capacity: what Replay.push keeps
+ *     and where it puts it.  No two lanes of a launch store to one entry.                                              */
+int64_t ddz_tr_ws_bytes(int64_t n_tables);
+int64_t ddz_tr_ring_bytes(int64_t capacity);
+int ddz_tr_ring_layout(int64_t capacity, int64_t* offsets);
+int ddz_tr_before(ddz_env_t* env, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity,
+                  const int32_t* chosen, const int32_t* greedy, const uint8_t* active, int trained_roles, void* stream);
+int ddz_tr_after(ddz_env_t* env, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity,
+                 const uint8_t* done, const int8_t* r, const float* reward, int replicate_reference_quirk, void* stream);
+
 /* Replaces the native get_state_prob_manual(known60, size1, size2) (server/core.py:26-33; Env.get_state_prob(),
  * envi.py:94, is the same function of the live table): known60 u8[n][60] = thermometer of the cards the actor can see
  * (own hand + everything played), sizes int32[n][2] = cards left of the next and the next-but-one player;
