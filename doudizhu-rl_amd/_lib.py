@@ -67,6 +67,11 @@ SYMBOLS = {
     "ddz_select_slab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "ddz_q_features": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p]),
+    "ddz_q_first_fwd": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ddz_q_first_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "ddz_q_first_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_q_fc1_tile_rows": (C.c_int, []),
     "ddz_q_need_scratch_bytes": (C.c_int64, [C.c_int64]),
     "ddz_q_need": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

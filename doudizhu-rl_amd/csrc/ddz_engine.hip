@@ -2475,6 +2475,7 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
 }
 
 #include "ddz_qnet.h"
+#include "ddz_qtrain.h"
 
 __global__ __launch_bounds__(BLOCK) void k_classify(const uint4* __restrict__ rows, int64_t n,
                                                     uint32_t* __restrict__ out) {
@@ -3704,6 +3705,71 @@ int ddz_select_slab(ddz_env_t* e, const float* q, const int32_t* counts, int64_t
 int ddz_q_features(int device, const float* face, int64_t n_tables, int planes, const float* wf, const float* bias,
                    const float* acnt, float* y, int64_t y_row_stride, void* stream) {
   return launch_q_features(device, face, n_tables, planes, wf, bias, acnt, y, y_row_stride, stream);
+}
+
+// ---- the learner's first layer, forward and backward (ddz_qtrain.h) ----
+static bool qt_planes(int planes) { return planes == 4 || planes == 6 || planes == 7 || planes == 9; }
+
+int ddz_q_first_fwd(int device, const float* face, const float* action, int64_t n, int planes, const float* const w[4],
+                    const float* const b[4], float* y, uint8_t* arg, void* stream) {
+  if (!qt_planes(planes) || n < 0) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (!w || !b || !face || !action || !y || !al(face, 16) || !al(action, 16) || !al(y, 16) || !al(arg, 16)) return DDZ_EINVAL;   // (arg may be null)
+  QtW p;
+  for (int k = 0; k < 4; ++k) {
+    if (!w[k] || !b[k] || !al(w[k], 4) || !al(b[k], 4)) return DDZ_EINVAL;
+    p.w[k] = w[k];
+    p.b[k] = b[k];
+  }
+  if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+  const dim3 grid((unsigned)((n + QT_TILE - 1) / QT_TILE)), block(QH);
+  hipStream_t st = (hipStream_t)stream;
+  const float4 *f = (const float4*)face, *a = (const float4*)action;
+  switch (planes) {
+    case 4: hipLaunchKernelGGL(k_qt_fwd<4>, grid, block, 0, st, f, a, n, p, y, arg); break;
+    case 6: hipLaunchKernelGGL(k_qt_fwd<6>, grid, block, 0, st, f, a, n, p, y, arg); break;
+    case 7: hipLaunchKernelGGL(k_qt_fwd<7>, grid, block, 0, st, f, a, n, p, y, arg); break;
+    default: hipLaunchKernelGGL(k_qt_fwd<9>, grid, block, 0, st, f, a, n, p, y, arg); break;
+  }
+  return check_launch();
+}
+
+int64_t ddz_q_first_bwd_ws_bytes(int64_t n, int planes) {
+  if (!qt_planes(planes) || n < 0 || n > ((int64_t)1 << 30)) return DDZ_EINVAL;
+  return qt_ws_bytes(n, planes);
+}
+
+int ddz_q_first_bwd(int device, const float* face, const float* action, int64_t n, int planes, const float* gy, const uint8_t* arg,
+                    float* const gw[4], float* const gb[4], void* ws, int64_t ws_bytes, void* stream) {
+  if (!qt_planes(planes) || n < 0) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (!gw || !gb || !face || !action || !gy || !arg || !ws) return DDZ_EINVAL;
+  if (!al(face, 16) || !al(action, 16) || !al(gy, 16) || !al(arg, 16) || !al(ws, 4)) return DDZ_EINVAL;
+  QtG q;
+  for (int k = 0; k < 4; ++k) {
+    if (!gw[k] || !gb[k] || !al(gw[k], 4) || !al(gb[k], 4)) return DDZ_EINVAL;
+    q.w[k] = gw[k];
+    q.b[k] = gb[k];
+  }
+  if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
+  if (ws_bytes < qt_ws_bytes(n, planes)) return DDZ_EINVAL;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+  const int64_t nb = qt_parts(n);
+  const dim3 grid((unsigned)nb), block(QH);
+  hipStream_t st = (hipStream_t)stream;
+  const float4 *f = (const float4*)face, *a = (const float4*)action;
+  float* part = (float*)ws;
+  switch (planes) {
+    case 4: hipLaunchKernelGGL(k_qt_bwd<4>, grid, block, 0, st, f, a, n, gy, arg, part); break;
+    case 6: hipLaunchKernelGGL(k_qt_bwd<6>, grid, block, 0, st, f, a, n, gy, arg, part); break;
+    case 7: hipLaunchKernelGGL(k_qt_bwd<7>, grid, block, 0, st, f, a, n, gy, arg, part); break;
+    default: hipLaunchKernelGGL(k_qt_bwd<9>, grid, block, 0, st, f, a, n, gy, arg, part); break;
+  }
+  hipLaunchKernelGGL(k_qt_reduce, dim3((unsigned)(10 * (planes + 1) + 4)), block, 0, st, (const float*)part, nb, planes + 1, q);
+  return check_launch();
 }
 
 // ---- the "needed rows" form of the ragged Q forward (ddz_qnet.h) ----

@@ -183,6 +183,56 @@ def _join(w, two):
         torch.cuda.current_stream(w["side"].device).wait_event(w["join"])
 
 
+def first_layer_torch(net, face, actions):
+    """The first layer of QNet.forward -- cat, conv1..conv4, cat, max-pool -- as the expressions of ddz_q_first_fwd /
+    ddz_q_first_bwd (include/ddz_env.h) in plain differentiable torch ops, any device: with x = the planes of face [n,P,15,4]
+    followed by actions [n,15,4],
+        s_k = b_k[o] + sum_{c, j < k} w_k[o][c][0][j] * x[n][c][r][j],   y[n][o * 15 + r] = max_k s_k   -> f32 [n,3840]
+    torch.max(dim) returns the FIRST index of a tie and routes the whole gradient there: max_pool2d's rule.  The statement the
+    two kernels are tested against; QNet.forward_fused on CPU tensors."""
+    n = actions.shape[0]
+    x = torch.cat((face, actions.unsqueeze(1)), dim=1).permute(0, 2, 1, 3)                  # [n,15,C,4]
+    s = []
+    for k, cv in enumerate((net.conv1, net.conv2, net.conv3, net.conv4), start=1):
+        w = cv.weight[:, :, 0, :]                                                         # [256,C,k]
+        s.append(x[..., :k].reshape(n * 15, -1) @ w.reshape(_CONV_CH, -1).t() + cv.bias)  # [n * 15, 256]
+    y = torch.stack(s, dim=-1).max(dim=-1).values                                         # the (1,4) pool: lowest k on a tie
+    return y.view(n, 15, _CONV_CH).permute(0, 2, 1).reshape(n, _CONV_CH * 15)
+
+
+class FirstLayer(torch.autograd.Function):
+    """first_layer_torch on the device by the engine's two kernels (csrc/ddz_qtrain.h): FirstLayer.apply(face, actions, w1, b1,
+    w2, b2, w3, b3, w4, b4) -> y f32 [n,3840].  The forward keeps the arg-max (one byte per value) for the backward, which
+    writes the eight parameter gradients -- deterministic, no atomics -- and hands autograd the ones it asked for.  face and
+    actions are data: one that requires grad is a ValueError.  With no parameter that requires grad no arg-max is written
+    (QNet.forward_fused makes the no-grad pass -- the target network's -- the same way, by engine.q_first_fwd itself)."""
+
+    @staticmethod
+    def forward(ctx, face, actions, *params):
+        from . import engine as E
+        if face.requires_grad or actions.requires_grad:
+            raise ValueError("FirstLayer has no gradient with respect to face or actions")
+        if len(params) != 8:
+            raise ValueError("FirstLayer.apply(face, actions, w1, b1, w2, b2, w3, b3, w4, b4)")
+        weights, biases = [p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]]
+        want = any(ctx.needs_input_grad[2:])
+        y, arg = E.q_first_fwd(face, actions, weights, biases, want_arg=want)
+        if want:
+            ctx.save_for_backward(face, actions, arg, *weights)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import engine as E
+        face, actions, arg, *weights = ctx.saved_tensors
+        gw, gb = E.q_first_bwd(face, actions, gy.contiguous(), arg, weights)
+        grads = [None, None]
+        for k in range(4):
+            grads += [gw[k], gb[k]]
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
+
+
 class QNet(nn.Module):
     """The reference's Q-network family (net.py:66-150: NetComplicated 5 input planes, NetMoreComplicated 8,
     NetCooperation 10, NetCooperationSimplify 7), same parameter names and shapes (state_dict-compatible); forward is
@@ -210,6 +260,26 @@ class QNet(nn.Module):
         y = torch.cat([f(x) for f in (self.conv1, self.conv2, self.conv3, self.conv4)], -1)
         y = self.pool(y).view(actions.shape[0], -1)
         z = self.conv_shunzi(x).view(actions.shape[0], -1)
+        h = self.drop(torch.cat([y, z], -1))
+        return self.fc2(F.relu(self.fc1(h)))
+
+    def forward_fused(self, face, actions):
+        """forward with the cat / conv1..4 / cat / pool chain as ONE stage that never materialises the [n,256,15,4] pre-pool tensor
+        -- FirstLayer (the engine's kernels) on device tensors, first_layer_torch on CPU tensors; conv_shunzi, dropout, fc1, relu
+        and fc2 are the same modules in the same order (one RNG state gives the literal's dropout mask).  No gradient of face /
+        actions."""
+        if face.dim() == 3:
+            face = face.unsqueeze(0).repeat((actions.shape[0], 1, 1, 1))
+        params = [p for cv in (self.conv1, self.conv2, self.conv3, self.conv4) for p in (cv.weight, cv.bias)]
+        if face.is_cuda and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            y = FirstLayer.apply(face.contiguous(), actions.contiguous(), *params)
+        elif face.is_cuda:                                   # a no-grad pass: no arg-max is written, nothing is kept
+            from .engine import q_first_fwd
+            y = q_first_fwd(face.contiguous(), actions.contiguous(), [p.detach() for p in params[0::2]],
+                            [p.detach() for p in params[1::2]], want_arg=False)[0]
+        else:
+            y = first_layer_torch(self, face, actions)
+        z = self.conv_shunzi(torch.cat((face, actions.unsqueeze(1)), dim=1)).view(actions.shape[0], -1)
         h = self.drop(torch.cat([y, z], -1))
         return self.fc2(F.relu(self.fc1(h)))
 
@@ -1050,12 +1120,14 @@ def epsilon_schedule(episode, high=EPSILON_HIGH, low=EPSILON_LOW, decay=DECAY):
     return low + (high - low) * math.exp(-1.0 * episode / decay)
 
 
-def td_step(policy, target, optimizer, batch, gamma=0.95):
+def td_step(policy, target, optimizer, batch, gamma=0.95, fused=False):
     """One perceive() update (dqn.py:33-48): y = r + (1 - done) * gamma * Q_target(s1, a1), MSE against
-    Q_policy(s0, a0), one optimizer step.  Returns the loss (a tensor: no host sync)."""
+    Q_policy(s0, a0), one optimizer step.  Returns the loss (a tensor: no host sync).  fused: both passes through
+    QNet.forward_fused (the first layer by the engine's forward / backward kernels) instead of the literal forward."""
+    q_target, q_policy = (target.forward_fused, policy.forward_fused) if fused else (target, policy)
     with torch.no_grad():
-        y = td_target(batch, target(batch["s1"], batch["a1"]), gamma)
-    loss = F.mse_loss(policy(batch["s0"], batch["a0"]).view(-1), y)
+        y = td_target(batch, q_target(batch["s1"], batch["a1"]), gamma)
+    loss = F.mse_loss(q_policy(batch["s0"], batch["a0"]).view(-1), y)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
@@ -1229,13 +1301,13 @@ class TrainLoop:
 
 def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, tables=4096, seed=0, log_every=100,
           model_every=1000, book=None, model_dir=None, win_dir=None, device="cuda:0", check_every=8, capacity=REPLAY_SIZE,
-          begin=None, log=None):
+          begin=None, log=None, fused=False, batch_size=BATCH_SIZE):
     """Game.train (game.py:183-238) on the batched engine, the counterpart of compete(): nets {"lord" | "down" | "up": QNet |
     None (the rule agent)}, train_dict which network roles keep training (default: all of them), reward_dict as REWARD_DICT.
     Lock-step iterations of TrainLoop over `tables` tables until `episodes` episodes have finished; every iteration each
-    trained role whose ring holds BATCH_SIZE entries takes one td_step on a batch sampled on the device (dqn.py:24-48: Adam
-    1e-4, a target network per role).  The host looks at the device every `check_every` iterations only (env.stats() and the
-    ring counts: the one sync): there it moves epsilon (epsilon_schedule of the episodes so far), copies policy -> target
+    trained role whose ring holds batch_size entries (default BATCH_SIZE, the reference's 256) takes one td_step(fused=fused) on
+    a batch of that size sampled on the device (dqn.py:24-48: Adam 1e-4, a target network per role).  The host looks at the
+    device every `check_every` iterations only (env.stats() and the ring counts: the one sync): there it moves epsilon (epsilon_schedule of the episodes so far), copies policy -> target
     every UPDATE_TARGET_EVERY episodes (dqn.py:73-80), writes the log line every log_every and the checkpoints
     <begin>_<role>_<episode> every model_every episodes (game.py:209-232; metrics.checkpoint_name / save_state_dict under
     model_dir, the win rates under win_dir) -- `episode` being the multiple of the interval that was crossed, since the tables
@@ -1246,6 +1318,9 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     import time
     from . import metrics
     from .engine import BatchedEnv
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
     nets = {r: v for r, v in nets.items()}
     for r, v in nets.items():
         if v is not None:
@@ -1278,12 +1353,13 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
             loop.step()
             for r in roles:
                 if ready[r]:
-                    loss[r] = td_step(policy[r], target[r], opt[r], loop.rec.sample(r, BATCH_SIZE, face_variant), GAMMA)
+                    loss[r] = td_step(policy[r], target[r], opt[r], loop.rec.sample(r, batch_size, face_variant), GAMMA,
+                                      fused=fused)
         it += int(check_every)
         s1 = env.stats()                                             # the host sync of the interval
         known = loop.rec.note_counts()
         for r in roles:
-            ready[r] = known[ROLE_ORDER.index(r)] >= BATCH_SIZE
+            ready[r] = known[ROLE_ORDER.index(r)] >= batch_size
         book.update(s1)
         prev, eps_done = eps_done, s1["episodes"] - s0["episodes"]
         for r in roles:

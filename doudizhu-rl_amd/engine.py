@@ -723,6 +723,67 @@ def q_features(face, wf, bias, acnt, y):
     return y
 
 
+def _q_first_operands(face, actions, weights, biases=None):
+    """shape / dtype / device / contiguity of the first layer's operands -> (device, n, planes)"""
+    dev = _require_gpu(face.device)
+    if face.dtype != torch.float32 or face.dim() != 4 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
+        raise ValueError("face must be a contiguous float32 [n,P,15,4] tensor")
+    n, P = int(face.shape[0]), int(face.shape[1])
+    if P not in (4, 6, 7, 9):
+        raise ValueError("face must have 4, 6, 7 or 9 planes")
+    if actions.dtype != torch.float32 or tuple(actions.shape) != (n, 15, 4) or not actions.is_contiguous() or actions.device != dev:
+        raise ValueError("actions must be a contiguous float32 [n,15,4] tensor on the face's device")
+    if len(weights) != 4 or (biases is not None and len(biases) != 4):
+        raise ValueError("weights / biases: those of conv1..conv4")
+    for k in range(4):
+        w = weights[k]
+        if w.dtype != torch.float32 or tuple(w.shape) != (256, P + 1, 1, k + 1) or not w.is_contiguous() or w.device != dev:
+            raise ValueError(f"weights[{k}] must be a contiguous float32 [256,{P + 1},1,{k + 1}] tensor on the face's device")
+        if biases is not None:
+            b = biases[k]
+            if b.dtype != torch.float32 or tuple(b.shape) != (256,) or not b.is_contiguous() or b.device != dev:
+                raise ValueError(f"biases[{k}] must be a contiguous float32 [256] tensor on the face's device")
+    return dev, n, P
+
+
+def _ptr4(tensors):
+    return (C.c_void_p * 4)(*[t.data_ptr() for t in tensors])
+
+
+def q_first_fwd(face, actions, weights, biases, want_arg=True):
+    """ddz_q_first_fwd: the learner's first layer -- cat, conv1..conv4, cat, max-pool of QNet.forward -- of a batch, the pre-pool
+    tensor never materialised: face f32 [n,P,15,4], actions f32 [n,15,4], weights / biases the nn.Conv2d parameters of conv1..4
+    as they are ([256,P+1,1,k], [256]) -> (y f32 [n,3840] in the order of net.py:94's view, arg u8 [n,3840] = the lowest conv
+    that attains the max -- what q_first_bwd routes by -- or None with want_arg=False).  No host sync."""
+    dev, n, P = _q_first_operands(face, actions, weights, biases)
+    y = torch.empty((n, 3840), dtype=torch.float32, device=dev)
+    arg = torch.empty((n, 3840), dtype=torch.uint8, device=dev) if want_arg else None
+    if n:
+        check(_lib.lib().ddz_q_first_fwd(dev.index, _p(face), _p(actions), n, P, _ptr4(weights), _ptr4(biases), _p(y), _p(arg),
+                                         _stream(dev)))
+    return y, arg
+
+
+def q_first_bwd(face, actions, gy, arg, weights):
+    """ddz_q_first_bwd: the gradients of conv1..conv4's parameters from gy f32 [n,3840] and q_first_fwd's arg u8 [n,3840] (the
+    conv that won takes the gradient), in the parameters' own shapes: (gw[4], gb[4]); `weights` give the shapes only.
+    Deterministic (no atomics: per-block partials, a fixed-order reduce); no gradient of face / actions.  No host sync."""
+    dev, n, P = _q_first_operands(face, actions, weights)
+    if gy.dtype != torch.float32 or tuple(gy.shape) != (n, 3840) or not gy.is_contiguous() or gy.device != dev:
+        raise ValueError("gy must be a contiguous float32 [n,3840] tensor on the face's device")
+    if arg is None or arg.dtype != torch.uint8 or tuple(arg.shape) != (n, 3840) or not arg.is_contiguous() or arg.device != dev:
+        raise ValueError("arg must be q_first_fwd's contiguous uint8 [n,3840] tensor")
+    L = _lib.lib()
+    if n == 0:
+        return [torch.zeros_like(w) for w in weights], [torch.zeros(256, dtype=torch.float32, device=dev) for _ in range(4)]
+    gw = [torch.empty_like(w) for w in weights]
+    gb = [torch.empty(256, dtype=torch.float32, device=dev) for _ in range(4)]
+    ws = torch.empty(int(L.ddz_q_first_bwd_ws_bytes(n, P)), dtype=torch.uint8, device=dev)
+    check(L.ddz_q_first_bwd(dev.index, _p(face), _p(actions), n, P, _p(gy), _p(arg), _ptr4(gw), _ptr4(gb), _p(ws), ws.numel(),
+                            _stream(dev)))
+    return gw, gb
+
+
 def q_need_scratch_bytes(n_tables):
     return int(_lib.lib().ddz_q_need_scratch_bytes(int(n_tables)))
 
