@@ -72,6 +72,11 @@ SYMBOLS = {
     "ddz_q_first_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "ddz_q_first_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_q_stage_fwd": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p]),
+    "ddz_q_stage_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "ddz_q_stage_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_q_fc1_tile_rows": (C.c_int, []),
     "ddz_q_need_scratch_bytes": (C.c_int64, [C.c_int64]),
     "ddz_q_need": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -130,6 +135,13 @@ SYMBOLS = {
     "ddz_device_status": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
     "ddz_debug_classify": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
+
+
+class QSrc(C.Structure):
+    """ddz_q_src_t: where the learner's stage (ddz_q_stage_fwd / ddz_q_stage_bwd) reads x from -- faces or packed replay rows"""
+    _fields_ = [("kind", C.c_int), ("planes", C.c_int), ("face", C.c_void_p), ("action", C.c_void_p), ("variant", C.c_int),
+                ("n_actions", C.c_int), ("states", C.c_void_p), ("ids", C.c_void_p), ("index", C.c_void_p), ("table", C.c_void_p),
+                ("n_rows", C.c_int64)]
 
 
 class DdzError(RuntimeError):

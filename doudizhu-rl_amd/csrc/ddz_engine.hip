@@ -2475,7 +2475,6 @@ __global__ __launch_bounds__(QH) void k_q_feat(const float4* __restrict__ face, 
 }
 
 #include "ddz_qnet.h"
-#include "ddz_qtrain.h"
 
 __global__ __launch_bounds__(BLOCK) void k_classify(const uint4* __restrict__ rows, int64_t n,
                                                     uint32_t* __restrict__ out) {
@@ -2605,6 +2604,7 @@ __global__ __launch_bounds__(BLOCK) void k_onehot(const uint8_t* __restrict__ ro
 }
 
 #include "ddz_replay.h"
+#include "ddz_qtrain.h"   // (after face_cell: the learner's stage stages its x tile from packed state rows too)
 
 // ------------------------------------------------------------------------------------
 // action table export and the compact trajectory record.
@@ -3707,8 +3707,29 @@ int ddz_q_features(int device, const float* face, int64_t n_tables, int planes, 
   return launch_q_features(device, face, n_tables, planes, wf, bias, acnt, y, y_row_stride, stream);
 }
 
-// ---- the learner's first layer, forward and backward (ddz_qtrain.h) ----
+// ---- the learner's first layer and its whole pre-fc1 stage, forward and backward (ddz_qtrain.h) ----
 static bool qt_planes(int planes) { return planes == 4 || planes == 6 || planes == 7 || planes == 9; }
+
+// one switch over the instances: key = planes (faces) or 16 + variant (rows)
+#define QT_INSTANCES(CALL)                                                                                                       \
+  switch (key) {                                                                                                                 \
+    case 4: CALL(4, -1); break;                                                                                                  \
+    case 6: CALL(6, -1); break;                                                                                                  \
+    case 7: CALL(7, -1); break;                                                                                                  \
+    case 9: CALL(9, -1); break;                                                                                                  \
+    case 16: CALL(4, 0); break;                                                                                                  \
+    case 17: CALL(7, 1); break;                                                                                                  \
+    case 18: CALL(9, 2); break;                                                                                                  \
+    case 19: CALL(6, 3); break;                                                                                                  \
+    default: return DDZ_EINVAL;                                                                                                  \
+  }
+
+static QtSrc qt_faces(const float* face, const float* action) {
+  QtSrc s = {};
+  s.face = (const float4*)face;
+  s.action = (const float4*)action;
+  return s;
+}
 
 int ddz_q_first_fwd(int device, const float* face, const float* action, int64_t n, int planes, const float* const w[4],
                     const float* const b[4], float* y, uint8_t* arg, void* stream) {
@@ -3724,14 +3745,12 @@ int ddz_q_first_fwd(int device, const float* face, const float* action, int64_t 
   if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
-  const dim3 grid((unsigned)((n + QT_TILE - 1) / QT_TILE)), block(QH);
-  hipStream_t st = (hipStream_t)stream;
-  const float4 *f = (const float4*)face, *a = (const float4*)action;
+  const QtSrc src = qt_faces(face, action);
   switch (planes) {
-    case 4: hipLaunchKernelGGL(k_qt_fwd<4>, grid, block, 0, st, f, a, n, p, y, arg); break;
-    case 6: hipLaunchKernelGGL(k_qt_fwd<6>, grid, block, 0, st, f, a, n, p, y, arg); break;
-    case 7: hipLaunchKernelGGL(k_qt_fwd<7>, grid, block, 0, st, f, a, n, p, y, arg); break;
-    default: hipLaunchKernelGGL(k_qt_fwd<9>, grid, block, 0, st, f, a, n, p, y, arg); break;
+    case 4: qt_launch_fwd<4, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
+    case 6: qt_launch_fwd<6, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
+    case 7: qt_launch_fwd<7, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
+    default: qt_launch_fwd<9, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
   }
   return check_launch();
 }
@@ -3757,18 +3776,98 @@ int ddz_q_first_bwd(int device, const float* face, const float* action, int64_t 
   if (ws_bytes < qt_ws_bytes(n, planes)) return DDZ_EINVAL;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
-  const int64_t nb = qt_parts(n);
-  const dim3 grid((unsigned)nb), block(QH);
-  hipStream_t st = (hipStream_t)stream;
-  const float4 *f = (const float4*)face, *a = (const float4*)action;
-  float* part = (float*)ws;
+  const QtSrc src = qt_faces(face, action);
   switch (planes) {
-    case 4: hipLaunchKernelGGL(k_qt_bwd<4>, grid, block, 0, st, f, a, n, gy, arg, part); break;
-    case 6: hipLaunchKernelGGL(k_qt_bwd<6>, grid, block, 0, st, f, a, n, gy, arg, part); break;
-    case 7: hipLaunchKernelGGL(k_qt_bwd<7>, grid, block, 0, st, f, a, n, gy, arg, part); break;
-    default: hipLaunchKernelGGL(k_qt_bwd<9>, grid, block, 0, st, f, a, n, gy, arg, part); break;
+    case 4: qt_launch_bwd<4, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
+    case 6: qt_launch_bwd<6, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
+    case 7: qt_launch_bwd<7, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
+    default: qt_launch_bwd<9, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
   }
-  hipLaunchKernelGGL(k_qt_reduce, dim3((unsigned)(10 * (planes + 1) + 4)), block, 0, st, (const float*)part, nb, planes + 1, q);
+  return check_launch();
+}
+
+static bool qt_source_known(const ddz_q_src_t* d) {
+  return d && (d->kind == DDZ_Q_SRC_FACES ? qt_planes(d->planes) : d->kind == DDZ_Q_SRC_ROWS && d->variant >= 0 && d->variant <= 3);
+}
+
+// the stage's source descriptor -> (QtSrc, instance key, planes), or false: an unknown kind / planes / variant, a null or
+// misaligned operand
+static bool qt_source(const ddz_q_src_t* d, QtSrc& s, int& key, int& planes) {
+  s = QtSrc{};
+  if (d->kind == DDZ_Q_SRC_FACES) {
+    if (!d->face || !d->action || !al(d->face, 16) || !al(d->action, 16)) return false;
+    s = qt_faces(d->face, d->action);
+    key = planes = d->planes;
+    return true;
+  }
+  if (!d->states || !d->ids || !d->table || d->n_rows <= 0 || d->n_rows > ((int64_t)1 << 30) || d->n_actions <= 0) return false;
+  if (!al(d->states, 16) || !al(d->ids, 4) || !al(d->index, 8)) return false;   // (index may be null)
+  s.states = d->states;
+  s.ids = d->ids;
+  s.index = d->index;
+  s.table = d->table;
+  s.n_rows = d->n_rows;
+  s.n_actions = d->n_actions;
+  key = 16 + d->variant;
+  planes = ddz_face_planes(d->variant);
+  return true;
+}
+
+int ddz_q_stage_fwd(int device, const ddz_q_src_t* source, int64_t n, const float* const w[5], const float* const b[5], float* h,
+                    int64_t h_stride, uint8_t* arg, void* stream) {
+  QtSrc src;
+  int key = 0, planes = 0;
+  if (n < 0 || h_stride != QS_LD) return DDZ_EINVAL;
+  if (!qt_source_known(source)) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (!qt_source(source, src, key, planes)) return DDZ_EINVAL;
+  if (!w || !b || !h || !al(h, 16) || !al(arg, 16)) return DDZ_EINVAL;   // (arg may be null)
+  QtW p;
+  for (int k = 0; k < 5; ++k) {
+    if (!w[k] || !b[k] || !al(w[k], 4) || !al(b[k], 4)) return DDZ_EINVAL;
+    if (k < 4) {
+      p.w[k] = w[k];
+      p.b[k] = b[k];
+    }
+  }
+  if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+#define QT_CALL(P, V) qt_launch_fwd<P, V, false>(src, n, p, w[4], b[4], h, arg, (hipStream_t)stream)
+  QT_INSTANCES(QT_CALL)
+#undef QT_CALL
+  return check_launch();
+}
+
+int64_t ddz_q_stage_bwd_ws_bytes(int64_t n, int planes) {
+  if (!qt_planes(planes) || n < 0 || n > ((int64_t)1 << 30)) return DDZ_EINVAL;
+  return qs_ws_bytes(n, planes);
+}
+
+int ddz_q_stage_bwd(int device, const ddz_q_src_t* source, int64_t n, const float* gh, int64_t gh_stride, const uint8_t* arg,
+                    float* const gw[5], float* const gb[5], void* ws, int64_t ws_bytes, void* stream) {
+  QtSrc src;
+  int key = 0, planes = 0;
+  if (n < 0 || gh_stride != QS_LD) return DDZ_EINVAL;
+  if (!qt_source_known(source)) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (!qt_source(source, src, key, planes)) return DDZ_EINVAL;
+  if (!gw || !gb || !gh || !arg || !ws || !al(gh, 16) || !al(arg, 16) || !al(ws, 4)) return DDZ_EINVAL;
+  QtG q;
+  for (int k = 0; k < 5; ++k) {
+    if (!gw[k] || !gb[k] || !al(gw[k], 4) || !al(gb[k], 4)) return DDZ_EINVAL;
+    if (k < 4) {
+      q.w[k] = gw[k];
+      q.b[k] = gb[k];
+    }
+  }
+  if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
+  if (ws_bytes < qs_ws_bytes(n, planes)) return DDZ_EINVAL;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+#define QT_CALL(P, V) qt_launch_bwd<P, V, false>(src, n, gh, arg, q, gw[4], gb[4], (float*)ws, (hipStream_t)stream)
+  QT_INSTANCES(QT_CALL)
+#undef QT_CALL
   return check_launch();
 }
 

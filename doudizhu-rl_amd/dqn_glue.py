@@ -233,6 +233,77 @@ class FirstLayer(torch.autograd.Function):
         return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
 
 
+def stage_torch(net, face, actions):
+    """Everything of QNet.forward in front of dropout / fc1 as the expressions of ddz_q_stage_fwd / ddz_q_stage_bwd
+    (include/ddz_env.h) in plain differentiable torch ops, any device: first_layer_torch, then conv_shunzi as one matmul over
+    the (plane, rank) pairs of every thermometer slot,
+        z[n][o * 4 + j] = bs[o] + sum_{c, r} ws[o][c][r][0] * x[n][c][r][j],
+    then net.py:97's cat -> h f32 [n,4864].  The statement the stage's kernels are tested against; QNet.forward_stage on CPU
+    tensors."""
+    n = actions.shape[0]
+    y = first_layer_torch(net, face, actions)
+    x = torch.cat((face, actions.unsqueeze(1)), dim=1)                                        # [n,C,15,4]
+    w = net.conv_shunzi.weight[:, :, :, 0].reshape(_CONV_CH, -1)                              # [256, C * 15]
+    z = x.reshape(n, -1, 4).permute(0, 2, 1).reshape(n * 4, -1) @ w.t() + net.conv_shunzi.bias   # [n * 4, 256]
+    return torch.cat((y, z.view(n, 4, _CONV_CH).permute(0, 2, 1).reshape(n, _CONV_CH * 4)), dim=1)
+
+
+class Stage(torch.autograd.Function):
+    """stage_torch on the device by the engine's kernels (csrc/ddz_qtrain.h): Stage.apply(source, w1, b1, w2, b2, w3, b3, w4, b4,
+    ws, bs) -> h f32 [n,4864], `source` the keyword operands of engine.q_stage_source -- {"face", "actions"} or {"states", "ids",
+    "index", "table", "variant"} (packed replay rows: no face is built).  FirstLayer's rules: the forward keeps the arg-max for
+    the backward, which writes the ten parameter gradients -- deterministic, no atomics -- and hands autograd the ones it asked
+    for; the source is data (a tensor of it that requires grad is a ValueError); with no parameter that requires grad no arg-max
+    is written and nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, source, *params):
+        from . import engine as E
+        if any(torch.is_tensor(v) and v.requires_grad for v in source.values()):
+            raise ValueError("Stage has no gradient with respect to its source")
+        if len(params) != 10:
+            raise ValueError("Stage.apply(source, w1, b1, w2, b2, w3, b3, w4, b4, ws, bs)")
+        weights, biases = [p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]]
+        want = any(ctx.needs_input_grad[1:])
+        h, arg = E.q_stage_fwd(weights, biases, want_arg=want, **source)
+        if want:
+            ctx.keys = [k for k, v in source.items() if torch.is_tensor(v)]
+            ctx.rest = {k: v for k, v in source.items() if not torch.is_tensor(v)}
+            ctx.save_for_backward(arg, *weights, *[source[k] for k in ctx.keys])
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gh):
+        from . import engine as E
+        arg, *rest = ctx.saved_tensors
+        weights, data = rest[:5], rest[5:]
+        gw, gb = E.q_stage_bwd(gh.contiguous(), arg, weights, **dict(zip(ctx.keys, data)), **ctx.rest)
+        grads = [None]
+        for k in range(5):
+            grads += [gw[k], gb[k]]
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
+
+
+class PackedBatch:
+    """A replay batch that stays packed (TransitionRecorder.sample_packed): a role's ring views s0 / s1 u8 [capacity,176],
+    a0 / a1 int32 [capacity], reward f32 [capacity], done u8 [capacity], the drawn entries index int64 [n] (inside the ring), the
+    action table int8 [n_actions,16] and the face variant.  QNet.forward_packed reads the state rows and action ids directly;
+    td_step gathers reward and done, nothing else."""
+    __slots__ = ("s0", "s1", "a0", "a1", "reward", "done", "index", "table", "variant")
+
+    def __init__(self, s0, s1, a0, a1, reward, done, index, table, variant):
+        from .engine import FACE_PLANES
+        if int(variant) not in range(len(FACE_PLANES)):
+            raise ValueError("variant must be a face variant 0..3")
+        self.s0, self.s1, self.a0, self.a1, self.reward, self.done = s0, s1, a0, a1, reward, done
+        self.index, self.table, self.variant = index, table, int(variant)
+
+    @property
+    def n(self):
+        return int(self.index.numel())
+
+
 class QNet(nn.Module):
     """The reference's Q-network family (net.py:66-150: NetComplicated 5 input planes, NetMoreComplicated 8,
     NetCooperation 10, NetCooperationSimplify 7), same parameter names and shapes (state_dict-compatible); forward is
@@ -282,6 +353,44 @@ class QNet(nn.Module):
         z = self.conv_shunzi(torch.cat((face, actions.unsqueeze(1)), dim=1)).view(actions.shape[0], -1)
         h = self.drop(torch.cat([y, z], -1))
         return self.fc2(F.relu(self.fc1(h)))
+
+
+    def _conv_params(self):
+        return [p for cv in (self.conv1, self.conv2, self.conv3, self.conv4, self.conv_shunzi) for p in (cv.weight, cv.bias)]
+
+    def _stage(self, **source):
+        """h [n,4864] by the engine's stage kernels: through Stage when a convolution parameter wants a gradient, else the no-grad
+        pass (no arg-max is written, nothing is kept)"""
+        params = self._conv_params()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return Stage.apply(source, *params)
+        from .engine import q_stage_fwd
+        return q_stage_fwd([p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]], want_arg=False, **source)[0]
+
+    def forward_stage(self, face, actions):
+        """forward with everything in front of dropout -- cat, conv1..4, cat, pool, conv_shunzi, the views, the cat -- as ONE stage
+        that writes h [n,4864] whole: Stage (the engine's kernels: two launches, no library convolution) on device tensors,
+        stage_torch on CPU tensors; dropout, fc1, relu and fc2 are the same modules in the same order (one RNG state gives the
+        literal's dropout mask).  No gradient of face / actions."""
+        if face.dim() == 3:
+            face = face.unsqueeze(0).repeat((actions.shape[0], 1, 1, 1))
+        h = self._stage(face=face.contiguous(), actions=actions.contiguous()) if face.is_cuda else stage_torch(self, face, actions)
+        return self.fc2(F.relu(self.fc1(self.drop(h))))
+
+    def forward_packed(self, batch, side):
+        """forward_stage on side 0 (s0, a0) or 1 (s1, a1) of a PackedBatch, the stage reading the ring's state rows and action
+        ids itself: no face, no thermometer and no library convolution.  Bit for bit forward_stage on what
+        TransitionRecorder.decode gives for the same index."""
+        from .engine import FACE_PLANES
+        if side not in (0, 1):
+            raise ValueError("side: 0 = (s0, a0), 1 = (s1, a1)")
+        if not isinstance(batch, PackedBatch):
+            raise ValueError("forward_packed takes a PackedBatch (TransitionRecorder.sample_packed)")
+        if FACE_PLANES[batch.variant] != self.planes:
+            raise ValueError(f"the network takes {self.planes} planes, face variant {batch.variant} has {FACE_PLANES[batch.variant]}")
+        states, ids = (batch.s0, batch.a0) if side == 0 else (batch.s1, batch.a1)
+        h = self._stage(states=states, ids=ids, index=batch.index, table=batch.table, variant=batch.variant)
+        return self.fc2(F.relu(self.fc1(self.drop(h))))
 
 
 class FactorisedQ:
@@ -1122,12 +1231,28 @@ def epsilon_schedule(episode, high=EPSILON_HIGH, low=EPSILON_LOW, decay=DECAY):
 
 def td_step(policy, target, optimizer, batch, gamma=0.95, fused=False):
     """One perceive() update (dqn.py:33-48): y = r + (1 - done) * gamma * Q_target(s1, a1), MSE against
-    Q_policy(s0, a0), one optimizer step.  Returns the loss (a tensor: no host sync).  fused: both passes through
-    QNet.forward_fused (the first layer by the engine's forward / backward kernels) instead of the literal forward."""
-    q_target, q_policy = (target.forward_fused, policy.forward_fused) if fused else (target, policy)
+    Q_policy(s0, a0), one optimizer step.  Returns the loss (a tensor: no host sync).  fused: True -- both passes through
+    QNet.forward_fused (the first layer by the engine's forward / backward kernels) -- or "stage" -- through QNet.forward_stage
+    (everything in front of dropout by the engine's kernels) -- instead of the literal forward.  A PackedBatch as `batch`
+    (TransitionRecorder.sample_packed) runs both passes through QNet.forward_packed, whatever `fused` says: two stage launches
+    per pass, no face, no library convolution; the reward and done gathers are the only other reads of the ring."""
+    if isinstance(batch, PackedBatch):
+        q_next = lambda: target.forward_packed(batch, 1)      # noqa: E731
+        q_now = lambda: policy.forward_packed(batch, 0)       # noqa: E731
+        tr = {"reward": batch.reward[batch.index], "done": batch.done[batch.index].bool()}
+    else:
+        if isinstance(fused, str):
+            if fused != "stage":
+                raise ValueError('fused: False, True or "stage"')
+            q_target, q_policy = target.forward_stage, policy.forward_stage
+        else:                                                  # (any other value by its truth, as before)
+            q_target, q_policy = (target.forward_fused, policy.forward_fused) if fused else (target, policy)
+        q_next = lambda: q_target(batch["s1"], batch["a1"])   # noqa: E731
+        q_now = lambda: q_policy(batch["s0"], batch["a0"])    # noqa: E731
+        tr = batch
     with torch.no_grad():
-        y = td_target(batch, q_target(batch["s1"], batch["a1"]), gamma)
-    loss = F.mse_loss(q_policy(batch["s0"], batch["a0"]).view(-1), y)
+        y = td_target(tr, q_next(), gamma)
+    loss = F.mse_loss(q_now().view(-1), y)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
@@ -1230,19 +1355,33 @@ class TransitionRecorder:
                 "s1": E.observe_states(f["s1"], index, variant), "a1": thermo(f["a1"]),
                 "reward": f["reward"][index], "done": f["done"][index].bool()}
 
-    def sample(self, role, k, variant, at_least=None):
-        """k entries drawn uniformly (with replacement, as Replay.sample) from the role's min(count, capacity) live entries, the
-        indices drawn ON THE DEVICE from the device count: no .item().  Whether the ring holds anything is the caller's
-        knowledge: at_least (default: known[role], which note_counts() refreshes at the caller's own sync points) is a
-        host-known lower bound of the count, and 0 is an argument error."""
+    def draw(self, role, k, at_least=None):
+        """int64 [k] device tensor: k entries drawn uniformly (with replacement, as Replay.sample) from the role's
+        min(count, capacity) live entries, ON THE DEVICE from the device count: no .item().  Whether the ring holds anything is
+        the caller's knowledge: at_least (default: known[role], which note_counts() refreshes at the caller's own sync points)
+        is a host-known lower bound of the count, and 0 is an argument error."""
         rid = _role_id(role)
         f = self._ring(role)
         lo = self.known[rid] if at_least is None else int(at_least)
         if lo <= 0:
             raise ValueError("sample() needs a host-known positive lower bound of the ring's count (note_counts(), or at_least=)")
         n = f["count"][0].clamp(min=1, max=self.capacity)
-        idx = (torch.rand(int(k), dtype=torch.float64, device=self.device) * n.double()).long().minimum(n - 1)
-        return self.decode(role, idx, variant)
+        return (torch.rand(int(k), dtype=torch.float64, device=self.device) * n.double()).long().minimum(n - 1)
+
+    def sample(self, role, k, variant, at_least=None):
+        """decode() of draw(role, k, at_least): the batch as faces and thermometers"""
+        return self.decode(role, self.draw(role, k, at_least), variant)
+
+    def packed(self, role, index, variant):
+        """the PackedBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
+        ring, nothing decoded, nothing copied but the index.  No host sync."""
+        f = self._ring(role)
+        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
+        return PackedBatch(f["s0"], f["s1"], f["a0"], f["a1"], f["reward"], f["done"], index, self._rows, variant)
+
+    def sample_packed(self, role, k, variant, at_least=None):
+        """packed() of draw(role, k, at_least): the batch sample() would decode for the same RNG state, left packed"""
+        return self.packed(role, self.draw(role, k, at_least), variant)
 
 
 class TrainLoop:
@@ -1306,7 +1445,8 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     None (the rule agent)}, train_dict which network roles keep training (default: all of them), reward_dict as REWARD_DICT.
     Lock-step iterations of TrainLoop over `tables` tables until `episodes` episodes have finished; every iteration each
     trained role whose ring holds batch_size entries (default BATCH_SIZE, the reference's 256) takes one td_step(fused=fused) on
-    a batch of that size sampled on the device (dqn.py:24-48: Adam 1e-4, a target network per role).  The host looks at the
+    a batch of that size sampled on the device (dqn.py:24-48: Adam 1e-4, a target network per role); fused="packed" leaves the
+    batch packed (sample_packed: the stage's kernels read the ring, no face is built).  The host looks at the
     device every `check_every` iterations only (env.stats() and the ring counts: the one sync): there it moves epsilon (epsilon_schedule of the episodes so far), copies policy -> target
     every UPDATE_TARGET_EVERY episodes (dqn.py:73-80), writes the log line every log_every and the checkpoints
     <begin>_<role>_<episode> every model_every episodes (game.py:209-232; metrics.checkpoint_name / save_state_dict under
@@ -1321,6 +1461,8 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     batch_size = int(batch_size)
     if batch_size <= 0:
         raise ValueError("batch_size must be positive")
+    if isinstance(fused, str) and fused not in ("stage", "packed"):
+        raise ValueError('fused: False, True, "stage" or "packed"')
     nets = {r: v for r, v in nets.items()}
     for r, v in nets.items():
         if v is not None:
@@ -1353,8 +1495,9 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
             loop.step()
             for r in roles:
                 if ready[r]:
-                    loss[r] = td_step(policy[r], target[r], opt[r], loop.rec.sample(r, batch_size, face_variant), GAMMA,
-                                      fused=fused)
+                    packed = isinstance(fused, str) and fused == "packed"
+                    batch = (loop.rec.sample_packed if packed else loop.rec.sample)(r, batch_size, face_variant)
+                    loss[r] = td_step(policy[r], target[r], opt[r], batch, GAMMA, fused=fused)
         it += int(check_every)
         s1 = env.stats()                                             # the host sync of the interval
         known = loop.rec.note_counts()

@@ -784,6 +784,106 @@ def q_first_bwd(face, actions, gy, arg, weights):
     return gw, gb
 
 
+STAGE_WIDTH = 4864      # the row of h: 3840 first-layer values (o * 15 + r), then conv_shunzi's 1024 (o * 4 + j)
+
+
+def q_stage_source(face=None, actions=None, states=None, ids=None, index=None, table=None, variant=None):
+    """The source of the learner's stage (ddz_q_src_t) from checked operands -> (descriptor, device, n, planes, kept tensors).
+    faces: face f32 [n,P,15,4] + actions f32 [n,15,4].  rows: states u8 [m,176] + ids int32 [m] (a replay ring's s0 + a0 or
+    s1 + a1), index int64 [n] or None (every row in order; the kernels clamp entries into the ring), table int8 [n_actions,16]
+    (action_table), variant 0..3.  The descriptor holds raw addresses: the caller keeps the tensors alive across the launch."""
+    src = _lib.QSrc()
+    if states is None:
+        if face is None or actions is None:
+            raise ValueError("the stage's source is face + actions, or states + ids + table + variant")
+        dev = _require_gpu(face.device)
+        if face.dtype != torch.float32 or face.dim() != 4 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
+            raise ValueError("face must be a contiguous float32 [n,P,15,4] tensor")
+        n, P = int(face.shape[0]), int(face.shape[1])
+        if P not in (4, 6, 7, 9):
+            raise ValueError("face must have 4, 6, 7 or 9 planes")
+        if actions.dtype != torch.float32 or tuple(actions.shape) != (n, 15, 4) or not actions.is_contiguous() or actions.device != dev:
+            raise ValueError("actions must be a contiguous float32 [n,15,4] tensor on the face's device")
+        src.kind, src.planes, src.face, src.action = 0, P, face.data_ptr(), actions.data_ptr()
+        return src, dev, n, P, (face, actions)
+    dev = _require_gpu(states.device)
+    if variant is None or not 0 <= int(variant) < len(FACE_PLANES):
+        raise ValueError("variant must be a face variant 0..3")
+    if states.dtype != torch.uint8 or states.dim() != 2 or states.shape[1] != NFIELDS * ROW or not states.is_contiguous() \
+            or states.shape[0] == 0 or states.data_ptr() % 16:
+        raise ValueError("states must be a contiguous, 16-byte aligned uint8 [m,176] tensor with m > 0")
+    m = int(states.shape[0])
+    if ids is None or ids.dtype != torch.int32 or tuple(ids.shape) != (m,) or not ids.is_contiguous() or ids.device != dev:
+        raise ValueError("ids must be a contiguous int32 [m] tensor on the states' device")
+    if table is None or table.dtype != torch.int8 or table.dim() != 2 or table.shape[1] != 16 or table.shape[0] == 0 \
+            or not table.is_contiguous() or table.device != dev:
+        raise ValueError("table must be the contiguous int8 [n_actions,16] action table on the states' device")
+    if index is None:
+        n = m
+    else:
+        if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != dev:
+            raise ValueError("index must be a contiguous int64 [n] tensor on the states' device")
+        n = int(index.numel())
+    src.kind, src.variant, src.n_actions, src.n_rows = 1, int(variant), int(table.shape[0]), m
+    src.states, src.ids, src.table = states.data_ptr(), ids.data_ptr(), table.data_ptr()
+    src.index = None if index is None else index.data_ptr()
+    return src, dev, n, FACE_PLANES[int(variant)], (states, ids, index, table)
+
+
+def _q_stage_params(dev, P, weights, biases=None):
+    if len(weights) != 5 or (biases is not None and len(biases) != 5):
+        raise ValueError("weights / biases: those of conv1..conv4 and conv_shunzi")
+    for k in range(5):
+        shape = (256, P + 1, 1, k + 1) if k < 4 else (256, P + 1, 15, 1)
+        w = weights[k]
+        if w.dtype != torch.float32 or tuple(w.shape) != shape or not w.is_contiguous() or w.device != dev:
+            raise ValueError(f"weights[{k}] must be a contiguous float32 {list(shape)} tensor on the source's device")
+        if biases is not None:
+            b = biases[k]
+            if b.dtype != torch.float32 or tuple(b.shape) != (256,) or not b.is_contiguous() or b.device != dev:
+                raise ValueError(f"biases[{k}] must be a contiguous float32 [256] tensor on the source's device")
+
+
+def _ptr5(tensors):
+    return (C.c_void_p * 5)(*[t.data_ptr() for t in tensors])
+
+
+def q_stage_fwd(weights, biases, want_arg=True, **source):
+    """ddz_q_stage_fwd: everything of QNet.forward in front of dropout / fc1 -- cat, conv1..conv4, cat, max-pool, conv_shunzi, the
+    views and the cat -- of a batch in two launches, from faces (face=, actions=) or straight from packed replay rows (states=,
+    ids=, index=, table=, variant=: q_stage_source), weights / biases the nn.Conv2d parameters of conv1..4 and conv_shunzi as they
+    are -> (h f32 [n,4864], arg u8 [n,3840] as q_first_fwd's, or None with want_arg=False).  No host sync."""
+    src, dev, n, P, keep = q_stage_source(**source)
+    _q_stage_params(dev, P, weights, biases)
+    h = torch.empty((n, STAGE_WIDTH), dtype=torch.float32, device=dev)
+    arg = torch.empty((n, 3840), dtype=torch.uint8, device=dev) if want_arg else None
+    if n:
+        check(_lib.lib().ddz_q_stage_fwd(dev.index, C.byref(src), n, _ptr5(weights), _ptr5(biases), _p(h), STAGE_WIDTH, _p(arg),
+                                         _stream(dev)))
+    return h, arg
+
+
+def q_stage_bwd(gh, arg, weights, **source):
+    """ddz_q_stage_bwd: the gradients of the ten convolution parameters from gh f32 [n,4864] and q_stage_fwd's arg, in the
+    parameters' own shapes: (gw[5], gb[5]); `weights` give the shapes only.  Deterministic (per-block partials, a fixed-order
+    reduce: three launches); no gradient of the data.  No host sync."""
+    src, dev, n, P, keep = q_stage_source(**source)
+    _q_stage_params(dev, P, weights)
+    if gh.dtype != torch.float32 or tuple(gh.shape) != (n, STAGE_WIDTH) or not gh.is_contiguous() or gh.device != dev:
+        raise ValueError("gh must be a contiguous float32 [n,4864] tensor on the source's device")
+    if arg is None or arg.dtype != torch.uint8 or tuple(arg.shape) != (n, 3840) or not arg.is_contiguous() or arg.device != dev:
+        raise ValueError("arg must be q_stage_fwd's contiguous uint8 [n,3840] tensor")
+    L = _lib.lib()
+    if n == 0:
+        return [torch.zeros_like(w) for w in weights], [torch.zeros(256, dtype=torch.float32, device=dev) for _ in range(5)]
+    gw = [torch.empty_like(w) for w in weights]
+    gb = [torch.empty(256, dtype=torch.float32, device=dev) for _ in range(5)]
+    ws = torch.empty(int(L.ddz_q_stage_bwd_ws_bytes(n, P)), dtype=torch.uint8, device=dev)
+    check(L.ddz_q_stage_bwd(dev.index, C.byref(src), n, _p(gh), STAGE_WIDTH, _p(arg), _ptr5(gw), _ptr5(gb), _p(ws), ws.numel(),
+                            _stream(dev)))
+    return gw, gb
+
+
 def q_need_scratch_bytes(n_tables):
     return int(_lib.lib().ddz_q_need_scratch_bytes(int(n_tables)))
 

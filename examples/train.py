@@ -6,11 +6,12 @@ autograd td_step per trained role per iteration.  Hyper-parameters are the refer
 reference's progress lines, the total wins and the checkpoints written.
 
   python examples/train.py [--lord-vs-rule] [--tables 4096] [--episodes 20000] [--log-every 5000] [--model-every 10000]
-                           [--model-dir models] [--win-dir outs/win_rates] [--fused] [--batch-size 256]
+                           [--model-dir models] [--win-dir outs/win_rates] [--fused | --packed] [--batch-size 256]
 
 Default: lord, down and up all train (three networks).  --lord-vs-rule: the reference's train.py as it stands -- the lord trains
 against the rule-based farmers (reward_dict {'lord': 100}).  --fused: td_step through QNet.forward_fused (the first layer by the
-engine's forward / backward kernels, csrc/ddz_qtrain.h); --batch-size: transitions per td_step (the reference's 256).
+engine's forward / backward kernels, csrc/ddz_qtrain.h); --packed: batches stay packed replay rows and both passes of td_step run
+QNet.forward_packed (two stage launches per pass, no face, no library convolution); --batch-size: transitions per td_step (the reference's 256).
 """
 import argparse
 import importlib
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--win-dir", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--packed", action="store_true")
     ap.add_argument("--batch-size", type=int, default=None)
     a = ap.parse_args()
     glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
@@ -53,7 +55,7 @@ def main():
     t0 = time.perf_counter()
     res = glue.train(FACE_VARIANT, nets, a.episodes, train_dict=train_dict, reward_dict=reward_dict, tables=a.tables,
                      seed=a.seed, log_every=a.log_every, model_every=a.model_every, book=book, model_dir=a.model_dir,
-                     win_dir=a.win_dir, log=lambda m: print(m, end=""), fused=a.fused,
+                     win_dir=a.win_dir, log=lambda m: print(m, end=""), fused="packed" if a.packed else a.fused,
                      batch_size=glue.BATCH_SIZE if a.batch_size is None else a.batch_size)
     dt = time.perf_counter() - t0
     eps = max(1, res["episodes"])

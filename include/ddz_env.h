@@ -330,6 +330,52 @@ int64_t ddz_q_first_bwd_ws_bytes(int64_t n, int planes);
 int ddz_q_first_bwd(int device_id, const float* face, const float* action, int64_t n, int planes, const float* gy,
                     const uint8_t* arg, float* const gw[4], float* const gb[4], void* ws, int64_t ws_bytes, void* stream);
 
+/* The learner's whole stage in front of dropout / fc1 (net.py:87-97: the first layer above, conv_shunzi, the view and the cat)
+ * for a replay batch, forward and backward, from faces or straight from packed replay rows: h f32 [n][4864] is written whole
+ * by two launches, the backward gives all ten convolution-parameter gradients (three launches), no face is materialised for
+ * the rows source and no library convolution runs.  With x[n][c][r][j] and C as above, w[0..3] / b[0..3] as above and
+ * w[4] = conv_shunzi.weight f32 [256][C][15][1], b[4] = conv_shunzi.bias f32 [256] (HOST arrays of five DEVICE pointers):
+ *   h[n][o * 15 + r]        = max_k s_k            the first layer; arg u8 [n][3840] as above (NULL: a no-grad pass)
+ *   h[n][3840 + o * 4 + j]  = b[4][o] + sum_{c < C, r < 15} w[4][o][c][r][0] * x[n][c][r][j]            o < 256, j < 4
+ * Backward, from gh f32 [n][4864] and arg, into gw[0..4] / gb[0..4] in the parameters' own shapes:
+ *   gw[0..3], gb[0..3]      = the first layer's, from the columns gh[n][o * 15 + r]: bit for bit those of the first-layer entry
+ *   gw[4][o][c][r][0]       = sum_{n, j} gh[n][3840 + o * 4 + j] * x[n][c][r][j]
+ *   gb[4][o]                = sum_{n, j} gh[n][3840 + o * 4 + j]
+ * The source of x is a descriptor:
+ *   kind DDZ_Q_SRC_FACES  planes in {4, 6, 7, 9}, face f32 [n][planes][15][4], action f32 [n][15][4] (as the first-layer entry)
+ *   kind DDZ_Q_SRC_ROWS   variant 0..3 (planes 4 / 7 / 9 / 6), states u8 [n_rows][176] and ids int32 [n_rows] (a replay ring's
+ *                         s0 + a0 or s1 + a1), index int64 [n] (NULL: sample i is entry i; entries are clamped into
+ *                         [0, n_rows)), table int8 [n_actions][16] (the rows the action-table entry point writes, so either
+ *                         rule set serves).  Sample i's planes are the face of `variant` of state row index[i] (the observe
+ *                         entry points' expression, bit for bit) and its action plane the thermometer of
+ *                         table[clamp(ids[index[i]], 0, n_actions - 1)] (slot j set iff count > j): for equal inputs both
+ *                         kinds give bit-equal h, arg and gradients.
+ * h_stride / gh_stride: the row stride in floats; 4864 is the one supported (else DDZ_EINVAL).  DETERMINISTIC as above: ws is
+ * caller-owned, at least ddz_q_stage_bwd_ws_bytes bytes (its size depends on n and planes alone), not initialised, not kept.
+ * fp32; face / action / states / h / gh / arg 16-byte aligned; stateless; every launch on `stream`, nothing on the host
+ * (capturable).  n = 0 is a no-op (DDZ_OK); an unknown kind / planes / variant, a null or misaligned operand and a short
+ * workspace are DDZ_EINVAL; n > 2^30 is DDZ_ECAP.  NaN operands are outside the contract.                          */
+#define DDZ_Q_SRC_FACES 0
+#define DDZ_Q_SRC_ROWS 1
+typedef struct ddz_q_src {
+  int kind;               /* DDZ_Q_SRC_FACES / DDZ_Q_SRC_ROWS */
+  int planes;             /* faces */
+  const float* face;      /* faces */
+  const float* action;    /* faces */
+  int variant;            /* rows */
+  int n_actions;          /* rows */
+  const uint8_t* states;  /* rows */
+  const int32_t* ids;     /* rows */
+  const int64_t* index;   /* rows; may be NULL */
+  const int8_t* table;    /* rows */
+  int64_t n_rows;         /* rows */
+} ddz_q_src_t;
+int ddz_q_stage_fwd(int device_id, const ddz_q_src_t* source, int64_t n, const float* const w[5], const float* const b[5],
+                    float* h, int64_t h_stride, uint8_t* arg, void* stream);
+int64_t ddz_q_stage_bwd_ws_bytes(int64_t n, int planes);
+int ddz_q_stage_bwd(int device_id, const ddz_q_src_t* source, int64_t n, const float* gh, int64_t gh_stride, const uint8_t* arg,
+                    float* const gw[5], float* const gb[5], void* ws, int64_t ws_bytes, void* stream);
+
 /* The reference's ragged Q forward -- policy_net(face, actions) over ALL legal actions of a state (game.py:95-104,
  * dqn.py:56,67; net.py:99-101 relu(fc1) -> fc2) -- for every table at once, over the slab lists as ddz_step_slab /
  * ddz_legal_slab left them, with the first layer factorised per (rank, count) and evaluated over NEEDED rows only: nothing
