@@ -1176,7 +1176,9 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     for (int it = (int)a.n_iters; it > 0; --it) {
       uint4 tr0 = make_uint4(0, 0, 0, 0);
       uint4 tr1 = make_uint4((uint32_t)role, ply << 16, episode, 0xFFFFFFFFu);
-      if (dnext >= 64u) {
+      uint32_t dn = rfl(dnext);  // the same value in every lane: a scalar branch, and the lane of the draw below
+      if (dn >= 64u) {
+        dn = 0;
         dnext = 0;
         uint32_t qk0 = a.k0, qk1 = a.k1;  // opaque: round keys are computed here, not hoisted and spilled
         asm volatile("" : "+s"(qk0), "+s"(qk1));
@@ -1189,7 +1191,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       const int64_t jn = STAGED ? a.n_iters - it : 0;         // iteration of this launch (staged form: its slab)
       const int64_t base = t * a.stride + (STAGED ? jn * a.it_rows : 0);
       int32_t* const cnt_p = a.counts + t + (STAGED ? jn * a.it_counts : 0);
-      const uint32_t draw = rl(draws, (int)dnext);
+      const uint32_t draw = rl(draws, (int)dn);
       stamps.mark(1);  // per-iteration setup: frozen check, draw refresh, hand/info select
       int n = 0, idx = -1;
       uint4 c = make_uint4(0, 0, 0, 0);  // TRAJ: the chosen row for the record, same value in every lane
@@ -1211,13 +1213,15 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       };
       const int fid = !IDS ? 0 : lane == 0 ? 0 : lane < 16 ? (lc0 == SINGLE ? 1 : lc0 == DOUBLE ? 16 : lc0 == TRIPLE ? 29 : 42) + fl.rr
                                  : lane < 29 ? 42 + fl.rr : ID_BIGBANG;   // the follow layout's canonical ids
+      // the rank ballots every list needs, once per ply
+      const uint32_t b1 = (uint32_t)__ballot(cntr >= 1), b4 = (uint32_t)__ballot(cntr >= 4);
       if (lc0 != EMPTY && lc0 <= TRIPLE) {
         // Two thirds of all plies follow a single, a pair or a triple.  Their legal list is pass + the higher groups of the
         // same size + bombs + rocket (card.py:307-325): never a tail.
         const int lv0 = (int)((info >> 8) & 0xFF);
         const uint32_t mlc = (uint32_t)__ballot(cntr >= lc0) & (lc0 == SINGLE ? M15 : M13);
-        const uint32_t mq = (uint32_t)__ballot(cntr >= 4) & M13;
-        const bool rocket = ((uint32_t)__ballot(cntr >= 1) & JOKERS) == JOKERS;
+        const uint32_t mq = b4 & M13;
+        const bool rocket = (b1 & JOKERS) == JOKERS;
         // the candidate mask is scalar: bit 0 pass | 1..15 groups | 16..28 bombs | 29 rocket
         const uint32_t okm = 1u | ((mlc & gt_mask(lv0)) << 1) | (mq << 16) | (rocket ? 1u << 29 : 0u);
         const uint32_t copies = ((uint32_t)lc0 & fl.grp) | fl.c4;  // category == group size here
@@ -1225,8 +1229,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         round_pick<TRAJ, false>(okm, pre, row, idx, (uint32_t)lc0, c, snib, scat, svlv, ncards);
         stamps.mark(5);  // follow of a single / pair / triple: list + pick
       } else {
-        const uint32_t m1 = (uint32_t)__ballot(cntr >= 1) & M15, m2 = (uint32_t)__ballot(cntr >= 2) & M13;
-        const uint32_t m3 = (uint32_t)__ballot(cntr >= 3) & M13, m4 = (uint32_t)__ballot(cntr >= 4) & M13;
+        const uint32_t m1 = b1 & M15, m2 = (uint32_t)__ballot(cntr >= 2) & M13;
+        const uint32_t m3 = (uint32_t)__ballot(cntr >= 3) & M13, m4 = b4 & M13;
         const bool jokers = (m1 & JOKERS) == JOKERS;
         const bool lead = lc0 == EMPTY;
         uint64_t okm;  // the legal lanes of the round: 55 lanes of the lead layout, 30 of the follow layout
@@ -1281,7 +1285,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           const int n1 = lead ? plan_scan_t<EM_STAGE, IDS, true, HotTabT<false>, false>(hand, f, hot, lane, o, pk)
                               : plan_scan_t<EM_STAGE, IDS, false, HotTabT<false>, false>(hand, f, hot, lane, o, pk);
           __builtin_amdgcn_wave_barrier();
-          n = n0 + n1;
+          n = (int)rfl((uint32_t)(n0 + n1));  // wave-uniform: the guard, the pick's two tests are scalar branches
           if (n > STAGE_CAP || n > a.stride) {  // cannot happen for a <= 20-card hand; never index past the slab
             if (lane == 0) atomicOr(a.status, 2);
             n = 0;
@@ -1297,7 +1301,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           }
           stamps.mark(3);  // hybrid: flush rows
           if (n > 0) {
-            idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83
+            idx = (int)rfl(__umulhi(draw, (uint32_t)n));  // random.choice(actions), envi.py:83
             if (idx < n0) {  // from the round: by lane number (its positions are rebuilt here, not held across the planner)
               if (lead) round_entry<true>(round_src<true>(okm, round_pre(okm), idx), 0u, snib, scat, svlv, ncards);
               else round_entry<false>(round_src<false>((uint32_t)okm, round_pre((uint32_t)okm), idx), (uint32_t)lc0, snib, scat, svlv, ncards);
@@ -1317,6 +1321,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         }
       }
       tr1.y |= (uint32_t)n & 0xFFFF;
+      // (this test stays a lane-mask branch: read through rfl or a ballot it costs the record-writing 12-wave variants
+      // 4..28 B of scratch and the headline 1.4 %, profiles/r10_notes.md)
       if (n <= 0) {
         tr1.x |= 2u << 24;
         idle += 1;
@@ -1331,7 +1337,11 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         // carried scalars
         const uint64_t hnew = hand - snib;
         if (snib) { trick = scat | (svlv << 8); passes = 0; } else { passes += 1; }
-        const bool won = hnew == 0;
+        // wave-uniform: a scalar branch.  Not in the staged 12-wave variants of the joker-kicker build: at their 80-VGPR
+        // budget the scalar form costs <0,0,1,12> 4 B of scratch per lane (24 -> 28, profiles/r10_notes.md), the lane-mask
+        // form none
+        constexpr bool WON_SCALAR = !(STAGED && RW != WPB && DDZ_NATIVE_JOKER_KICKERS);
+        const bool won = WON_SCALAR ? rfl((uint32_t)hnew | (uint32_t)(hnew >> 32)) == 0u : hnew == 0;
         const uint32_t o_reward = won ? (role == 1 ? 0xFFu : 1u) : 0u;  // rule_play.py:14
         tr0 = c;
         tr1.x |= (uint32_t)won << 8 | o_reward << 16;
