@@ -200,7 +200,16 @@ int ddz_observe_states(int device_id, const uint8_t* states, const int64_t* inde
  *   Order: emit g of a call into a ring, g = the number of lower-numbered tables that emit into that ring in this call (a
  *     scan over the tables, no atomics), gets sequence number count + g.  A call that emits E > capacity into one ring writes
  *     the last `capacity` of them only, at count .. count + capacity - 1, and count moves by capacity: what Replay.push keeps
- *     and where it puts it.  No two lanes of a launch store to one entry.                                              */
+ *     and where it puts it.  No two lanes of a launch store to one entry.
+ *   A role byte above 2 (a corrupted import; every other entry point reads it as role 0): the table takes no part in
+ *     ddz_tr_before -- nothing is recorded, its slots and flags are left alone, it does not stop being fresh -- because a
+ *     slot is addressed by the role.  ddz_tr_after does not read the role byte.
+ *   A NULL ring for a role that is pending on a finished table (ddz_tr_after names no trained roles): that role's terminal
+ *     transition is dropped; the table's flags move as they do with a ring.
+ *   A count the caller did not zero: any int64 is taken as it stands, sequence number s lives at entry s mod capacity with
+ *     the non-negative remainder, so a negative count still stores inside the ring.
+ *   Both calls store to the entries named above and to nothing else of a ring: an entry that takes no emit, and the padding
+ *     between the fields, keep their bytes.  (tests/test_gpu_recorder_cases.py)                                      */
 int64_t ddz_tr_ws_bytes(int64_t n_tables);
 int64_t ddz_tr_ring_bytes(int64_t capacity);
 int ddz_tr_ring_layout(int64_t capacity, int64_t* offsets);

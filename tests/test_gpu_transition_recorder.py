@@ -5,7 +5,10 @@ reward constants; the faces it decodes are ddz_observe's expression on the store
 
 Ring counts: Replay.push keeps the last `size` rows of a larger push and advances its head by what it stored; the recorder's
 count advances the same way (the total ever WRITTEN), so entry for entry the ring is the Replay tensor, wrap and overflow
-included -- the tests compare in slot order with no re-ordering."""
+included -- the tests compare in slot order with no re-ordering.
+
+These runs see what one policy reaches from a fresh deal; the kernels' edges (the scan's second trip, overflow boundaries, counts
+past 2^31, NULL rings, role bytes above 2, stores outside the live entries) are in tests/test_gpu_recorder_cases.py."""
 import importlib
 import math
 import os
