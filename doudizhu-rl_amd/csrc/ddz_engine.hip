@@ -6,6 +6,8 @@
 //             lists in fixed-stride slabs; every list starts with one closed-form round built from the hand's rank masks
 //             (nine plies in ten: that round is the whole list), planner + LDS staging list for the tail of the rest
 //             (see the comment at the kernel).
+//   k_playout (ddz_playout.h; ddz_playout) win counts of random playouts for every legal move of every table: one wavefront per
+//             (table, chunk), the root in registers, every ply from k_rollout's device functions, no list stored.
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
 //             or slab lists with F_SLAB = apply + enumerate in the same launch):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
@@ -1397,6 +1399,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     ws[0] += s_ply; ws[3] += s_rows;
   }
 }
+
+#include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move, from k_rollout's device functions
 
 // write-once output streams (`face`, thermometer planes): nontemporal 16-byte stores.  Measured on k_observe
 // at 524,288 tables (0.6-1.2 GB per call): 3.1 TB/s with plain stores, 5.3-5.7 TB/s with these.
@@ -3441,6 +3445,39 @@ int ddz_rollout_random(ddz_env_t* e, int64_t n_iters, int32_t* counts, int8_t* r
     return check_launch();
   }
   return DDZ_OK;
+}
+
+int ddz_playout(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int32_t* wins, int64_t* totals,
+                void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
+  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  const int64_t blocks = (e->T * chunks + PLAYOUT_WAVES - 1) / PLAYOUT_WAVES;  // one wavefront per (table, chunk)
+  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  PlayoutArgs a;
+  a.state = e->state; a.T = e->T;
+  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  a.K = (uint32_t)n_playouts; a.chunks = (uint32_t)chunks; a.stride = stride;
+  a.wins = wins; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  hipLaunchKernelGGL(k_playout, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int ddz_playout_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* wins, int32_t* choice,
+                       void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!counts || !ids || !wins || !choice || !al(counts, 4) || !al(ids, 4) || !al(wins, 4) || !al(choice, 4)) return DDZ_EINVAL;
+  if (stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const int64_t per = BLOCK / 64;
+  hipLaunchKernelGGL(k_playout_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
+                     stride, wins, choice, e->T);
+  return check_launch();
 }
 
 int ddz_rollout_random_csr(ddz_env_t* e, int64_t n_iters, int32_t* offsets, int8_t* rows, int32_t* ids, int64_t cap,

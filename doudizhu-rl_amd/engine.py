@@ -559,6 +559,58 @@ class BatchedEnv:
                                           _stream(self.device)))
         self._legal_fresh = self._slab_fresh = self._csr_fresh = False
 
+    # ---- playout evaluation (flat Monte Carlo over perfect information) ----
+    def playout(self, n_playouts, salt=0, chunks=None, wins=None, totals=None):
+        """Win counts of uniformly random playouts for EVERY legal move of every running table (playout spec v1, DESIGN.md 4;
+        the reference's Monte-Carlo player, server/mcts/interface.py:15-45, as flat Monte Carlo): wins int32 [T, stride], entry
+        [t, j] = how many of the n_playouts playouts that start with move j of table t's slab list (legal_slab() order) ended
+        with a winner on the actor's side (the lord alone, or either farmer).  The env is only read.  One memset + one launch
+        on the current stream, nothing on the host: capturable.
+        salt: a different salt gives different draws for the same state; chunks: wavefronts per table (default: enough to
+        fill the device when there are few tables; the result does not depend on it); wins: an int32 [T * stride] buffer to
+        reuse (zeroed here); totals: int64 [4] on the device, += {moves applied, playouts run, playouts stopped unfinished, -}."""
+        st = self.slab_stride
+        if st < MAX_LEGAL_PER_TABLE:
+            raise ValueError(f"playouts need row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        if not self._slab_fresh:        # wins[t, j] is read against the lists of the current state (the check step_slab makes)
+            self.legal_slab()
+        n_playouts = int(n_playouts)
+        if not 1 <= n_playouts < (1 << 23):
+            raise ValueError("n_playouts must be in [1, 2^23)")
+        if chunks is None:
+            # a launch lasts as long as its heaviest wavefront, and lists are 1 .. 497 moves long: enough chunks to fill the
+            # device (four rounds of its 256 x 24 resident wavefronts) and to cut the longest table's share to a few playouts
+            # per move, but no more than ~1.5 M wavefronts in all -- one that finds nothing to do still sizes the root's list
+            # (measured, profiles/r11_notes.md: 12 .. 24 chunks are best at K = 8, 24 .. 96 at K = 64)
+            fill = -(-24576 // self.T)
+            chunks = max(1, min(max(fill, min(3 * n_playouts, 96)), max(fill, 1572864 // self.T), 8192))
+        if wins is None:
+            wins = torch.empty(self.T * st, dtype=torch.int32, device=self.device)
+        elif wins.dtype != torch.int32 or wins.device != self.device or wins.numel() != self.T * st or not wins.is_contiguous():
+            raise ValueError("wins must be a contiguous int32 [T * stride] tensor on the env's device")
+        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
+                                   or not totals.is_contiguous()):
+            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
+        wins.zero_()                    # (an enqueued memset of the whole buffer)
+        check(self.lib.ddz_playout(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, _p(wins), _p(totals),
+                                   _stream(self.device)))
+        return wins.view(self.T, st)
+
+    def playout_choose(self, n_playouts, salt=0, out=None, chunks=None):
+        """The flat Monte-Carlo move of every table: int32 [T] canonical action ids, the FIRST maximum of playout()'s win
+        counts over each table's list (ties to the lowest index), -1 for idle tables.  Feed them to
+        step_slab(mode=STEP_IDS)."""
+        if self.ids is None:
+            raise ValueError("playout_choose needs the action ids of the lists (want_ids=True)")
+        self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None))
+        if out is None:
+            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
+        check(self.lib.ddz_playout_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
+                                          _p(self._playout_wins), _p(out), _stream(self.device)))
+        return out
+
     def rollout_random_csr(self, n_iters, traj=None, batch=None):
         """The same loop with packed CSR lists (offsets/rows/ids as legal() returns them: afterwards they hold the lists
         of the last iteration's pre-step states).  Same states and trajectories as rollout_random.

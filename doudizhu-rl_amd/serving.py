@@ -13,7 +13,7 @@ ddz_get_moves), so a served observation is bit-identical to the one of a live ta
 import numpy as np
 import torch
 
-from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, NFIELDS, ROW, get_moves)
+from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, NFIELDS, ROW, action_table, get_moves)
 
 
 def _counts(cards):
@@ -69,6 +69,92 @@ def state_to_payloads(state):
                     "left": {r: int(s[F_HAND0 + r, 15]) for r in range(3)},
                     "last_taken": {r: cards(s[F_RECENT0 + r]) for r in range(3)}})
     return out
+
+
+def combo_category(counts):
+    """The category (card.py:13-28: 0 pass, 1 single ... 12 rocket, 13 / 14 four with two) of a count vector that is a
+    combination of the action space -- the byte a state's recent_handout row carries behind its counts, which a payload
+    does not hold.  A vector that is no combination gives 0 (read as "nothing to beat")."""
+    c = [int(x) for x in counts[:15]]
+    n = [sum(1 for x in c if x == k) for k in range(5)]           # ranks held exactly k times
+
+    def chain(k):                                                  # the ranks held k times are consecutive, within 3..A
+        r = [i for i, x in enumerate(c) if x == k]
+        return r[-1] - r[0] + 1 == len(r) and r[-1] < 12
+
+    if not any(c) or max(c) > 4 or c[13] > 1 or c[14] > 1:
+        return 0
+    if n[2] == n[3] == n[4] == 0:
+        if n[1] == 1:
+            return 1
+        if n[1] == 2 and c[13] and c[14]:
+            return 12
+        return 7 if n[1] >= 5 and chain(1) else 0
+    if n[1] == n[3] == n[4] == 0:
+        return 2 if n[2] == 1 else 8 if 3 <= n[2] <= 10 and chain(2) else 0
+    if n[1] == n[2] == n[4] == 0:
+        return 3 if n[3] == 1 else 9 if 2 <= n[3] <= 6 and chain(3) else 0
+    if n[1] == n[2] == n[3] == 0:
+        return 4 if n[4] == 1 else 0
+    if n[3] and not n[4]:
+        if not n[2] and n[1] == n[3]:
+            return 5 if n[3] == 1 else 10 if n[3] <= 5 and chain(3) else 0
+        if not n[1] and n[2] == n[3]:
+            return 6 if n[3] == 1 else 11 if n[3] <= 4 and chain(3) else 0
+        return 0
+    if n[4] == 1 and not n[3]:
+        if not n[2] and n[1] == 2:
+            return 13
+        if not n[1] and n[2] == 2:
+            return 14
+    return 0
+
+
+def full_payloads_to_state(payloads):
+    """uint8 [n, 11, 16] state rows of n payloads of the reference's Monte-Carlo player (server/mcts/interface.py:15-35): the
+    serving payload plus hand_card {0, 1, 2}, the cards of ALL three players as rank values 3..17.  Every hand row is filled
+    (its byte 15 = the number of cards listed) and every recent_handout row carries its category byte, so the rows are what a
+    live table holds -- apart from ply and episode, which a payload does not say (0) -- and every kernel that reads a table
+    reads them: legal lists, steps, playouts."""
+    st = payloads_to_state(payloads)
+    for i, p in enumerate(payloads):
+        for r in range(3):
+            hand = _counts(_get(p["hand_card"], r))
+            st[i, F_HAND0 + r, :15] = hand
+            st[i, F_HAND0 + r, 15] = hand.sum()
+            st[i, F_RECENT0 + r, 15] = combo_category(st[i, F_RECENT0 + r])
+    return st
+
+
+def state_to_full_payloads(state):
+    """state_to_payloads plus hand_card {0, 1, 2}: the payload of the reference's Monte-Carlo player for every table."""
+    if isinstance(state, BatchedEnv):
+        state = state.state
+    if torch.is_tensor(state):
+        state = state.detach().cpu().numpy()
+    st = np.asarray(state, np.uint8).reshape(-1, NFIELDS, ROW)
+    ranks = np.arange(3, 18)
+    out = state_to_payloads(st)
+    for s, p in zip(st, out):
+        p["hand_card"] = {r: [int(x) for x in np.repeat(ranks, s[F_HAND0 + r, :15].astype(int))] for r in range(3)}
+    return out
+
+
+def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0):
+    """The reference's mcts(payload) (server/mcts/interface.py:15-45) as flat Monte Carlo, for a batch of requests: every
+    legal move of every request is followed by n_playouts uniformly random playouts over the three known hands
+    (BatchedEnv.playout_choose) and the move with the most wins for the requester's side is returned -- per request a list
+    of rank values 3..17 ([] = pass), or None where the request has no move (a finished game)."""
+    n = len(payloads)
+    if n == 0:
+        return []
+    dev = torch.device(device)
+    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
+    env.state_import(torch.from_numpy(full_payloads_to_state(payloads)).view(-1))
+    ids = env.playout_choose(n_playouts, salt=salt).cpu().numpy()
+    table = action_table(dev).cpu().numpy()
+    ranks = np.arange(3, 18)
+    return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
 
 
 class BatchedPredictorInputs:

@@ -263,6 +263,36 @@ int ddz_rollout_random(ddz_env_t* env, int64_t n_iters, int32_t* counts, int8_t*
                        int32_t* ids, int64_t stride, int64_t* stats, uint8_t* traj,
                        void* stream);
 
+/* Playout evaluation (the reference's Monte-Carlo player as flat Monte Carlo: server/mcts/interface.py:15-45 with
+ * default_policy.py:4-10 and the reward of tree.py:71-81; perfect information: all three hands of the state are used).
+ * "Playout spec v1" (DESIGN.md 4): for every running table t (dealt, not done) with legal list L in slab order (what
+ * ddz_legal_slab writes, n = |L|), every move index j < n and every playout number k < n_playouts: start from a copy of the
+ * table's state, apply L[j] as ddz_step does without auto-reset, then, while the table is not done, apply the move at index
+ * (draw * A) >> 32 of the state's legal list (A its size; A = 0, an imported state outside the domain, stops the playout) with
+ *   draw = philox4x32_10(counter = (gid_lo, gid_hi, k << 9 | j, 4 << 16 | ply), key = (seed_lo ^ salt_lo, seed_hi)).x,
+ * gid = table_id_base + t, ply = the u16 ply counter of the state being stepped (RNG domain 4; domains 1..3 are unchanged).
+ * At most DDZ_PLAYOUT_MAX_PLIES moves are applied per playout, the root move included (>= the 162 plies of the longest game).
+ *   wins int32 [T * stride], stride >= DDZ_SLAB_MIN_STRIDE: wins[t * stride + j] += the playouts of move j that ended with a
+ *     winner on the root actor's side (the lord alone, or either farmer) -- entry j belongs to row j of ddz_legal_slab's slab at
+ *     the same state.  The caller zeroes what it wants counted from zero; idle tables (done / not dealt) run nothing and their
+ *     entries, like every entry at or beyond n, are left as they are.
+ *   totals (device int64[4], may be NULL) += {moves applied (root moves included), playouts run, playouts that stopped
+ *     unfinished (0 on every state play reaches), -}.
+ *   chunks >= 1 (at most 2^20): wavefronts per table.  The n * n_playouts playouts of a table are dealt round-robin over its
+ *     chunks, so one table -- also one with a long list and n_playouts = 1 -- fills the device; wins and totals do not depend on it
+ *     (integer sums; 32-bit atomic adds where chunks share a move).  1 <= n_playouts < 2^23.
+ * The env is only read: state, lists and statistics are untouched.  One launch on `stream`, nothing on the host (capturable).
+ * A root list that would exceed `stride` or the kernel's staging capacity (impossible for hands of <= 20 cards) raises status
+ * bit 1 and the table runs nothing.
+ * ddz_playout_choose: choice[t] = ids[t * stride + the first maximum of wins[t * stride + 0 .. counts[t])] (ties to the lowest
+ * index, as torch.argmax in dqn.py:60), -1 where counts[t] <= 0: feed it to ddz_step_slab(DDZ_STEP_IDS).  counts / ids as
+ * ddz_legal_slab wrote them; a small launch over the live entries only. */
+#define DDZ_PLAYOUT_MAX_PLIES 192
+int ddz_playout(ddz_env_t* env, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int32_t* wins,
+                int64_t* totals, void* stream);
+int ddz_playout_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* wins,
+                       int32_t* choice, void* stream);
+
 /* The same random-policy loop with the lists in the CSR layout of ddz_legal (offsets/rows/ids
  * packed across tables).  CSR bases need a scan over all tables, so this variant is one
  * launch per iteration: the fused kernel writes the list of the current state, steps, and
