@@ -284,6 +284,9 @@ int ddz_rollout_random(ddz_env_t* env, int64_t n_iters, int32_t* counts, int8_t*
  * The env is only read: state, lists and statistics are untouched.  One launch on `stream`, nothing on the host (capturable).
  * A root list that would exceed `stride` or the kernel's staging capacity (impossible for hands of <= 20 cards) raises status
  * bit 1 and the table runs nothing.
+ * A running table whose ACTOR's hand is empty (an imported state outside the domain: ddz_step ends a table with the card that
+ * empties a hand) has the empty list, as a lead and facing a combination alike: nothing runs, its wins and the totals stay as
+ * they are, and the status word is not touched.
  * ddz_playout_choose: choice[t] = ids[t * stride + the first maximum of wins[t * stride + 0 .. counts[t])] (ties to the lowest
  * index, as torch.argmax in dqn.py:60), -1 where counts[t] <= 0: feed it to ddz_step_slab(DDZ_STEP_IDS).  counts / ids as
  * ddz_legal_slab wrote them; a small launch over the live entries only. */
