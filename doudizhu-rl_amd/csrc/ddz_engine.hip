@@ -3447,12 +3447,9 @@ int ddz_rollout_random(ddz_env_t* e, int64_t n_iters, int32_t* counts, int8_t* r
   return DDZ_OK;
 }
 
-int ddz_playout(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int32_t* wins, int64_t* totals,
-                void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
-  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+// ddz_playout / ddz_playout_hidden / ddz_playout_worlds: one launch of k_playout<hidden>
+static int launch_playout(bool hidden, ddz_env_t* e, int64_t K, uint64_t salt, int64_t chunks, int64_t stride, int roles, int32_t* wins,
+                          int64_t* totals, uint8_t* worlds, void* stream) {
   const int64_t blocks = (e->T * chunks + PLAYOUT_WAVES - 1) / PLAYOUT_WAVES;  // one wavefront per (table, chunk)
   if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
   DeviceGuard g(e->device);
@@ -3460,10 +3457,43 @@ int ddz_playout(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks,
   PlayoutArgs a;
   a.state = e->state; a.T = e->T;
   a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
-  a.K = (uint32_t)n_playouts; a.chunks = (uint32_t)chunks; a.stride = stride;
+  a.K = (uint32_t)K; a.chunks = (uint32_t)chunks; a.stride = stride;
   a.wins = wins; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
-  hipLaunchKernelGGL(k_playout, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
+  a.roles = (uint32_t)roles; a.worlds = worlds;
+  if (hidden) hipLaunchKernelGGL(k_playout<true>, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_playout<false>, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
   return check_launch();
+}
+
+int ddz_playout(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int32_t* wins, int64_t* totals,
+                void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
+  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  return launch_playout(false, e, n_playouts, salt, chunks, stride, 7, wins, totals, nullptr, stream);
+}
+
+int ddz_playout_hidden(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int roles, int32_t* wins,
+                       int64_t* totals, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
+  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (roles < 0 || roles > 7) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  return launch_playout(true, e, n_playouts, salt, chunks, stride, roles, wins, totals, nullptr, stream);
+}
+
+int ddz_playout_worlds(ddz_env_t* e, int64_t n_worlds, uint64_t salt, int roles, uint8_t* out, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!out) return DDZ_EINVAL;
+  if (n_worlds < 1 || n_worlds >= (1ll << 23) || roles < 0 || roles > 7) return DDZ_EINVAL;
+  if (e->T * n_worlds > 0x7FFFFFFF) return DDZ_ECAP;
+  // wavefronts per table: enough to fill the device when there are few tables, never more than there are worlds
+  int64_t chunks = (24576 + e->T - 1) / (e->T > 0 ? e->T : 1);
+  if (chunks > n_worlds) chunks = n_worlds;
+  if (chunks < 1) chunks = 1;
+  return launch_playout(true, e, n_worlds, salt, chunks, DDZ_SLAB_MIN_STRIDE, roles, nullptr, nullptr, out, stream);
 }
 
 int ddz_playout_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* wins, int32_t* choice,

@@ -17,6 +17,14 @@
 // first ply, (draw * A) >> 32 afterwards -- from the round by lane number or from the staged tail, and the apply on the packed
 // hands.  No list is stored; global traffic is the root read, one atomicAdd per (item, move) with wins and three for the totals.
 // The playout loop is a counted `for` over DDZ_PLAYOUT_MAX_PLIES: no state, however inconsistent, makes a wavefront spin.
+//
+// k_playout<true> is "playout spec v2 (hidden hands)", DESIGN.md 4: the two opponents' count bytes are never read.  The wave
+// decodes once what the actor has not seen (deck - own hand - taken) as a 54-lane pool mask and the opponents' hand SIZES, checks
+// the domain once (status bit 6 and nothing runs outside it), and redeals at the top of a playout whose playout number k differs
+// from the one before: lane c draws the key of card c (RNG domain 5, keyed by (gid, k) alone: every root move of a table sees the
+// same K worlds), the pool is ranked by (key, c) through LDS as deal_wave_lds ranks a deal -- the wave's staging list is dead
+// between two playouts, its first 64 words hold the keys -- and two ballots give the hands.  The ply loop is the open one.  The
+// open instance is what it was: everything of the hidden form stands under `if constexpr (HIDDEN)`.
 struct PlayoutArgs {
   const uint8_t* state;
   int64_t T;
@@ -28,10 +36,39 @@ struct PlayoutArgs {
   int32_t* wins;
   unsigned long long* totals;  // {moves applied, playouts run, playouts stopped unfinished, -} or null
   int32_t* status;
+  // hidden form only
+  uint32_t roles;           // bit r: tables whose actor is role r take part (the others are idle)
+  uint8_t* worlds;          // null, or [T][K][2][16]: the worlds alone (ddz_playout_worlds), no playout runs
 };
+
+constexpr uint64_t DECK_NIB = 0x0114444444444444ull;  // four of the ranks 3 .. 2, one of each joker
 
 constexpr int PLAYOUT_WAVES = 12;  // 74 KB of LDS per block: two blocks per CU = 6 waves per SIMD (as k_rollout's dense variants)
 
+// world k of a table (playout spec v2): the hands of the next and of the previous player as nibble words.  `pool`: this lane's
+// card (Deal v2's numbering) is unseen; keys: 64 x 8 bytes of the calling wave; 1 <= n_next.
+__device__ inline void redeal_wave(uint64_t gid, uint32_t k, uint32_t k0, uint32_t k1, int lane, bool pool, int n_next,
+                                   uint64_t* keys, uint64_t& o_next, uint64_t& o_prev) {
+  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), k, (5u << 16) | (uint32_t)(lane >> 2)), k0, k1);
+  const int w = lane & 3;
+  const uint32_t key = w == 0 ? d.x : w == 1 ? d.y : w == 2 ? d.z : d.w;
+  const uint64_t kk = pool ? ((uint64_t)key << 6) | (uint32_t)lane : ~0ull;  // a card outside the pool ranks behind every pool card
+  keys[lane] = kk;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  int pos = 0;
+#pragma unroll 9
+  for (int j = 0; j < 54; j += 2) {
+    const ulonglong2 v = *(const ulonglong2*)&keys[j];
+    pos += (v.x < kk ? 1 : 0) + (v.y < kk ? 1 : 0);
+  }
+  o_next = nib_from_cards(__ballot(pool && pos < n_next));
+  o_prev = nib_from_cards(__ballot(pool && pos >= n_next));
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();   // the keys are read: the staging list is the ply loop's again
+}
+
+template <bool HIDDEN>
 __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a) {
   __shared__ HotTabT<false> hot;
   __shared__ uint64_t s_stage[PLAYOUT_WAVES][STAGE_CAP];
@@ -56,8 +93,12 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
   if (role0 > 2) role0 = 0;
   if (!(((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF))) return;  // not dealt, or done: nothing runs, wins stay as they are
   const uint32_t ply0 = my & 0xFFFF;
-  const uint64_t hc0 = rl64(P, DDZ_F_HAND0 + role0), hn0 = rl64(P, DDZ_F_HAND0 + (role0 == 2 ? 0 : role0 + 1)),
-                 hp0 = rl64(P, DDZ_F_HAND0 + (role0 == 0 ? 2 : role0 - 1));
+  const uint64_t hc0 = rl64(P, DDZ_F_HAND0 + role0);
+  uint64_t hn0 = 0, hp0 = 0;
+  if constexpr (!HIDDEN) {
+    hn0 = rl64(P, DDZ_F_HAND0 + (role0 == 2 ? 0 : role0 + 1));
+    hp0 = rl64(P, DDZ_F_HAND0 + (role0 == 0 ? 2 : role0 - 1));
+  }
   uint32_t trick0 = mk_info(EMPTY, 0, 1);  // the combo to beat (envi.py:103-109) as (trick, passes since it was played)
   int passes0 = 0;
   {
@@ -67,6 +108,39 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
     else if (n2) { trick0 = info_of_row(n2, (int)rl(aux, DDZ_F_RECENT0 + rp1)); passes0 = 1; }
   }
   const uint64_t gid = a.gid_base + (uint64_t)t;
+  // hidden form: the pool of unseen cards and the opponents' hand sizes, the domain checked once
+  bool pool = false;
+  int n_next = 0;
+  uint32_t world_k = 0xFFFFFFFFu;   // the playout number the world below was dealt for (K < 2^23: none yet)
+  uint64_t wn = 0, wp = 0;
+  if constexpr (HIDDEN) {
+    if (!((a.roles >> role0) & 1u)) return;   // not this call's seat: idle
+    const uint64_t taken = rl64(P, DDZ_F_TAKEN);
+    n_next = (int)rl(aux, DDZ_F_HAND0 + (role0 == 2 ? 0 : role0 + 1));
+    const int n_prev = (int)rl(aux, DDZ_F_HAND0 + (role0 == 0 ? 2 : role0 - 1));
+    const int sh = 4 * (lane & 15);
+    const int deck = lane < 13 ? 4 : lane < 15 ? 1 : 0;
+    const bool over = (int)((hc0 >> sh) & 15) + (int)((taken >> sh) & 15) > deck;   // unseen_r < 0
+    const bool bad = __ballot(lane < 15 && over) != 0ull;
+    const uint64_t unseen = DECK_NIB - hc0 - taken;   // (no borrow between nibbles where !bad; not used otherwise)
+    if (bad || n_next < 1 || n_prev < 1 || nib_sum(unseen) != n_next + n_prev) {
+      if (lane == 0 && chunk == 0) atomicOr(a.status, 64);
+      return;   // outside the domain: nothing runs, wins stay as they are
+    }
+    const int rank = lane < 52 ? lane >> 2 : lane - 39;   // card -> rank: 52 = BJ (13), 53 = CJ (14)
+    const int cnt = (int)((unseen >> (4 * (rank & 15))) & 15);
+    pool = lane < 52 ? (lane & 3) < cnt : (lane < 54 && cnt == 1);
+    if (a.worlds) {   // ddz_playout_worlds: row 0 = the next player's counts and size, row 1 = the previous player's
+      for (uint32_t k = chunk; k < a.K; k += a.chunks) {
+        redeal_wave(gid, k, a.k0, a.k1, lane, pool, n_next, stage, wn, wp);
+        const uint64_t h = lane < 16 ? wn : wp;
+        const int b = lane & 15;
+        const uint32_t v = b < 15 ? (uint32_t)((h >> (4 * b)) & 15) : (uint32_t)(lane < 16 ? n_next : n_prev);
+        if (lane < 32) a.worlds[(((int64_t)t * a.K + k) << 5) + lane] = (uint8_t)v;
+      }
+      return;
+    }
+  }
   int32_t* const wins = a.wins + t * a.stride;
   uint64_t total = 0;          // n * K, known behind the probe
   uint64_t w = chunk;          // the next playout of this item
@@ -89,6 +163,15 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
     }
     // a private copy of the root
     uint64_t hc = hc0, hn = hn0, hp = hp0;
+    if constexpr (HIDDEN) {
+      if (!probe) {   // (the probe sizes the root's list: the actor's hand alone)
+        if (k != world_k) {   // (an item whose chunks divide by K stays with one world)
+          redeal_wave(gid, k, a.k0, a.k1, lane, pool, n_next, stage, wn, wp);
+          world_k = k;
+        }
+        hn = wn; hp = wp;
+      }
+    }
     uint32_t trick = trick0, ply = ply0;
     int passes = passes0, role = role0;
     uint32_t draws = 0, dnext = 64;  // lane l holds the draw of the ply l behind the last refill; 64 = refill

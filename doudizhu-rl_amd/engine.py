@@ -559,8 +559,8 @@ class BatchedEnv:
                                           _stream(self.device)))
         self._legal_fresh = self._slab_fresh = self._csr_fresh = False
 
-    # ---- playout evaluation (flat Monte Carlo over perfect information) ----
-    def playout(self, n_playouts, salt=0, chunks=None, wins=None, totals=None):
+    # ---- playout evaluation (flat Monte Carlo: over perfect information, or over sampled hidden hands) ----
+    def playout(self, n_playouts, salt=0, chunks=None, wins=None, totals=None, hidden=False, roles=0b111):
         """Win counts of uniformly random playouts for EVERY legal move of every running table (playout spec v1, DESIGN.md 4;
         the reference's Monte-Carlo player, server/mcts/interface.py:15-45, as flat Monte Carlo): wins int32 [T, stride], entry
         [t, j] = how many of the n_playouts playouts that start with move j of table t's slab list (legal_slab() order) ended
@@ -568,7 +568,17 @@ class BatchedEnv:
         on the current stream, nothing on the host: capturable.
         salt: a different salt gives different draws for the same state; chunks: wavefronts per table (default: enough to
         fill the device when there are few tables; the result does not depend on it); wins: an int32 [T * stride] buffer to
-        reuse (zeroed here); totals: int64 [4] on the device, += {moves applied, playouts run, playouts stopped unfinished, -}."""
+        reuse (zeroed here); totals: int64 [4] on the device, += {moves applied, playouts run, playouts stopped unfinished, -}.
+        hidden=True (playout spec v2): the opponents' hands are not read but dealt anew for every playout number from the
+        cards the actor has not seen (deck - own hand - taken) with their known sizes, every move of a table on the same
+        n_playouts worlds -- the evaluation a seat may use, and the one a state from a plain serving payload allows.  A table
+        whose hand, taken row and sizes do not add up to a deck runs nothing and raises status bit 6.  roles (hidden form
+        only): bit r set = tables whose actor is role r take part, the others are idle."""
+        roles = int(roles)
+        if not 0 <= roles <= 7:
+            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        if not hidden and roles != 0b111:
+            raise ValueError("roles needs hidden=True (the open form evaluates every running table)")
         st = self.slab_stride
         if st < MAX_LEGAL_PER_TABLE:
             raise ValueError(f"playouts need row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
@@ -592,17 +602,41 @@ class BatchedEnv:
                                    or not totals.is_contiguous()):
             raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
         wins.zero_()                    # (an enqueued memset of the whole buffer)
-        check(self.lib.ddz_playout(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, _p(wins), _p(totals),
-                                   _stream(self.device)))
+        if hidden:
+            check(self.lib.ddz_playout_hidden(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, roles, _p(wins),
+                                              _p(totals), _stream(self.device)))
+        else:
+            check(self.lib.ddz_playout(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, _p(wins), _p(totals),
+                                       _stream(self.device)))
         return wins.view(self.T, st)
 
-    def playout_choose(self, n_playouts, salt=0, out=None, chunks=None):
+    def playout_worlds(self, n_worlds, salt=0, roles=0b111, out=None):
+        """The worlds playout(hidden=True) plays on, alone (ddz_playout_worlds): uint8 [T, n_worlds, 2, 16], [t, k, 0] = the
+        15 counts and the size of the NEXT player's hand in world k of table t, [t, k, 1] = the PREVIOUS player's -- a
+        uniform deal of the cards the actor has not seen, with the known hand sizes.  A sampler for any search built on
+        top.  Rows of idle tables, of tables `roles` leaves out and of tables outside the domain (status bit 6) are zero
+        (left as they are in a buffer handed in as `out`).  The env is only read; one launch, capturable."""
+        n_worlds, roles = int(n_worlds), int(roles)
+        if not 1 <= n_worlds < (1 << 23) or self.T * n_worlds > 0x7FFFFFFF:
+            raise ValueError("n_worlds must be in [1, 2^23) and T * n_worlds below 2^31")
+        if not 0 <= roles <= 7:
+            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        if out is None:
+            out = torch.zeros((self.T, n_worlds, 2, ROW), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or out.numel() != self.T * n_worlds * 2 * ROW or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 [T, n_worlds, 2, 16] tensor on the env's device")
+        check(self.lib.ddz_playout_worlds(self._h, n_worlds, int(salt) & 0xFFFFFFFF, roles, _p(out), _stream(self.device)))
+        return out.view(self.T, n_worlds, 2, ROW)
+
+    def playout_choose(self, n_playouts, salt=0, out=None, chunks=None, hidden=False, roles=0b111):
         """The flat Monte-Carlo move of every table: int32 [T] canonical action ids, the FIRST maximum of playout()'s win
         counts over each table's list (ties to the lowest index), -1 for idle tables.  Feed them to
-        step_slab(mode=STEP_IDS)."""
+        step_slab(mode=STEP_IDS).  hidden / roles: as playout() -- a table that the hidden form leaves out (its actor not in
+        `roles`, or outside the domain) has all-zero counts and so gets the first move of its list: mask the ids by role."""
         if self.ids is None:
             raise ValueError("playout_choose needs the action ids of the lists (want_ids=True)")
-        self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None))
+        self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None),
+                                          hidden=hidden, roles=roles)
         if out is None:
             out = torch.empty(self.T, dtype=torch.int32, device=self.device)
         elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():

@@ -126,6 +126,17 @@ def full_payloads_to_state(payloads):
     return st
 
 
+def payloads_to_playout_state(payloads):
+    """payloads_to_state plus the category byte of every recent_handout row (combo_category): the rows that hidden-hand
+    playouts read (BatchedEnv.playout(hidden=True): own hand, taken, recent rows WITH category, the others' hand sizes) from
+    the plain serving payload -- no hand_card."""
+    st = payloads_to_state(payloads)
+    for i in range(len(st)):
+        for r in range(3):
+            st[i, F_RECENT0 + r, 15] = combo_category(st[i, F_RECENT0 + r])
+    return st
+
+
 def state_to_full_payloads(state):
     """state_to_payloads plus hand_card {0, 1, 2}: the payload of the reference's Monte-Carlo player for every table."""
     if isinstance(state, BatchedEnv):
@@ -140,18 +151,23 @@ def state_to_full_payloads(state):
     return out
 
 
-def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0):
+def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=False):
     """The reference's mcts(payload) (server/mcts/interface.py:15-45) as flat Monte Carlo, for a batch of requests: every
     legal move of every request is followed by n_playouts uniformly random playouts over the three known hands
     (BatchedEnv.playout_choose) and the move with the most wins for the requester's side is returned -- per request a list
-    of rank values 3..17 ([] = pass), or None where the request has no move (a finished game)."""
+    of rank values 3..17 ([] = pass), or None where the request has no move (a finished game).
+    hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and the playouts
+    run on hands dealt from the cards the requester has not seen (playout spec v2)."""
     n = len(payloads)
     if n == 0:
         return []
     dev = torch.device(device)
     env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
-    env.state_import(torch.from_numpy(full_payloads_to_state(payloads)).view(-1))
-    ids = env.playout_choose(n_playouts, salt=salt).cpu().numpy()
+    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
+    env.state_import(torch.from_numpy(st).view(-1))
+    ids = env.playout_choose(n_playouts, salt=salt, hidden=hidden).cpu().numpy()
+    if hidden and env.status() & 64:
+        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
     table = action_table(dev).cpu().numpy()
     ranks = np.arange(3, 18)
     return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]

@@ -296,6 +296,31 @@ int ddz_playout(ddz_env_t* env, int64_t n_playouts, uint64_t salt, int64_t chunk
 int ddz_playout_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* wins,
                        int32_t* choice, void* stream);
 
+/* Playouts over HIDDEN hands ("playout spec v2"): what ddz_playout computes, but with the two opponents' hands
+ * sampled per playout number from the cards the actor has not seen -- their 15 count bytes are NEVER read, so a state built
+ * from the plain serving payload (own hand, histories, hand sizes) is evaluated as the live table it describes.  Read of a
+ * running table with actor `role`: the actor's hand row, the taken row, the recent rows with their category bytes, the meta
+ * row, and byte 15 (cards left) of the other two hand rows.
+ *   unseen_r = deck_r - hand[role]_r - taken_r (deck_r = 4 for the ranks 0..12, 1 for each joker); card c of Deal v2's
+ *     numbering (rank c / 4 for c < 52, 52 = BJ, 53 = CJ) is in the pool iff (c & 3) < unseen_{c/4}, resp. unseen_13 / unseen_14
+ *     = 1; n_next = left[(role + 1) % 3], n_prev = left[(role + 2) % 3].
+ *   Domain: 0 <= unseen_r <= deck_r for every rank, n_next >= 1, n_prev >= 1, sum unseen = n_next + n_prev.  A running table
+ *     outside it runs nothing, its wins and the totals stay as they are, and status bit 6 is raised.
+ *   World k: pool card c draws key_c = philox4x32_10((gid_lo, gid_hi, k, 5 << 16 | c >> 2), (seed_lo ^ salt_lo, seed_hi))[c & 3]
+ *     (RNG domain 5; domains 1..4 are unchanged); the pool is ranked by (key, c); the n_next lowest cards are the next
+ *     player's hand, the others the previous player's.  A world depends on (gid, k, seed, salt) only: every root move of a
+ *     table is played on the same n_playouts worlds (common random numbers); vary salt for fresh worlds per decision.
+ *   Playout (j, k) is ddz_playout's, word for word, from the root with the opponents' hands replaced by world k: the draws
+ *     of domain 4, the root move, the score, DDZ_PLAYOUT_MAX_PLIES, totals, idle tables and the independence from `chunks`.
+ *   roles: bit r set = tables whose actor is role r take part, the others are idle (7 = every table).
+ * ddz_playout_worlds: the worlds alone.  out uint8 [T][n_worlds][2][16]: [t][k][0] = the 15 counts and the size (byte 15) of
+ * the next player's hand in world k of table t, [t][k][1] = the previous player's.  Idle tables, tables `roles` leaves out and
+ * tables outside the domain (status bit 6) are left as they are.  1 <= n_worlds < 2^23, T * n_worlds <= 2^31 - 1.
+ * Both: the env is only read; one launch on `stream`, nothing on the host (capturable). */
+int ddz_playout_hidden(ddz_env_t* env, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int roles,
+                       int32_t* wins, int64_t* totals, void* stream);
+int ddz_playout_worlds(ddz_env_t* env, int64_t n_worlds, uint64_t salt, int roles, uint8_t* out, void* stream);
+
 /* The same random-policy loop with the lists in the CSR layout of ddz_legal (offsets/rows/ids
  * packed across tables).  CSR bases need a scan over all tables, so this variant is one
  * launch per iteration: the fused kernel writes the list of the current state, steps, and
@@ -651,7 +676,9 @@ int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
  * hang guard (never in a working launch; the ids of that launch are not to be trusted), bit4 the sequential
  * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a move of ddz_q_slab_needed (or of a network table of
  * ddz_q_roles_slab) whose (rank, count)
- * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing).
+ * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing), bit6 a running
+ * table of ddz_playout_hidden / ddz_playout_worlds outside the hidden-hand domain (its hand, taken row and hand sizes do not
+ * add up to a deck): that table ran nothing.
  * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
 /* the same word for the STATELESS rule-agent entry point (ddz_auto_choose has no handle): one per device, bits as above
