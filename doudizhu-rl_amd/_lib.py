@@ -60,6 +60,10 @@ SYMBOLS = {
     "ddz_playout_hidden": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "ddz_playout_worlds": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "ddz_search_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "ddz_search": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_search_choose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ddz_rollout_random_csr": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_rollout_csr_staging_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),

@@ -8,6 +8,8 @@
 //             (see the comment at the kernel).
 //   k_playout (ddz_playout.h; ddz_playout) win counts of random playouts for every legal move of every table: one wavefront per
 //             (table, chunk), the root in registers, every ply from k_rollout's device functions, no list stored.
+//   k_search  (ddz_search.h; ddz_search) UCT tree search around those playouts: one wavefront per (table, tree), the tree in a
+//             caller-provided workspace, the descent re-applies stored moves, the playout is k_playout's ply.
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
 //             or slab lists with F_SLAB = apply + enumerate in the same launch):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
@@ -1401,6 +1403,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 }
 
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move, from k_rollout's device functions
+#include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 
 // write-once output streams (`face`, thermometer planes): nontemporal 16-byte stores.  Measured on k_observe
 // at 524,288 tables (0.6-1.2 GB per call): 3.1 TB/s with plain stores, 5.3-5.7 TB/s with these.
@@ -2777,6 +2780,13 @@ int build_table_locked(int device) {
     }
     free(recs); free(tab); free(nibs); free(ids);
   }
+  if (rc == DDZ_OK) {  // search spec v1: LN[N] = (float)log((double)N) from the host's libm (LN[0] is never read)
+    static float ln[DDZ_SEARCH_MAX_BUDGET + 1];
+    ln[0] = 0.0f;
+    for (int i = 1; i <= DDZ_SEARCH_MAX_BUDGET; ++i) ln[i] = (float)log((double)i);
+    r = hipMemcpyToSymbol(HIP_SYMBOL(g_search_ln), ln, sizeof(ln));
+    if (r != hipSuccess) rc = hip_fail(r);
+  }
   return rc;
 }
 
@@ -3507,6 +3517,57 @@ int ddz_playout_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, 
   const int64_t per = BLOCK / 64;
   hipLaunchKernelGGL(k_playout_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
                      stride, wins, choice, e->T);
+  return check_launch();
+}
+
+// ddz_search: one launch of k_search<hidden>, one wavefront per (table, tree); the tree lives in the caller's workspace
+int64_t ddz_search_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
+  if (n_tables < 0 || budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return -1;
+  return (int64_t)search_tree_bytes(budget) * n_tables * trees;
+}
+
+int ddz_search(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles, int64_t stride,
+               int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!visits || !wins || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
+  if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536 || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (mode != DDZ_SEARCH_REFERENCE && mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
+  if (!(c >= 0.0f) || !(c <= 3.0e38f)) return DDZ_EINVAL;   // (finite and not negative: values order as their bit patterns)
+  if (roles < 0 || roles > 7 || (!hidden && roles != 7)) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  if (work_bytes < ddz_search_work_bytes(e->T, budget, trees)) return DDZ_ECAP;
+  const int64_t blocks = (e->T * trees + SEARCH_WAVES - 1) / SEARCH_WAVES;
+  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  SearchArgs a;
+  a.state = e->state; a.T = e->T;
+  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  a.budget = (uint32_t)budget; a.trees = (uint32_t)trees; a.mode = (uint32_t)mode; a.c = c;
+  a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  a.roles = (uint32_t)roles; a.work = (uint8_t*)work; a.tree_bytes = search_tree_bytes(budget); a.hash_log = search_hash_log(budget);
+  void* ln = nullptr;
+  const hipError_t r = hipGetSymbolAddress(&ln, HIP_SYMBOL(g_search_ln));
+  if (r != hipSuccess) return hip_fail(r);
+  a.ln = (const float*)ln;
+  if (blocks == 0) return DDZ_OK;
+  if (hidden) hipLaunchKernelGGL(k_search<true>, dim3((unsigned)blocks), dim3(SEARCH_WAVES * 64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_search<false>, dim3((unsigned)blocks), dim3(SEARCH_WAVES * 64), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,
+                      const int32_t* wins, int32_t* choice, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!counts || !ids || !visits || !wins || !choice) return DDZ_EINVAL;
+  if (!al(counts, 4) || !al(ids, 4) || !al(visits, 4) || !al(wins, 4) || !al(choice, 4)) return DDZ_EINVAL;
+  if (stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const int64_t per = BLOCK / 64;
+  hipLaunchKernelGGL(k_search_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
+                     stride, visits, wins, choice, e->T);
   return check_launch();
 }
 

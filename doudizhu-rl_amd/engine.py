@@ -645,6 +645,88 @@ class BatchedEnv:
                                           _p(self._playout_wins), _p(out), _stream(self.device)))
         return out
 
+    # ---- UCT tree search around the playouts (search spec v1) ----
+    SEARCH_MODES = {"reference": 0, "sides": 1}
+    SEARCH_MAX_BUDGET = 4096
+
+    def search(self, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111, visits=None, wins=None,
+               totals=None):
+        """UCT tree search on every running table (search spec v1; the reference's MCTS player,
+        server/mcts/interface.py:37-43 with get_bestchild.py and tree.py:33-51): `trees` independent trees of `budget`
+        iterations each per table, their root statistics summed.  -> (visits, wins), int32 [T, stride] each: entry [t, j] =
+        the visits of root move j of table t's slab list (legal_slab() order) and how many of them ended with a winner on the
+        actor's side.  The env is only read.  Two memsets + one launch on the current stream: capturable.
+        trees (default: enough to fill the device when there are few tables, at most 64); mode: "reference" follows
+        get_bestchild.py literally (the maximum at the root actor's own nodes, the minimum at every other node), "sides"
+        takes the maximum of the mover's side's win ratio at every node; c: the exploration constant (0.7 in the reference);
+        salt: different draws for the same state; hidden=True: tree c plays on world c of playout(hidden=True) -- `trees`
+        determinizations of the opponents' hands, the opponents' count bytes never read; roles (hidden only): bit r set =
+        tables whose actor is role r take part.  visits / wins: int32 [T * stride] buffers to reuse (zeroed here); totals:
+        int64 [4] on the device, += {moves applied, iterations run, iterations scored unfinished, nodes created}.  The
+        trees live in a workspace of ddz_search_work_bytes(T, budget, trees) bytes cached on the env."""
+        roles = int(roles)
+        if not 0 <= roles <= 7:
+            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        if not hidden and roles != 0b111:
+            raise ValueError("roles needs hidden=True (the open form searches every running table)")
+        if mode not in self.SEARCH_MODES:
+            raise ValueError('mode is "reference" or "sides"')
+        st = self.slab_stride
+        if st < MAX_LEGAL_PER_TABLE:
+            raise ValueError(f"search needs row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        budget = int(budget)
+        if not 1 <= budget <= self.SEARCH_MAX_BUDGET:
+            raise ValueError(f"budget must be in [1, {self.SEARCH_MAX_BUDGET}]")
+        c = float(c)
+        if not 0.0 <= c < 3.0e38:
+            raise ValueError("c must be finite and not negative")
+        if trees is None:       # one wavefront per (table, tree): the device holds 256 x 24 of them
+            trees = max(1, min(64, 6144 // self.T))
+        trees = int(trees)
+        if not 1 <= trees <= 65536:
+            raise ValueError("trees must be in [1, 65536]")
+        if not self._slab_fresh:        # entry [t, j] is read against the lists of the current state
+            self.legal_slab()
+        bufs = []
+        for name, b in (("visits", visits), ("wins", wins)):
+            if b is None:
+                b = torch.empty(self.T * st, dtype=torch.int32, device=self.device)
+            elif b.dtype != torch.int32 or b.device != self.device or b.numel() != self.T * st or not b.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 [T * stride] tensor on the env's device")
+            bufs.append(b)
+        visits, wins = bufs
+        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
+                                   or not totals.is_contiguous()):
+            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
+        need = int(self.lib.ddz_search_work_bytes(self.T, budget, trees))
+        if need < 0:
+            raise ValueError("no workspace size for these arguments")
+        work = getattr(self, "_search_work", None)
+        if work is None or work.numel() < need:
+            self._search_work = work = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        visits.zero_()
+        wins.zero_()
+        check(self.lib.ddz_search(self._h, budget, trees, self.SEARCH_MODES[mode], c, int(salt) & 0xFFFFFFFF, int(bool(hidden)),
+                                  roles, st, _p(visits), _p(wins), _p(totals), _p(work), work.numel(), _stream(self.device)))
+        return visits.view(self.T, st), wins.view(self.T, st)
+
+    def search_choose(self, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111, out=None):
+        """The UCT move of every table: int32 [T] canonical action ids, the first maximum of wins / visits over the visited
+        root moves of search() (get_bestchild_: the win ratio alone; ties to the lowest index), -1 where nothing was visited
+        (idle tables, tables the hidden form leaves out).  Feed them to step_slab(mode=STEP_IDS)."""
+        if self.ids is None:
+            raise ValueError("search_choose needs the action ids of the lists (want_ids=True)")
+        v, w = self.search(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles,
+                           visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
+        self._search_visits, self._search_wins = v.view(-1), w.view(-1)
+        if out is None:
+            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
+        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
+                                         _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
+        return out
+
     def rollout_random_csr(self, n_iters, traj=None, batch=None):
         """The same loop with packed CSR lists (offsets/rows/ids as legal() returns them: afterwards they hold the lists
         of the last iteration's pre-step states).  Same states and trajectories as rollout_random.

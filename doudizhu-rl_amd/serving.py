@@ -173,6 +173,28 @@ def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=Fa
     return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
 
 
+def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, trees=None, mode="reference", c=0.7):
+    """The reference's mcts(payload) (server/mcts/interface.py:15-45) itself, for a batch of requests: a UCT tree search of
+    `budget` iterations per tree from every request's state (BatchedEnv.search_choose; the reference runs 1000) and the root
+    move with the best win ratio for the requester's side is returned -- per request a list of rank values 3..17 ([] =
+    pass), or None where the request has no move (a finished game).
+    hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and tree c
+    searches world c of the hands dealt from the cards the requester has not seen (`trees` determinizations)."""
+    n = len(payloads)
+    if n == 0:
+        return []
+    dev = torch.device(device)
+    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
+    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
+    env.state_import(torch.from_numpy(st).view(-1))
+    ids = env.search_choose(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden).cpu().numpy()
+    if hidden and env.status() & 64:
+        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
+    table = action_table(dev).cpu().numpy()
+    ranks = np.arange(3, 18)
+    return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+
+
 class BatchedPredictorInputs:
     """face / valid_actions of server/core.py's Predictor for a batch of payloads."""
 

@@ -5,6 +5,7 @@ player of server/mcts/interface.py:15-45 without its tree) against random farmer
 them.  Prints both win rates from env.stats().
 
   python examples/flat_mc.py [--tables 1024] [--playouts 16] [--iterations 400] [--seed 0] [--hidden] [--match]
+  python examples/flat_mc.py --search BUDGET [--trees 1] [--mode reference] [--tables 256] [--iterations 200]
 
 --hidden: the playouts do not read the farmers' hands; they run on hands dealt anew, per playout number, from the cards the
 lord has not seen (playout spec v2, BatchedEnv.playout_choose(hidden=True, roles=0b010): only the lord's tables are
@@ -12,6 +13,11 @@ evaluated).  This is the evaluation a seat may use: the open form looks at the o
 --match: the hidden-playout lord against the RULE farmers (env.auto_choose(0b101)) instead of random ones: the two id vectors
 are merged with torch.where and stepped with step_slab(STEP_IDS); the win counts come from env.stats().  The win rate this
 prints has not been measured anywhere in this repository's notes: quote it only with that said.
+
+--search BUDGET: a UCT lord (BatchedEnv.search_choose: --trees trees of BUDGET iterations, search spec v1) against flat
+Monte-Carlo farmers at an EQUAL number of playouts per decision -- the farmers' playouts per move are BUDGET * trees divided by
+the mean size of their lists on that iteration -- and, as the yardstick, the same match with a flat Monte-Carlo lord given the
+same number.  Both seats see all three hands.  Printed as the lord's win rate in both matches.
 
 The playouts are computed for every table on every iteration and used where the lord is to move (the other tables take -1 =
 the engine's random move): simple, and three times the work a loop that asks only for the lord's tables would do.
@@ -32,6 +38,28 @@ def rates(s):
     return f"{s['episodes']} episodes: lord {s['lord_wins'] / e:.1%}, farmers {(s['up_wins'] + s['down_wins']) / e:.1%}"
 
 
+def seat_match(pkg, a, dev, uct):
+    """the lord by UCT (uct=True) or by flat Monte Carlo, the farmers by flat Monte Carlo, at budget * trees playouts a move"""
+    env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
+    env.reset()
+    lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    farm = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    per_move = a.search * a.trees
+    for it in range(a.iterations):
+        counts = env.legal_slab()[0]
+        is_lord = env.role == 1
+        n_farm = counts[~is_lord].float().mean().item() if (~is_lord).any().item() else 1.0
+        n_lord = counts[is_lord].float().mean().item() if is_lord.any().item() else 1.0
+        if uct:
+            env.search_choose(a.search, trees=a.trees, mode=a.mode, salt=it, out=lord)
+        else:
+            env.playout_choose(max(1, round(per_move / max(n_lord, 1.0))), salt=it, out=lord)
+        env.playout_choose(max(1, round(per_move / max(n_farm, 1.0))), salt=it + (1 << 20), out=farm)
+        env.step_slab(torch.where(is_lord, lord, farm), pkg.STEP_IDS, auto_reset=True)
+    assert env.status() == 0
+    return env.stats()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", type=int, default=1024)
@@ -40,9 +68,22 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--hidden", action="store_true", help="sample the farmers' hands per playout instead of reading them")
     ap.add_argument("--match", action="store_true", help="a hidden-playout lord against the rule farmers")
+    ap.add_argument("--search", type=int, default=0, metavar="BUDGET", help="a UCT lord against flat Monte-Carlo farmers")
+    ap.add_argument("--trees", type=int, default=1, help="--search: trees per table")
+    ap.add_argument("--mode", default="reference", choices=("reference", "sides"), help="--search: the selection rule")
     a = ap.parse_args()
     pkg = importlib.import_module("doudizhu-rl_amd")
     dev = torch.device("cuda:0")
+    if a.search:
+        t0 = time.perf_counter()
+        uct = seat_match(pkg, a, dev, True)
+        dt = time.perf_counter() - t0
+        flat = seat_match(pkg, a, dev, False)
+        print(f"UCT lord ({a.trees} x {a.search} iterations, mode {a.mode}) vs flat Monte-Carlo farmers at "
+              f"{a.search * a.trees} playouts per move: {rates(uct)}  [{dt / a.iterations * 1e3:.2f} ms per iteration at "
+              f"{a.tables} tables]")
+        print(f"flat Monte-Carlo lord vs the same farmers, {a.search * a.trees} playouts per move: {rates(flat)}")
+        return
     env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
     env.reset()
     env.legal_slab()

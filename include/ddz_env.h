@@ -321,6 +321,63 @@ int ddz_playout_hidden(ddz_env_t* env, int64_t n_playouts, uint64_t salt, int64_
                        int32_t* wins, int64_t* totals, void* stream);
 int ddz_playout_worlds(ddz_env_t* env, int64_t n_worlds, uint64_t salt, int roles, uint8_t* out, void* stream);
 
+/* UCT tree search around the playouts: the reference's MCTS player (server/mcts/interface.py:37-43: tree_policy ->
+ * default_policy -> backup, 1000 times; get_bestchild.py; tree.py:33-51), batched.  "Search spec v1 (UCT)" (DESIGN.md 4), for
+ * every running table t (dealt, not done) and every tree c < trees; the trees of a table are independent (root parallelism)
+ * and their root statistics are summed.
+ *   Node: a state reached from the root by a path of moves.  It carries its actor, n = the size of its legal list in slab
+ *     (ascending canonical id) order, the children created so far (each belongs to one list index), visits V and reward W
+ *     (u32), and whether the move that led to it emptied a hand (terminal, winner = the mover).  Node 0 is the table's state;
+ *     a root with an empty list runs nothing (visits, wins and totals stay as they are).
+ *   Iteration i < budget (1 <= budget <= DDZ_SEARCH_MAX_BUDGET; the reference uses 1000): start at the root; while the node is
+ *     not terminal and has n > 0: if fewer than n children exist, EXPAND the node and stop descending, otherwise go to the
+ *     SELECTED child.  A non-terminal node with n = 0 (an imported state outside the domain) ends the iteration with reward 0,
+ *     counted as unfinished; so does a non-terminal node DDZ_SEARCH_MAX_DEPTH moves below the root (beyond the 162 plies of the
+ *     longest game: no state of the domain reaches it).
+ *   Selection at a fully expanded node with visits N: child j with (V_j, W_j) has, in fp32 from correctly rounded single
+ *     operations with nothing fused, mean = W_j / V_j, bonus = c * sqrt((2 * LN[N]) / V_j), value = mean + bonus, where
+ *     LN[N] = (float)log((double)N) is a table of DDZ_SEARCH_MAX_BUDGET + 1 floats that the library fills from the host's libm
+ *     once per device (ddz_search copies nothing from the host).  c >= 0 (0.7 in get_bestchild.py:4).
+ *     mode DDZ_SEARCH_REFERENCE (get_bestchild.py:20-32, literally): the maximum of value at a node whose actor is the ROOT's
+ *     actor, the minimum of value at every other node -- the partner farmer's included.
+ *     mode DDZ_SEARCH_SIDES: the maximum of value at a node whose actor is on the root actor's side (the lord alone, or either
+ *     farmer), otherwise the maximum of (V_j - W_j) / V_j + bonus.
+ *     Ties go to the LOWEST list index (the reference draws among ties: a departure, as ddz_playout_choose's).
+ *   Expansion: with u = the untried list indices, the ((draw_e * u) >> 32)-th of them in ascending order,
+ *     draw_e = philox4x32_10((gid_lo, gid_hi, c << 16 | i, 6 << 16), key).x, key = (seed_lo ^ salt_lo, seed_hi), gid =
+ *     table_id_base + t (RNG domain 6; domains 1..5 are unchanged).  The lead list has no pass, so tree.py:43's rejection loop
+ *     has nothing to reject.  The child's n is the size of its state's list.
+ *   Playout from the new child: playout spec v1's rule, index (draw * A) >> 32 of the state's list, draw =
+ *     philox4x32_10((gid_lo, gid_hi, c << 16 | i, 7 << 16 | ply), key).x (domain 7), ply = the u16 ply counter of the state
+ *     being stepped; at most DDZ_PLAYOUT_MAX_PLIES moves are applied from the child, a playout that stops unfinished scores 0.
+ *     A terminal child, or a terminal node reached by selection, scores without a playout.  Score: 1 if the winner is on the
+ *     ROOT actor's side (tree.py:71-81), else 0.
+ *   Backup: V += 1 and W += score on every node of the path, the root included.
+ *   visits / wins int32 [T * stride], stride >= DDZ_SLAB_MIN_STRIDE: [t * stride + j] += the V / W of root child j, summed
+ *     over the table's trees (32-bit integer atomics: the result does not depend on scheduling).  The caller zeroes them.
+ *   totals (device int64[4], may be NULL) += {moves applied (descent and playout), iterations run, iterations scored
+ *     unfinished, nodes created}.
+ *   hidden != 0: tree c plays on world k = c of playout spec v2 (the same deal of domain 5, the same domain check with status
+ *     bit 6, the same `roles` mask; the opponents' count bytes are never read): trees = the number of determinizations.
+ *     roles must be 7 in the open form.
+ *   work: caller-owned device scratch of >= ddz_search_work_bytes(T, budget, trees) bytes, 16-byte aligned; a smaller buffer
+ *     is DDZ_ECAP from the host.  Per tree it holds budget + 1 node records and an open-addressing table of the power of two
+ *     >= 2 * (budget + 1) entries keyed by (parent, list index): a function of the budget alone in every position, no overflow
+ *     mode.  Nothing in it has to be initialised and nothing in it is an output.  1 <= trees <= 65536.
+ * The env is only read.  One launch on `stream`, nothing on the host (capturable).
+ * ddz_search_choose: choice[t] = ids[t * stride + the first maximum of wins / visits over the entries j < counts[t] with
+ * visits > 0], compared exactly as w_a * v_b > w_b * v_a in 64-bit integers (get_bestchild_: the win ratio alone), ties to
+ * the lowest index; -1 where nothing was visited.  Feed it to ddz_step_slab(DDZ_STEP_IDS). */
+#define DDZ_SEARCH_MAX_BUDGET 4096
+#define DDZ_SEARCH_MAX_DEPTH 192
+#define DDZ_SEARCH_REFERENCE 0
+#define DDZ_SEARCH_SIDES 1
+int64_t ddz_search_work_bytes(int64_t n_tables, int64_t budget, int64_t trees);
+int ddz_search(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+               int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream);
+int ddz_search_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,
+                      const int32_t* wins, int32_t* choice, void* stream);
+
 /* The same random-policy loop with the lists in the CSR layout of ddz_legal (offsets/rows/ids
  * packed across tables).  CSR bases need a scan over all tables, so this variant is one
  * launch per iteration: the fused kernel writes the list of the current state, steps, and
