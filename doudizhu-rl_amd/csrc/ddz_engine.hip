@@ -1404,6 +1404,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move, from k_rollout's device functions
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
+#include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
 
 // write-once output streams (`face`, thermometer planes): nontemporal 16-byte stores.  Measured on k_observe
 // at 524,288 tables (0.6-1.2 GB per call): 3.1 TB/s with plain stores, 5.3-5.7 TB/s with these.
@@ -3568,6 +3569,50 @@ int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, i
   const int64_t per = BLOCK / 64;
   hipLaunchKernelGGL(k_search_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
                      stride, visits, wins, choice, e->T);
+  return check_launch();
+}
+
+// ddz_cfr: k_cfr_head zeroes the workspace's head (the slot counter), then one launch of k_cfr, one wavefront per table
+int64_t ddz_cfr_work_bytes(int64_t slots) {
+  if (slots < 0 || slots > (1ll << 24)) return -1;
+  return (int64_t)CFR_HEAD_BYTES + slots * (int64_t)CFR_SLOT_BYTES;
+}
+
+int ddz_cfr(ddz_env_t* e, int iterations, int roles, int64_t slots, void* work, int64_t work_bytes, int32_t* n, int32_t* ids,
+            double* sigma, double* value, int64_t* totals, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!work || !n || !ids || !sigma || !value) return DDZ_EINVAL;
+  if (!al(work, 16) || !al(n, 4) || !al(ids, 4) || !al(sigma, 8) || !al(value, 8) || !al(totals, 8)) return DDZ_EINVAL;
+  if (iterations < 0 || iterations > DDZ_CFR_MAX_ITERATIONS || roles < 0 || roles > 7) return DDZ_EINVAL;
+  const int64_t need = ddz_cfr_work_bytes(slots);
+  if (need < 0) return DDZ_EINVAL;
+  if (work_bytes < need) return DDZ_ECAP;
+  const int64_t blocks = (e->T + CFR_WAVES - 1) / CFR_WAVES;
+  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  if (blocks == 0) return DDZ_OK;
+  // the head is zeroed by a one-wave launch, not by hipMemsetAsync: the captured memset node held the right pointer, value 0
+  // and width 256 and its first launch zeroed, but every later launch of the instantiated graph filled the head with a stale
+  // 16-byte pattern (profiles/r14_notes.md 5), and every table found no slot
+  hipLaunchKernelGGL(k_cfr_head, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)work);
+  CfrArgs a;
+  a.state = e->state; a.T = e->T; a.iterations = (uint32_t)iterations; a.roles = (uint32_t)roles; a.slots = slots;
+  a.work = (uint8_t*)work; a.n = n; a.ids = ids; a.sigma = sigma; a.value = value; a.totals = (unsigned long long*)totals;
+  a.status = e->sc.status;
+  hipLaunchKernelGGL(k_cfr, dim3((unsigned)blocks), dim3(CFR_WAVES * 64), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int ddz_cfr_choose(ddz_env_t* e, const int32_t* n, const int32_t* ids, const double* sigma, uint64_t salt, int greedy,
+                   int32_t* choice, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!n || !ids || !sigma || !choice || !al(n, 4) || !al(ids, 4) || !al(sigma, 8) || !al(choice, 4)) return DDZ_EINVAL;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  if (e->T == 0) return DDZ_OK;
+  hipLaunchKernelGGL(k_cfr_choose, dim3((unsigned)((e->T + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, n, ids, sigma,
+                     (uint32_t)e->seed ^ (uint32_t)salt, (uint32_t)(e->seed >> 32), e->gid_base, greedy, choice, e->T);
   return check_launch();
 }
 

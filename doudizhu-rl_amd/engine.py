@@ -727,6 +727,76 @@ class BatchedEnv:
                                          _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
         return out
 
+    # ---- the CFR endgame solver (CFR spec v1) ----
+    CFR_STRIDE = 16
+    CFR_MAX_ITERATIONS = 64
+
+    def cfr_default_slots(self):
+        """slots of cfr() where none are asked for: endgames are a small share of live tables, so T / 16, at least 64, never
+        more than T -- 108 MiB of workspace up to 1,024 tables, 6.75 GiB at 65,536"""
+        return min(self.T, max(64, self.T // 16))
+
+    def cfr(self, iterations=8, roles=0b111, slots=None, totals=None, out=None):
+        """The reference's final_card (server/CFR.py: 8 iterations of vanilla CFR over every deal of the unseen cards) for
+        every table that is an endgame: running, its actor in `roles`, at most 6 cards in the three hands together (CFR spec
+        v1).  -> (n, ids, sigma, value): n int32 [T] = the size of the actor's legal list (0 idle, -1 not an
+        endgame -- more than 6 cards, no status bit -- or rows that do not add up, status bit 6; -2 no workspace slot or over
+        a capacity, status bit 7); ids int32 [T, 16] the list's canonical ids (-1 padded); sigma float64 [T, 16] the
+        strategy at (actor, its hand, no action); value float64 [T] the last iteration's value of the game for the lord.
+        Only the actor's hand, the taken and recent rows and the others' hand SIZES are read: a state from a plain serving
+        payload is solved as the live table it describes.  Bit-identical from run to run.  The env is only read; two launches
+        (the workspace head's zeroing, the solver) on the current stream: capturable.
+        slots: endgames solved per call (default cfr_default_slots(): T / 16, at least 64, at most T); each owns 1,728 KiB of
+        a workspace that stays cached on the env (slots * 1.69 MiB: 108 MiB at 64 slots, 6.75 GiB at 4,096).  Tables beyond
+        the slots report -2 and can be solved by a second call with more slots or with `roles` / fewer tables.
+        totals: int64 [4] on the device, += {deals, nodes, information sets, (set, action) pairs}.  out: the four tensors of
+        an earlier call, to reuse."""
+        iterations, roles = int(iterations), int(roles)
+        if not 0 <= iterations <= self.CFR_MAX_ITERATIONS:
+            raise ValueError(f"iterations must be in [0, {self.CFR_MAX_ITERATIONS}]")
+        if not 0 <= roles <= 7:
+            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        slots = self.cfr_default_slots() if slots is None else int(slots)
+        need = int(self.lib.ddz_cfr_work_bytes(slots))
+        if slots < 0 or need < 0:
+            raise ValueError("slots must be in [0, 2^24]")
+        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
+                                   or not totals.is_contiguous()):
+            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
+        if out is None:
+            out = (torch.empty(self.T, dtype=torch.int32, device=self.device),
+                   torch.empty((self.T, self.CFR_STRIDE), dtype=torch.int32, device=self.device),
+                   torch.empty((self.T, self.CFR_STRIDE), dtype=torch.float64, device=self.device),
+                   torch.empty(self.T, dtype=torch.float64, device=self.device))
+        n, ids, sigma, value = out
+        for x, dt, numel in ((n, torch.int32, self.T), (ids, torch.int32, self.T * self.CFR_STRIDE),
+                             (sigma, torch.float64, self.T * self.CFR_STRIDE), (value, torch.float64, self.T)):
+            if x.dtype != dt or x.device != self.device or x.numel() != numel or not x.is_contiguous():
+                raise ValueError("out must be the (n, ids, sigma, value) tensors of an earlier call")
+        work = getattr(self, "_cfr_work", None)
+        if work is None or work.numel() < need:
+            self._cfr_work = work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        check(self.lib.ddz_cfr(self._h, iterations, roles, slots, _p(work), work.numel(), _p(n), _p(ids), _p(sigma), _p(value),
+                               _p(totals), _stream(self.device)))
+        return n, ids, sigma, value
+
+    def cfr_choose(self, iterations=8, roles=0b111, slots=None, salt=0, greedy=False, solved=None, out=None):
+        """The CFR move of every endgame table: int32 [T] canonical action ids for step_slab(mode=STEP_IDS), -1 where cfr()
+        solved nothing (n <= 0: mask by it).  greedy: the first maximum of sigma; otherwise sampled from sigma as the
+        reference's choose() does, with the engine's own draw (RNG domain 8, keyed by the table id, the seed and `salt`).
+        solved: the (n, ids, sigma, value) of an earlier cfr() call to choose from (no solve)."""
+        if solved is None:
+            solved = self.cfr(iterations, roles=roles, slots=slots, out=getattr(self, "_cfr_out", None))
+            self._cfr_out = solved
+        n, ids, sigma, _ = solved
+        if out is None:
+            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
+        check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), int(salt) & 0xFFFFFFFF, int(bool(greedy)), _p(out),
+                                      _stream(self.device)))
+        return out
+
     def rollout_random_csr(self, n_iters, traj=None, batch=None):
         """The same loop with packed CSR lists (offsets/rows/ids as legal() returns them: afterwards they hold the lists
         of the last iteration's pre-step states).  Same states and trajectories as rollout_random.

@@ -13,7 +13,7 @@ ddz_get_moves), so a served observation is bit-identical to the one of a live ta
 import numpy as np
 import torch
 
-from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, NFIELDS, ROW, action_table, get_moves)
+from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, NFIELDS, ROW, action_table, auto_choose, get_moves)
 
 
 def _counts(cards):
@@ -193,6 +193,113 @@ def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, 
     table = action_table(dev).cpu().numpy()
     ranks = np.arange(3, 18)
     return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+
+
+def _id_cards(ids, device):
+    """canonical action ids -> rank lists 3..17 ([] = pass)"""
+    table = action_table(device).cpu().numpy()
+    ranks = np.arange(3, 18)
+    return [[int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+
+
+def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=False):
+    """The reference's final_card(payload) (server/CFR.py:520-538) for a batch of PLAIN serving payloads (no hand_card): every
+    request is packed by payloads_to_playout_state, solved by BatchedEnv.cfr (CFR spec v1: `iterations` iterations of
+    vanilla CFR over every deal of the cards the requester has not seen; the reference runs 8) and answered with a move
+    sampled from the strategy at the requester's hand (BatchedEnv.cfr_choose: the engine's draw, keyed by the request's
+    position in the batch, `seed` and `salt`; greedy: the first maximum instead).  -> per request a list of rank values
+    3..17, [] for a pass.  ValueError where a request is no endgame (more than 6 cards in the three hands, or a finished
+    game), where cur_cards, history and left do not add up to a deck (status bit 6), or where the solver's capacities do not
+    hold it (status bit 7)."""
+    n = len(payloads)
+    if n == 0:
+        return []
+    dev = torch.device(device)
+    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
+    env.state_import(torch.from_numpy(payloads_to_playout_state(payloads)).view(-1))
+    solved = env.cfr(iterations, slots=n)
+    ids = env.cfr_choose(salt=salt, greedy=greedy, solved=solved).cpu().numpy()
+    status = env.status()
+    if status & 64:
+        raise ValueError("a payload is outside the endgame domain: cur_cards, history and left do not add up to a deck")
+    if status & 128:
+        raise ValueError("an endgame exceeds the solver's capacities")
+    if (ids < 0).any():
+        raise ValueError("a payload is no endgame: more than 6 cards are left, or the game is over")
+    return _id_cards(ids, dev)
+
+
+class Predictor:
+    """The reference's serving predictor (server/core.py:74-118 Predictor.act) for a batch of payloads, with its three-way
+    switch and thresholds: the rule agent while the requester holds 12 or more cards, CFR when the three hands together hold
+    6 cards or fewer, the Q-network otherwise.  Every reply is {"model": "Rule" | "CFR" | "RL1", "data": cards} (rank values
+    3..17, [] = pass); the reference's `msg` string is not reproduced, and a payload without cards gets {"model": None,
+    "data": []} (core.py:75-76).
+      Rule  the project's batched rule agent (ddz_auto_choose, rule_based/utils/rule_based_model.py).  The reference's serving
+            process imports a tuned variant of it (server/rule_utils); that variant is NOT built here.
+      CFR   cfr_act (final_card).
+      RL1   BatchedPredictorInputs (face + legal moves) and the greedy move of the role's QNet over them (dqn.py:61-71).
+    nets: {role: QNet} for the roles 0 up / 1 lord / 2 down that may reach the RL branch (core.py:18-24 id2ai)."""
+
+    RULE_MIN_CARDS = 12      # core.py:80
+    CFR_MAX_TOTAL = 6        # core.py:88
+
+    def __init__(self, nets, device="cuda:0", variant=3, iterations=8, seed=0):
+        self.nets, self.device = nets, torch.device(device)
+        self.inputs = BatchedPredictorInputs(self.device, variant)
+        self.iterations, self.seed = iterations, seed
+
+    @classmethod
+    def route(cls, payload):
+        """"Rule" / "CFR" / "RL1" as core.py:78-104 picks it, None for a payload without cards"""
+        if not payload["cur_cards"]:
+            return None
+        if len(payload["cur_cards"]) >= cls.RULE_MIN_CARDS:
+            return "Rule"
+        if sum(int(_get(payload["left"], r)) for r in range(3)) <= cls.CFR_MAX_TOTAL:
+            return "CFR"
+        return "RL1"
+
+    def act(self, payloads, salt=0, greedy=False):
+        from .dqn_glue import ragged_q
+        routes = [self.route(p) for p in payloads]
+        out = [{"model": r, "data": []} for r in routes]
+        pick = lambda name: [i for i, r in enumerate(routes) if r == name]
+        rule, cfr, rl = pick("Rule"), pick("CFR"), pick("RL1")
+        if rule:
+            sub = [payloads[i] for i in rule]
+            hands = np.zeros((len(sub), ROW), np.int8)
+            lasts = np.zeros((len(sub), ROW), np.int8)
+            for k, p in enumerate(sub):
+                role = int(p["role_id"])
+                hands[k, :15] = _counts(p["cur_cards"])
+                lasts[k, :15] = _counts(_get(p["last_taken"], (role + 2) % 3) or _get(p["last_taken"], (role + 1) % 3))
+            left = [[int(_get(p["left"], r)) for r in range(3)] for p in sub]
+            ids = auto_choose(torch.from_numpy(hands).to(self.device), torch.from_numpy(lasts).to(self.device), left,
+                              [int(p["role_id"]) for p in sub]).cpu().numpy()
+            if (ids < 0).any():
+                raise ValueError("the rule agent has no move for a payload (no legal combination)")
+            for i, cards in zip(rule, _id_cards(ids, self.device)):
+                out[i]["data"] = cards
+        if cfr:
+            moves = cfr_act([payloads[i] for i in cfr], self.iterations, self.device, salt=salt, seed=self.seed, greedy=greedy)
+            for i, cards in zip(cfr, moves):
+                out[i]["data"] = cards
+        for role in sorted({int(payloads[i]["role_id"]) for i in rl}):
+            idx = [i for i in rl if int(payloads[i]["role_id"]) == role]
+            sub = [payloads[i] for i in idx]
+            net = self.nets[role]
+            with torch.no_grad():
+                face = self.inputs.face(sub)
+                _, offsets, rows = self.inputs.valid_actions(sub)
+                q = ragged_q(net, face, rows, offsets)
+            off = offsets.cpu().numpy()
+            rows_h, q_h = rows.cpu().numpy(), q.cpu().numpy()
+            ranks = np.arange(3, 18)
+            for k, i in enumerate(idx):
+                j = off[k] + int(np.argmax(q_h[off[k]:off[k + 1]]))       # torch.argmax: the first maximum (dqn.py:70)
+                out[i]["data"] = [int(x) for x in np.repeat(ranks, rows_h[j, :15].astype(int))]
+        return out
 
 
 class BatchedPredictorInputs:

@@ -378,6 +378,59 @@ int ddz_search(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c,
 int ddz_search_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,
                       const int32_t* wins, int32_t* choice, void* stream);
 
+/* The CFR endgame solver: the reference's final_card (server/CFR.py: deal / initiate_game / VanillaCFR.run(8)), the engine
+ * its predictor uses when the three hands hold 6 cards or fewer (server/core.py:88), batched.  "CFR spec v1" (DESIGN.md 4):
+ * the reference's computation with everything it leaves to chance pinned.  Seats are the reference's player numbers, 0 lord /
+ * 1 down / 2 up = role (seat + 1) % 3, and the turn order is seat 0, 1, 2.
+ *   Domain: a running table (dealt, not done) with actor `role` whose bit is set in `roles`, left[role] = the cards of its hand
+ *     row, left of the other two = byte 15 of their hand rows (their count bytes are NEVER read, as in playout spec v2), with
+ *     every left >= 1, left[0] + left[1] + left[2] <= DDZ_CFR_MAX_CARDS, pool_r = deck_r - taken_r >= 0, sum pool = sum left,
+ *     and the actor's hand row inside pool.  Read besides: the recent rows with their category bytes and the meta row.
+ *     n[t] = 0 for an idle table (not running, or its actor not in `roles`); n[t] = -1 and NO status bit for a running table
+ *     with more than DDZ_CFR_MAX_CARDS cards ("not an endgame": what a dispatcher tests); n[t] = -1 and status bit 6 where the
+ *     rows do not add up.  The combination to beat and its owner: the previous seat's recent row if non-empty, else the row
+ *     of the seat before it, else a lead owned by the actor.
+ *   Deals: every distinct assignment of pool to the seats by per-rank counts with the seats' sizes, ordered as CFR.py:deal
+ *     yields them (ranks ascending; per rank the lord's count, then down's count, ascending); D <= DDZ_CFR_MAX_DEALS, each
+ *     weighs 1 / D.
+ *   Tree of a deal: a node's actions are the legal list of its state in slab order (ascending canonical id, pass first when
+ *     following); after a pass the next seat leads if it owns the combination to beat, else it faces the same combination
+ *     (CFR.py:152-174); a node where a hand is empty is terminal with utility +1 if that hand is the lord's, else -1.
+ *   Information set: (mover, the mover's hand in the deal, the actions from the root); at most one node per deal.
+ *   Arithmetic: IEEE double, every operation rounded on its own, nothing fused.  sigma starts at 1 / n.  Iteration (the
+ *     reference runs 8; 0 <= iterations <= DDZ_CFR_MAX_ITERATIONS): reaches ra, rb, rc start at 1 and the mover's is multiplied
+ *     by sigma[a] towards child a; value = ((0 + s0 * u0) + s1 * u1) + ... in action order; cfr_reach = rb * rc, ra * rc,
+ *     ra * rb for mover 0, 1, 2; R[I][a] += cfr_reach * (u_a - value), negated for a farmer, IN ASCENDING DEAL ORDER (the
+ *     reference walks a Python set: this is the pinning); after all deals sigma_a = max(R_a, 0) / S, S = the positive R_a
+ *     added in action order, and 1 / n where S <= 0; value_t = (1 / D) * (u_root(0) + u_root(1) + ...).
+ *   Result: n[t] = the size of the actor's legal list, ids[t][j] its canonical ids, sigma[t][j] the row of the information
+ *     set (actor, its actual hand, no action), value[t] = the last iteration's value_t (0 with no iteration).  ids and sigma
+ *     are [T][DDZ_CFR_STRIDE], written whole for every table (ids -1 / sigma 0 beyond n and where nothing is solved).
+ *     totals (device int64[4], may be NULL) += {deals, nodes, information sets, (information set, action) pairs} of the
+ *     solved tables.  The result is bit-identical from run to run: no floating-point atomics, no order left to scheduling.
+ *   Workspace: ddz_cfr_work_bytes(slots) bytes, 16-byte aligned, nothing in it to initialise: a head with a counter (zeroed
+ *     by a one-wave launch of this call) and `slots` slots of about 1.7 MiB.  Every table inside the domain takes one
+ *     slot; one that finds none, or whose forest exceeds a capacity (DDZ_CFR_MAX_NODES, DDZ_CFR_MAX_INFOSETS, ...: twice what
+ *     any endgame was measured to need, tools/cfr_sweep.py), gets n[t] = -2 and status bit 7.  slots >= 0.
+ * The env is only read.  Two launches on `stream` (the head's zeroing, the solver), nothing on the host (capturable).
+ * ddz_cfr_choose: choice[t] = ids[t][j], -1 where n[t] <= 0.  greedy != 0: j = the first maximum of sigma[t].  Otherwise, as
+ *   the reference's choose(): u = x * 2^-32 with x = philox4x32_10((gid_lo, gid_hi, 0, 8 << 16), (seed_lo ^ salt_lo, seed_hi)).x
+ *   (RNG domain 8; domains 1..7 are unchanged), j = the first index with u below the running sum of sigma in list order,
+ *   else the last index with sigma_j > 0.  Feed it to ddz_step_slab(DDZ_STEP_IDS). */
+#define DDZ_CFR_MAX_CARDS 6
+#define DDZ_CFR_STRIDE 16
+#define DDZ_CFR_MAX_DEALS 90        /* 6! / (2! 2! 2!) */
+#define DDZ_CFR_MAX_ACTIONS 8       /* a hand of at most 4 cards has at most 5 moves */
+#define DDZ_CFR_MAX_DEPTH 24        /* at most 6 plays, each followed by at most 2 passes */
+#define DDZ_CFR_MAX_NODES 32768     /* measured maximum 10,512 */
+#define DDZ_CFR_MAX_INFOSETS 8192   /* measured maximum 2,835 */
+#define DDZ_CFR_MAX_ITERATIONS 64
+int64_t ddz_cfr_work_bytes(int64_t slots);
+int ddz_cfr(ddz_env_t* env, int iterations, int roles, int64_t slots, void* work, int64_t work_bytes, int32_t* n, int32_t* ids,
+            double* sigma, double* value, int64_t* totals, void* stream);
+int ddz_cfr_choose(ddz_env_t* env, const int32_t* n, const int32_t* ids, const double* sigma, uint64_t salt, int greedy,
+                   int32_t* choice, void* stream);
+
 /* The same random-policy loop with the lists in the CSR layout of ddz_legal (offsets/rows/ids
  * packed across tables).  CSR bases need a scan over all tables, so this variant is one
  * launch per iteration: the fused kernel writes the list of the current state, steps, and
@@ -735,7 +788,8 @@ int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
  * ddz_q_roles_slab) whose (rank, count)
  * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing), bit6 a running
  * table of ddz_playout_hidden / ddz_playout_worlds outside the hidden-hand domain (its hand, taken row and hand sizes do not
- * add up to a deck): that table ran nothing.
+ * add up to a deck): that table ran nothing -- and a running table of ddz_cfr with at most DDZ_CFR_MAX_CARDS cards whose rows
+ * do not add up; bit7 a table of ddz_cfr that found no workspace slot or whose forest exceeds a capacity (n = -2).
  * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
 /* the same word for the STATELESS rule-agent entry point (ddz_auto_choose has no handle): one per device, bits as above
