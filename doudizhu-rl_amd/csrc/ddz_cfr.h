@@ -1,22 +1,24 @@
 // ddz_cfr.h -- k_cfr / k_cfr_choose: the CFR endgame solver ("CFR spec v1"; the reference's final_card /
 // initiate_game / VanillaCFR, server/CFR.py, with everything it leaves to chance pinned).  Included by ddz_engine.hip behind
-// ddz_search.h, inside its anonymous namespace: no other kernel is touched, the legal lists are search_list / search_entry of
-// ddz_search.h (k_playout's ply: the device keeps one statement of the rules).
+// ddz_ply.h, inside its anonymous namespace.  The root decode (play_root_decode), the domain test (unseen_pool), the legal
+// lists (ply_list / ply_entry: the device keeps one statement of the rules) and the wavefront-scope accesses (sld / sst /
+// search_fence) are ddz_ply.h's, shared with k_playout and k_search.
 //
 // One wavefront per TABLE; a table inside the domain takes one workspace SLOT from a counter at the head of the workspace
 // (zeroed by k_cfr_head, a one-wave launch in front of k_cfr) and keeps it for the launch.  Seats are the reference's player
 // numbers: 0 lord, 1 down, 2 up = role (seat + 1) % 3; the turn order is seat 0, 1, 2.
 //
 // PHASES of a wave.
-//   decode   the root as k_search<hidden> reads it: the actor's hand row, the taken row, the recent rows with their category
-//            bytes, the meta row, byte 15 of the other two hand rows -- never the opponents' count bytes.
+//   decode   the root as k_search<true> reads it (play_root_decode, unseen_pool): the actor's hand row, the taken row, the
+//            recent rows with their category bytes, the meta row, byte 15 of the other two hand rows -- never the opponents'
+//            count bytes.
 //   deals    every assignment of pool = deck - taken to the seats by per-rank counts, in CFR.py:deal's order: the pool has
 //            K <= 6 distinct ranks, a deal is a mixed-radix number over them (digit = (lord's count, down's count) in
 //            lexicographic order, the lowest rank the most significant), a lane decodes one number per round and a ballot
 //            ranks the valid ones.  Deal d is node d.
 //   forest   built ONCE, breadth-first over all deals: node i is expanded in index order, its children are appended behind
-//            the last node, so every level is deal-ordered.  Wave-uniform: one node per trip, search_list for its list,
-//            search_entry per action.  While it is built, node i's state (three hands, the combination to beat and its owner,
+//            the last node, so every level is deal-ordered.  Wave-uniform: one node per trip, ply_list for its list,
+//            ply_entry per action.  While it is built, node i's state (three hands, the combination to beat and its owner,
 //            its history id and deal) lies in the 32 bytes that hold its reaches and value afterwards: no record keeps a state.
 //            THE BUILD IS THE COST: it is serial in the nodes (63 lanes idle outside the list code), and one worst-case table
 //            (10,512 nodes) takes 20 ms of which the eight iterations' sweeps are the small part (profiles/r14_notes.md).  Do not
@@ -182,44 +184,33 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   if (lane < DDZ_CFR_STRIDE) { out_ids[lane] = -1; out_sigma[lane] = 0.0; }
   if (lane == 0) { a.value[t] = 0.0; a.n[t] = 0; }
   // ---- decode (as k_search<true>)
-  const uint64_t P = pack_row(R);
-  const uint32_t aux = R.w >> 24;
-  const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
-  int role0 = mx & 0xFF;
-  if (role0 > 2) role0 = 0;
-  if (!(((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF))) return;   // not dealt, or done
+  const PlayRoot root = play_root_decode(R);
+  if (!root.running) return;   // not dealt, or done
+  const int role0 = root.role0;
   if (!((a.roles >> role0) & 1u)) return;
-  const int rprev = role0 == 0 ? 2 : role0 - 1, rnext = role0 == 2 ? 0 : role0 + 1;
-  const uint64_t hc0 = rl64(P, DDZ_F_HAND0 + role0);
-  const uint64_t taken = rl64(P, DDZ_F_TAKEN);
-  const int n_next = (int)rl(aux, DDZ_F_HAND0 + rnext), n_prev = (int)rl(aux, DDZ_F_HAND0 + rprev);
+  const int rnext = role_next(role0);
+  const uint64_t hc0 = root.hc0;
   const int n_me = nib_sum(hc0);
+  int n_next, n_prev;
+  uint64_t unseen;
+  bool pool_lane;
+  const bool inside = unseen_pool(root, lane, n_next, n_prev, unseen, pool_lane);
   if (n_me + n_next + n_prev > DDZ_CFR_MAX_CARDS) {   // not an endgame
     if (lane == 0) a.n[t] = -1;
     return;
   }
-  {
-    const int sh = 4 * (lane & 15);
-    const int deck = lane < 13 ? 4 : lane < 15 ? 1 : 0;
-    const int tk = (int)((taken >> sh) & 15), hd = (int)((hc0 >> sh) & 15);
-    const bool bad = __ballot(lane < 15 && (tk > deck || hd > deck - tk)) != 0ull;
-    const uint64_t pool_ = DECK_NIB - taken;   // (no borrow between nibbles where !bad; not used otherwise)
-    if (bad || n_me < 1 || n_next < 1 || n_prev < 1 || nib_sum(pool_) != n_me + n_next + n_prev) {
-      if (lane == 0) { a.n[t] = -1; atomicOr(a.status, 64); }
-      return;
-    }
+  // unseen_pool is the domain of this spec too: per rank `taken > deck || hand > deck - taken` is `hand + taken > deck` for
+  // counts that are not negative, and where that holds for no rank deck - taken = unseen + hand without a borrow, so
+  // `sum(deck - taken) != n_me + n_next + n_prev` is `sum(unseen) != n_next + n_prev`.  The actor's own hand is not empty.
+  if (!inside || n_me < 1) {
+    if (lane == 0) { a.n[t] = -1; atomicOr(a.status, 64); }
+    return;
   }
-  const uint64_t pool = DECK_NIB - taken;
+  const uint64_t pool = unseen + hc0;   // deck - taken
   // the combination to beat and its owner (final_card: the previous seat's, else the one before, else a lead of the actor's)
-  const int first = role0 == 0 ? 2 : role0 - 1;   // the actor's seat
-  uint32_t trick0 = mk_info(EMPTY, 0, 1);
-  int owner0 = first;
-  {
-    const uint64_t n1 = rl64(P, DDZ_F_RECENT0 + rprev), n2 = rl64(P, DDZ_F_RECENT0 + rnext);
-    if (n1) { trick0 = info_of_row(n1, (int)rl(aux, DDZ_F_RECENT0 + rprev)); owner0 = first == 0 ? 2 : first - 1; }
-    else if (n2) { trick0 = info_of_row(n2, (int)rl(aux, DDZ_F_RECENT0 + rnext)); owner0 = first == 2 ? 0 : first + 1; }
-  }
-  trick0 = rfl(trick0);
+  const int first = role_prev(role0);   // the actor's seat
+  const uint32_t trick0 = rfl(root.trick0);
+  const int owner0 = root.lead0 ? first : root.passes0 ? role_next(first) : role_prev(first);
   // ---- a slot
   uint32_t slot = 0;
   if (lane == 0) slot = atomicAdd((uint32_t*)a.work, 1u);
@@ -246,13 +237,13 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   int n_root = 0;
   if (!over) {
     uint64_t okm; int n0;
-    n_root = search_list(hc0, trick0, hot, lane, stage, svl, okm, n0);
+    n_root = ply_list(hc0, trick0, hot, lane, stage, svl, okm, n0);
     __builtin_amdgcn_wave_barrier();
     if (n_root < 1 || n_root > DDZ_CFR_MAX_ACTIONS) over = true;
     for (int j = 0; j < DDZ_CFR_MAX_ACTIONS; ++j) {
       if (over || j >= n_root) break;
       uint64_t snib; uint32_t scat, svlv;
-      search_entry(okm, n0, j, trick0, stage, svl, snib, scat, svlv);
+      ply_entry(okm, n0, j, trick0, stage, svl, snib, scat, svlv);
       const int id = cfr_action_id(snib, scat, svlv);
       if (id < 0) over = true;
       else if (lane == 0) out_ids[j] = id;
@@ -339,7 +330,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
       const int mover = (int)((uint32_t)first + depth) % 3;
       const uint64_t hand = mover == 0 ? h0 : mover == 1 ? h1 : h2;
       uint64_t okm; int n0;
-      const int n = search_list(hand, trick, hot, lane, stage, svl, okm, n0);
+      const int n = ply_list(hand, trick, hot, lane, stage, svl, okm, n0);
       __builtin_amdgcn_wave_barrier();
       if (n < 1 || n > DDZ_CFR_MAX_ACTIONS || nn + (uint32_t)n > CFR_N) { over = true; break; }
       // the information set: (history, the mover's hand in the deal)
@@ -369,7 +360,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
       for (int j = 0; j < DDZ_CFR_MAX_ACTIONS; ++j) {
         if (j >= n) break;
         uint64_t snib; uint32_t scat, svlv;
-        search_entry(okm, n0, j, trick, stage, svl, snib, scat, svlv);
+        ply_entry(okm, n0, j, trick, stage, svl, snib, scat, svlv);
         const int id = cfr_action_id(snib, scat, svlv);
         if (id < 0) { over = true; break; }
         bool hnew;

@@ -7,9 +7,12 @@
 //             (nine plies in ten: that round is the whole list), planner + LDS staging list for the tail of the rest
 //             (see the comment at the kernel).
 //   k_playout (ddz_playout.h; ddz_playout) win counts of random playouts for every legal move of every table: one wavefront per
-//             (table, chunk), the root in registers, every ply from k_rollout's device functions, no list stored.
+//             (table, chunk), the root in registers, no list stored.
 //   k_search  (ddz_search.h; ddz_search) UCT tree search around those playouts: one wavefront per (table, tree), the tree in a
-//             caller-provided workspace, the descent re-applies stored moves, the playout is k_playout's ply.
+//             caller-provided workspace, the descent re-applies stored moves.
+//   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
+//             These three share ddz_ply.h: the root decode, the hidden-hand domain and redeal, and a ply (list, entry, apply,
+//             draw) built from k_rollout's device functions -- each stated once.
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
 //             or slab lists with F_SLAB = apply + enumerate in the same launch):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
@@ -1402,7 +1405,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
   }
 }
 
-#include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move, from k_rollout's device functions
+#include "ddz_ply.h"      // the root decode, the hidden-hand domain and a ply, shared by the three kernels below
+#include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
 

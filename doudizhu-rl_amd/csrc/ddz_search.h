@@ -1,8 +1,8 @@
 // ddz_search.h -- k_search / k_search_choose: UCT tree search around the playouts ("search spec v1 (UCT)"; the
 // reference's MCTS player: server/mcts/interface.py:37-43 with tree_policy / get_bestchild.py / tree.py:33-51 / backup.py).
-// Included by ddz_engine.hip behind ddz_playout.h, inside its anonymous namespace: k_rollout and k_playout are not touched, the
-// ply below is k_playout's restated on the same device functions (the rank-mask tests, round_pre / round_src / round_entry,
-// plan_scan_t<EM_STAGE> into the wave's LDS list, the packed apply, the 64-draw Philox refill, redeal_wave).
+// Included by ddz_engine.hip behind ddz_ply.h and ddz_playout.h, inside its anonymous namespace.  The root decode, the
+// hidden-hand domain, the redeal, every piece of a ply (ply_list, ply_entry, ply_apply, ply_draw) and the wavefront-scope
+// accesses to the tree (sld / sst / search_fence) are ddz_ply.h's, shared with k_playout and k_cfr; this header holds the tree.
 //
 // One wavefront per WORK ITEM (table t, tree c).  The wave decodes the root once into wave-uniform values (as k_playout), then
 // runs `budget` iterations of {descent, expansion, playout, backup} on its own tree.  The descent RE-APPLIES stored moves from
@@ -64,15 +64,6 @@ inline uint64_t search_tree_bytes(int64_t budget) { return search_nodes_bytes(bu
 
 __device__ float g_search_ln[DDZ_SEARCH_MAX_BUDGET + 1];   // filled from libm with the record table (build_table_locked)
 
-__device__ __forceinline__ uint64_t sld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ uint32_t sld32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ void sst64(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ void sst32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ void search_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // the child of (parent, list index j), SEARCH_NONE where none was created.  Per lane; at most H probes.
 __device__ __forceinline__ uint32_t search_find(const uint64_t* tab, uint32_t hlog, uint32_t key) {
   const uint32_t hmask = (1u << hlog) - 1u;
@@ -108,83 +99,6 @@ __device__ __forceinline__ float search_value(uint32_t w, uint32_t v, float two_
   return mean + bonus;
 }
 
-// the legal list of the state (hand, info) as k_playout's ply sees it: the closed-form round's legal lanes as a mask, the
-// planner's tail staged into the wave's LDS list; returns the list's size (n0 = the round's share)
-template <typename HT>
-__device__ __forceinline__ int search_list(uint64_t hand, uint32_t info, const HT& hot, int lane, uint64_t* stage, uint16_t* svl,
-                                           uint64_t& okm_out, int& n0_out) {
-  const int lc0 = (int)(info & 0xFF);
-  const bool lead = lc0 == EMPTY;
-  const int cntr = lane < 15 ? (int)((hand >> (4 * (lane & 15))) & 15) : 0;
-  const uint32_t b1 = (uint32_t)__ballot(cntr >= 1), b4 = (uint32_t)__ballot(cntr >= 4);
-  uint64_t okm = 0;
-  bool tail = false;
-  if ((b1 & M15) == 0) {
-    // an empty hand on a running state (outside the domain): the empty list
-  } else if (!lead && lc0 <= TRIPLE) {
-    const int lv0 = (int)((info >> 8) & 0xFF);
-    const uint32_t mlc = (uint32_t)__ballot(cntr >= lc0) & (lc0 == SINGLE ? M15 : M13);
-    const bool rocket = (b1 & JOKERS) == JOKERS;
-    okm = 1u | ((mlc & gt_mask(lv0)) << 1) | ((b4 & M13) << 16) | (rocket ? 1u << 29 : 0u);
-  } else {
-    const uint32_t m1 = b1 & M15, m2 = (uint32_t)__ballot(cntr >= 2) & M13;
-    const uint32_t m3 = (uint32_t)__ballot(cntr >= 3) & M13, m4 = b4 & M13;
-    const bool jokers = (m1 & JOKERS) == JOKERS;
-    if (lead) {
-      tail = m3 != 0 || run_starts(m1 & M12, 5) != 0 || run_starts(m2 & M12, 3) != 0;
-      okm = (uint64_t)m1 | (uint64_t)m2 << 15 | (uint64_t)m3 << 28 | (uint64_t)m4 << 41 | (jokers && !tail ? 1ull << 54 : 0ull);
-    } else {
-      const int lv0 = (int)((info >> 8) & 0xFF), ll0 = (int)((info >> 16) & 0xFF);
-      const uint32_t ab = gt_mask(lv0);
-      uint32_t cand = 0, bombs = m4, may = 0;
-      bool rocket = jokers;
-      if (lc0 == QUADRIC) { cand = m4 & ab; bombs = 0; }
-      else if (lc0 == BIGBANG) { bombs = 0; rocket = false; }
-      else if (lc0 == THREE_ONE || lc0 == THREE_TWO) may = m3 & ab;
-      else if (lc0 == SINGLE_LINE) may = run_starts(m1 & M12, ll0) & ab;
-      else if (lc0 == DOUBLE_LINE) may = run_starts(m2 & M12, ll0) & ab;
-      else if (lc0 == TRIPLE_LINE || lc0 == THREE_ONE_LINE || lc0 == THREE_TWO_LINE) may = run_starts(m3 & M12, ll0) & ab;
-      else if (lc0 == FOUR_TAKE_ONE || lc0 == FOUR_TAKE_TWO) may = m4 & ab;
-      tail = may != 0;
-      okm = 1u | (cand << 1) | (bombs << 16) | (rocket && !tail ? 1u << 29 : 0u);
-    }
-  }
-  const int n0 = __builtin_popcountll(okm);
-  int n = n0;
-  if (tail) {
-    const Out o{nullptr, nullptr, 0, 0, stage, svl, nullptr};
-    Pick pk{-1, 0, 0, 0, 0};
-    const Follow f = follow_of(info);
-    const int n1 = lead ? plan_scan_t<EM_STAGE, false, true, HT, false>(hand, f, hot, lane, o, pk)
-                        : plan_scan_t<EM_STAGE, false, false, HT, false>(hand, f, hot, lane, o, pk);
-    __builtin_amdgcn_wave_barrier();
-    n = (int)rfl((uint32_t)(n0 + n1));
-  }
-  okm_out = okm;
-  n0_out = n0;
-  return n;
-}
-
-// entry idx < n of the list search_list left: the nibble word, the category and the value/len byte pair (wave-uniform)
-__device__ __forceinline__ void search_entry(uint64_t okm, int n0, int idx, uint32_t info, const uint64_t* stage, const uint16_t* svl,
-                                             uint64_t& snib, uint32_t& scat, uint32_t& svlv) {
-  const int lc0 = (int)(info & 0xFF);
-  const bool lead = lc0 == EMPTY;
-  uint32_t ncards = 0;
-  snib = 0; scat = 0; svlv = 0;
-  if (idx < n0) {
-    if (lead) round_entry<true>(round_src<true>(okm, round_pre(okm), idx), 0u, snib, scat, svlv, ncards);
-    else round_entry<false>(round_src<false>((uint32_t)okm, round_pre((uint32_t)okm), idx), (uint32_t)lc0, snib, scat, svlv, ncards);
-  } else {
-    const uint64_t e = stage[idx - n0];
-    const uint64_t anib = e & 0x0FFFFFFFFFFFFFFFull;
-    snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
-    scat = rfl((uint32_t)(e >> 60));
-    svlv = rfl((uint32_t)svl[idx - n0]);
-  }
-  (void)ncards;
-}
-
 template <bool HIDDEN>
 __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   __shared__ HotTabT<false> hot;
@@ -204,46 +118,23 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   uint64_t* stage = s_stage[wv];
   uint16_t* svl = s_svl[wv];
   uint16_t* path = s_path[wv];
-  // the root, decoded once (as k_playout decodes it)
-  const uint64_t P = pack_row(R);
-  const uint32_t aux = R.w >> 24;
-  const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
-  int role0 = mx & 0xFF;
-  if (role0 > 2) role0 = 0;
-  if (!(((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF))) return;  // not dealt, or done: nothing runs
-  const uint32_t ply0 = my & 0xFFFF;
-  const uint64_t hc0 = rl64(P, DDZ_F_HAND0 + role0);
+  const PlayRoot root = play_root_decode(R);
+  if (!root.running) return;  // not dealt, or done: nothing runs
+  const int role0 = root.role0;
   uint64_t hn0 = 0, hp0 = 0;
-  if constexpr (!HIDDEN) {
-    hn0 = rl64(P, DDZ_F_HAND0 + (role0 == 2 ? 0 : role0 + 1));
-    hp0 = rl64(P, DDZ_F_HAND0 + (role0 == 0 ? 2 : role0 - 1));
-  }
-  uint32_t trick0 = mk_info(EMPTY, 0, 1);
-  int passes0 = 0;
-  {
-    const int rm1 = role0 == 0 ? 2 : role0 - 1, rp1 = role0 == 2 ? 0 : role0 + 1;
-    const uint64_t n1 = rl64(P, DDZ_F_RECENT0 + rm1), n2 = rl64(P, DDZ_F_RECENT0 + rp1);
-    if (n1) trick0 = info_of_row(n1, (int)rl(aux, DDZ_F_RECENT0 + rm1));
-    else if (n2) { trick0 = info_of_row(n2, (int)rl(aux, DDZ_F_RECENT0 + rp1)); passes0 = 1; }
-  }
   const uint64_t gid = a.gid_base + (uint64_t)t;
-  if constexpr (HIDDEN) {   // tree c plays on world k = c of playout spec v2: the same pool, the same domain, the same deal
+  if constexpr (!HIDDEN) {
+    hn0 = rl64(root.P, DDZ_F_HAND0 + role_next(role0));
+    hp0 = rl64(root.P, DDZ_F_HAND0 + role_prev(role0));
+  } else {   // tree c plays on world k = c of playout spec v2: the same pool, the same domain, the same deal
     if (!((a.roles >> role0) & 1u)) return;
-    const uint64_t taken = rl64(P, DDZ_F_TAKEN);
-    const int n_next = (int)rl(aux, DDZ_F_HAND0 + (role0 == 2 ? 0 : role0 + 1));
-    const int n_prev = (int)rl(aux, DDZ_F_HAND0 + (role0 == 0 ? 2 : role0 - 1));
-    const int sh = 4 * (lane & 15);
-    const int deck = lane < 13 ? 4 : lane < 15 ? 1 : 0;
-    const bool over = (int)((hc0 >> sh) & 15) + (int)((taken >> sh) & 15) > deck;
-    const bool bad = __ballot(lane < 15 && over) != 0ull;
-    const uint64_t unseen = DECK_NIB - hc0 - taken;
-    if (bad || n_next < 1 || n_prev < 1 || nib_sum(unseen) != n_next + n_prev) {
+    int n_next, n_prev;
+    uint64_t unseen;
+    bool pool;
+    if (!unseen_pool(root, lane, n_next, n_prev, unseen, pool)) {
       if (lane == 0 && tree == 0) atomicOr(a.status, 64);
-      return;
+      return;   // outside the domain: nothing runs, the workspace is not touched
     }
-    const int rank = lane < 52 ? lane >> 2 : lane - 39;
-    const int cnt = (int)((unseen >> (4 * (rank & 15))) & 15);
-    const bool pool = lane < 52 ? (lane & 3) < cnt : (lane < 54 && cnt == 1);
     redeal_wave(gid, tree, a.k0, a.k1, lane, pool, n_next, stage, hn0, hp0);
   }
   const bool root_lord = role0 == 1;
@@ -255,8 +146,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   int n_root;
   {
     uint64_t okm; int n0;
-    const uint32_t info = rfl((passes0 >= 2) ? mk_info(EMPTY, 0, 1) : trick0);
-    n_root = search_list(hc0, info, hot, lane, stage, svl, okm, n0);
+    n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
     __builtin_amdgcn_wave_barrier();
     if (n_root > STAGE_CAP || n_root > a.stride) {
       if (lane == 0) atomicOr(a.status, 2);
@@ -276,9 +166,9 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   unsigned long long s_moves = 0;
   uint32_t s_unfinished = 0;
   for (uint32_t it = 0; it < a.budget; ++it) {
-    uint64_t hc = hc0, hn = hn0, hp = hp0;
-    uint32_t trick = trick0, ply = ply0;
-    int passes = passes0, role = role0;
+    uint64_t hc = root.hc0, hn = hn0, hp = hp0;
+    uint32_t trick = root.trick0, ply = root.ply0;
+    int passes = root.passes0, role = role0;
     uint32_t node = 0;
     int depth = 0;          // path[0 .. depth] are the nodes backed up
     int winner = -1;
@@ -296,11 +186,11 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       const int n = (int)((meta >> 16) & 0x3FFu);
       if (n <= 0 || d == DDZ_SEARCH_MAX_DEPTH) break;   // outside the domain: reward 0, unfinished
       const uint32_t nchild = rfl(sld32((const uint32_t*)(nr + 20)));
-      const uint32_t info = rfl((passes >= 2) ? mk_info(EMPTY, 0, 1) : trick);
+      const uint32_t info = ply_info(trick, passes);
       if ((int)nchild < n) {
         // ---- expansion: the (draw_e * u) >> 32-th untried list index, ascending
         uint64_t okm; int n0;
-        const int nn = search_list(hc, info, hot, lane, stage, svl, okm, n0);
+        const int nn = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
         if (nn != n) break;   // (cannot happen: the state of a node is a function of its path)
         const uint32_t u = (uint32_t)n - nchild;
         const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
@@ -325,7 +215,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
         }
         if (idx < 0 || idx >= n) break;   // (cannot happen: u untried indices exist)
         uint64_t snib; uint32_t scat, svlv;
-        search_entry(okm, n0, idx, info, stage, svl, snib, scat, svlv);
+        ply_entry(okm, n0, idx, info, stage, svl, snib, scat, svlv);
         made = nnodes++;
         made_move = snib | ((uint64_t)scat << 60);
         made_meta = svlv & 0xFFFFu;
@@ -333,33 +223,25 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
           search_insert(tab, hlog, node * 512u + (uint32_t)idx + 1u, made);
           sst32((uint32_t*)(nodes + (uint64_t)node * NODE_BYTES + 20), nchild + 1u);
         }
-        const uint64_t hnew = hc - snib;
-        if (snib) { trick = scat | (svlv << 8); passes = 0; } else { passes += 1; }
         s_moves += 1;
-        ply += 1;
-        __builtin_amdgcn_wave_barrier();
-        if (rfl((uint32_t)hnew | (uint32_t)(hnew >> 32)) == 0u) {
+        if (ply_apply(snib, scat, svlv, hc, hn, hp, trick, passes, role, ply)) {
           winner = role;
           made_meta |= (1u << 26) | ((uint32_t)role << 27);
           break;
         }
-        role = role == 2 ? 0 : role + 1;
-        hc = hn; hn = hp; hp = hnew;
-        // ---- playout from the new child: k_playout's ply, draws of domain 7 keyed by (gid, tree, iteration, ply)
+        // ---- playout from the new child: draws of domain 7 keyed by (gid, tree, iteration, ply)
         uint32_t draws = 0, dnext = 64;
         for (int s = 0; s < DDZ_PLAYOUT_MAX_PLIES; ++s) {
           uint32_t dn = rfl(dnext);
           if (dn >= 64u) {
             dn = 0;
             dnext = 0;
-            draws = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it,
-                                             (7u << 16) | ((ply + (uint32_t)lane) & 0xFFFFu)), a.k0, a.k1).x;
+            draws = ply_draw(gid, (tree << 16) | it, 7u << 16, ply, lane, a.k0, a.k1);
           }
           const uint32_t draw = rl(draws, (int)dn);
-          const uint64_t hand = hc;
-          const uint32_t pinfo = rfl((passes >= 2) ? mk_info(EMPTY, 0, 1) : trick);
+          const uint32_t pinfo = ply_info(trick, passes);
           uint64_t pokm; int pn0;
-          int pn = search_list(hand, pinfo, hot, lane, stage, svl, pokm, pn0);
+          int pn = ply_list(hc, pinfo, hot, lane, stage, svl, pokm, pn0);
           if (pn > STAGE_CAP) {
             if (lane == 0) atomicOr(a.status, 2);
             pn = 0;
@@ -368,19 +250,13 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
           if (pn <= 0) break;   // stopped unfinished
           const int pidx = (int)rfl(__umulhi(draw, (uint32_t)pn));
           uint64_t pnib; uint32_t pcat, pvl;
-          search_entry(pokm, pn0, pidx, pinfo, stage, svl, pnib, pcat, pvl);
-          const uint64_t hnew2 = hand - pnib;
-          if (pnib) { trick = pcat | (pvl << 8); passes = 0; } else { passes += 1; }
+          ply_entry(pokm, pn0, pidx, pinfo, stage, svl, pnib, pcat, pvl);
           s_moves += 1;
-          ply += 1;
           dnext += 1;
-          __builtin_amdgcn_wave_barrier();
-          if (rfl((uint32_t)hnew2 | (uint32_t)(hnew2 >> 32)) == 0u) {
+          if (ply_apply(pnib, pcat, pvl, hc, hn, hp, trick, passes, role, ply)) {
             winner = role;
             break;
           }
-          role = role == 2 ? 0 : role + 1;
-          hc = hn; hn = hp; hp = hnew2;
         }
         break;
       }
@@ -417,12 +293,8 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       const uint64_t anib = mv & 0x0FFFFFFFFFFFFFFFull;
       const uint64_t snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
       const uint32_t scat = rfl((uint32_t)(mv >> 60)), svlv = rfl(cmeta & 0xFFFFu);
-      const uint64_t hnew = hc - snib;
-      if (snib) { trick = scat | (svlv << 8); passes = 0; } else { passes += 1; }
       s_moves += 1;
-      ply += 1;
-      role = role == 2 ? 0 : role + 1;
-      hc = hn; hn = hp; hp = hnew;
+      ply_turn(ply_play(snib, scat, svlv, hc, trick, passes, ply), hc, hn, hp, role);   // (an emptied hand: the child is terminal, the next trip scores it)
       node = child;
       depth += 1;
       if (lane == 0) path[depth] = (uint16_t)child;

@@ -81,3 +81,14 @@ def batch(oracle, rows, g, scramble=None):
               "outside: a hand outside the pool"]
     assert len(states) <= 32
     return np.stack(states), names
+
+
+def taken_above_deck(oracle, rows, scramble=None):
+    """-> states uint8 [2, 11, 16]: batch()'s base table, and a copy whose taken row says five 3s (no hand holds a 3) and
+    one 5 fewer, so that the pool still counts as many cards as the hands: outside the domain by the negative pool count alone"""
+    base = case_state(oracle, rows, [2, 1, 2], vec([4, 9, 9, 13, 15]), 1, vec([]), 1, 3, scramble)
+    over = base.copy()
+    over[cr.F_TAKEN, 0] += 1
+    over[cr.F_TAKEN, 2] -= 1
+    assert over[cr.F_TAKEN, 0] == 5 and not base[cr.F_HAND0:cr.F_HAND0 + 3, 0].any()
+    return np.stack([base, over])

@@ -80,6 +80,17 @@ def test_batch_exactly(pkg, oracle, cases, iterations):
         assert (want[2][0, :k] == 1.0 / k).all() and (want[3] == 0).all()
 
 
+def test_taken_above_the_deck(pkg, oracle):
+    """a rank taken more often than the deck holds it, the pool's size still right: n = -1 and status bit 6 from the
+    per-rank test alone (the domain test k_cfr shares with the hidden-hand playouts and search)"""
+    states = cc.taken_above_deck(oracle, oracle.action_table()[0])
+    want = cr.cfr(oracle, states, 2)
+    assert want[0][0] > 0 and want[0][1] == -1 and want[5] == cr.STATUS_DOMAIN
+    env = _env(pkg, states)
+    _same(_run(env, 2), want)
+    assert env.status() == cr.STATUS_DOMAIN
+
+
 def test_coverage(oracle, cases):
     """what the batch makes the kernel walk through (the restatement's sizes; nothing runs on the device here)"""
     states, names = cases

@@ -10,10 +10,13 @@ import torch
 
 import constructed_states as cs
 import playout_cases as pc
+import playout_hidden_cases as hc
 import playout_reference as pr
 import search_reference as sr
 
 pytestmark = pytest.mark.gpu
+SENTINEL = 0x3F3F3F3F
+OUT_OF_DOMAIN = 64                                # status bit 6
 GAMES = ((21, 0), (4, 2 ** 32 + 12345))       # (seed, table_id_base): the second puts the high half of gid into the counter
 SMALL = 3                                     # the first SMALL hand-built tables are the endgames the 300-iteration trees grow on
 
@@ -159,6 +162,55 @@ def test_hidden(pkg, oracle, games, trees, roles):
         for r in ((role[t] + 1) % 3, (role[t] + 2) % 3):
             blind[t, r, :15] = 0
     _same(_run(_env(pkg, blind, *GAMES[0]), 64, trees=trees, hidden=True, roles=roles, salt=3), want)
+
+
+def _raw_hidden(pkg, env, budget, trees, salt):
+    """ddz_search (hidden form) on visits / wins pre-filled with SENTINEL (BatchedEnv.search zeroes its own)"""
+    env.legal_slab()
+    n = env.T * env.slab_stride
+    v = torch.full((n,), SENTINEL, dtype=torch.int32, device=_dev())
+    w = torch.full((n,), SENTINEL, dtype=torch.int32, device=_dev())
+    totals = torch.zeros(4, dtype=torch.int64, device=_dev())
+    need = env.lib.ddz_search_work_bytes(env.T, budget, trees)
+    work = torch.empty(need, dtype=torch.uint8, device=_dev())
+    rc = env.lib.ddz_search(env._h, budget, trees, env.SEARCH_MODES["reference"], 0.7, salt, 1, 0b111, env.slab_stride,
+                            v.data_ptr(), w.data_ptr(), totals.data_ptr(), work.data_ptr(), need, None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return (v.view(env.T, -1).cpu().numpy().astype(np.int64), w.view(env.T, -1).cpu().numpy().astype(np.int64),
+            totals.cpu().numpy())
+
+
+def test_hidden_out_of_domain_between_running_tables(pkg, oracle):
+    """k_search<true> on roots outside the hidden-hand domain (playout spec v2): status bit 6, nothing of theirs written,
+    the tables between them searched as the reference searches them"""
+    budget, trees, salt, seed, base = 8, 2, 3, 4, 2 ** 40
+    names, bad = hc.out_of_domain()
+    good = hc.degenerate()[1]
+    st = np.zeros((2 * len(bad), 11, 16), np.uint8)
+    st[0::2], st[1::2] = good[:len(bad)], bad
+    want = sr.search(oracle, st, budget, trees=trees, seed=seed, gid_base=base, salt=salt, hidden=True)
+    assert (want[0][0::2].sum(1) == budget * trees).all() and not want[0][1::2].any()   # the reference's own result first
+    assert want[2][1] == budget * trees * len(bad)
+    env = _env(pkg, st, seed, base)
+    assert env.status() == 0
+    v, w, tot = _raw_hidden(pkg, env, budget, trees, salt)
+    assert env.status() & OUT_OF_DOMAIN
+    assert (v[1::2] == SENTINEL).all() and (w[1::2] == SENTINEL).all(), "a table outside the domain was written"
+    assert np.array_equal(v[0::2] - SENTINEL, want[0][0::2]) and np.array_equal(w[0::2] - SENTINEL, want[1][0::2])
+    assert np.array_equal(tot, want[2])
+    # one violation at a time: each raises the bit on its own, the table beside it is searched
+    pair = sr.search(oracle, np.stack([good[0], bad[0]]), budget, trees=trees, seed=seed, salt=salt, hidden=True)
+    for i, name in enumerate(names):
+        one = _env(pkg, np.stack([good[0], bad[i]]), seed, 0)
+        v, w, tot = _raw_hidden(pkg, one, budget, trees, salt)
+        assert one.status() & OUT_OF_DOMAIN, name
+        assert (v[1] == SENTINEL).all() and (w[1] == SENTINEL).all(), name
+        assert np.array_equal(v[0] - SENTINEL, pair[0][0]) and np.array_equal(w[0] - SENTINEL, pair[1][0]), name
+        assert np.array_equal(tot, pair[2]), name
+    clean = _env(pkg, good, seed, 0)
+    _raw_hidden(pkg, clean, budget, trees, salt)
+    assert clean.status() == 0
 
 
 def test_joker_kicker_build(pkg, oracle, jk):
