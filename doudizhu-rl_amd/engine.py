@@ -39,6 +39,36 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _ptrs(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _chk(x, name, dtype, dev, shape=None, numel=None, at_least=None, where="on the same device", why="", pinned=False,
+         none_ok=False):
+    """The one test of a caller's buffer before its address reaches the library: `x` has `dtype`, lives on `dev` (pinned: or in
+    pinned host memory, which the device reads and writes), is contiguous, and has exactly `shape`, exactly `numel` elements or
+    `at_least` that many (none of the three: a byte workspace whose size travels with its address, for the library to test)
+    -> x, or ValueError.  none_ok: None passes as None.  why: what the message cannot show otherwise."""
+    if x is None and none_ok:
+        return None
+    if (x is None or x.dtype != dtype or not x.is_contiguous()
+            or (x.device != dev and not (pinned and x.device.type == "cpu" and x.is_pinned()))
+            or (shape is not None and tuple(x.shape) != tuple(shape)) or (numel is not None and x.numel() != numel)
+            or (at_least is not None and x.numel() < at_least)):
+        size = list(shape) if shape is not None else [numel] if numel is not None else f"[>= {at_least or 0}]"
+        raise ValueError(f"{name} must be a contiguous {dtype} {size} tensor {where}{why}")
+    return x
+
+
+def _roles_mask(roles, hidden=True, name="roles"):
+    roles = int(roles)
+    if not 0 <= roles <= 7:
+        raise ValueError(f"{name} is a mask of the role bits 0 (up), 1 (lord), 2 (down)")
+    if not hidden and roles != 0b111:
+        raise ValueError(f"{name} needs hidden=True (the open form takes every running table)")
+    return roles
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -128,6 +158,58 @@ class BatchedEnv:
     def hands(self):
         return self.state.view(self.T, NFIELDS, ROW)[:, F_HAND0:F_HAND0 + 3]
 
+    # ---- a caller's buffers: every one passes _chk before its address reaches the library ----
+    def _arg(self, x, name, dtype, **size):
+        return _chk(x, name, dtype, self.device, where="on the env's device", **size)
+
+    def _traj(self, traj, n_iters=1):
+        return self._arg(traj, "traj", torch.uint8, numel=n_iters * self.T * TRAJ_BYTES, none_ok=True)
+
+    def _totals(self, totals):
+        return self._arg(totals, "totals", torch.int64, at_least=4, none_ok=True)
+
+    def _ids_out(self, out):
+        """int32 [T] to write ids / list indices into, made if None (a host_mirror env also takes pinned host memory)"""
+        if out is None:
+            return torch.empty(self.T, dtype=torch.int32, device=self.device)
+        return self._arg(out, "out", torch.int32, numel=self.T, pinned=self.host_mirror)
+
+    def _slab_counts(self, x, name):
+        """int32 [T * stride] of a number per list entry, made if None"""
+        if x is None:
+            return torch.empty(self.T * self.slab_stride, dtype=torch.int32, device=self.device)
+        return self._arg(x, name, torch.int32, numel=self.T * self.slab_stride)
+
+    def _q_slab_arg(self, q):
+        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
+            q = q.to(device=self.device, dtype=torch.float32).contiguous()
+        if q.numel() != self.T * self.slab_stride:
+            raise ValueError("q must be [T, stride]")
+        return q
+
+    def _face_out(self, out, variant, name="out"):
+        """float32 [T,P,15,4] for the faces of `variant`, made if None"""
+        P = FACE_PLANES[variant]
+        if out is None:
+            return torch.empty((self.T, P, 15, 4), dtype=torch.float32, device=self.device)
+        return self._arg(out, name, torch.float32, numel=self.T * P * 60, why=f" ([T,{P},15,4])")
+
+    def _shared_rows_out(self, n_nets, ws, row_capacity, rows, rep, seg):
+        """what a shared-row finder writes, n_nets partitions of row_capacity rows"""
+        self._arg(ws, "ws", torch.uint8)
+        self._arg(rows, "rows", torch.int32, shape=(self.T, 16))
+        self._arg(rep, "rep", torch.int32, at_least=n_nets * int(row_capacity))
+        self._arg(seg, "seg", torch.int32, at_least=40 * n_nets)
+
+    def _cfr_tensors(self, t, name):
+        """the (n, ids, sigma, value) of a cfr() call, handed back as `name`; value: checked by cfr(), which alone writes it"""
+        n, ids, sigma, value = t
+        why = f" (of {name}: the (n, ids, sigma, value) of an earlier cfr() call)"
+        self._arg(n, "n", torch.int32, numel=self.T, why=why)
+        self._arg(ids, "ids", torch.int32, numel=self.T * self.CFR_STRIDE, why=why)
+        self._arg(sigma, "sigma", torch.float64, numel=self.T * self.CFR_STRIDE, why=why)
+        return n, ids, sigma, value
+
     # ---- verbs ----
     def reset(self, mask=None):
         """Env.reset() + prepare() (envi.py:30-36, game.py:170-171) for masked tables."""
@@ -158,6 +240,7 @@ class BatchedEnv:
         (-1 = engine RNG for that table), what auto_choose() returns.  Returns (done u8[T], r i8[T],
         illegal u8[T]); r = -1 lord won, +1 farmers won (rule_play.py:14)."""
         self._need_legal()
+        self._traj(traj)
         if mode in (STEP_CHOICE, STEP_IDS):
             sel = sel.to(device=self.device, dtype=torch.int32).contiguous()
             if sel.numel() != self.T:
@@ -168,9 +251,6 @@ class BatchedEnv:
                 raise ValueError("rows must be [T,16] int8")
         elif mode != STEP_RANDOM:
             raise ValueError("bad step mode")
-        if traj is not None and (traj.dtype != torch.uint8 or traj.numel() != self.T * TRAJ_BYTES
-                                 or not traj.is_contiguous()):
-            raise ValueError("traj must be a contiguous uint8 [T,32] tensor")
         check(self.lib.ddz_step(self._h, mode, _p(sel) if mode != STEP_RANDOM else None,
                                 _p(self.offsets), _p(self.rows), int(bool(auto_reset)),
                                 _p(self.done), _p(self.reward), _p(self.illegal), _p(traj),
@@ -199,10 +279,8 @@ class BatchedEnv:
         canonical action ids, -1 for the other tables (-2 = DDZ_AUTO_INVALID: a state the agent cannot decide, which
         DDZ_STEP_IDS flags illegal -- never a silent random move).  stats: optional int64 [T,2] {combinations, search nodes} of the full
         enumeration; without it the kernel runs an exact branch and bound (same ids, ~3x faster)."""
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
-        if stats is not None and (stats.dtype != torch.int64 or stats.numel() != 2 * self.T or not stats.is_contiguous()):
-            raise ValueError("stats must be a contiguous int64 [T,2] tensor")
+        out = self._ids_out(out)
+        self._arg(stats, "stats", torch.int64, numel=2 * self.T, none_ok=True)
         if _debug_kernel is not None:  # test hook: 1 = the sequential cross-check kernel, 2 = the product kernel
             check(self.lib.ddz_debug_auto_choose_state(self._h, int(_debug_kernel), int(auto_roles), _p(out), _p(stats),
                                                        _stream(self.device)))
@@ -221,18 +299,13 @@ class BatchedEnv:
 
     def observe(self, variant=3, out=None):
         """`face` of every table: f32 [T,P,15,4] (envi.py:87-96,165-217)."""
-        P = FACE_PLANES[variant]
-        if out is None:
-            out = torch.empty((self.T, P, 15, 4), dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.numel() != self.T * P * 60 or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 [T,{P},15,4] tensor")
+        out = self._face_out(out, variant)
         check(self.lib.ddz_observe(self._h, int(variant), _p(out), _stream(self.device)))
         return out
 
     # ---- the transition recorder (csrc/ddz_replay.h; dqn_glue.TransitionRecorder) ----
     def _check_tr(self, ws, rings, capacity, need):
-        if ws.dtype != torch.uint8 or ws.device != self.device or not ws.is_contiguous() or ws.numel() < tr_ws_bytes(self.T):
-            raise ValueError("ws must be a contiguous uint8 device tensor of tr_ws_bytes(T) bytes")
+        self._arg(ws, "ws", torch.uint8, at_least=tr_ws_bytes(self.T), why=" (tr_ws_bytes(T) bytes)")
         if len(rings) != 3:
             raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
         nbytes = tr_ring_bytes(capacity)
@@ -240,30 +313,21 @@ class BatchedEnv:
             if ring is None:
                 if (need >> k) & 1:
                     raise ValueError("a trained role needs a ring")
-            elif ring.dtype != torch.uint8 or ring.device != self.device or not ring.is_contiguous() or ring.numel() != nbytes:
-                raise ValueError("a ring must be a contiguous uint8 device tensor of tr_ring_bytes(capacity) bytes")
+            else:
+                self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (tr_ring_bytes(capacity) bytes)")
         return (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rings]), nbytes
 
-    def _ids_arg(self, x, name):
-        if x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous() or x.numel() != self.T:
-            raise ValueError(f"{name} must be a contiguous int32 [T] device tensor")
-        return x
-
-    def _u8_arg(self, x, name, dtype=torch.uint8):
-        if x.dtype == torch.bool and dtype == torch.uint8:
-            x = x.to(torch.uint8)
-        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or x.numel() != self.T:
-            raise ValueError(f"{name} must be a contiguous {dtype} [T] device tensor")
-        return x
+    def _u8_arg(self, x, name):
+        """uint8 [T]; a bool [T] is converted"""
+        return self._arg(x.to(torch.uint8) if x.dtype == torch.bool else x, name, torch.uint8, numel=self.T)
 
     def tr_before(self, ws, rings, capacity, chosen, greedy, active=None, trained_roles=0b111):
         """ddz_tr_before: close and open transitions on the CURRENT states (call it before the step).  chosen / greedy int32 [T]
         canonical action ids, active u8 / bool [T] or None (all tables), trained_roles: bit r = role r.  No host sync."""
-        trained_roles = int(trained_roles)
-        if trained_roles & ~7:
-            raise ValueError("trained_roles is a mask of the role bits 0 (up), 1 (lord), 2 (down)")
+        trained_roles = _roles_mask(trained_roles, name="trained_roles")
         ptrs, nbytes = self._check_tr(ws, rings, capacity, trained_roles)
-        chosen, greedy = self._ids_arg(chosen, "chosen"), self._ids_arg(greedy, "greedy")
+        self._arg(chosen, "chosen", torch.int32, numel=self.T)
+        self._arg(greedy, "greedy", torch.int32, numel=self.T)
         if active is not None:
             active = self._u8_arg(active, "active")
         check(self.lib.ddz_tr_before(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(chosen), _p(greedy), _p(active),
@@ -273,7 +337,7 @@ class BatchedEnv:
         """ddz_tr_after: the terminal transitions of the finished tables (call it after step(auto_reset=False), before the
         re-deal).  done u8 [T], r i8 [T] as the step wrote them, reward: three floats in role order up, lord, down."""
         ptrs, nbytes = self._check_tr(ws, rings, capacity, 0)
-        done, r = self._u8_arg(done, "done"), self._u8_arg(r, "r", torch.int8)
+        done, r = self._u8_arg(done, "done"), self._arg(r, "r", torch.int8, numel=self.T)
         if len(reward) != 3:
             raise ValueError("reward: three floats in role order up, lord, down")
         check(self.lib.ddz_tr_after(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(done), _p(r),
@@ -285,9 +349,8 @@ class BatchedEnv:
         the current legal list; dqn.py:50-71).  Returns int32[T] indices for step(STEP_CHOICE)."""
         if not self._csr_fresh:   # after slab_to_csr() the offsets already describe the current lists: no ddz_legal
             self._need_legal()
+        out = self._ids_out(out)
         q = q.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
         check(self.lib.ddz_select(self._h, _p(q), _p(self.offsets), float(epsilon), _p(out),
                                   _stream(self.device)))
         return out
@@ -297,12 +360,7 @@ class BatchedEnv:
         int32[T] indices for step_slab(STEP_CHOICE).  Same greedy / epsilon-greedy rule and RNG as select()."""
         if not self._slab_fresh:
             self.legal_slab()
-        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
-            q = q.to(device=self.device, dtype=torch.float32).contiguous()
-        if q.numel() != self.T * self.slab_stride:
-            raise ValueError("q must be [T, stride]")
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        out, q = self._ids_out(out), self._q_slab_arg(q)
         check(self.lib.ddz_select_slab(self._h, _p(q), self._pp["counts"], self.slab_stride, float(epsilon), _p(out),
                                        _stream(self.device)))
         return out
@@ -313,10 +371,10 @@ class BatchedEnv:
         writes row_index int32 [T,64], seg int32 [40] and row_cnt uint8 [row_capacity] (device); nothing crosses to the host."""
         if not self._slab_fresh:
             self.legal_slab()
-        if (row_index.dtype != torch.int32 or tuple(row_index.shape) != (self.T, 64) or not row_index.is_contiguous()
-                or seg.dtype != torch.int32 or seg.numel() < 40 or scratch.dtype != torch.uint8
-                or row_cnt.dtype != torch.uint8 or row_cnt.numel() < int(row_capacity)):
-            raise ValueError("row_index must be int32 [T,64], seg int32 [40], scratch uint8, row_cnt uint8 [row_capacity]")
+        self._arg(scratch, "scratch", torch.uint8)
+        self._arg(row_index, "row_index", torch.int32, shape=(self.T, 64))
+        self._arg(seg, "seg", torch.int32, at_least=40)
+        self._arg(row_cnt, "row_cnt", torch.uint8, at_least=int(row_capacity))
         check(self.lib.ddz_q_need(self._h, self._pp["counts"], self._pp["rows"], self.slab_stride, int(row_capacity),
                                   _p(scratch), scratch.numel(), _p(row_index), _p(seg), _p(row_cnt), _stream(self.device)))
 
@@ -326,9 +384,7 @@ class BatchedEnv:
         variant 3 (EnvCooperationSimplify): direct-addressed, ws uint8 [q_shared_ws_bytes()]; variants 1 / 2 (EnvComplicated /
         EnvCooperation): ddz_q_shared_rows_hashed, ws uint8 [q_shared_hash_ws_bytes(T)], row_capacity >= 15 T + 15 tiles (any
         other variant: DdzError).  Nothing crosses to the host."""
-        if (rows.dtype != torch.int32 or tuple(rows.shape) != (self.T, 16) or not rows.is_contiguous() or rep.dtype != torch.int32
-                or rep.numel() < int(row_capacity) or seg.dtype != torch.int32 or seg.numel() < 40 or ws.dtype != torch.uint8):
-            raise ValueError("rows must be int32 [T,16], rep int32 [row_capacity], seg int32 [40], ws uint8")
+        self._shared_rows_out(1, ws, row_capacity, rows, rep, seg)
         if int(variant) == 3:
             check(self.lib.ddz_q_shared_rows(self._h, _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep), _p(seg),
                                              _stream(self.device)))
@@ -340,14 +396,14 @@ class BatchedEnv:
         """the argument checks of q_shared_need (n_nets None: one partition) and q_roles_need (n_nets slot-major partitions of
         row_capacity rows, a segment table each); returns the number of partitions"""
         N = 1 if n_nets is None else int(n_nets)
-        for x, shp in ((row_index, (self.T, 64)), (row_index2, (self.T, 64)), (rows, (self.T, 16))):
-            if x.dtype != torch.int32 or tuple(x.shape) != shp or not x.is_contiguous():
-                raise ValueError("row_index / row_index2 must be int32 [T,64], rows int32 [T,16]")
-        if (drep.dtype != torch.int32 or drep.numel() < N * int(row_capacity) or row_cnt.dtype != torch.uint8
-                or row_cnt.numel() < N * int(row_capacity) or dseg.dtype != torch.int32 or dseg.numel() < 40 * N
-                or sseg.dtype != torch.int32 or sseg.numel() < 40 * N or ws.dtype != torch.uint8):
-            raise ValueError("drep int32 [row_capacity], row_cnt uint8 [row_capacity], dseg / sseg int32 [40], ws uint8" if n_nets is None
-                             else "drep int32 / row_cnt uint8 [n_nets * row_capacity], dseg / sseg int32 [n_nets,40], ws uint8")
+        self._arg(row_index, "row_index", torch.int32, shape=(self.T, 64))
+        self._arg(rows, "rows", torch.int32, shape=(self.T, 16))
+        self._arg(sseg, "sseg", torch.int32, at_least=40 * N)
+        self._arg(ws, "ws", torch.uint8)
+        self._arg(row_index2, "row_index2", torch.int32, shape=(self.T, 64))
+        self._arg(drep, "drep", torch.int32, at_least=N * int(row_capacity))
+        self._arg(dseg, "dseg", torch.int32, at_least=40 * N)
+        self._arg(row_cnt, "row_cnt", torch.uint8, at_least=N * int(row_capacity))
         return N
 
     def q_shared_need(self, row_index, rows, sseg, shared_row_capacity, ws, row_capacity, row_index2, drep, dseg, row_cnt):
@@ -357,28 +413,28 @@ class BatchedEnv:
         check(self.lib.ddz_q_shared_need(self._h, _p(row_index), _p(rows), _p(sseg), int(shared_row_capacity), _p(ws), ws.numel(),
                                          int(row_capacity), _p(row_index2), _p(drep), _p(dseg), _p(row_cnt), _stream(self.device)))
 
-    def _check_q_slab(self, n_nets, h0, d, out, slot=None, w2=None, b2=None):
-        """the argument checks of q_slab_needed (n_nets None: `out` may be None and is then made) and q_roles_slab (+ the per-slot
-        operands), behind a fresh legal_slab(); returns (hidden, out)"""
+    def _check_q_slab(self, n_nets, h0, d, row_index, w2, b2, out, slot=None):
+        """the argument checks of q_slab_needed (n_nets None: one network, and `out` may be None and is then made) and q_roles_slab
+        (+ slot), behind a fresh legal_slab(); returns (hidden, out)"""
         if not self._slab_fresh:
             self.legal_slab()
-        H = int(h0.shape[-1])
-        for x, shp in ((h0, (self.T, H)), (d, (d.shape[0], H))):
-            if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != self.device:
-                raise ValueError("h0 must be float32 [T,hidden], d float32 [rows,hidden], contiguous, on the engine's device")
+        H, N = int(h0.shape[-1]), 1 if n_nets is None else int(n_nets)
+        self._arg(h0, "h0", torch.float32, shape=(self.T, H))
+        self._arg(d, "d", torch.float32, shape=(d.shape[0], H))
+        self._arg(row_index, "row_index", torch.int32, shape=(self.T, 64))
+        self._arg(w2, "w2", torch.float32, numel=N * H)
+        self._arg(b2, "b2", torch.float32, numel=N)
         if out is None and n_nets is None:
             out = torch.zeros((self.T, self.slab_stride), dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.numel() != self.T * self.slab_stride or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [T, stride] tensor")
-        if n_nets is not None and (slot.dtype != torch.int8 or slot.numel() != self.T or w2.numel() != int(n_nets) * H
-                                   or b2.numel() != int(n_nets)):
-            raise ValueError("slot must be int8 [T], w2 float32 [n_nets,hidden], b2 float32 [n_nets]")
+        self._arg(out, "out", torch.float32, numel=self.T * self.slab_stride)
+        if n_nets is not None:
+            self._arg(slot, "slot", torch.int8, numel=self.T)
         return H, out
 
     def q_slab_needed(self, h0, d, row_index, w2, b2, out=None):
         """ddz_q_slab_needed: q f32 [T, stride] of every legal move from h0 f32 [T,256], d f32 [rows,256] (with z folded in by
         q_fc1_rows), row_index."""
-        H, out = self._check_q_slab(None, h0, d, out)
+        H, out = self._check_q_slab(None, h0, d, row_index, w2, b2, out)
         check(self.lib.ddz_q_slab_needed(self._h, _p(h0), _p(d), int(d.shape[0]), _p(row_index), H, _p(w2), _p(b2),
                                          self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
         return out
@@ -390,10 +446,8 @@ class BatchedEnv:
         int32 [n_nets * row_capacity], seg int32 [n_nets, 40] (per slot, relative to its partition of row_capacity rows), slot
         int8 [T] (-1 = rule table).  ws uint8 [q_roles_ws_bytes(T, variant, n_nets)]."""
         N = int(n_nets)
-        if (rows.dtype != torch.int32 or tuple(rows.shape) != (self.T, 16) or not rows.is_contiguous() or rep.dtype != torch.int32
-                or rep.numel() < N * int(row_capacity) or seg.dtype != torch.int32 or seg.numel() < 40 * N or ws.dtype != torch.uint8
-                or slot.dtype != torch.int8 or slot.numel() != self.T):
-            raise ValueError("rows must be int32 [T,16], rep int32 [n_nets * row_capacity], seg int32 [n_nets,40], slot int8 [T], ws uint8")
+        self._shared_rows_out(N, ws, row_capacity, rows, rep, seg)
+        self._arg(slot, "slot", torch.int8, numel=self.T)
         m = (C.c_int32 * 3)(*[int(x) for x in net_of_role])
         check(self.lib.ddz_q_roles_rows(self._h, int(variant), m, N, _p(ws), ws.numel(), int(row_capacity), _p(rows), _p(rep), _p(seg),
                                         _p(slot), _stream(self.device)))
@@ -407,7 +461,7 @@ class BatchedEnv:
     def q_roles_slab(self, n_nets, slot, h0, d, row_index, w2, b2, out):
         """ddz_q_roles_slab: q_slab_needed with the weights of each table's slot (w2 f32 [n_nets,256], b2 f32 [n_nets]); every
         entry of a rule table (slot < 0) is left alone."""
-        H, out = self._check_q_slab(n_nets, h0, d, out, slot, w2, b2)
+        H, out = self._check_q_slab(n_nets, h0, d, row_index, w2, b2, out, slot)
         check(self.lib.ddz_q_roles_slab(self._h, int(n_nets), _p(slot), _p(h0), _p(d), int(d.shape[0]), _p(row_index), H, _p(w2), _p(b2),
                                         self._pp["counts"], self._pp["rows"], self.slab_stride, _p(out), _stream(self.device)))
         return out
@@ -441,8 +495,8 @@ class BatchedEnv:
         W = self.lib.ddz_mask_words()
         if out is None:
             out = torch.empty((self.T, W), dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or tuple(out.shape) != (self.T, W) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous int32 [T,{W}] tensor")
+        else:
+            self._arg(out, "out", torch.int32, shape=(self.T, W))
         check(self.lib.ddz_legal_mask(self._h, _p(out), _stream(self.device)))
         if not unpack:
             return out
@@ -473,6 +527,7 @@ class BatchedEnv:
         states (game.py:95-106 + envi.py:98-116).  Returns (done, r, illegal) like step()."""
         if not self._slab_fresh:
             self.legal_slab()
+        self._traj(traj)
         pinned = sel is not None and sel.device.type == "cpu" and sel.is_pinned()   # (pinned host memory is device-readable)
         if mode in (STEP_CHOICE, STEP_IDS):
             if sel.dtype != torch.int32 or (sel.device != self.device and not pinned) or not sel.is_contiguous():  # (the host
@@ -486,9 +541,6 @@ class BatchedEnv:
                 raise ValueError("rows must be [T,16] int8")
         elif mode != STEP_RANDOM:
             raise ValueError("bad step mode")
-        if traj is not None and (traj.dtype != torch.uint8 or traj.numel() != self.T * TRAJ_BYTES
-                                 or not traj.is_contiguous()):
-            raise ValueError("traj must be a contiguous uint8 [T,32] tensor")
         pp = self._pp
         check(self.lib.ddz_step_slab(self._h, mode, _p(sel) if mode != STEP_RANDOM else None, pp["counts"],
                                      pp["rows"], pp["ids"], self.slab_stride, 1 if auto_reset else 0,
@@ -505,20 +557,10 @@ class BatchedEnv:
         face | None); bit-identical to the three separate calls."""
         if not self._slab_fresh:
             self.legal_slab()
-        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
-            q = q.to(device=self.device, dtype=torch.float32).contiguous()
-        if q.numel() != self.T * self.slab_stride:
-            raise ValueError("q must be [T, stride]")
-        face = None
-        if face_variant is not None:
-            P = FACE_PLANES[face_variant]
-            face = face_out if face_out is not None else torch.empty((self.T, P, 15, 4), dtype=torch.float32, device=self.device)
-            if face.dtype != torch.float32 or face.numel() != self.T * P * 60 or not face.is_contiguous():
-                raise ValueError(f"face_out must be a contiguous float32 [T,{P},15,4] tensor")
-        if traj is not None and (traj.dtype != torch.uint8 or traj.numel() != self.T * TRAJ_BYTES or not traj.is_contiguous()):
-            raise ValueError("traj must be a contiguous uint8 [T,32] tensor")
-        if choice_out is not None and (choice_out.dtype != torch.int32 or choice_out.numel() != self.T):
-            raise ValueError("choice_out must be int32 [T]")
+        self._traj(traj)
+        self._arg(choice_out, "choice_out", torch.int32, numel=self.T, none_ok=True)
+        face = None if face_variant is None else self._face_out(face_out, face_variant, "face_out")
+        q = self._q_slab_arg(q)
         pp = self._pp
         check(self.lib.ddz_policy_step_slab(self._h, _p(q), float(epsilon), pp["counts"], pp["rows"], pp["ids"],
                                             self.slab_stride, 1 if auto_reset else 0, pp["done"], pp["reward"],
@@ -551,9 +593,7 @@ class BatchedEnv:
         iteration's *pre-step* states are left in the slab layout (counts, slab_rows())."""
         if self.slab_stride < MAX_LEGAL_PER_TABLE:
             raise ValueError(f"rollout needs row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
-        if traj is not None and (traj.dtype != torch.uint8 or not traj.is_contiguous()
-                                 or traj.numel() != n_iters * self.T * TRAJ_BYTES):
-            raise ValueError("traj must be a contiguous uint8 [n_iters,T,32] tensor")
+        self._traj(traj, n_iters)
         check(self.lib.ddz_rollout_random(self._h, int(n_iters), _p(self.counts), _p(self.rows),
                                           _p(self.ids), self.slab_stride, _p(self._stats), _p(traj),
                                           _stream(self.device)))
@@ -574,11 +614,7 @@ class BatchedEnv:
         n_playouts worlds -- the evaluation a seat may use, and the one a state from a plain serving payload allows.  A table
         whose hand, taken row and sizes do not add up to a deck runs nothing and raises status bit 6.  roles (hidden form
         only): bit r set = tables whose actor is role r take part, the others are idle."""
-        roles = int(roles)
-        if not 0 <= roles <= 7:
-            raise ValueError("roles is a mask of the three roles (0 .. 7)")
-        if not hidden and roles != 0b111:
-            raise ValueError("roles needs hidden=True (the open form evaluates every running table)")
+        roles = _roles_mask(roles, hidden)
         st = self.slab_stride
         if st < MAX_LEGAL_PER_TABLE:
             raise ValueError(f"playouts need row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
@@ -594,14 +630,9 @@ class BatchedEnv:
             # (measured, profiles/r11_notes.md: 12 .. 24 chunks are best at K = 8, 24 .. 96 at K = 64)
             fill = -(-24576 // self.T)
             chunks = max(1, min(max(fill, min(3 * n_playouts, 96)), max(fill, 1572864 // self.T), 8192))
-        if wins is None:
-            wins = torch.empty(self.T * st, dtype=torch.int32, device=self.device)
-        elif wins.dtype != torch.int32 or wins.device != self.device or wins.numel() != self.T * st or not wins.is_contiguous():
-            raise ValueError("wins must be a contiguous int32 [T * stride] tensor on the env's device")
-        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
-                                   or not totals.is_contiguous()):
-            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
-        wins.zero_()                    # (an enqueued memset of the whole buffer)
+        wins = self._slab_counts(wins, "wins")
+        self._totals(totals)
+        wins.zero_()                   # (an enqueued memset of the whole buffer)
         if hidden:
             check(self.lib.ddz_playout_hidden(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, roles, _p(wins),
                                               _p(totals), _stream(self.device)))
@@ -616,15 +647,14 @@ class BatchedEnv:
         uniform deal of the cards the actor has not seen, with the known hand sizes.  A sampler for any search built on
         top.  Rows of idle tables, of tables `roles` leaves out and of tables outside the domain (status bit 6) are zero
         (left as they are in a buffer handed in as `out`).  The env is only read; one launch, capturable."""
-        n_worlds, roles = int(n_worlds), int(roles)
+        n_worlds = int(n_worlds)
         if not 1 <= n_worlds < (1 << 23) or self.T * n_worlds > 0x7FFFFFFF:
             raise ValueError("n_worlds must be in [1, 2^23) and T * n_worlds below 2^31")
-        if not 0 <= roles <= 7:
-            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        roles = _roles_mask(roles)
         if out is None:
             out = torch.zeros((self.T, n_worlds, 2, ROW), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or out.device != self.device or out.numel() != self.T * n_worlds * 2 * ROW or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 [T, n_worlds, 2, 16] tensor on the env's device")
+        else:
+            self._arg(out, "out", torch.uint8, numel=self.T * n_worlds * 2 * ROW, why=" ([T, n_worlds, 2, 16])")
         check(self.lib.ddz_playout_worlds(self._h, n_worlds, int(salt) & 0xFFFFFFFF, roles, _p(out), _stream(self.device)))
         return out.view(self.T, n_worlds, 2, ROW)
 
@@ -635,12 +665,9 @@ class BatchedEnv:
         `roles`, or outside the domain) has all-zero counts and so gets the first move of its list: mask the ids by role."""
         if self.ids is None:
             raise ValueError("playout_choose needs the action ids of the lists (want_ids=True)")
+        out = self._ids_out(out)
         self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None),
                                           hidden=hidden, roles=roles)
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
         check(self.lib.ddz_playout_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
                                           _p(self._playout_wins), _p(out), _stream(self.device)))
         return out
@@ -664,11 +691,7 @@ class BatchedEnv:
         tables whose actor is role r take part.  visits / wins: int32 [T * stride] buffers to reuse (zeroed here); totals:
         int64 [4] on the device, += {moves applied, iterations run, iterations scored unfinished, nodes created}.  The
         trees live in a workspace of ddz_search_work_bytes(T, budget, trees) bytes cached on the env."""
-        roles = int(roles)
-        if not 0 <= roles <= 7:
-            raise ValueError("roles is a mask of the three roles (0 .. 7)")
-        if not hidden and roles != 0b111:
-            raise ValueError("roles needs hidden=True (the open form searches every running table)")
+        roles = _roles_mask(roles, hidden)
         if mode not in self.SEARCH_MODES:
             raise ValueError('mode is "reference" or "sides"')
         st = self.slab_stride
@@ -687,17 +710,8 @@ class BatchedEnv:
             raise ValueError("trees must be in [1, 65536]")
         if not self._slab_fresh:        # entry [t, j] is read against the lists of the current state
             self.legal_slab()
-        bufs = []
-        for name, b in (("visits", visits), ("wins", wins)):
-            if b is None:
-                b = torch.empty(self.T * st, dtype=torch.int32, device=self.device)
-            elif b.dtype != torch.int32 or b.device != self.device or b.numel() != self.T * st or not b.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous int32 [T * stride] tensor on the env's device")
-            bufs.append(b)
-        visits, wins = bufs
-        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
-                                   or not totals.is_contiguous()):
-            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
+        visits, wins = self._slab_counts(visits, "visits"), self._slab_counts(wins, "wins")
+        self._totals(totals)
         need = int(self.lib.ddz_search_work_bytes(self.T, budget, trees))
         if need < 0:
             raise ValueError("no workspace size for these arguments")
@@ -716,13 +730,10 @@ class BatchedEnv:
         (idle tables, tables the hidden form leaves out).  Feed them to step_slab(mode=STEP_IDS)."""
         if self.ids is None:
             raise ValueError("search_choose needs the action ids of the lists (want_ids=True)")
+        out = self._ids_out(out)
         v, w = self.search(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles,
                            visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
         self._search_visits, self._search_wins = v.view(-1), w.view(-1)
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
         check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
                                          _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
         return out
@@ -751,28 +762,22 @@ class BatchedEnv:
         the slots report -2 and can be solved by a second call with more slots or with `roles` / fewer tables.
         totals: int64 [4] on the device, += {deals, nodes, information sets, (set, action) pairs}.  out: the four tensors of
         an earlier call, to reuse."""
-        iterations, roles = int(iterations), int(roles)
+        iterations = int(iterations)
         if not 0 <= iterations <= self.CFR_MAX_ITERATIONS:
             raise ValueError(f"iterations must be in [0, {self.CFR_MAX_ITERATIONS}]")
-        if not 0 <= roles <= 7:
-            raise ValueError("roles is a mask of the three roles (0 .. 7)")
+        roles = _roles_mask(roles)
         slots = self.cfr_default_slots() if slots is None else int(slots)
         need = int(self.lib.ddz_cfr_work_bytes(slots))
         if slots < 0 or need < 0:
             raise ValueError("slots must be in [0, 2^24]")
-        if totals is not None and (totals.dtype != torch.int64 or totals.device != self.device or totals.numel() < 4
-                                   or not totals.is_contiguous()):
-            raise ValueError("totals must be a contiguous int64 [4] tensor on the env's device")
+        self._totals(totals)
         if out is None:
             out = (torch.empty(self.T, dtype=torch.int32, device=self.device),
                    torch.empty((self.T, self.CFR_STRIDE), dtype=torch.int32, device=self.device),
                    torch.empty((self.T, self.CFR_STRIDE), dtype=torch.float64, device=self.device),
                    torch.empty(self.T, dtype=torch.float64, device=self.device))
-        n, ids, sigma, value = out
-        for x, dt, numel in ((n, torch.int32, self.T), (ids, torch.int32, self.T * self.CFR_STRIDE),
-                             (sigma, torch.float64, self.T * self.CFR_STRIDE), (value, torch.float64, self.T)):
-            if x.dtype != dt or x.device != self.device or x.numel() != numel or not x.is_contiguous():
-                raise ValueError("out must be the (n, ids, sigma, value) tensors of an earlier call")
+        n, ids, sigma, value = self._cfr_tensors(out, "out")
+        self._arg(value, "value", torch.float64, numel=self.T, why=" (of out)")
         work = getattr(self, "_cfr_work", None)
         if work is None or work.numel() < need:
             self._cfr_work = work = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -785,14 +790,11 @@ class BatchedEnv:
         solved nothing (n <= 0: mask by it).  greedy: the first maximum of sigma; otherwise sampled from sigma as the
         reference's choose() does, with the engine's own draw (RNG domain 8, keyed by the table id, the seed and `salt`).
         solved: the (n, ids, sigma, value) of an earlier cfr() call to choose from (no solve)."""
+        out = self._ids_out(out)
         if solved is None:
             solved = self.cfr(iterations, roles=roles, slots=slots, out=getattr(self, "_cfr_out", None))
             self._cfr_out = solved
-        n, ids, sigma, _ = solved
-        if out is None:
-            out = torch.empty(self.T, dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or out.device != self.device or out.numel() != self.T or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int32 [T] tensor on the env's device")
+        n, ids, sigma, _ = self._cfr_tensors(solved, "solved")
         check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), int(salt) & 0xFFFFFFFF, int(bool(greedy)), _p(out),
                                       _stream(self.device)))
         return out
@@ -806,9 +808,7 @@ class BatchedEnv:
         less the launch's prologue weighs (tools/csr_batch_probe.py: 65,536 tables 1.95 G steps/s at 4 iterations per batch,
         2.81 G at 32); batch=0: the one-launch-per-iteration form (ddz_rollout_random_csr: CSR bases depend on every table,
         so each iteration waits for the scan of the one before)."""
-        if traj is not None and (traj.dtype != torch.uint8 or not traj.is_contiguous()
-                                 or traj.numel() != n_iters * self.T * TRAJ_BYTES):
-            raise ValueError("traj must be a contiguous uint8 [n_iters,T,32] tensor")
+        self._traj(traj, n_iters)
         if batch is None:
             per = self.T * MAX_LEGAL_PER_TABLE * (20 if self.ids is not None else 16)
             batch = max(2, min(512, CSR_STAGING_BYTES // per))
@@ -878,21 +878,19 @@ def observe_states(states, index=None, variant=3, out=None):
     BatchedEnv.observe's expression, bit for bit, on rows that are not an environment's.  No host sync."""
     dev = _require_gpu(states.device)
     P = FACE_PLANES[variant]
-    if states.dtype != torch.uint8 or not states.is_contiguous() or states.numel() % (NFIELDS * ROW):
-        raise ValueError("states must be a contiguous uint8 tensor of 176-byte rows")
     m = states.numel() // (NFIELDS * ROW)
+    _chk(states, "states", torch.uint8, dev, numel=m * NFIELDS * ROW, why=" (176-byte rows)")
     if index is None:
         n = m
     else:
-        if index.dtype != torch.int64 or index.device != dev or not index.is_contiguous() or index.dim() != 1:
-            raise ValueError("index must be a contiguous int64 [n] tensor on the states' device")
         n = index.numel()
+        _chk(index, "index", torch.int64, dev, shape=(n,))
         if n and m == 0:
             raise ValueError("index into an empty states tensor")
     if out is None:
         out = torch.empty((n, P, 15, 4), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != n * P * 60 or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 [n,{P},15,4] tensor")
+    else:
+        _chk(out, "out", torch.float32, dev, numel=n * P * 60, why=f" ([n,{P},15,4])")
     if n:
         check(_lib.lib().ddz_observe_states(dev.index, _p(states), _p(index), n, int(variant), _p(out), _stream(dev)))
     return out
@@ -948,44 +946,47 @@ def q_features(face, wf, bias, acnt, y):
     y f32 [15,5,T,K] (K >= 256; columns >= 256 and counts 2..4 of the joker ranks are left alone).
     dqn_glue.FactorisedQ.tables drives it."""
     L = _lib.lib()
-    dev = _require_gpu(face.device)
-    T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor")
-    if y.dtype != torch.float32 or tuple(y.shape[:3]) != (15, 5, T) or not y.is_contiguous() or y.device != dev:
-        raise ValueError("y must be a contiguous float32 [15,5,T,K] tensor on the same device")
-    for w, n in ((wf, P * 4 * 1024), (bias, 1024), (acnt, 5 * 4 * 256)):
-        if w.dtype != torch.float32 or w.numel() != n or not w.is_contiguous() or w.device != dev:
-            raise ValueError("weight tables must be contiguous float32 device tensors: wf [P*4,1024], bias [1024], acnt [5,4,256]")
+    dev, T, P = _face_arg(face)
+    _chk(y, "y", torch.float32, dev, shape=(15, 5, T, y.shape[3] if y.dim() == 4 else 0), why=" ([15,5,T,K])")
+    _weight_tables(dev, P, 1, wf, bias, acnt)
     check(L.ddz_q_features(dev.index, _p(face), T, P, _p(wf), _p(bias), _p(acnt), _p(y), int(y.shape[3]), _stream(dev)))
     return y
 
 
-def _q_first_operands(face, actions, weights, biases=None):
-    """shape / dtype / device / contiguity of the first layer's operands -> (device, n, planes)"""
+def _face_arg(face, planes=None):
+    """face float32 [n,P,15,4], P among `planes` (None: any) -> (device, n, P).  The face anchors the device of its call: a CPU
+    tensor is a DdzError before any shape is looked at."""
     dev = _require_gpu(face.device)
-    if face.dtype != torch.float32 or face.dim() != 4 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [n,P,15,4] tensor")
-    n, P = int(face.shape[0]), int(face.shape[1])
-    if P not in (4, 6, 7, 9):
-        raise ValueError("face must have 4, 6, 7 or 9 planes")
-    if actions.dtype != torch.float32 or tuple(actions.shape) != (n, 15, 4) or not actions.is_contiguous() or actions.device != dev:
-        raise ValueError("actions must be a contiguous float32 [n,15,4] tensor on the face's device")
-    if len(weights) != 4 or (biases is not None and len(biases) != 4):
-        raise ValueError("weights / biases: those of conv1..conv4")
-    for k in range(4):
-        w = weights[k]
-        if w.dtype != torch.float32 or tuple(w.shape) != (256, P + 1, 1, k + 1) or not w.is_contiguous() or w.device != dev:
-            raise ValueError(f"weights[{k}] must be a contiguous float32 [256,{P + 1},1,{k + 1}] tensor on the face's device")
-        if biases is not None:
-            b = biases[k]
-            if b.dtype != torch.float32 or tuple(b.shape) != (256,) or not b.is_contiguous() or b.device != dev:
-                raise ValueError(f"biases[{k}] must be a contiguous float32 [256] tensor on the face's device")
+    n, P = (int(face.shape[0]), int(face.shape[1])) if face.dim() == 4 else (0, 0)
+    if planes is not None and P not in planes:
+        raise ValueError(f"face must be [n,P,15,4] with P among {sorted(planes)}")
+    _chk(face, "face", torch.float32, dev, shape=(n, P, 15, 4))
     return dev, n, P
 
 
-def _ptr4(tensors):
-    return (C.c_void_p * 4)(*[t.data_ptr() for t in tensors])
+def _faces_arg(face, actions):
+    """the learner's faces: face float32 [n,P,15,4] + actions float32 [n,15,4] -> (device, n, P)"""
+    dev, n, P = _face_arg(face, FACE_PLANES)
+    _chk(actions, "actions", torch.float32, dev, shape=(n, 15, 4))
+    return dev, n, P
+
+
+def _conv_params(dev, P, count, weights, biases=None):
+    """the nn.Conv2d parameters of conv1..conv4 (count 4) and conv_shunzi (count 5) as they are"""
+    if len(weights) != count or (biases is not None and len(biases) != count):
+        raise ValueError("weights / biases: those of conv1..conv4" + (" and conv_shunzi" if count == 5 else ""))
+    for k in range(count):
+        _chk(weights[k], f"weights[{k}]", torch.float32, dev, shape=(256, P + 1, 1, k + 1) if k < 4 else (256, P + 1, 15, 1))
+        if biases is not None:
+            _chk(biases[k], f"biases[{k}]", torch.float32, dev, shape=(256,))
+
+
+def _weight_tables(dev, P, n_nets, wf, bias, *acnt):
+    """the first layer's tables of n_nets networks: wf [P*4,1024], bias [1024] and, where the call takes it, acnt [5,4,256] each"""
+    _chk(wf, "wf", torch.float32, dev, numel=n_nets * P * 4 * 1024, why=" ([P*4,1024] per network)")
+    _chk(bias, "bias", torch.float32, dev, numel=n_nets * 1024)
+    for a in acnt:
+        _chk(a, "acnt", torch.float32, dev, numel=n_nets * 5 * 4 * 256)
 
 
 def q_first_fwd(face, actions, weights, biases, want_arg=True):
@@ -993,11 +994,12 @@ def q_first_fwd(face, actions, weights, biases, want_arg=True):
     tensor never materialised: face f32 [n,P,15,4], actions f32 [n,15,4], weights / biases the nn.Conv2d parameters of conv1..4
     as they are ([256,P+1,1,k], [256]) -> (y f32 [n,3840] in the order of net.py:94's view, arg u8 [n,3840] = the lowest conv
     that attains the max -- what q_first_bwd routes by -- or None with want_arg=False).  No host sync."""
-    dev, n, P = _q_first_operands(face, actions, weights, biases)
+    dev, n, P = _faces_arg(face, actions)
+    _conv_params(dev, P, 4, weights, biases)
     y = torch.empty((n, 3840), dtype=torch.float32, device=dev)
     arg = torch.empty((n, 3840), dtype=torch.uint8, device=dev) if want_arg else None
     if n:
-        check(_lib.lib().ddz_q_first_fwd(dev.index, _p(face), _p(actions), n, P, _ptr4(weights), _ptr4(biases), _p(y), _p(arg),
+        check(_lib.lib().ddz_q_first_fwd(dev.index, _p(face), _p(actions), n, P, _ptrs(weights), _ptrs(biases), _p(y), _p(arg),
                                          _stream(dev)))
     return y, arg
 
@@ -1006,18 +1008,17 @@ def q_first_bwd(face, actions, gy, arg, weights):
     """ddz_q_first_bwd: the gradients of conv1..conv4's parameters from gy f32 [n,3840] and q_first_fwd's arg u8 [n,3840] (the
     conv that won takes the gradient), in the parameters' own shapes: (gw[4], gb[4]); `weights` give the shapes only.
     Deterministic (no atomics: per-block partials, a fixed-order reduce); no gradient of face / actions.  No host sync."""
-    dev, n, P = _q_first_operands(face, actions, weights)
-    if gy.dtype != torch.float32 or tuple(gy.shape) != (n, 3840) or not gy.is_contiguous() or gy.device != dev:
-        raise ValueError("gy must be a contiguous float32 [n,3840] tensor on the face's device")
-    if arg is None or arg.dtype != torch.uint8 or tuple(arg.shape) != (n, 3840) or not arg.is_contiguous() or arg.device != dev:
-        raise ValueError("arg must be q_first_fwd's contiguous uint8 [n,3840] tensor")
+    dev, n, P = _faces_arg(face, actions)
+    _conv_params(dev, P, 4, weights)
+    _chk(gy, "gy", torch.float32, dev, shape=(n, 3840))
+    _chk(arg, "arg", torch.uint8, dev, shape=(n, 3840), why=" (q_first_fwd's arg)")
     L = _lib.lib()
     if n == 0:
         return [torch.zeros_like(w) for w in weights], [torch.zeros(256, dtype=torch.float32, device=dev) for _ in range(4)]
     gw = [torch.empty_like(w) for w in weights]
     gb = [torch.empty(256, dtype=torch.float32, device=dev) for _ in range(4)]
     ws = torch.empty(int(L.ddz_q_first_bwd_ws_bytes(n, P)), dtype=torch.uint8, device=dev)
-    check(L.ddz_q_first_bwd(dev.index, _p(face), _p(actions), n, P, _p(gy), _p(arg), _ptr4(gw), _ptr4(gb), _p(ws), ws.numel(),
+    check(L.ddz_q_first_bwd(dev.index, _p(face), _p(actions), n, P, _p(gy), _p(arg), _ptrs(gw), _ptrs(gb), _p(ws), ws.numel(),
                             _stream(dev)))
     return gw, gb
 
@@ -1034,56 +1035,24 @@ def q_stage_source(face=None, actions=None, states=None, ids=None, index=None, t
     if states is None:
         if face is None or actions is None:
             raise ValueError("the stage's source is face + actions, or states + ids + table + variant")
-        dev = _require_gpu(face.device)
-        if face.dtype != torch.float32 or face.dim() != 4 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-            raise ValueError("face must be a contiguous float32 [n,P,15,4] tensor")
-        n, P = int(face.shape[0]), int(face.shape[1])
-        if P not in (4, 6, 7, 9):
-            raise ValueError("face must have 4, 6, 7 or 9 planes")
-        if actions.dtype != torch.float32 or tuple(actions.shape) != (n, 15, 4) or not actions.is_contiguous() or actions.device != dev:
-            raise ValueError("actions must be a contiguous float32 [n,15,4] tensor on the face's device")
+        dev, n, P = _faces_arg(face, actions)
         src.kind, src.planes, src.face, src.action = 0, P, face.data_ptr(), actions.data_ptr()
         return src, dev, n, P, (face, actions)
     dev = _require_gpu(states.device)
     if variant is None or not 0 <= int(variant) < len(FACE_PLANES):
         raise ValueError("variant must be a face variant 0..3")
-    if states.dtype != torch.uint8 or states.dim() != 2 or states.shape[1] != NFIELDS * ROW or not states.is_contiguous() \
-            or states.shape[0] == 0 or states.data_ptr() % 16:
-        raise ValueError("states must be a contiguous, 16-byte aligned uint8 [m,176] tensor with m > 0")
-    m = int(states.shape[0])
-    if ids is None or ids.dtype != torch.int32 or tuple(ids.shape) != (m,) or not ids.is_contiguous() or ids.device != dev:
-        raise ValueError("ids must be a contiguous int32 [m] tensor on the states' device")
-    if table is None or table.dtype != torch.int8 or table.dim() != 2 or table.shape[1] != 16 or table.shape[0] == 0 \
-            or not table.is_contiguous() or table.device != dev:
-        raise ValueError("table must be the contiguous int8 [n_actions,16] action table on the states' device")
-    if index is None:
-        n = m
-    else:
-        if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != dev:
-            raise ValueError("index must be a contiguous int64 [n] tensor on the states' device")
-        n = int(index.numel())
-    src.kind, src.variant, src.n_actions, src.n_rows = 1, int(variant), int(table.shape[0]), m
+    m, n_actions = int(states.shape[0]), 0 if table is None else int(table.shape[0])
+    if m == 0 or n_actions == 0 or states.data_ptr() % 16:
+        raise ValueError("states must be 16-byte aligned with m > 0 rows, table the action table")
+    _chk(states, "states", torch.uint8, dev, shape=(m, NFIELDS * ROW))
+    _chk(ids, "ids", torch.int32, dev, shape=(m,))
+    _chk(table, "table", torch.int8, dev, shape=(n_actions, 16), why=" (action_table)")
+    n = m if index is None else int(index.numel())
+    _chk(index, "index", torch.int64, dev, shape=(n,), none_ok=True)
+    src.kind, src.variant, src.n_actions, src.n_rows = 1, int(variant), n_actions, m
     src.states, src.ids, src.table = states.data_ptr(), ids.data_ptr(), table.data_ptr()
     src.index = None if index is None else index.data_ptr()
     return src, dev, n, FACE_PLANES[int(variant)], (states, ids, index, table)
-
-
-def _q_stage_params(dev, P, weights, biases=None):
-    if len(weights) != 5 or (biases is not None and len(biases) != 5):
-        raise ValueError("weights / biases: those of conv1..conv4 and conv_shunzi")
-    for k in range(5):
-        shape = (256, P + 1, 1, k + 1) if k < 4 else (256, P + 1, 15, 1)
-        w = weights[k]
-        if w.dtype != torch.float32 or tuple(w.shape) != shape or not w.is_contiguous() or w.device != dev:
-            raise ValueError(f"weights[{k}] must be a contiguous float32 {list(shape)} tensor on the source's device")
-        if biases is not None:
-            b = biases[k]
-            if b.dtype != torch.float32 or tuple(b.shape) != (256,) or not b.is_contiguous() or b.device != dev:
-                raise ValueError(f"biases[{k}] must be a contiguous float32 [256] tensor on the source's device")
-
-
-def _ptr5(tensors):
-    return (C.c_void_p * 5)(*[t.data_ptr() for t in tensors])
 
 
 def q_stage_fwd(weights, biases, want_arg=True, **source):
@@ -1092,11 +1061,11 @@ def q_stage_fwd(weights, biases, want_arg=True, **source):
     ids=, index=, table=, variant=: q_stage_source), weights / biases the nn.Conv2d parameters of conv1..4 and conv_shunzi as they
     are -> (h f32 [n,4864], arg u8 [n,3840] as q_first_fwd's, or None with want_arg=False).  No host sync."""
     src, dev, n, P, keep = q_stage_source(**source)
-    _q_stage_params(dev, P, weights, biases)
+    _conv_params(dev, P, 5, weights, biases)
     h = torch.empty((n, STAGE_WIDTH), dtype=torch.float32, device=dev)
     arg = torch.empty((n, 3840), dtype=torch.uint8, device=dev) if want_arg else None
     if n:
-        check(_lib.lib().ddz_q_stage_fwd(dev.index, C.byref(src), n, _ptr5(weights), _ptr5(biases), _p(h), STAGE_WIDTH, _p(arg),
+        check(_lib.lib().ddz_q_stage_fwd(dev.index, C.byref(src), n, _ptrs(weights), _ptrs(biases), _p(h), STAGE_WIDTH, _p(arg),
                                          _stream(dev)))
     return h, arg
 
@@ -1106,18 +1075,16 @@ def q_stage_bwd(gh, arg, weights, **source):
     parameters' own shapes: (gw[5], gb[5]); `weights` give the shapes only.  Deterministic (per-block partials, a fixed-order
     reduce: three launches); no gradient of the data.  No host sync."""
     src, dev, n, P, keep = q_stage_source(**source)
-    _q_stage_params(dev, P, weights)
-    if gh.dtype != torch.float32 or tuple(gh.shape) != (n, STAGE_WIDTH) or not gh.is_contiguous() or gh.device != dev:
-        raise ValueError("gh must be a contiguous float32 [n,4864] tensor on the source's device")
-    if arg is None or arg.dtype != torch.uint8 or tuple(arg.shape) != (n, 3840) or not arg.is_contiguous() or arg.device != dev:
-        raise ValueError("arg must be q_stage_fwd's contiguous uint8 [n,3840] tensor")
+    _conv_params(dev, P, 5, weights)
+    _chk(gh, "gh", torch.float32, dev, shape=(n, STAGE_WIDTH))
+    _chk(arg, "arg", torch.uint8, dev, shape=(n, 3840), why=" (q_stage_fwd's arg)")
     L = _lib.lib()
     if n == 0:
         return [torch.zeros_like(w) for w in weights], [torch.zeros(256, dtype=torch.float32, device=dev) for _ in range(5)]
     gw = [torch.empty_like(w) for w in weights]
     gb = [torch.empty(256, dtype=torch.float32, device=dev) for _ in range(5)]
     ws = torch.empty(int(L.ddz_q_stage_bwd_ws_bytes(n, P)), dtype=torch.uint8, device=dev)
-    check(L.ddz_q_stage_bwd(dev.index, C.byref(src), n, _p(gh), STAGE_WIDTH, _p(arg), _ptr5(gw), _ptr5(gb), _p(ws), ws.numel(),
+    check(L.ddz_q_stage_bwd(dev.index, C.byref(src), n, _p(gh), STAGE_WIDTH, _p(arg), _ptrs(gw), _ptrs(gb), _p(ws), ws.numel(),
                             _stream(dev)))
     return gw, gb
 
@@ -1130,19 +1097,11 @@ def q_features_needed(face, wf, bias, acnt, row_index, y0, dy):
     """ddz_q_features_needed: first layer into y0 f32 [T, 15 * 256] (count 0 of every rank) and dy f32 [rows, 256]
     (Y[count] - Y[0] at the row of every needed (table, rank, count): row_index from BatchedEnv.q_need)."""
     L = _lib.lib()
-    dev = _require_gpu(face.device)
-    T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor")
-    if y0 is not None and (y0.dtype != torch.float32 or tuple(y0.shape) != (T, 15 * 256) or not y0.is_contiguous() or y0.device != dev):
-        raise ValueError("y0 must be a contiguous float32 [T, 3840] tensor on the same device (or None: dy alone)")
-    if dy.dtype != torch.float32 or dy.dim() != 2 or dy.shape[1] != 256 or not dy.is_contiguous() or dy.device != dev:
-        raise ValueError("dy must be a contiguous float32 [rows, 256] tensor on the same device")
-    if row_index.dtype != torch.int32 or tuple(row_index.shape) != (T, 64) or not row_index.is_contiguous() or row_index.device != dev:
-        raise ValueError("row_index must be a contiguous int32 [T,64] tensor on the same device")
-    for w, n in ((wf, P * 4 * 1024), (bias, 1024), (acnt, 5 * 4 * 256)):
-        if w.dtype != torch.float32 or w.numel() != n or not w.is_contiguous() or w.device != dev:
-            raise ValueError("weight tables must be contiguous float32 device tensors: wf [P*4,1024], bias [1024], acnt [5,4,256]")
+    dev, T, P = _face_arg(face)
+    _weight_tables(dev, P, 1, wf, bias, acnt)
+    _chk(row_index, "row_index", torch.int32, dev, shape=(T, 64))
+    _chk(y0, "y0", torch.float32, dev, shape=(T, 15 * 256), none_ok=True, why=" (or None: dy alone)")
+    _chk(dy, "dy", torch.float32, dev, shape=(dy.shape[0], 256))
     check(L.ddz_q_features_needed(dev.index, _p(face), T, P, _p(wf), _p(bias), _p(acnt), _p(row_index), _p(y0), _p(dy),
                                   int(dy.shape[0]), _stream(dev)))
 
@@ -1152,9 +1111,9 @@ def q_fc1_dense(a, w, c):
     L = _lib.lib()
     dev = _require_gpu(a.device)
     n, k = int(a.shape[0]), int(a.shape[1])
-    for x, shp in ((a, (n, k)), (w, (k, 256)), (c, (n, 256))):
-        if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != dev:
-            raise ValueError("a [n,k], w [k,256], c [n,256]: contiguous float32 tensors on one device")
+    _chk(a, "a", torch.float32, dev, shape=(n, k))
+    _chk(w, "w", torch.float32, dev, shape=(k, 256))
+    _chk(c, "c", torch.float32, dev, shape=(n, 256))
     check(L.ddz_q_fc1_dense(dev.index, _p(a), n, k, _p(w), _p(c), _stream(dev)))
     return c
 
@@ -1165,16 +1124,14 @@ def q_fc1_rows(dy, seg, row_cnt, w2, z, d):
     L = _lib.lib()
     dev = _require_gpu(dy.device)
     n = int(dy.shape[0])
-    for x, shp in ((dy, (n, 256)), (d, (n, 256)), (w2, (15, 256, 256))):
-        if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != dev:
-            raise ValueError("dy / d [rows,256], w2 [15,256,256]: contiguous float32 tensors on one device")
-    if seg.dtype != torch.int32 or seg.numel() < 40 or seg.device != dev:
-        raise ValueError("seg must be int32 [40] on the same device")
+    _chk(dy, "dy", torch.float32, dev, shape=(n, 256))
+    _chk(seg, "seg", torch.int32, dev, at_least=40)
     if (row_cnt is None) != (z is None):
         raise ValueError("row_cnt and z: both or neither")
-    if z is not None and (row_cnt.dtype != torch.uint8 or row_cnt.numel() < n or row_cnt.device != dev or z.dtype != torch.float32
-                          or z.numel() != 75 * 256 or not z.is_contiguous() or z.device != dev):
-        raise ValueError("row_cnt must be uint8 [rows], z float32 [15,5,256], on the same device")
+    _chk(row_cnt, "row_cnt", torch.uint8, dev, at_least=n, none_ok=True)
+    _chk(w2, "w2", torch.float32, dev, shape=(15, 256, 256))
+    _chk(z, "z", torch.float32, dev, numel=75 * 256, none_ok=True, why=" ([15,5,256])")
+    _chk(d, "d", torch.float32, dev, shape=(n, 256))
     check(L.ddz_q_fc1_rows(dev.index, _p(dy), _p(seg), _p(row_cnt), _p(w2), _p(z), _p(d), n, _stream(dev)))
     return d
 
@@ -1204,24 +1161,17 @@ def q_features_rows(face, wf, bias, rep, seg, ys, mz=None, g=None):
     instance 16 t + r, from BatchedEnv.q_shared_rows); face f32 [T,P,15,4], P = 6, 7 or 9; ys [rows, shared_row_width(P)]:
     + the row's column values behind the 256."""
     L = _lib.lib()
-    dev = _require_gpu(face.device)
-    T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or P not in SHARED_PLANES or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor, P = 6, 7 or 9 (the faces the shared rows key)")
+    dev, T, P = _face_arg(face, SHARED_PLANES)
     n = int(ys.shape[0])
     w_ = shared_row_width(P)
-    if ys.dtype != torch.float32 or ys.dim() != 2 or ys.shape[1] not in (256, w_) or not ys.is_contiguous() or ys.device != dev:
-        raise ValueError(f"ys must be a contiguous float32 [rows,256] (or [rows,{w_}]: + the column values) tensor on the same device")
-    if rep.dtype != torch.int32 or rep.numel() < n or rep.device != dev or seg.dtype != torch.int32 or seg.numel() < 40 or seg.device != dev:
-        raise ValueError("rep must be int32 [rows], seg int32 [40], on the same device")
-    for w, k in ((wf, P * 4 * 1024), (bias, 1024)):
-        if w.dtype != torch.float32 or w.numel() != k or not w.is_contiguous() or w.device != dev:
-            raise ValueError("weight tables must be contiguous float32 device tensors: wf [P*4,1024], bias [1024]")
+    _weight_tables(dev, P, 1, wf, bias)
+    _chk(rep, "rep", torch.int32, dev, at_least=n)
+    _chk(seg, "seg", torch.int32, dev, at_least=40)
+    _chk(ys, "ys", torch.float32, dev, shape=(n, 256 if ys.shape[1:] == (256,) else w_), why=" (or [rows,256])")
     if (mz is None) != (g is None):
         raise ValueError("mz and g: both or neither")
-    if mz is not None and (mz.dtype != torch.float32 or tuple(mz.shape) != (P * 60, 256) or not mz.is_contiguous() or mz.device != dev
-                           or g.dtype != torch.float32 or tuple(g.shape) != (n, 256) or not g.is_contiguous() or g.device != dev):
-        raise ValueError("mz must be float32 [60 P, 256], g float32 [rows, 256], contiguous, on the same device")
+    _chk(mz, "mz", torch.float32, dev, shape=(P * 60, 256), none_ok=True)
+    _chk(g, "g", torch.float32, dev, shape=(n, 256), none_ok=True)
     check(L.ddz_q_features_rows(dev.index, _p(face), T, P, _p(wf), _p(bias), _p(rep), _p(seg), _p(ys), int(ys.shape[1]), n, _p(mz), _p(g),
                                 _stream(dev)))
     return ys
@@ -1233,11 +1183,10 @@ def q_fc1_rows_k(y, seg, w2k, g, accumulate=False):
     L = _lib.lib()
     dev = _require_gpu(y.device)
     n, k = int(y.shape[0]), int(y.shape[1])
-    for x, shp in ((y, (n, k)), (g, (n, 256)), (w2k, (15, k, 256))):
-        if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != dev:
-            raise ValueError("y [rows,k], g [rows,256], w2k [15,k,256]: contiguous float32 tensors on one device")
-    if seg.dtype != torch.int32 or seg.numel() < 40 or seg.device != dev:
-        raise ValueError("seg must be int32 [40] on the same device")
+    _chk(y, "y", torch.float32, dev, shape=(n, k))
+    _chk(seg, "seg", torch.int32, dev, at_least=40)
+    _chk(w2k, "w2k", torch.float32, dev, shape=(15, k, 256))
+    _chk(g, "g", torch.float32, dev, shape=(n, 256))
     check(L.ddz_q_fc1_rows_k(dev.index, _p(y), k, _p(seg), _p(w2k), _p(g), n, 1 if accumulate else 0, _stream(dev)))
     return g
 
@@ -1253,21 +1202,13 @@ def q_features_drows(face, wf, bias, acnt, rep, drep, dseg, dy):
     """ddz_q_features_drows: dy f32 [rows,256] = Y[c] - Y[0] of the column of every shared D row (drep: D row -> 4 * shared row
     + c - 1, rep: shared row -> instance; from BatchedEnv.q_shared_need / q_shared_rows); face f32 [T,P,15,4], P = 6, 7 or 9."""
     L = _lib.lib()
-    dev = _require_gpu(face.device)
-    T, P = int(face.shape[0]), int(face.shape[1])
-    if face.dtype != torch.float32 or P not in SHARED_PLANES or tuple(face.shape[2:]) != (15, 4) or not face.is_contiguous():
-        raise ValueError("face must be a contiguous float32 [T,P,15,4] tensor, P = 6, 7 or 9 (the faces the shared rows key)")
+    dev, T, P = _face_arg(face, SHARED_PLANES)
     n = int(dy.shape[0])
-    if dy.dtype != torch.float32 or dy.dim() != 2 or dy.shape[1] != 256 or not dy.is_contiguous() or dy.device != dev:
-        raise ValueError("dy must be a contiguous float32 [rows,256] tensor on the same device")
-    for x in (rep, drep, dseg):
-        if x.dtype != torch.int32 or x.device != dev or not x.is_contiguous():
-            raise ValueError("rep / drep / dseg must be contiguous int32 tensors on the same device")
-    if drep.numel() < n or dseg.numel() < 40:
-        raise ValueError("drep must hold a slot per row of dy, dseg 40 ints")
-    for w, k in ((wf, P * 4 * 1024), (bias, 1024), (acnt, 5 * 4 * 256)):
-        if w.dtype != torch.float32 or w.numel() != k or not w.is_contiguous() or w.device != dev:
-            raise ValueError("weight tables must be contiguous float32 device tensors: wf [P*4,1024], bias [1024], acnt [5,4,256]")
+    _weight_tables(dev, P, 1, wf, bias, acnt)
+    _chk(rep, "rep", torch.int32, dev)
+    _chk(drep, "drep", torch.int32, dev, at_least=n)
+    _chk(dseg, "dseg", torch.int32, dev, at_least=40)
+    _chk(dy, "dy", torch.float32, dev, shape=(n, 256))
     check(L.ddz_q_features_drows(dev.index, _p(face), T, P, _p(wf), _p(bias), _p(acnt), _p(rep), rep.numel(), _p(drep), _p(dseg),
                                  _p(dy), n, _stream(dev)))
     return dy
@@ -1279,13 +1220,10 @@ def q_gather_h0(g, rows, h0, base=None):
     L = _lib.lib()
     dev = _require_gpu(g.device)
     T = int(h0.shape[0])
-    for x, shp in ((g, (int(g.shape[0]), 256)), (h0, (T, 256))):
-        if x.dtype != torch.float32 or tuple(x.shape) != shp or not x.is_contiguous() or x.device != dev:
-            raise ValueError("g [g_rows,256], h0 [T,256]: contiguous float32 tensors on one device")
-    if rows.dtype != torch.int32 or tuple(rows.shape) != (T, 16) or not rows.is_contiguous() or rows.device != dev:
-        raise ValueError("rows must be a contiguous int32 [T,16] tensor on the same device")
-    if base is not None and (base.dtype != torch.float32 or base.numel() != 256 or not base.is_contiguous() or base.device != dev):
-        raise ValueError("base must be a contiguous float32 [256] tensor on the same device")
+    _chk(g, "g", torch.float32, dev, shape=(g.shape[0], 256))
+    _chk(rows, "rows", torch.int32, dev, shape=(T, 16))
+    _chk(h0, "h0", torch.float32, dev, shape=(T, 256))
+    _chk(base, "base", torch.float32, dev, numel=256, none_ok=True)
     check(L.ddz_q_gather_h0(dev.index, _p(g), int(g.shape[0]), _p(rows), T, _p(base), _p(h0), _stream(dev)))
     return h0
 
@@ -1305,43 +1243,40 @@ def q_roles_need_ws_bytes(shared_row_capacity, n_nets):
     return n
 
 
-def _roles_dev(*xs):
-    dev = _require_gpu(xs[0].device)
-    for x in xs:
-        if x.device != dev or not x.is_contiguous():
-            raise ValueError("contiguous tensors on one device")
-    return dev
-
-
 def q_roles_features_rows(face, n_nets, wf, bias, rep, seg, ys, row_capacity):
     """ddz_q_roles_features_rows: q_features_rows on every slot's partition of ys [n_nets * row_capacity, shared_row_width(P)]
     with the slot's wf [n_nets, P*4, 1024] / bias [n_nets, 1024]."""
-    dev = _roles_dev(face, wf, bias, rep, seg, ys)
-    T, P, N = int(face.shape[0]), int(face.shape[1]), int(n_nets)
-    if (face.dtype != torch.float32 or P not in SHARED_PLANES or ys.dtype != torch.float32 or ys.shape[0] < N * int(row_capacity)
-            or wf.numel() != N * P * 4 * 1024 or bias.numel() != N * 1024):
-        raise ValueError("face f32 [T,P,15,4] (P = 6, 7, 9), ys f32 [n_nets * row_capacity, width], wf [n_nets,P*4,1024], bias [n_nets,1024]")
-    check(_lib.lib().ddz_q_roles_features_rows(dev.index, _p(face), T, P, N, _p(wf), _p(bias), _p(rep), _p(seg), _p(ys), int(ys.shape[1]),
+    (dev, T, P), N = _face_arg(face, SHARED_PLANES), int(n_nets)
+    _weight_tables(dev, P, N, wf, bias)
+    _chk(rep, "rep", torch.int32, dev, at_least=N * int(row_capacity))
+    _chk(seg, "seg", torch.int32, dev, at_least=40 * N)
+    _chk(ys, "ys", torch.float32, dev, at_least=N * int(row_capacity) * int(ys.shape[-1]), why=" ([n_nets * row_capacity, width])")
+    check(_lib.lib().ddz_q_roles_features_rows(dev.index, _p(face), T, P, N, _p(wf), _p(bias), _p(rep), _p(seg), _p(ys), int(ys.shape[-1]),
                                                int(row_capacity), _stream(dev)))
     return ys
 
 
 def q_roles_fc1_rows_k(n_nets, y, seg, w2k, g, row_capacity):
     """ddz_q_roles_fc1_rows_k: g[row] = y[row] @ w2k[slot][rank of the row] on every slot's partition; w2k f32 [n_nets,15,k,256]."""
-    dev = _roles_dev(y, seg, w2k, g)
-    N, k = int(n_nets), int(y.shape[1])
-    if y.shape[0] < N * int(row_capacity) or g.shape[0] < N * int(row_capacity) or w2k.numel() != N * 15 * k * 256:
-        raise ValueError("y [n_nets * row_capacity, k], g [n_nets * row_capacity, 256], w2k [n_nets,15,k,256]")
+    dev = _require_gpu(y.device)
+    N, k, rows = int(n_nets), int(y.shape[-1]), int(n_nets) * int(row_capacity)
+    _chk(y, "y", torch.float32, dev, at_least=rows * k, why=" ([n_nets * row_capacity, k])")
+    _chk(seg, "seg", torch.int32, dev, at_least=40 * N)
+    _chk(w2k, "w2k", torch.float32, dev, numel=N * 15 * k * 256, why=" ([n_nets,15,k,256])")
+    _chk(g, "g", torch.float32, dev, at_least=rows * 256, why=" ([n_nets * row_capacity, 256])")
     check(_lib.lib().ddz_q_roles_fc1_rows_k(dev.index, N, _p(y), k, _p(seg), _p(w2k), _p(g), int(row_capacity), _stream(dev)))
     return g
 
 
 def q_roles_gather_h0(n_nets, g, rows, slot, base, h0):
     """ddz_q_roles_gather_h0: h0[t] = base[slot[t]] + sum_r g[rows[t, r]] (rank order); rule tables (slot < 0) left alone."""
-    dev = _roles_dev(g, rows, slot, base, h0)
+    dev = _require_gpu(g.device)
     T = int(h0.shape[0])
-    if tuple(rows.shape) != (T, 16) or slot.dtype != torch.int8 or slot.numel() != T or base.numel() != int(n_nets) * 256:
-        raise ValueError("rows int32 [T,16], slot int8 [T], base f32 [n_nets,256]")
+    _chk(g, "g", torch.float32, dev, shape=(g.shape[0], 256))
+    _chk(rows, "rows", torch.int32, dev, shape=(T, 16))
+    _chk(slot, "slot", torch.int8, dev, numel=T)
+    _chk(base, "base", torch.float32, dev, numel=int(n_nets) * 256)
+    _chk(h0, "h0", torch.float32, dev, shape=(T, 256))
     check(_lib.lib().ddz_q_roles_gather_h0(dev.index, int(n_nets), _p(g), int(g.shape[0]), _p(rows), _p(slot), T, _p(base), _p(h0),
                                            _stream(dev)))
     return h0
@@ -1349,10 +1284,12 @@ def q_roles_gather_h0(n_nets, g, rows, slot, base, h0):
 
 def q_roles_features_drows(face, n_nets, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy, row_capacity):
     """ddz_q_roles_features_drows: q_features_drows on every slot's partition (acnt f32 [n_nets,5,4,256])."""
-    dev = _roles_dev(face, wf, bias, acnt, rep, drep, dseg, dy)
-    T, P, N = int(face.shape[0]), int(face.shape[1]), int(n_nets)
-    if dy.shape[0] < N * int(row_capacity) or acnt.numel() != N * 5 * 4 * 256 or rep.numel() < N * int(shared_row_capacity):
-        raise ValueError("dy [n_nets * row_capacity, 256], acnt [n_nets,5,4,256], rep [n_nets * shared_row_capacity]")
+    (dev, T, P), N = _face_arg(face, SHARED_PLANES), int(n_nets)
+    _weight_tables(dev, P, N, wf, bias, acnt)
+    _chk(rep, "rep", torch.int32, dev, at_least=N * int(shared_row_capacity))
+    _chk(drep, "drep", torch.int32, dev, at_least=N * int(row_capacity))
+    _chk(dseg, "dseg", torch.int32, dev, at_least=40 * N)
+    _chk(dy, "dy", torch.float32, dev, at_least=N * int(row_capacity) * 256, why=" ([n_nets * row_capacity, 256])")
     check(_lib.lib().ddz_q_roles_features_drows(dev.index, _p(face), T, P, N, _p(wf), _p(bias), _p(acnt), _p(rep), int(shared_row_capacity),
                                                 _p(drep), _p(dseg), _p(dy), int(row_capacity), _stream(dev)))
     return dy
@@ -1360,10 +1297,14 @@ def q_roles_features_drows(face, n_nets, wf, bias, acnt, rep, shared_row_capacit
 
 def q_roles_fc1_rows(n_nets, dy, seg, row_cnt, w2, z, d, row_capacity):
     """ddz_q_roles_fc1_rows: d[row] = dy[row] @ w2[slot][rank] + z[slot][rank][row_cnt[row]] on every slot's partition."""
-    dev = _roles_dev(dy, seg, row_cnt, w2, z, d)
-    N = int(n_nets)
-    if w2.numel() != N * 15 * 256 * 256 or z.numel() != N * 75 * 256 or d.shape[0] < N * int(row_capacity):
-        raise ValueError("w2 [n_nets,15,256,256], z [n_nets,15,5,256], dy / d [n_nets * row_capacity, 256]")
+    dev = _require_gpu(dy.device)
+    N, rows = int(n_nets), int(n_nets) * int(row_capacity)
+    _chk(dy, "dy", torch.float32, dev, at_least=rows * 256, why=" ([n_nets * row_capacity, 256])")
+    _chk(seg, "seg", torch.int32, dev, at_least=40 * N)
+    _chk(row_cnt, "row_cnt", torch.uint8, dev, at_least=rows)
+    _chk(w2, "w2", torch.float32, dev, numel=N * 15 * 256 * 256, why=" ([n_nets,15,256,256])")
+    _chk(z, "z", torch.float32, dev, numel=N * 75 * 256, why=" ([n_nets,15,5,256])")
+    _chk(d, "d", torch.float32, dev, at_least=rows * 256, why=" ([n_nets * row_capacity, 256])")
     check(_lib.lib().ddz_q_roles_fc1_rows(dev.index, N, _p(dy), _p(seg), _p(row_cnt), _p(w2), _p(z), _p(d), int(row_capacity),
                                           _stream(dev)))
     return d
@@ -1396,6 +1337,19 @@ def pack_trajectory(traj, native_joker_kickers=False):
     return out
 
 
+def _hands_lasts(hands, lasts, dev):
+    """the queries of the stateless verbs: count rows of any integer type, [n,15] or [n,16], as int8 [n,16] on `dev` each -> (hands,
+    lasts, n)"""
+    def pad(x, name, n):
+        x = x.to(device=dev, dtype=torch.int8)
+        if x.dim() == 2 and x.shape[1] == 15:
+            x = torch.nn.functional.pad(x, (0, 1))
+        return _chk(x.contiguous(), name, torch.int8, dev, shape=(n, ROW), why=" (or [n,15])")
+
+    n = len(hands)
+    return pad(hands, "hands", n), pad(lasts, "lasts", n), n
+
+
 def get_moves(hands, lasts, want_ids=True, row_capacity=None, native_joker_kickers=False):
     """Batched r.get_moves(hand15, last15) (envi.py:111): hands/lasts int8 [n,15|16] on the
     GPU.  Returns (offsets[n+1] i32, rows[total,16] i8, ids[total] i32 | None); one host sync
@@ -1403,17 +1357,7 @@ def get_moves(hands, lasts, want_ids=True, row_capacity=None, native_joker_kicke
     L = _lib.lib(jk=native_joker_kickers)
     NUM_ACTIONS = L.ddz_num_actions()
     dev = _require_gpu(hands.device)
-
-    def pad(x):
-        x = x.to(device=dev, dtype=torch.int8)
-        if x.shape[1] == 15:
-            x = torch.nn.functional.pad(x, (0, 1))
-        return x.contiguous()
-
-    hands, lasts = pad(hands), pad(lasts)
-    n = hands.shape[0]
-    if lasts.shape[0] != n:
-        raise ValueError("hands and lasts must have the same length")
+    hands, lasts, n = _hands_lasts(hands, lasts, dev)
     cap = int(row_capacity) if row_capacity is not None else min(n * NUM_ACTIONS, 0x7FFFFFFF)
     offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
     scratch = torch.zeros(L.ddz_scratch_bytes(n), dtype=torch.uint8, device=dev)
@@ -1445,15 +1389,7 @@ def auto_choose(hands, lasts, left, role, want_stats=False):
     Returns int32[n] canonical action ids (0 = pass, -2 = invalid query) (and int64 [n,2] {combinations, nodes})."""
     L = _lib.lib()
     dev = _require_gpu(hands.device)
-
-    def pad(x):
-        x = x.to(device=dev, dtype=torch.int8)
-        if x.shape[1] == 15:
-            x = torch.nn.functional.pad(x, (0, 1))
-        return x.contiguous()
-
-    hands, lasts = pad(hands), pad(lasts)
-    n = hands.shape[0]
+    hands, lasts, n = _hands_lasts(hands, lasts, dev)
     info = torch.zeros((n, 4), dtype=torch.uint8, device=dev)
     info[:, :3] = torch.as_tensor(left, device=dev).reshape(n, 3).to(torch.uint8)
     info[:, 3] = torch.as_tensor(role, device=dev).reshape(n).to(torch.uint8)
@@ -1489,17 +1425,7 @@ def get_moves_slab(hands, lasts, want_ids=True, native_joker_kickers=False, out=
     `out` = a previous result to write into (no allocation)."""
     L = _lib.lib(jk=native_joker_kickers)
     dev = _require_gpu(hands.device)
-
-    def pad(x):
-        x = x.to(device=dev, dtype=torch.int8)
-        if x.shape[1] == 15:
-            x = torch.nn.functional.pad(x, (0, 1))
-        return x.contiguous()
-
-    hands, lasts = pad(hands), pad(lasts)
-    n = hands.shape[0]
-    if lasts.shape[0] != n:
-        raise ValueError("hands and lasts must have the same length")
+    hands, lasts, n = _hands_lasts(hands, lasts, dev)
     if out is None:
         counts = torch.empty(n, dtype=torch.int32, device=dev)
         rows = torch.empty((n, MAX_LEGAL_PER_TABLE, ROW), dtype=torch.int8, device=dev)
@@ -1507,6 +1433,10 @@ def get_moves_slab(hands, lasts, want_ids=True, native_joker_kickers=False, out=
         status = torch.zeros(1, dtype=torch.int32, device=dev)
     else:
         counts, rows, ids, status = out
+        _chk(counts, "counts", torch.int32, dev, numel=n, why=" (out[0])")
+        _chk(rows, "rows", torch.int8, dev, numel=n * MAX_LEGAL_PER_TABLE * ROW, why=" (out[1])")
+        _chk(ids, "ids", torch.int32, dev, numel=n * MAX_LEGAL_PER_TABLE, none_ok=True, why=" (out[2])")
+        _chk(status, "status", torch.int32, dev, numel=1, why=" (out[3])")
         status.zero_()
     check(L.ddz_get_moves_slab(dev.index, _p(hands), _p(lasts), n, _p(counts), _p(rows), _p(ids), MAX_LEGAL_PER_TABLE,
                                _p(status), _stream(dev)))

@@ -1,0 +1,353 @@
+"""CPU: engine.py hands raw addresses to the library, so every tensor a caller supplies must be refused there -- ValueError, and no
+library call -- unless it has the dtype, the device, the contiguity and the size the kernels assume.
+
+A BatchedEnv is built without a device (object.__new__, CPU buffers, a stand-in library that records every launch and answers
+size queries); the module functions run with _require_gpu answering the device it is given.  The table below names every
+verb / function that takes a caller's tensor and every such parameter.  From a valid call one parameter at a time is made
+  dtype   another dtype of the same width class
+  strided a non-contiguous view of the right shape
+  short   one element short          over    one element over (exact sizes only)
+  device  a tensor on another device (the meta device: nothing is read from it)
+and, per call, the env's / the anchor's device is set to cuda:0 while every tensor stays on the CPU.  The valid call must
+reach the library exactly as often as the verb launches.
+
+Size classes of a parameter: "exact" (shape or numel fixed by the call), "min" (at least so many elements: the valid call
+passes exactly the minimum), "free" (the tensor's own shape defines the sizes of the call), "bytes" (a workspace whose byte
+count travels to the library with its address: the library tests it), "size" (an input the verb converts: only its size is
+refused)."""
+import importlib
+
+import pytest
+import torch
+
+T, STRIDE = 4, 512
+CAP = T * STRIDE
+N, RC = 2, 4                      # networks / row capacity per network of the per-role forms
+P, W = 6, 288                     # planes of face variant 3 and its shared row width
+f32, f64, i8, u8, i32, i64 = torch.float32, torch.float64, torch.int8, torch.uint8, torch.int32, torch.int64
+OTHER = {f32: f64, f64: f32, i32: i64, i64: i32, u8: i8, i8: u8}
+CPU, CUDA = torch.device("cpu"), torch.device("cuda", 0)
+SIZE_QUERIES = {"ddz_mask_words": 424, "ddz_num_actions": 13527}
+
+
+def z(*shape, dt=f32):
+    return torch.zeros(shape, dtype=dt)
+
+
+class StandIn:
+    """the library: a launch records its name and succeeds; a size query answers a positive size and is not recorded"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("ddz_"):
+            raise AttributeError(name)
+        if name.endswith("_bytes") or name in SIZE_QUERIES:
+            return lambda *a: SIZE_QUERIES.get(name, 64)
+        return lambda *a: self.calls.append(name) or 0
+
+
+@pytest.fixture()
+def E(monkeypatch):
+    E = importlib.import_module("doudizhu-rl_amd.engine")
+    lib = StandIn()
+    monkeypatch.setattr(E._lib, "lib", lambda jk=False: lib)
+    monkeypatch.setattr(E, "_stream", lambda device: None)
+    monkeypatch.setattr(E, "_require_gpu", lambda device: torch.device(device))
+    return E
+
+
+def launches(E):
+    return E._lib.lib().calls
+
+
+def make_env(E, device=CPU):
+    env = object.__new__(E.BatchedEnv)
+    env.lib, env.device, env.T, env.cap, env._h = E._lib.lib(), device, T, CAP, None
+    env.host_mirror = env.native_joker_kickers = False
+    env.state, env.scratch, env.offsets = z(T * 176, dt=u8), z(64, dt=u8), z(T + 1, dt=i32)
+    env.rows, env.ids, env.counts = z(CAP, 16, dt=i8), z(CAP, dt=i32), z(T, dt=i32)
+    env.done, env.reward, env.illegal, env._stats = z(T, dt=u8), z(T, dt=i8), z(T, dt=u8), z(8, dt=i64)
+    env._legal_fresh = env._slab_fresh = env._csr_fresh = True
+    env._pp = {k: E._p(getattr(env, k)) for k in ("counts", "rows", "ids", "done", "reward", "illegal", "offsets")}
+    return env
+
+
+# ---- the valid arguments ----
+def face():
+    return z(T, P, 15, 4)
+
+
+def tables(n=None):
+    lead = () if n is None else (n,)
+    return {"wf": z(*lead, P * 4, 1024), "bias": z(*lead, 1024), "acnt": z(*lead, 5, 4, 256)}
+
+
+def convs(count):
+    return {"weights": [z(256, P + 1, 1, k + 1) if k < 4 else z(256, P + 1, 15, 1) for k in range(count)],
+            "biases": [z(256) for _ in range(count)]}
+
+
+def rings():
+    return [None, z(64, dt=u8), z(64, dt=u8)]
+
+
+def cfr_out():
+    return (z(T, dt=i32), z(T, 16, dt=i32), z(T, 16, dt=f64), z(T, dt=f64))
+
+
+def need_args(n):
+    return {"row_index": z(T, 64, dt=i32), "rows": z(T, 16, dt=i32), "sseg": z(n, 40, dt=i32), "ws": z(64, dt=u8),
+            "row_index2": z(T, 64, dt=i32), "drep": z(n * RC, dt=i32), "dseg": z(n, 40, dt=i32), "row_cnt": z(n * RC, dt=u8)}
+
+
+def slab_args(n):
+    return {"h0": z(T, 8), "d": z(5, 8), "row_index": z(T, 64, dt=i32), "w2": z(n, 8), "b2": z(n), "out": z(T, STRIDE)}
+
+
+def packed_rows():
+    return {"states": z(3, 176, dt=u8), "ids": z(3, dt=i32), "index": z(2, dt=i64), "table": z(5, 16, dt=i8)}
+
+
+NEED = {"row_index": "exact", "rows": "exact", "sseg": "min", "ws": "bytes", "row_index2": "exact", "drep": "min", "dseg": "min",
+        "row_cnt": "min"}
+SLAB = {"h0": "exact", "d": "exact", "row_index": "exact", "w2": "exact", "b2": "exact", "out": "exact"}
+TABLES = {"wf": "exact", "bias": "exact", "acnt": "exact"}
+FACES = {"face": "exact", "actions": "exact"}
+CONV4 = {f"{kind}.{k}": "exact" for kind in ("weights", "biases") for k in range(4)}
+CONV5 = {f"{kind}.{k}": "exact" for kind in ("weights", "biases") for k in range(5)}
+ROWS = {"states": "exact", "ids": "exact", "index": "free", "table": "exact"}
+CFR4 = {"out.0": "exact", "out.1": "exact", "out.2": "exact", "out.3": "exact"}
+
+# name: (who: "env" | "module", the call (target, arguments) -> None, the valid arguments, {parameter: size class}, launches)
+CASES = {
+    "step": ("env", lambda e, a: e.step(z(T, dt=i32), **a), lambda: {"traj": z(T, 32, dt=u8)}, {"traj": "exact"}, ["ddz_step"]),
+    "step_slab": ("env", lambda e, a: e.step_slab(z(T, dt=i32), **a), lambda: {"traj": z(T, 32, dt=u8)}, {"traj": "exact"},
+                  ["ddz_step_slab"]),
+    "policy_step_slab": ("env", lambda e, a: e.policy_step_slab(z(T, STRIDE), face_variant=3, **a),
+                         lambda: {"face_out": face(), "choice_out": z(T, dt=i32), "traj": z(T, 32, dt=u8)},
+                         {"face_out": "exact", "choice_out": "exact", "traj": "exact"}, ["ddz_policy_step_slab"]),
+    "rollout_random": ("env", lambda e, a: e.rollout_random(2, **a), lambda: {"traj": z(2, T, 32, dt=u8)}, {"traj": "exact"},
+                       ["ddz_rollout_random"]),
+    "rollout_random_csr": ("env", lambda e, a: e.rollout_random_csr(2, batch=0, **a), lambda: {"traj": z(2, T, 32, dt=u8)},
+                           {"traj": "exact"}, ["ddz_rollout_random_csr"]),
+    "auto_choose": ("env", lambda e, a: e.auto_choose(**a), lambda: {"out": z(T, dt=i32), "stats": z(T, 2, dt=i64)},
+                    {"out": "exact", "stats": "exact"}, ["ddz_auto_choose_state"]),
+    "observe": ("env", lambda e, a: e.observe(3, **a), lambda: {"out": face()}, {"out": "exact"}, ["ddz_observe"]),
+    "legal_mask": ("env", lambda e, a: e.legal_mask(**a), lambda: {"out": z(T, 424, dt=i32)}, {"out": "exact"}, ["ddz_legal_mask"]),
+    "select": ("env", lambda e, a: e.select(z(9), **a), lambda: {"out": z(T, dt=i32)}, {"out": "exact"}, ["ddz_select"]),
+    "select_slab": ("env", lambda e, a: e.select_slab(z(T, STRIDE), **a), lambda: {"out": z(T, dt=i32)}, {"out": "exact"},
+                    ["ddz_select_slab"]),
+    "tr_before": ("env", lambda e, a: e.tr_before(capacity=8, trained_roles=0b110, **a),
+                  lambda: {"ws": z(64, dt=u8), "rings": rings(), "chosen": z(T, dt=i32), "greedy": z(T, dt=i32), "active": z(T, dt=u8)},
+                  {"ws": "min", "rings.1": "exact", "rings.2": "exact", "chosen": "exact", "greedy": "exact", "active": "exact"},
+                  ["ddz_tr_before"]),
+    "tr_after": ("env", lambda e, a: e.tr_after(capacity=8, reward=(1.0, -1.0, 1.0), **a),
+                 lambda: {"ws": z(64, dt=u8), "rings": rings(), "done": z(T, dt=u8), "r": z(T, dt=i8)},
+                 {"ws": "min", "rings.1": "exact", "rings.2": "exact", "done": "exact", "r": "exact"}, ["ddz_tr_after"]),
+    "q_need": ("env", lambda e, a: e.q_need(RC, **a),
+               lambda: {"scratch": z(64, dt=u8), "row_index": z(T, 64, dt=i32), "seg": z(40, dt=i32), "row_cnt": z(RC, dt=u8)},
+               {"scratch": "bytes", "row_index": "exact", "seg": "min", "row_cnt": "min"}, ["ddz_q_need"]),
+    "q_shared_rows": ("env", lambda e, a: e.q_shared_rows(row_capacity=RC, **a),
+                      lambda: {"ws": z(64, dt=u8), "rows": z(T, 16, dt=i32), "rep": z(RC, dt=i32), "seg": z(40, dt=i32)},
+                      {"ws": "bytes", "rows": "exact", "rep": "min", "seg": "min"}, ["ddz_q_shared_rows"]),
+    "q_shared_rows_hashed": ("env", lambda e, a: e.q_shared_rows(row_capacity=RC, variant=1, **a),
+                             lambda: {"ws": z(64, dt=u8), "rows": z(T, 16, dt=i32), "rep": z(RC, dt=i32), "seg": z(40, dt=i32)},
+                             {"ws": "bytes", "rows": "exact", "rep": "min", "seg": "min"}, ["ddz_q_shared_rows_hashed"]),
+    "q_shared_need": ("env", lambda e, a: e.q_shared_need(shared_row_capacity=RC, row_capacity=RC, **a), lambda: need_args(1), NEED,
+                      ["ddz_q_shared_need"]),
+    "q_roles_need": ("env", lambda e, a: e.q_roles_need(N, shared_row_capacity=RC, row_capacity=RC, **a), lambda: need_args(N), NEED,
+                     ["ddz_q_roles_need"]),
+    "q_slab_needed": ("env", lambda e, a: e.q_slab_needed(**a), lambda: slab_args(1), SLAB, ["ddz_q_slab_needed"]),
+    "q_roles_slab": ("env", lambda e, a: e.q_roles_slab(N, **a), lambda: dict(slab_args(N), slot=z(T, dt=i8)),
+                     dict(SLAB, slot="exact"), ["ddz_q_roles_slab"]),
+    "q_roles_rows": ("env", lambda e, a: e.q_roles_rows(3, (0, 1, -1), N, row_capacity=RC, **a),
+                     lambda: {"ws": z(64, dt=u8), "rows": z(T, 16, dt=i32), "rep": z(N * RC, dt=i32), "seg": z(N, 40, dt=i32),
+                              "slot": z(T, dt=i8)},
+                     {"ws": "bytes", "rows": "exact", "rep": "min", "seg": "min", "slot": "exact"}, ["ddz_q_roles_rows"]),
+    "playout": ("env", lambda e, a: e.playout(4, **a), lambda: {"wins": z(CAP, dt=i32), "totals": z(4, dt=i64)},
+                {"wins": "exact", "totals": "min"}, ["ddz_playout"]),
+    "playout_hidden": ("env", lambda e, a: e.playout(4, hidden=True, roles=0b010, **a),
+                       lambda: {"wins": z(CAP, dt=i32), "totals": z(4, dt=i64)}, {"wins": "exact", "totals": "min"},
+                       ["ddz_playout_hidden"]),
+    "playout_worlds": ("env", lambda e, a: e.playout_worlds(3, **a), lambda: {"out": z(T, 3, 2, 16, dt=u8)}, {"out": "exact"},
+                       ["ddz_playout_worlds"]),
+    "playout_choose": ("env", lambda e, a: e.playout_choose(4, **a), lambda: {"out": z(T, dt=i32)}, {"out": "exact"},
+                       ["ddz_playout", "ddz_playout_choose"]),
+    "search": ("env", lambda e, a: e.search(8, trees=2, **a),
+               lambda: {"visits": z(CAP, dt=i32), "wins": z(CAP, dt=i32), "totals": z(4, dt=i64)},
+               {"visits": "exact", "wins": "exact", "totals": "min"}, ["ddz_search"]),
+    "search_choose": ("env", lambda e, a: e.search_choose(8, trees=2, **a), lambda: {"out": z(T, dt=i32)}, {"out": "exact"},
+                      ["ddz_search", "ddz_search_choose"]),
+    "cfr": ("env", lambda e, a: e.cfr(**a), lambda: {"totals": z(4, dt=i64), "out": cfr_out()}, dict(CFR4, totals="min"), ["ddz_cfr"]),
+    "cfr_choose": ("env", lambda e, a: e.cfr_choose(**a), lambda: {"out": z(T, dt=i32)}, {"out": "exact"},
+                   ["ddz_cfr", "ddz_cfr_choose"]),
+    "cfr_choose_solved": ("env", lambda e, a: e.cfr_choose(**a), lambda: {"solved": cfr_out(), "out": z(T, dt=i32)},
+                          {"solved.0": "exact", "solved.1": "exact", "solved.2": "exact", "out": "exact"}, ["ddz_cfr_choose"]),
+    "state_import": ("env", lambda e, a: e.state_import(**a), lambda: {"state": z(T * 176, dt=u8)}, {"state": "size"},
+                     ["ddz_invalidate"]),
+    "observe_states": ("module", lambda E, a: E.observe_states(variant=3, **a),
+                       lambda: {"states": z(3, 176, dt=u8), "index": z(2, dt=i64), "out": z(2, P, 15, 4)},
+                       {"states": "exact", "index": "free", "out": "exact"}, ["ddz_observe_states"]),
+    "q_features": ("module", lambda E, a: E.q_features(**a), lambda: dict(tables(), face=face(), y=z(15, 5, T, 256)),
+                   dict(TABLES, face="exact", y="exact"), ["ddz_q_features"]),
+    "q_first_fwd": ("module", lambda E, a: E.q_first_fwd(**a), lambda: dict(convs(4), face=face(), actions=z(T, 15, 4)),
+                    dict(FACES, **CONV4), ["ddz_q_first_fwd"]),
+    "q_first_bwd": ("module", lambda E, a: E.q_first_bwd(**a),
+                    lambda: {"face": face(), "actions": z(T, 15, 4), "gy": z(T, 3840), "arg": z(T, 3840, dt=u8),
+                             "weights": convs(4)["weights"]},
+                    dict(FACES, gy="exact", arg="exact", **{f"weights.{k}": "exact" for k in range(4)}), ["ddz_q_first_bwd"]),
+    "q_stage_fwd_faces": ("module", lambda E, a: E.q_stage_fwd(**a), lambda: dict(convs(5), face=face(), actions=z(T, 15, 4)),
+                          dict(FACES, **CONV5), ["ddz_q_stage_fwd"]),
+    "q_stage_fwd_rows": ("module", lambda E, a: E.q_stage_fwd(variant=3, **a), lambda: dict(convs(5), **packed_rows()),
+                         dict(ROWS, **CONV5), ["ddz_q_stage_fwd"]),
+    "q_stage_bwd_faces": ("module", lambda E, a: E.q_stage_bwd(**a),
+                          lambda: {"gh": z(T, 4864), "arg": z(T, 3840, dt=u8), "weights": convs(5)["weights"], "face": face(),
+                                   "actions": z(T, 15, 4)},
+                          dict(FACES, gh="exact", arg="exact", **{f"weights.{k}": "exact" for k in range(5)}), ["ddz_q_stage_bwd"]),
+    "q_stage_bwd_rows": ("module", lambda E, a: E.q_stage_bwd(variant=3, **a),
+                         lambda: dict(packed_rows(), gh=z(2, 4864), arg=z(2, 3840, dt=u8), weights=convs(5)["weights"]),
+                         dict(ROWS, gh="exact", arg="exact", **{f"weights.{k}": "exact" for k in range(5)}), ["ddz_q_stage_bwd"]),
+    "q_features_needed": ("module", lambda E, a: E.q_features_needed(**a),
+                          lambda: dict(tables(), face=face(), row_index=z(T, 64, dt=i32), y0=z(T, 3840), dy=z(5, 256)),
+                          dict(TABLES, face="exact", row_index="exact", y0="exact", dy="exact"), ["ddz_q_features_needed"]),
+    "q_fc1_dense": ("module", lambda E, a: E.q_fc1_dense(**a), lambda: {"a": z(3, 16), "w": z(16, 256), "c": z(3, 256)},
+                    {"a": "free", "w": "exact", "c": "exact"}, ["ddz_q_fc1_dense"]),
+    "q_fc1_rows": ("module", lambda E, a: E.q_fc1_rows(**a),
+                   lambda: {"dy": z(5, 256), "seg": z(40, dt=i32), "row_cnt": z(5, dt=u8), "w2": z(15, 256, 256), "z": z(15, 5, 256),
+                            "d": z(5, 256)},
+                   {"dy": "exact", "seg": "min", "row_cnt": "min", "w2": "exact", "z": "exact", "d": "exact"}, ["ddz_q_fc1_rows"]),
+    "q_features_rows": ("module", lambda E, a: E.q_features_rows(**a),
+                        lambda: {"face": face(), "wf": z(P * 4, 1024), "bias": z(1024), "rep": z(5, dt=i32), "seg": z(40, dt=i32),
+                                 "ys": z(5, W), "mz": z(P * 60, 256), "g": z(5, 256)},
+                        {"face": "exact", "wf": "exact", "bias": "exact", "rep": "min", "seg": "min", "ys": "exact", "mz": "exact",
+                         "g": "exact"}, ["ddz_q_features_rows"]),
+    "q_fc1_rows_k": ("module", lambda E, a: E.q_fc1_rows_k(**a),
+                     lambda: {"y": z(5, 16), "seg": z(40, dt=i32), "w2k": z(15, 16, 256), "g": z(5, 256)},
+                     {"y": "free", "seg": "min", "w2k": "exact", "g": "exact"}, ["ddz_q_fc1_rows_k"]),
+    "q_features_drows": ("module", lambda E, a: E.q_features_drows(**a),
+                         lambda: dict(tables(), face=face(), rep=z(5, dt=i32), drep=z(5, dt=i32), dseg=z(40, dt=i32), dy=z(5, 256)),
+                         dict(TABLES, face="exact", rep="bytes", drep="min", dseg="min", dy="exact"), ["ddz_q_features_drows"]),
+    "q_gather_h0": ("module", lambda E, a: E.q_gather_h0(**a),
+                    lambda: {"g": z(5, 256), "rows": z(T, 16, dt=i32), "h0": z(T, 256), "base": z(256)},
+                    {"g": "exact", "rows": "exact", "h0": "exact", "base": "exact"}, ["ddz_q_gather_h0"]),
+    "q_roles_features_rows": ("module", lambda E, a: E.q_roles_features_rows(n_nets=N, row_capacity=RC, **a),
+                              lambda: {"face": face(), "wf": z(N, P * 4, 1024), "bias": z(N, 1024), "rep": z(N * RC, dt=i32),
+                                       "seg": z(N, 40, dt=i32), "ys": z(N * RC, W)},
+                              {"face": "exact", "wf": "exact", "bias": "exact", "rep": "min", "seg": "min", "ys": "min"},
+                              ["ddz_q_roles_features_rows"]),
+    "q_roles_fc1_rows_k": ("module", lambda E, a: E.q_roles_fc1_rows_k(n_nets=N, row_capacity=RC, **a),
+                           lambda: {"y": z(N * RC, 16), "seg": z(N, 40, dt=i32), "w2k": z(N, 15, 16, 256), "g": z(N * RC, 256)},
+                           {"y": "min", "seg": "min", "w2k": "exact", "g": "min"}, ["ddz_q_roles_fc1_rows_k"]),
+    "q_roles_gather_h0": ("module", lambda E, a: E.q_roles_gather_h0(n_nets=N, **a),
+                          lambda: {"g": z(N * RC, 256), "rows": z(T, 16, dt=i32), "slot": z(T, dt=i8), "base": z(N, 256),
+                                   "h0": z(T, 256)},
+                          {"g": "exact", "rows": "exact", "slot": "exact", "base": "exact", "h0": "exact"}, ["ddz_q_roles_gather_h0"]),
+    "q_roles_features_drows": ("module", lambda E, a: E.q_roles_features_drows(n_nets=N, shared_row_capacity=RC, row_capacity=RC, **a),
+                               lambda: dict(tables(N), face=face(), rep=z(N * RC, dt=i32), drep=z(N * RC, dt=i32),
+                                            dseg=z(N, 40, dt=i32), dy=z(N * RC, 256)),
+                               dict(TABLES, face="exact", rep="min", drep="min", dseg="min", dy="min"), ["ddz_q_roles_features_drows"]),
+    "q_roles_fc1_rows": ("module", lambda E, a: E.q_roles_fc1_rows(n_nets=N, row_capacity=RC, **a),
+                         lambda: {"dy": z(N * RC, 256), "seg": z(N, 40, dt=i32), "row_cnt": z(N * RC, dt=u8), "w2": z(N, 15, 256, 256),
+                                  "z": z(N, 15, 5, 256), "d": z(N * RC, 256)},
+                         {"dy": "min", "seg": "min", "row_cnt": "min", "w2": "exact", "z": "exact", "d": "min"}, ["ddz_q_roles_fc1_rows"]),
+    "get_moves_slab": ("module", lambda E, a: E.get_moves_slab(**a),
+                       lambda: {"hands": z(3, 16, dt=i8), "lasts": z(3, 15, dt=i8),
+                                "out": (z(3, dt=i32), z(3, STRIDE, 16, dt=i8), z(3, STRIDE, dt=i32), z(1, dt=i32))},
+                       dict(CFR4, hands="size", lasts="size"), ["ddz_get_moves_slab"]),
+    "auto_choose_queries": ("module", lambda E, a: E.auto_choose(left=z(3, 3, dt=i32), role=z(3, dt=i32), **a),
+                            lambda: {"hands": z(3, 15, dt=i8), "lasts": z(3, 16, dt=i8)}, {"hands": "size", "lasts": "size"},
+                            ["ddz_auto_choose"]),
+}
+# the verbs that convert their inputs to the device first cannot be asked with a device that does not exist
+NO_ANCHOR = {"state_import", "get_moves_slab", "auto_choose_queries"}
+
+
+def strided(x):
+    return x.new_zeros(tuple(x.shape[:-1]) + (2 * x.shape[-1],))[..., ::2]
+
+
+CORRUPT = {
+    "dtype": lambda x: x.to(OTHER[x.dtype]),
+    "strided": strided,
+    "short": lambda x: x.reshape(-1)[:-1].clone(),
+    "over": lambda x: torch.cat((x.reshape(-1), x.reshape(-1)[:1])),
+    "device": lambda x: torch.empty(x.shape, dtype=x.dtype, device="meta"),
+}
+KINDS = {"exact": ("dtype", "strided", "short", "over", "device"), "min": ("dtype", "strided", "short", "device"),
+         "free": ("dtype", "strided", "device"), "bytes": ("dtype", "strided", "device"), "size": ("short", "over")}
+
+
+def corrupted(args, param, kind):
+    name, _, k = param.partition(".")
+    if k:
+        items = list(args[name])
+        x = items[int(k)]
+        items[int(k)] = CORRUPT[kind](x)
+        args[name] = type(args[name])(items)
+    else:
+        x = args[name]
+        args[name] = CORRUPT[kind](x)
+    return x
+
+
+def _bad_cases():
+    for case, (_, _, _, params, _) in CASES.items():
+        for param, size in params.items():
+            for kind in KINDS[size]:
+                yield case, param, kind
+
+
+def _run(E, case, args, device=CPU):
+    who, call = CASES[case][:2]
+    call(make_env(E, device) if who == "env" else E, args)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_valid_call_reaches_the_library(E, case):
+    _run(E, case, CASES[case][2]())
+    assert launches(E) == CASES[case][4]
+
+
+@pytest.mark.parametrize("case,param,kind", _bad_cases())
+def test_one_bad_tensor_is_refused_before_the_library(E, case, param, kind):
+    args = CASES[case][2]()
+    x = corrupted(args, param, kind)
+    if kind == "strided" and x.numel() < 2:
+        assert strided(x).is_contiguous()              # a single element has no stride to get wrong
+        return
+    with pytest.raises(ValueError):
+        _run(E, case, args)
+    assert launches(E) == []
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if c not in NO_ANCHOR])
+def test_tensors_of_another_device_than_the_anchor_are_refused(E, case, monkeypatch):
+    monkeypatch.setattr(E, "_require_gpu", lambda device: CUDA)
+    with pytest.raises(ValueError):
+        _run(E, case, CASES[case][2](), CUDA)
+    assert launches(E) == []
+
+
+def test_semantics_that_stay(E):
+    env = make_env(E)
+    # a bool `active` is converted, a pinned `out` is a host_mirror env's alone, None where a tensor is needed is refused
+    env.tr_before(z(64, dt=u8), rings(), 8, z(T, dt=i32), z(T, dt=i32), active=torch.ones(T, dtype=torch.bool), trained_roles=0b110)
+    assert launches(E) == ["ddz_tr_before"]
+    with pytest.raises(ValueError):
+        env.tr_before(z(64, dt=u8), [None, None, None], 8, z(T, dt=i32), z(T, dt=i32), trained_roles=0b010)     # no ring
+    with pytest.raises(ValueError):
+        env.q_roles_slab(N, **dict(slab_args(N), slot=z(T, dt=i8), out=None))
+    # the coercing sites keep coercing
+    env.select_slab(z(T, STRIDE, dt=f64))
+    env.step_slab(z(T, dt=i64), E.STEP_IDS)
+    env.reset(torch.ones(T, dtype=torch.bool))
+    with pytest.raises(ValueError):
+        env.select_slab(z(T, STRIDE - 1))
+    # the ranges stay where they were
+    for bad in (lambda: env.playout(4, roles=8), lambda: env.playout(4, roles=0b010), lambda: env.search(8, roles=-1),
+                lambda: env.cfr(roles=9), lambda: env.playout_worlds(3, roles=8), lambda: env.tr_before(None, rings(), 8, None, None,
+                                                                                                          trained_roles=8)):
+        with pytest.raises(ValueError):
+            bad()
