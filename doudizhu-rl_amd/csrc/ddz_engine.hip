@@ -13,6 +13,8 @@
 //   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
 //             These three share ddz_ply.h: the root decode, the hidden-hand domain and redeal, and a ply (list, entry, apply,
 //             draw) built from k_rollout's device functions -- each stated once.
+//   k_solve   (ddz_solve.h; ddz_solve) the exact endgame solver, a fourth caller of ddz_ply.h: one wavefront per (table, world,
+//             chunk), a depth-first search with its transposition table in the caller's workspace.
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
 //             or slab lists with F_SLAB = apply + enumerate in the same launch):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
@@ -1409,6 +1411,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
+#include "ddz_solve.h"    // k_solve / k_solve_choose: exact open-hand minimax per root move, one wavefront per (table, world, chunk)
 
 // write-once output streams (`face`, thermometer planes): nontemporal 16-byte stores.  Measured on k_observe
 // at 524,288 tables (0.6-1.2 GB per call): 3.1 TB/s with plain stores, 5.3-5.7 TB/s with these.
@@ -3617,6 +3620,64 @@ int ddz_cfr_choose(ddz_env_t* e, const int32_t* n, const int32_t* ids, const dou
   if (e->T == 0) return DDZ_OK;
   hipLaunchKernelGGL(k_cfr_choose, dim3((unsigned)((e->T + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, n, ids, sigma,
                      (uint32_t)e->seed ^ (uint32_t)salt, (uint32_t)(e->seed >> 32), e->gid_base, greedy, choice, e->T);
+  return check_launch();
+}
+
+// ddz_solve: one launch of k_solve<hidden>, one wavefront per (table, world, chunk); its table lives in the caller's workspace
+static bool solve_sizes_ok(int64_t worlds, int64_t chunks, int64_t tt_entries) {
+  return worlds >= 1 && worlds <= 65536 && chunks >= 1 && chunks <= 65536 && tt_entries >= 1 && tt_entries <= DDZ_SOLVE_MAX_TT &&
+         (tt_entries & (tt_entries - 1)) == 0;
+}
+
+int64_t ddz_solve_work_bytes(int64_t n_tables, int64_t worlds, int64_t chunks, int64_t tt_entries) {
+  if (n_tables < 0 || n_tables > 0x7FFFFFFF || !solve_sizes_ok(worlds, chunks, tt_entries)) return -1;
+  const int64_t items = n_tables * worlds;   // < 2^47
+  if (items > (1ll << 40) / chunks) return -1;
+  if (items * chunks > (1ll << 60) / (tt_entries * SOLVE_ENTRY_BYTES)) return -1;
+  return items * chunks * tt_entries * SOLVE_ENTRY_BYTES;
+}
+
+int ddz_solve(ddz_env_t* e, int64_t budget, int max_cards, int64_t worlds, int hidden, int roles, uint64_t salt, int64_t chunks,
+              int64_t tt_entries, int64_t stride, int32_t* n, int32_t* wins, int32_t* unknown, int64_t* totals, void* work,
+              int64_t work_bytes, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!n || !wins || !unknown || !work) return DDZ_EINVAL;
+  if (!al(n, 4) || !al(wins, 4) || !al(unknown, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
+  if (budget < 1 || budget > DDZ_SOLVE_MAX_BUDGET || max_cards < 1 || max_cards > DDZ_SOLVE_MAX_CARDS) return DDZ_EINVAL;
+  if (!solve_sizes_ok(worlds, chunks, tt_entries) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (roles < 0 || roles > 7 || (!hidden && (roles != 7 || worlds != 1))) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  const int64_t need = ddz_solve_work_bytes(e->T, worlds, chunks, tt_entries);
+  if (need < 0 || work_bytes < need) return DDZ_ECAP;
+  const int64_t blocks = (e->T * worlds * chunks + SOLVE_WAVES - 1) / SOLVE_WAVES;
+  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  if (blocks == 0) return DDZ_OK;
+  SolveArgs a;
+  a.state = e->state; a.T = e->T;
+  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  a.budget = (uint32_t)budget; a.max_cards = (uint32_t)max_cards; a.worlds = (uint32_t)worlds; a.chunks = (uint32_t)chunks;
+  a.roles = (uint32_t)roles; a.tt_entries = (uint32_t)tt_entries; a.stride = stride;
+  a.n = n; a.wins = wins; a.unknown = unknown; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  a.work = (uint8_t*)work;
+  if (hidden) hipLaunchKernelGGL(k_solve<true>, dim3((unsigned)blocks), dim3(SOLVE_WAVES * 64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_solve<false>, dim3((unsigned)blocks), dim3(SOLVE_WAVES * 64), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int ddz_solve_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, int64_t worlds,
+                     const int32_t* wins, const int32_t* unknown, int32_t* choice, int32_t* value, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!counts || !ids || !wins || !unknown || !choice || !value) return DDZ_EINVAL;
+  if (!al(counts, 4) || !al(ids, 4) || !al(wins, 4) || !al(unknown, 4) || !al(choice, 4) || !al(value, 4)) return DDZ_EINVAL;
+  if (stride < DDZ_SLAB_MIN_STRIDE || worlds < 1 || worlds > 65536) return DDZ_EINVAL;
+  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  if (e->T == 0) return DDZ_OK;
+  hipLaunchKernelGGL(k_solve_choose, dim3((unsigned)((e->T + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
+                     stride, (int32_t)worlds, wins, unknown, choice, value, e->T);
   return check_launch();
 }
 

@@ -799,6 +799,100 @@ class BatchedEnv:
                                       _stream(self.device)))
         return out
 
+    # ---- the exact endgame solver (solve spec v1) ----
+    SOLVE_MAX_CARDS = 20
+    SOLVE_MAX_BUDGET = 1 << 30
+    SOLVE_MAX_TT = 1 << 20
+
+    def _solve_tensors(self, t, name):
+        """the (n, wins, unknown) of a solve() call, handed back as `name`"""
+        n, wins, unknown = t
+        why = f" (of {name}: the (n, wins, unknown) of an earlier solve() call)"
+        self._arg(n, "n", torch.int32, numel=self.T, why=why)
+        self._arg(wins, "wins", torch.int32, numel=self.T * self.slab_stride, why=why)
+        self._arg(unknown, "unknown", torch.int32, numel=self.T * self.slab_stride, why=why)
+        return n, wins, unknown
+
+    def solve(self, budget=65536, max_cards=12, worlds=1, hidden=False, roles=0b111, salt=0, chunks=1, tt_entries=4096, out=None,
+              totals=None):
+        """The exact value of every legal move of every table that is an endgame (solve spec v1): open-hand
+        minimax of the win / lose game between the lord and the two farmers, a depth-first search with a transposition table
+        per root move.  -> (n, wins, unknown): n int32 [T] = the size of the actor's legal list where the table was solved (0
+        idle; -1 not an endgame -- more than max_cards cards in the three hands, no status bit -- or, hidden form, rows that do
+        not add up to a deck, status bit 6); wins int32 [T, stride], entry [t, j] = 1 iff after move j of table t's slab
+        list (legal_slab() order) the actor's side wins under best play of both sides; unknown int32 [T, stride], 1 where the
+        search of move j ran out of `budget` nodes (its wins entry is 0 then).  Where unknown is 0, wins is a fact about the
+        game: it depends on none of budget, chunks and tt_entries.  The env is only read.  Two memsets + one launch on the
+        current stream, nothing on the host: capturable.
+        budget: nodes per root move; max_cards <= 20; hidden=True: the opponents' hands are not read but dealt `worlds` times
+        from the cards the actor has not seen, exactly the worlds playout_worlds(worlds, salt) returns, and wins / unknown
+        are sums over them (perfect-information Monte Carlo: the root list is the same in every world); roles (hidden form
+        only): bit r set = tables whose actor is role r take part.  The open form takes worlds=1.  chunks: wavefronts per
+        (table, world), chunk c solves the root moves j = c (mod chunks) with a table of its own; tt_entries: entries of a
+        transposition table, a power of two (32 bytes each; T * worlds * chunks of them live in a workspace cached on the
+        env: 128 KiB per wavefront at the default).  totals: int64 [4] on the device, += {nodes, table hits, root moves
+        solved, root moves unknown}.  out: the three tensors of an earlier call, to reuse (wins / unknown are zeroed here)."""
+        hidden = bool(hidden)
+        roles = _roles_mask(roles, hidden)
+        st = self.slab_stride
+        if st < MAX_LEGAL_PER_TABLE:
+            raise ValueError(f"solve needs row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        budget, max_cards, worlds, chunks, tt_entries = int(budget), int(max_cards), int(worlds), int(chunks), int(tt_entries)
+        if not 1 <= budget <= self.SOLVE_MAX_BUDGET:
+            raise ValueError(f"budget must be in [1, {self.SOLVE_MAX_BUDGET}]")
+        if not 1 <= max_cards <= self.SOLVE_MAX_CARDS:
+            raise ValueError(f"max_cards must be in [1, {self.SOLVE_MAX_CARDS}]")
+        if not 1 <= worlds <= 65536 or (not hidden and worlds != 1):
+            raise ValueError("worlds must be in [1, 65536], and 1 in the open form (hidden=False)")
+        if not 1 <= chunks <= 65536:
+            raise ValueError("chunks must be in [1, 65536]")
+        if not 1 <= tt_entries <= self.SOLVE_MAX_TT or tt_entries & (tt_entries - 1):
+            raise ValueError(f"tt_entries must be a power of two in [1, {self.SOLVE_MAX_TT}]")
+        if not self._slab_fresh:        # entry [t, j] is read against the lists of the current state
+            self.legal_slab()
+        self._totals(totals)
+        if out is None:
+            out = (torch.empty(self.T, dtype=torch.int32, device=self.device),
+                   torch.empty(self.T * st, dtype=torch.int32, device=self.device),
+                   torch.empty(self.T * st, dtype=torch.int32, device=self.device))
+        n, wins, unknown = self._solve_tensors(out, "out")
+        need = int(self.lib.ddz_solve_work_bytes(self.T, worlds, chunks, tt_entries))
+        if need < 0:
+            raise ValueError("no workspace size for these arguments")
+        work = getattr(self, "_solve_work", None)
+        if work is None or work.numel() < need:
+            self._solve_work = work = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        wins.zero_()
+        unknown.zero_()
+        check(self.lib.ddz_solve(self._h, budget, max_cards, worlds, int(hidden), roles, int(salt) & 0xFFFFFFFF, chunks, tt_entries,
+                                 st, _p(n), _p(wins), _p(unknown), _p(totals), _p(work), work.numel(), _stream(self.device)))
+        return n, wins.view(self.T, st), unknown.view(self.T, st)
+
+    def solve_choose(self, budget=65536, max_cards=12, worlds=1, hidden=False, roles=0b111, salt=0, chunks=1, tt_entries=4096,
+                     solved=None, out=None, value=None):
+        """The solver's move of every endgame table -> (ids, value): ids int32 [T] canonical action ids for
+        step_slab(mode=STEP_IDS), the first move with the most wins, among equals the first with the fewest unknown, -1 for
+        tables without a list (idle); value int32 [T] = 1 where that move is proven winning (it wins in every world), 0 where
+        every move is proven losing, else -1.  A running table that solve() left out (n = -1) has all-zero counts and so gets
+        the first move of its list and value 0: mask by n.  solved: the (n, wins, unknown) of an earlier solve() call with
+        the same `worlds` to choose from (no solve)."""
+        if self.ids is None:
+            raise ValueError("solve_choose needs the action ids of the lists (want_ids=True)")
+        out = self._ids_out(out)
+        if value is None:
+            value = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        self._arg(value, "value", torch.int32, numel=self.T)
+        worlds = int(worlds)
+        if not 1 <= worlds <= 65536:
+            raise ValueError("worlds must be in [1, 65536]")
+        if solved is None:
+            solved = self.solve(budget, max_cards, worlds, hidden, roles, salt, chunks, tt_entries, out=getattr(self, "_solve_out", None))
+            self._solve_out = tuple(x.view(-1) for x in solved)
+        _, wins, unknown = self._solve_tensors(tuple(x.view(-1) if x is not None and x.is_contiguous() else x for x in solved), "solved")
+        check(self.lib.ddz_solve_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, worlds, _p(wins), _p(unknown),
+                                        _p(out), _p(value), _stream(self.device)))
+        return out, value
+
     def rollout_random_csr(self, n_iters, traj=None, batch=None):
         """The same loop with packed CSR lists (offsets/rows/ids as legal() returns them: afterwards they hold the lists
         of the last iteration's pre-step states).  Same states and trajectories as rollout_random.

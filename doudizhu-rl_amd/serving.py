@@ -229,6 +229,36 @@ def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=Fals
     return _id_cards(ids, dev)
 
 
+def solve_act(payloads, budget=65536, max_cards=12, worlds=1, device="cuda:0", salt=0, seed=0, hidden=False, chunks=1,
+              tt_entries=4096, want_value=False):
+    """The exact endgame move for a batch of requests (BatchedEnv.solve / solve_choose, solve spec v1): every legal move of
+    every request is searched to the end of the game and a move that is proven to win for the requester's side is returned
+    where there is one -- per request a list of rank values 3..17, [] for a pass.  want_value: -> (moves, values), values[i]
+    = 1 the move is proven winning, 0 every move is proven losing, -1 neither (a search ran out of `budget`, or the worlds
+    disagree).
+    hidden=False: FULL payloads (with hand_card, as full_payloads_to_state reads them), solved over the three known hands.
+    hidden=True: the PLAIN serving payloads (no hand_card; one that is there is not read): `worlds` deals of the cards the
+    requester has not seen are solved and the move that wins in the most of them is returned (perfect-information Monte
+    Carlo).  ValueError where a request is no endgame (more than max_cards cards in the three hands, or a finished game)
+    or, hidden form, where cur_cards, history and left do not add up to a deck (status bit 6)."""
+    n = len(payloads)
+    if n == 0:
+        return ([], []) if want_value else []
+    dev = torch.device(device)
+    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
+    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
+    env.state_import(torch.from_numpy(st).view(-1))
+    solved = env.solve(budget, max_cards, worlds if hidden else 1, hidden, salt=salt, chunks=chunks, tt_entries=tt_entries)
+    ids, value = env.solve_choose(worlds=worlds if hidden else 1, solved=solved)
+    ids, value, size = ids.cpu().numpy(), value.cpu().numpy(), solved[0].cpu().numpy()
+    if hidden and env.status() & 64:
+        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
+    if (size <= 0).any():
+        raise ValueError(f"a payload is no endgame: more than {int(max_cards)} cards are left, or the game is over")
+    moves = _id_cards(ids, dev)
+    return (moves, [int(v) for v in value]) if want_value else moves
+
+
 class Predictor:
     """The reference's serving predictor (server/core.py:74-118 Predictor.act) for a batch of payloads, with its three-way
     switch and thresholds: the rule agent while the requester holds 12 or more cards, CFR when the three hands together hold

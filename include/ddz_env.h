@@ -431,6 +431,66 @@ int ddz_cfr(ddz_env_t* env, int iterations, int roles, int64_t slots, void* work
 int ddz_cfr_choose(ddz_env_t* env, const int32_t* n, const int32_t* ids, const double* sigma, uint64_t salt, int greedy,
                    int32_t* choice, void* stream);
 
+/* The exact endgame solver: open-hand minimax of the two-sided win / lose game (the lord against the two farmers) for every
+ * root move of every table that is an endgame.  The reference has no such solver; "Solve spec v1"  is the
+ * engine's own, pinned by a CPU restatement on the oracle (tests/solve_reference.py).
+ *   Domain: a running table (dealt, not done) whose actor's bit is set in `roles` and whose three hands together hold
+ *     1 .. max_cards cards, max_cards <= DDZ_SOLVE_MAX_CARDS.  Open form (hidden == 0; worlds must be 1 and roles 7): the
+ *     three hand rows are read.  Hidden form (hidden != 0, worlds = K >= 1): the actor's hand row and byte 15 of the other two
+ *     hand rows are read -- the opponents' count bytes NEVER -- and world k < K is world k of playout spec v2, exactly what
+ *     ddz_playout_worlds(K, salt) returns (the same deal of RNG domain 5 keyed by (gid, k), the same domain test).
+ *     n[t] = the size of the actor's legal list where the table was solved, 0 for an idle table (not running, or its actor
+ *     not in `roles`), -1 and NO status bit for a running table with more than max_cards cards ("not an endgame": what a
+ *     dispatcher tests), -1 and status bit 6 where the hidden form's rows do not add up to a deck.
+ *   Value: the mover whose hand empties wins for its side (the lord alone, or either farmer).  wins[t * stride + j] += 1 for
+ *     every world in which, after move j of table t's slab list (ddz_legal_slab order), the ROOT ACTOR's side wins under best
+ *     play of both sides; unknown[t * stride + j] += 1 for every world in which the search of move j ran out of `budget` (that
+ *     world adds nothing to wins).  Entries of tables that were not solved are not touched.  The caller zeroes both arrays
+ *     (int32 [T * stride], stride >= DDZ_SLAB_MIN_STRIDE); 32-bit integer atomics, the result does not depend on scheduling.
+ *     Where unknown is 0, wins is a fact about the game: it does not depend on budget, chunks or tt_entries.
+ *   Search of root move j (budget nodes of its own; no cut among the root moves): the move is applied; if it empties the
+ *     actor's hand the actor's side has won, else the position behind it is ENTERED.  A position is (the three hands, the
+ *     combination to beat, the passes since it was played, the mover); two passes hand the lead back, and a position whose
+ *     passes reached 2 IS the lead position (nothing to beat, no passes).  Entering a position: if the nodes of move j have
+ *     reached budget, move j is unknown and its search ends; else nodes += 1, the table is probed and a hit returns its value
+ *     (hits += 1); else the children are tried in list order (slab order, pass first when following): a child whose move
+ *     empties the mover's hand wins for the mover at once -- it is not entered and counts no node -- any other child is
+ *     entered, and its value is the mover's where both movers are on one side, the opposite otherwise.  The first child
+ *     that wins for the mover's side ends the position as won (the cut); with no such child -- or an empty list -- it is
+ *     lost.  A finished position is stored in the table; the positions an exhausted budget leaves open are not.
+ *   Transposition table: tt_entries entries (a power of two, 1 .. DDZ_SOLVE_MAX_TT) per (table, world, chunk), direct
+ *     mapped, always replaced, empty before the first root move of the chunk and shared by its root moves in ascending
+ *     order.  With hc / hn / hp the hands of the mover, the next and the previous player as 15 nibbles (rank r at bits
+ *     4r .. 4r+3) and cb the cards of the combination to beat in the same form, the key is x = hc | mover << 60, y = hn,
+ *     z = hp, w = cb | passes << 60 (w = 0 for the lead position), all of which an entry holds and a hit compares, and
+ *     slot = low 32 bits of h, h = x * 0x9E3779B97F4A7C15 ^ y * 0xC2B2AE3D27D4EB4F ^ z * 0x165667B19E3779F9 ^
+ *     w * 0x85EBCA77C2B2AE63, h ^= h >> 29, h *= 0xBF58476D1CE4E5B9, h ^= h >> 32 (mod 2^64), masked by tt_entries - 1.
+ *   Work split: one wavefront per (table, world, chunk); chunk c solves the root moves j = c (mod chunks).  1 <= chunks <=
+ *     65536, 1 <= worlds <= 65536, 1 <= budget <= DDZ_SOLVE_MAX_BUDGET.
+ *   Depth: a move that is no pass removes a card, at most two passes follow one and at most two precede the first, the
+ *     last move of a game is no pass: at most 3 * cards moves, DDZ_SOLVE_MAX_DEPTH frames.  A deeper search (impossible
+ *     inside the domain) raises status bit 8 and leaves its move unknown.
+ *   totals (device int64[4], may be NULL) += {nodes, table hits, root moves solved, root moves unknown}: with the order,
+ *     the node count and the table fixed as above they are functions of the arguments, as unknown is.
+ *   work: caller-owned device scratch of >= ddz_solve_work_bytes(T, worlds, chunks, tt_entries) bytes (32 per entry),
+ *     16-byte aligned; a smaller buffer is DDZ_ECAP from the host.  Nothing in it has to be initialised: a wavefront clears
+ *     its own table.
+ * The env is only read.  One launch on `stream`, nothing on the host (capturable).
+ * ddz_solve_choose: choice[t] = ids[t * stride + j], j = the first maximum of wins over the entries j < counts[t], among
+ *   equal wins the first with the fewest unknown (remaining ties to the lowest index); -1 where counts[t] <= 0.  value[t] = 1
+ *   where that move is proven winning (wins = worlds), 0 where every move is proven losing (wins = unknown = 0 throughout),
+ *   else -1 (also where counts[t] <= 0).  Feed choice to ddz_step_slab(DDZ_STEP_IDS). */
+#define DDZ_SOLVE_MAX_CARDS 20      /* one full hand */
+#define DDZ_SOLVE_MAX_DEPTH 60      /* 3 * DDZ_SOLVE_MAX_CARDS */
+#define DDZ_SOLVE_MAX_BUDGET (1 << 30)
+#define DDZ_SOLVE_MAX_TT (1 << 20)
+int64_t ddz_solve_work_bytes(int64_t n_tables, int64_t worlds, int64_t chunks, int64_t tt_entries);
+int ddz_solve(ddz_env_t* env, int64_t budget, int max_cards, int64_t worlds, int hidden, int roles, uint64_t salt, int64_t chunks,
+              int64_t tt_entries, int64_t stride, int32_t* n, int32_t* wins, int32_t* unknown, int64_t* totals, void* work,
+              int64_t work_bytes, void* stream);
+int ddz_solve_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, int64_t worlds,
+                     const int32_t* wins, const int32_t* unknown, int32_t* choice, int32_t* value, void* stream);
+
 /* The same random-policy loop with the lists in the CSR layout of ddz_legal (offsets/rows/ids
  * packed across tables).  CSR bases need a scan over all tables, so this variant is one
  * launch per iteration: the fused kernel writes the list of the current state, steps, and
@@ -789,7 +849,9 @@ int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
  * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing), bit6 a running
  * table of ddz_playout_hidden / ddz_playout_worlds outside the hidden-hand domain (its hand, taken row and hand sizes do not
  * add up to a deck): that table ran nothing -- and a running table of ddz_cfr with at most DDZ_CFR_MAX_CARDS cards whose rows
- * do not add up; bit7 a table of ddz_cfr that found no workspace slot or whose forest exceeds a capacity (n = -2).
+ * do not add up, or of the hidden form of ddz_solve with at most max_cards cards whose rows do not add up; bit7 a table of
+ * ddz_cfr that found no workspace slot or whose forest exceeds a capacity (n = -2); bit8 a search of ddz_solve deeper than
+ * DDZ_SOLVE_MAX_DEPTH (impossible inside its domain: that root move is left unknown).
  * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
 /* the same word for the STATELESS rule-agent entry point (ddz_auto_choose has no handle): one per device, bits as above
