@@ -1,15 +1,15 @@
 // ddz_cfr.h -- k_cfr / k_cfr_choose: the CFR endgame solver ("CFR spec v1"; the reference's final_card /
 // initiate_game / VanillaCFR, server/CFR.py, with everything it leaves to chance pinned).  Included by ddz_engine.hip behind
-// ddz_ply.h, inside its anonymous namespace.  The root decode (play_root_decode), the domain test (unseen_pool), the legal
-// lists (ply_list / ply_entry: the device keeps one statement of the rules) and the wavefront-scope accesses (sld / sst /
-// search_fence) are ddz_ply.h's, shared with k_playout and k_search.
+// ddz_ply.h, inside its anonymous namespace.  The entry into a table (table_enter), the root with the domain test
+// (root_hands<true>), the legal lists (ply_list / ply_entry: the device keeps one statement of the rules) and the
+// wavefront-scope accesses (rfl64 / sld / sst / search_fence) are ddz_ply.h's, shared with k_playout, k_search and k_solve.
 //
 // One wavefront per TABLE; a table inside the domain takes one workspace SLOT from a counter at the head of the workspace
 // (zeroed by k_cfr_head, a one-wave launch in front of k_cfr) and keeps it for the launch.  Seats are the reference's player
 // numbers: 0 lord, 1 down, 2 up = role (seat + 1) % 3; the turn order is seat 0, 1, 2.
 //
 // PHASES of a wave.
-//   decode   the root as k_search<true> reads it (play_root_decode, unseen_pool): the actor's hand row, the taken row, the
+//   decode   the root as k_search<true> reads it (root_hands<true>): the actor's hand row, the taken row, the
 //            recent rows with their category bytes, the meta row, byte 15 of the other two hand rows -- never the opponents'
 //            count bytes.
 //   deals    every assignment of pool = deck - taken to the seats by per-rank counts, in CFR.py:deal's order: the pool has
@@ -56,9 +56,7 @@
 // node of parent / set / first child / next member / action / kind = 320 KiB; 8 B x 8,192 set records, 2 x 8 B x 8,192 R and
 // sigma, 8 B x 16,384 + 8 B x 8,192 table entries = 384 KiB.  (The 1 MB the design aimed at assumed 16,384 nodes; follow roots
 // doubled the measured maximum.)
-struct CfrArgs {
-  const uint8_t* state;
-  int64_t T;
+struct CfrArgs : PlyArgs {   // (no draw in the solver: the key is not read)
   uint32_t iterations, roles;
   int64_t slots;
   uint8_t* work;            // 256 bytes of head (the slot counter), then slots x CFR_SLOT_BYTES
@@ -67,7 +65,6 @@ struct CfrArgs {
   double* sigma;            // [T][DDZ_CFR_STRIDE]
   double* value;            // [T]
   unsigned long long* totals;
-  int32_t* status;
 };
 
 constexpr int CFR_WAVES = 4;                      // 36,464 B of LDS per block
@@ -100,7 +97,6 @@ __device__ __forceinline__ void sst16(uint16_t* p, uint32_t v) { __hip_atomic_st
 __device__ __forceinline__ void sst8(uint8_t* p, uint32_t v) { __hip_atomic_store(p, (uint8_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ double sldf(const double* p) { return __longlong_as_double((long long)sld64((const uint64_t*)p)); }
 __device__ __forceinline__ void sstf(double* p, double v) { sst64((uint64_t*)p, (uint64_t)__double_as_longlong(v)); }
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32); }
 
 // a hand of at most 4 cards in 16 bits: nibble j = 1 + the rank of its j-th lowest card
 __device__ __forceinline__ uint32_t cfr_hand16(uint64_t nib) {
@@ -169,11 +165,8 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = (int)rfl(threadIdx.x >> 6);
   const int64_t t = (int64_t)blockIdx.x * CFR_WAVES + wv;
-  uint4 R = make_uint4(0, 0, 0, 0);
-  if (t < a.T && lane < DDZ_NFIELDS) R = ((const uint4*)(a.state + t * STATE_ROW_BYTES))[lane];
-  hot_fill<CFR_WAVES * 64>(hot);
-  __syncthreads();   // the block's only barrier
-  if (t >= a.T) return;
+  uint4 R;
+  if (!table_enter<CFR_WAVES>(a, t, lane, hot, R)) return;
   uint64_t* stage = s_stage[wv];
   uint16_t* svl = s_svl[wv];
   uint16_t* dl = s_deal[wv];
@@ -184,17 +177,13 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   if (lane < DDZ_CFR_STRIDE) { out_ids[lane] = -1; out_sigma[lane] = 0.0; }
   if (lane == 0) { a.value[t] = 0.0; a.n[t] = 0; }
   // ---- decode (as k_search<true>)
-  const PlayRoot root = play_root_decode(R);
-  if (!root.running) return;   // not dealt, or done
+  const RootHands rh = root_hands<true>(R, a.roles, lane);
+  if (rh.kind == ROOT_IDLE) return;   // not dealt, done, or not this call's seat
+  const PlayRoot& root = rh.root;
   const int role0 = root.role0;
-  if (!((a.roles >> role0) & 1u)) return;
   const int rnext = role_next(role0);
   const uint64_t hc0 = root.hc0;
-  const int n_me = nib_sum(hc0);
-  int n_next, n_prev;
-  uint64_t unseen;
-  bool pool_lane;
-  const bool inside = unseen_pool(root, lane, n_next, n_prev, unseen, pool_lane);
+  const int n_me = rh.n_me, n_next = rh.n_next, n_prev = rh.n_prev;
   if (n_me + n_next + n_prev > DDZ_CFR_MAX_CARDS) {   // not an endgame
     if (lane == 0) a.n[t] = -1;
     return;
@@ -202,11 +191,11 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   // unseen_pool is the domain of this spec too: per rank `taken > deck || hand > deck - taken` is `hand + taken > deck` for
   // counts that are not negative, and where that holds for no rank deck - taken = unseen + hand without a borrow, so
   // `sum(deck - taken) != n_me + n_next + n_prev` is `sum(unseen) != n_next + n_prev`.  The actor's own hand is not empty.
-  if (!inside || n_me < 1) {
+  if (rh.kind == ROOT_OUTSIDE || n_me < 1) {
     if (lane == 0) { a.n[t] = -1; atomicOr(a.status, 64); }
     return;
   }
-  const uint64_t pool = unseen + hc0;   // deck - taken
+  const uint64_t pool = rh.unseen + hc0;   // deck - taken
   // the combination to beat and its owner (final_card: the previous seat's, else the one before, else a lead of the actor's)
   const int first = role_prev(role0);   // the actor's seat
   const uint32_t trick0 = rfl(root.trick0);

@@ -11,12 +11,12 @@
 //   k_search  (ddz_search.h; ddz_search) UCT tree search around those playouts: one wavefront per (table, tree), the tree in a
 //             caller-provided workspace, the descent re-applies stored moves.
 //   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
-//             These three share ddz_ply.h: the root decode, the hidden-hand domain and redeal, and a ply (list, entry, apply,
-//             draw) built from k_rollout's device functions -- each stated once.
-//   k_solve   (ddz_solve.h; ddz_solve) the exact endgame solver, a fourth caller of ddz_ply.h: one wavefront per (table, world,
-//             chunk), a depth-first search with its transposition table in the caller's workspace.
-//   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives; CSR lists,
-//             or slab lists with F_SLAB = apply + enumerate in the same launch):
+//   k_solve   (ddz_solve.h; ddz_solve) the exact endgame solver: one wavefront per (table, world, chunk), a depth-first search
+//             with its transposition table in the caller's workspace.
+//             These four share ddz_ply.h: the entry into a table, the root with its hands and the hidden-hand domain, the
+//             redeal, and a ply (list, entry, apply, draw) built from k_rollout's device functions -- each stated once.
+//   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives) on CSR lists; with
+//             F_SLAB the lists of the current state alone, in the slab layout (stepping on slab lists is k_slab's):
 //             lanes 0..10 load the table's 11 packed rows (176 contiguous bytes), then
 //             [enumerate] the combo enumerator + follow filter (r.get_moves, envi.py:111;
 //                 rules utils.py:45-63 get_mask, card.py:307-325 bigger_than) as a pruned
@@ -692,12 +692,12 @@ struct TableArgs {
 template <int FLAGS, int MODE, bool IDS>
 __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
   constexpr bool ENUM = FLAGS & F_ENUM, STEP = FLAGS & F_STEP, RESET = FLAGS & F_RESET;
-  // F_SLAB: the lists live in fixed-stride slabs, so a launch applies the selections to the lists of the
-  // previous launch AND writes the lists of the new state: one launch per lock-step iteration, no CSR scan
+  // F_SLAB: the lists of the current state go into fixed-stride slabs, no CSR scan (ddz_legal_slab).  Stepping on slab lists
+  // is k_slab's
   constexpr bool SLAB = (FLAGS & F_SLAB) != 0;
+  static_assert(!(SLAB && STEP), "k_slab steps on slab lists");
   constexpr bool COUNT = !SLAB && (FLAGS & (F_STEP | F_RESET | F_COUNT)) != 0;
   constexpr bool PICK = ENUM && STEP && MODE == DDZ_STEP_RANDOM;
-  Stamps<8> stamps;
   const int lane = threadIdx.x & 63;
   const int wv = (int)rfl(threadIdx.x >> 6);
   const int64_t t0 = ((int64_t)blockIdx.x * WPB + wv) * a.tpw;
@@ -718,21 +718,8 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
     loc0 = a.cur_local[t0];
     if (lane < ntab) cnt_l = a.cur_counts[t0 + lane];
   }
-  uint4 pre_row = make_uint4(0, 0, 0, 0);  // F_SLAB + CHOICE: lane i prefetches the selected row of table t0 + i
-  int pre_idx = -1;
-  if (SLAB && STEP && lane < ntab) {
-    cnt_l = a.slab_counts[t0 + lane];
-    if (cnt_l < 0 || cnt_l > a.stride) cnt_l = 0;
-    if (MODE == DDZ_STEP_CHOICE) {
-      pre_idx = ((const int32_t*)a.sel)[t0 + lane];
-      if (pre_idx < 0 || pre_idx >= cnt_l) pre_idx = -1;
-      if (pre_idx >= 0) pre_row = a.rows[(t0 + lane) * a.stride + pre_idx];
-    }
-  }
-  stamps.mark(0);  // prologue loads issued
   hot_fill<TB>(hot);
   __syncthreads();
-  stamps.mark(1);  // hot fill + barrier
   if (ENUM && ntab > 0) base = (int64_t)wave_sum(part) + loc0;
   for (int i = 0; i < ntab; ++i) {
     const int64_t t = t0 + i;
@@ -758,7 +745,6 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
     uint32_t qinfo = mk_info(EMPTY, 0, 1);
     int cnt = 0;
     Pick pk{-1, 0, 0, 0, 0};
-    stamps.mark(2);  // decode
     if (ENUM) {
       cnt = (int)rl((uint32_t)cnt_l, i);
       if (lane == 0) a.offsets[t] = (int32_t)base;
@@ -777,14 +763,11 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
     if (STEP) {
       int64_t off = base;
       int A = cnt;
-      if (SLAB) {
-        off = t * a.stride;
-        A = (int)rl((uint32_t)cnt_l, i);
-      } else if (!ENUM) {
+      if (!ENUM) {
         off = a.offsets[t];
         A = a.offsets[t + 1] - (int32_t)off;
       }
-      if (!SLAB && (off < 0 || off + A > a.cap)) A = 0;  // list was truncated: nothing to pick from
+      if (off < 0 || off + A > a.cap) A = 0;  // list was truncated: nothing to pick from
       const bool frozen = !active || A <= 0;
       int idx = -1;
       uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;  // the chosen row, wave-uniform
@@ -799,12 +782,8 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
             idx = (int)__umulhi(rfl(d.x), (uint32_t)A);
           }
         } else if (MODE == DDZ_STEP_CHOICE) {
-          if (SLAB) {
-            idx = (int)rl((uint32_t)pre_idx, i);
-          } else {
-            idx = ((const int32_t*)a.sel)[t];
-            if (idx < 0 || idx >= A) idx = -1;
-          }
+          idx = ((const int32_t*)a.sel)[t];
+          if (idx < 0 || idx >= A) idx = -1;
         } else {  // wave-parallel search of the segment for the wanted counts
           constexpr int NIDS = DDZ_NUM_ACTIONS + 24 * DDZ_NATIVE_JOKER_KICKERS;
           const bool id_ok = MODE != DDZ_STEP_IDS || (sel_id >= 0 && sel_id < NIDS);
@@ -819,9 +798,7 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
             if (hb) idx = j0 + __builtin_ctzll(hb);
           }
         }
-        if (idx >= 0 && SLAB && MODE == DDZ_STEP_CHOICE) {
-          c0 = rl(pre_row.x, i); c1 = rl(pre_row.y, i); c2 = rl(pre_row.z, i); c3 = rl(pre_row.w, i);
-        } else if (idx >= 0 && !PICK) {
+        if (idx >= 0 && !PICK) {
           const uint4 r = a.rows[off + idx];
           c0 = rfl(r.x); c1 = rfl(r.y); c2 = rfl(r.z); c3 = rfl(r.w);
         }
@@ -893,7 +870,6 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
         qhand = h1; qinfo = mk_info(EMPTY, 0, 1);
       }
     }
-    stamps.mark(3);  // select + apply + outputs
     if (changed) {
       if (lane < DDZ_NFIELDS) trow[lane] = R;  // one coalesced 176-byte store
       if (COUNT || SLAB) {                     // query of the new actor
@@ -919,18 +895,14 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
       if (lane == 0) a.slab_counts[t] = n;
       slab_rows += n;
     }
-    stamps.mark(4);  // state store + list of the new state
     base += cnt;
   }
-  stamps.set(5, (unsigned long long)ntab);
-  stamps.store(t0, lane == 0 && ntab > 0 && SLAB && STEP);
   if (ENUM && ntab > 0 && t0 + ntab == a.T && lane == 0) {
     a.offsets[a.T] = (int32_t)base;
     *a.legal_rows += base;
   }
   if (SLAB && ntab > 0 && lane == 0) {  // each wave owns its statistics slot (as in k_rollout)
     int64_t* ws = a.blk_stats + 4 * ((int64_t)blockIdx.x * WPB + wv);
-    if (STEP) { ws[0] += s_ply; ws[1] += s_eps; ws[2] += (int64_t)s_lord | ((int64_t)s_up << 32); }
     ws[3] += slab_rows;
   }
   if (COUNT) {
@@ -1407,7 +1379,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
   }
 }
 
-#include "ddz_ply.h"      // the root decode, the hidden-hand domain and a ply, shared by the three kernels below
+#include "ddz_ply.h"      // the entry into a table, the root with its hands and a ply, shared by the four kernels below
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
@@ -2862,9 +2834,7 @@ int launch_table(ddz_env* e, const Io& io, hipStream_t st) {
   else
     hipLaunchKernelGGL((k_table<FLAGS, MODE, false>), grid, block, 0, st, a);
   int rc = check_launch();
-  if (rc == DDZ_OK && (FLAGS & F_SLAB)) {
-    if (FLAGS & F_STEP) e->counts_valid = false;  // the state moved on without refreshing the CSR scan buffers
-  } else if (rc == DDZ_OK && (FLAGS & (F_STEP | F_RESET | F_COUNT))) {
+  if (rc == DDZ_OK && !(FLAGS & F_SLAB) && (FLAGS & (F_STEP | F_RESET | F_COUNT))) {
     e->parity = nxt;
     e->counts_valid = true;
   }
@@ -2874,6 +2844,42 @@ int launch_table(ddz_env* e, const Io& io, hipStream_t st) {
 int ensure_counts(ddz_env* e, hipStream_t st) {
   if (e->counts_valid) return DDZ_OK;
   return launch_table<F_COUNT, 0>(e, Io{}, st);
+}
+
+// ---- the four move evaluators (k_playout, k_search, k_cfr, k_solve): what their entry points share, stated once ----
+// PlyArgs' six fields (ddz_ply.h) of an evaluator's arguments; k_cfr draws nothing and does not read the key
+template <typename Args>
+void ply_args(Args& a, const ddz_env* e, uint64_t salt) {
+  a.state = e->state; a.T = e->T;
+  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  a.status = e->sc.status;
+}
+// a buffer of `stride` entries per table, indexed in 32 bits.  Stands behind every other argument test of its caller.
+int slab_args_ok(const ddz_env* e, int64_t stride) {
+  if (stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  return e->T * stride > 0x7FFFFFFF ? DDZ_ECAP : DDZ_OK;
+}
+bool roles_ok(int roles, bool hidden) { return roles >= 0 && roles <= 7 && (hidden || roles == 7); }
+// `items` work items, `per` of them to a block -> the grid in *blocks, or DDZ_ECAP where 31 bits do not hold it
+int grid_of(int64_t items, int per, int64_t* blocks) {
+  *blocks = (items + per - 1) / per;
+  return *blocks > 0x7FFFFFFF ? DDZ_ECAP : DDZ_OK;
+}
+// the two-way launch of an evaluator: blocks of WAVES wavefronts
+template <auto OPEN, auto HIDDEN, int WAVES, typename A>
+int launch_hidden(bool hidden, int64_t blocks, void* stream, const A& a) {
+  if (hidden) hipLaunchKernelGGL(HIDDEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(OPEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+// a *_choose kernel over the env's tables, `per` tables to a block of BLOCK threads
+template <auto K, typename... Q>
+int launch_choose(ddz_env* e, int per, void* stream, Q... args) {
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  if (e->T == 0) return DDZ_OK;
+  hipLaunchKernelGGL(K, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, args..., e->T);
+  return check_launch();
 }
 
 }  // namespace
@@ -3465,47 +3471,44 @@ int ddz_rollout_random(ddz_env_t* e, int64_t n_iters, int32_t* counts, int8_t* r
   return DDZ_OK;
 }
 
-// ddz_playout / ddz_playout_hidden / ddz_playout_worlds: one launch of k_playout<hidden>
+// ddz_playout / ddz_playout_hidden / ddz_playout_worlds: one launch of k_playout<hidden>, one wavefront per (table, chunk)
 static int launch_playout(bool hidden, ddz_env_t* e, int64_t K, uint64_t salt, int64_t chunks, int64_t stride, int roles, int32_t* wins,
                           int64_t* totals, uint8_t* worlds, void* stream) {
-  const int64_t blocks = (e->T * chunks + PLAYOUT_WAVES - 1) / PLAYOUT_WAVES;  // one wavefront per (table, chunk)
-  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  int64_t blocks;
+  if (grid_of(e->T * chunks, PLAYOUT_WAVES, &blocks)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   PlayoutArgs a;
-  a.state = e->state; a.T = e->T;
-  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  ply_args(a, e, salt);
   a.K = (uint32_t)K; a.chunks = (uint32_t)chunks; a.stride = stride;
-  a.wins = wins; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  a.wins = wins; a.totals = (unsigned long long*)totals;
   a.roles = (uint32_t)roles; a.worlds = worlds;
-  if (hidden) hipLaunchKernelGGL(k_playout<true>, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_playout<false>, dim3((unsigned)blocks), dim3(PLAYOUT_WAVES * 64), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return launch_hidden<k_playout<false>, k_playout<true>, PLAYOUT_WAVES>(hidden, blocks, stream, a);
+}
+
+static int playout_checked(bool hidden, ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int roles,
+                           int32_t* wins, int64_t* totals, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
+  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || !roles_ok(roles, hidden)) return DDZ_EINVAL;
+  if (const int rc = slab_args_ok(e, stride)) return rc;
+  return launch_playout(hidden, e, n_playouts, salt, chunks, stride, roles, wins, totals, nullptr, stream);
 }
 
 int ddz_playout(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int32_t* wins, int64_t* totals,
                 void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
-  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
-  return launch_playout(false, e, n_playouts, salt, chunks, stride, 7, wins, totals, nullptr, stream);
+  return playout_checked(false, e, n_playouts, salt, chunks, stride, 7, wins, totals, stream);
 }
 
 int ddz_playout_hidden(ddz_env_t* e, int64_t n_playouts, uint64_t salt, int64_t chunks, int64_t stride, int roles, int32_t* wins,
                        int64_t* totals, void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!wins || !al(wins, 4) || !al(totals, 8)) return DDZ_EINVAL;
-  if (n_playouts < 1 || n_playouts >= (1ll << 23) || chunks < 1 || chunks > (1ll << 20) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (roles < 0 || roles > 7) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
-  return launch_playout(true, e, n_playouts, salt, chunks, stride, roles, wins, totals, nullptr, stream);
+  return playout_checked(true, e, n_playouts, salt, chunks, stride, roles, wins, totals, stream);
 }
 
 int ddz_playout_worlds(ddz_env_t* e, int64_t n_worlds, uint64_t salt, int roles, uint8_t* out, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
   if (!out) return DDZ_EINVAL;
-  if (n_worlds < 1 || n_worlds >= (1ll << 23) || roles < 0 || roles > 7) return DDZ_EINVAL;
+  if (n_worlds < 1 || n_worlds >= (1ll << 23) || !roles_ok(roles, true)) return DDZ_EINVAL;
   if (e->T * n_worlds > 0x7FFFFFFF) return DDZ_ECAP;
   // wavefronts per table: enough to fill the device when there are few tables, never more than there are worlds
   int64_t chunks = (24576 + e->T - 1) / (e->T > 0 ? e->T : 1);
@@ -3518,14 +3521,8 @@ int ddz_playout_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, 
                        void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
   if (!counts || !ids || !wins || !choice || !al(counts, 4) || !al(ids, 4) || !al(wins, 4) || !al(choice, 4)) return DDZ_EINVAL;
-  if (stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  const int64_t per = BLOCK / 64;
-  hipLaunchKernelGGL(k_playout_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
-                     stride, wins, choice, e->T);
-  return check_launch();
+  if (const int rc = slab_args_ok(e, stride)) return rc;
+  return launch_choose<k_playout_choose>(e, BLOCK / 64, stream, counts, ids, stride, wins, choice);
 }
 
 // ddz_search: one launch of k_search<hidden>, one wavefront per (table, tree); the tree lives in the caller's workspace
@@ -3538,30 +3535,27 @@ int ddz_search(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, u
                int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
   if (!visits || !wins || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
-  if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536 || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
+  if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return DDZ_EINVAL;
   if (mode != DDZ_SEARCH_REFERENCE && mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
   if (!(c >= 0.0f) || !(c <= 3.0e38f)) return DDZ_EINVAL;   // (finite and not negative: values order as their bit patterns)
-  if (roles < 0 || roles > 7 || (!hidden && roles != 7)) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  if (!roles_ok(roles, hidden)) return DDZ_EINVAL;
+  if (const int rc = slab_args_ok(e, stride)) return rc;
   if (work_bytes < ddz_search_work_bytes(e->T, budget, trees)) return DDZ_ECAP;
-  const int64_t blocks = (e->T * trees + SEARCH_WAVES - 1) / SEARCH_WAVES;
-  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  int64_t blocks;
+  if (grid_of(e->T * trees, SEARCH_WAVES, &blocks)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   SearchArgs a;
-  a.state = e->state; a.T = e->T;
-  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  ply_args(a, e, salt);
   a.budget = (uint32_t)budget; a.trees = (uint32_t)trees; a.mode = (uint32_t)mode; a.c = c;
-  a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals;
   a.roles = (uint32_t)roles; a.work = (uint8_t*)work; a.tree_bytes = search_tree_bytes(budget); a.hash_log = search_hash_log(budget);
   void* ln = nullptr;
   const hipError_t r = hipGetSymbolAddress(&ln, HIP_SYMBOL(g_search_ln));
   if (r != hipSuccess) return hip_fail(r);
   a.ln = (const float*)ln;
   if (blocks == 0) return DDZ_OK;
-  if (hidden) hipLaunchKernelGGL(k_search<true>, dim3((unsigned)blocks), dim3(SEARCH_WAVES * 64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_search<false>, dim3((unsigned)blocks), dim3(SEARCH_WAVES * 64), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return launch_hidden<k_search<false>, k_search<true>, SEARCH_WAVES>(hidden, blocks, stream, a);
 }
 
 int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,
@@ -3569,14 +3563,8 @@ int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, i
   if (!good(e)) return DDZ_EHANDLE;
   if (!counts || !ids || !visits || !wins || !choice) return DDZ_EINVAL;
   if (!al(counts, 4) || !al(ids, 4) || !al(visits, 4) || !al(wins, 4) || !al(choice, 4)) return DDZ_EINVAL;
-  if (stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  const int64_t per = BLOCK / 64;
-  hipLaunchKernelGGL(k_search_choose, dim3((unsigned)((e->T + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
-                     stride, visits, wins, choice, e->T);
-  return check_launch();
+  if (const int rc = slab_args_ok(e, stride)) return rc;
+  return launch_choose<k_search_choose>(e, BLOCK / 64, stream, counts, ids, stride, visits, wins, choice);
 }
 
 // ddz_cfr: k_cfr_head zeroes the workspace's head (the slot counter), then one launch of k_cfr, one wavefront per table
@@ -3590,12 +3578,12 @@ int ddz_cfr(ddz_env_t* e, int iterations, int roles, int64_t slots, void* work, 
   if (!good(e)) return DDZ_EHANDLE;
   if (!work || !n || !ids || !sigma || !value) return DDZ_EINVAL;
   if (!al(work, 16) || !al(n, 4) || !al(ids, 4) || !al(sigma, 8) || !al(value, 8) || !al(totals, 8)) return DDZ_EINVAL;
-  if (iterations < 0 || iterations > DDZ_CFR_MAX_ITERATIONS || roles < 0 || roles > 7) return DDZ_EINVAL;
+  if (iterations < 0 || iterations > DDZ_CFR_MAX_ITERATIONS || !roles_ok(roles, true)) return DDZ_EINVAL;
   const int64_t need = ddz_cfr_work_bytes(slots);
   if (need < 0) return DDZ_EINVAL;
   if (work_bytes < need) return DDZ_ECAP;
-  const int64_t blocks = (e->T + CFR_WAVES - 1) / CFR_WAVES;
-  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  int64_t blocks;
+  if (grid_of(e->T, CFR_WAVES, &blocks)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   if (blocks == 0) return DDZ_OK;
@@ -3604,9 +3592,9 @@ int ddz_cfr(ddz_env_t* e, int iterations, int roles, int64_t slots, void* work, 
   // 16-byte pattern (profiles/r14_notes.md 5), and every table found no slot
   hipLaunchKernelGGL(k_cfr_head, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)work);
   CfrArgs a;
-  a.state = e->state; a.T = e->T; a.iterations = (uint32_t)iterations; a.roles = (uint32_t)roles; a.slots = slots;
+  ply_args(a, e, 0);
+  a.iterations = (uint32_t)iterations; a.roles = (uint32_t)roles; a.slots = slots;
   a.work = (uint8_t*)work; a.n = n; a.ids = ids; a.sigma = sigma; a.value = value; a.totals = (unsigned long long*)totals;
-  a.status = e->sc.status;
   hipLaunchKernelGGL(k_cfr, dim3((unsigned)blocks), dim3(CFR_WAVES * 64), 0, (hipStream_t)stream, a);
   return check_launch();
 }
@@ -3615,12 +3603,9 @@ int ddz_cfr_choose(ddz_env_t* e, const int32_t* n, const int32_t* ids, const dou
                    int32_t* choice, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
   if (!n || !ids || !sigma || !choice || !al(n, 4) || !al(ids, 4) || !al(sigma, 8) || !al(choice, 4)) return DDZ_EINVAL;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  if (e->T == 0) return DDZ_OK;
-  hipLaunchKernelGGL(k_cfr_choose, dim3((unsigned)((e->T + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, n, ids, sigma,
-                     (uint32_t)e->seed ^ (uint32_t)salt, (uint32_t)(e->seed >> 32), e->gid_base, greedy, choice, e->T);
-  return check_launch();
+  PlyArgs k;
+  ply_args(k, e, salt);
+  return launch_choose<k_cfr_choose>(e, BLOCK, stream, n, ids, sigma, k.k0, k.k1, k.gid_base, greedy, choice);
 }
 
 // ddz_solve: one launch of k_solve<hidden>, one wavefront per (table, world, chunk); its table lives in the caller's workspace
@@ -3644,26 +3629,23 @@ int ddz_solve(ddz_env_t* e, int64_t budget, int max_cards, int64_t worlds, int h
   if (!n || !wins || !unknown || !work) return DDZ_EINVAL;
   if (!al(n, 4) || !al(wins, 4) || !al(unknown, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
   if (budget < 1 || budget > DDZ_SOLVE_MAX_BUDGET || max_cards < 1 || max_cards > DDZ_SOLVE_MAX_CARDS) return DDZ_EINVAL;
-  if (!solve_sizes_ok(worlds, chunks, tt_entries) || stride < DDZ_SLAB_MIN_STRIDE) return DDZ_EINVAL;
-  if (roles < 0 || roles > 7 || (!hidden && (roles != 7 || worlds != 1))) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
+  if (!solve_sizes_ok(worlds, chunks, tt_entries)) return DDZ_EINVAL;
+  if (!roles_ok(roles, hidden) || (!hidden && worlds != 1)) return DDZ_EINVAL;
+  if (const int rc = slab_args_ok(e, stride)) return rc;
   const int64_t need = ddz_solve_work_bytes(e->T, worlds, chunks, tt_entries);
   if (need < 0 || work_bytes < need) return DDZ_ECAP;
-  const int64_t blocks = (e->T * worlds * chunks + SOLVE_WAVES - 1) / SOLVE_WAVES;
-  if (blocks > 0x7FFFFFFF) return DDZ_ECAP;
+  int64_t blocks;
+  if (grid_of(e->T * worlds * chunks, SOLVE_WAVES, &blocks)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   if (blocks == 0) return DDZ_OK;
   SolveArgs a;
-  a.state = e->state; a.T = e->T;
-  a.k0 = (uint32_t)e->seed ^ (uint32_t)salt; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  ply_args(a, e, salt);
   a.budget = (uint32_t)budget; a.max_cards = (uint32_t)max_cards; a.worlds = (uint32_t)worlds; a.chunks = (uint32_t)chunks;
   a.roles = (uint32_t)roles; a.tt_entries = (uint32_t)tt_entries; a.stride = stride;
-  a.n = n; a.wins = wins; a.unknown = unknown; a.totals = (unsigned long long*)totals; a.status = e->sc.status;
+  a.n = n; a.wins = wins; a.unknown = unknown; a.totals = (unsigned long long*)totals;
   a.work = (uint8_t*)work;
-  if (hidden) hipLaunchKernelGGL(k_solve<true>, dim3((unsigned)blocks), dim3(SOLVE_WAVES * 64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_solve<false>, dim3((unsigned)blocks), dim3(SOLVE_WAVES * 64), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return launch_hidden<k_solve<false>, k_solve<true>, SOLVE_WAVES>(hidden, blocks, stream, a);
 }
 
 int ddz_solve_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, int64_t worlds,
@@ -3671,14 +3653,9 @@ int ddz_solve_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, in
   if (!good(e)) return DDZ_EHANDLE;
   if (!counts || !ids || !wins || !unknown || !choice || !value) return DDZ_EINVAL;
   if (!al(counts, 4) || !al(ids, 4) || !al(wins, 4) || !al(unknown, 4) || !al(choice, 4) || !al(value, 4)) return DDZ_EINVAL;
-  if (stride < DDZ_SLAB_MIN_STRIDE || worlds < 1 || worlds > 65536) return DDZ_EINVAL;
-  if (e->T * stride > 0x7FFFFFFF) return DDZ_ECAP;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  if (e->T == 0) return DDZ_OK;
-  hipLaunchKernelGGL(k_solve_choose, dim3((unsigned)((e->T + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, counts, ids,
-                     stride, (int32_t)worlds, wins, unknown, choice, value, e->T);
-  return check_launch();
+  if (worlds < 1 || worlds > 65536) return DDZ_EINVAL;
+  if (const int rc = slab_args_ok(e, stride)) return rc;
+  return launch_choose<k_solve_choose>(e, BLOCK, stream, counts, ids, stride, (int32_t)worlds, wins, unknown, choice, value);
 }
 
 int ddz_rollout_random_csr(ddz_env_t* e, int64_t n_iters, int32_t* offsets, int8_t* rows, int32_t* ids, int64_t cap,
@@ -4361,9 +4338,9 @@ int ddz_q_slab_needed(ddz_env_t* e, const float* h0, const float* d, int64_t row
 
 // per-role networks (ddz_qnet.h section 7): every buffer holds n_nets slot-major partitions of row_capacity rows, seg / dseg
 // n_nets blocks of QN_SEG_WORDS ints in the single-network layout, relative to the slot's partition
-static bool roles_ok(int n_nets) { return n_nets >= 1 && n_nets <= 3; }
+static bool n_nets_ok(int n_nets) { return n_nets >= 1 && n_nets <= 3; }
 int64_t ddz_q_roles_ws_bytes(int64_t n_tables, int variant, int n_nets) {
-  if (!roles_ok(n_nets) || n_tables <= 0 || n_tables > ((int64_t)1 << 26)) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || n_tables <= 0 || n_tables > ((int64_t)1 << 26)) return DDZ_EINVAL;
   if (variant == 3) return (int64_t)n_nets * QSH_WS_INTS * 4;        // slots [N][15 * QSH_COLS] | cnt [N][15][cpr] | base [N][15][cpr]
   if (variant != 1 && variant != 2) return DDZ_EINVAL;
   const int64_t R = qsh_hash_region(n_tables), cpr = R / QSH_CHUNK;
@@ -4372,7 +4349,7 @@ int64_t ddz_q_roles_ws_bytes(int64_t n_tables, int variant, int n_nets) {
 int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int n_nets, void* ws, int64_t ws_bytes, int64_t row_capacity,
                      int32_t* rows, int32_t* rep, int32_t* seg, int8_t* slot, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
-  if (!roles_ok(n_nets) || !net_of_role || (variant != 1 && variant != 2 && variant != 3)) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !net_of_role || (variant != 1 && variant != 2 && variant != 3)) return DDZ_EINVAL;
   uint32_t map = 0;
   bool used[3] = {false, false, false};
   for (int k = 0; k < 3; ++k) {
@@ -4422,7 +4399,7 @@ int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int 
 }
 int ddz_q_roles_features_rows(int device, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf, const float* bias,
                               const int32_t* rep, const int32_t* seg, float* ys, int64_t ys_ld, int64_t row_capacity, void* stream) {
-  if (!roles_ok(n_nets) || !face || !wf || !bias || !rep || !seg || !ys || n_tables <= 0) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !face || !wf || !bias || !rep || !seg || !ys || n_tables <= 0) return DDZ_EINVAL;
   if (planes != 6 && planes != 7 && planes != 9) return DDZ_EINVAL;
   if (ys_ld != QH && ys_ld != QH + (4 * planes + 15) / 16 * 16) return DDZ_EINVAL;
   if (!al(face, 16) || !al(wf, 4) || !al(bias, 4) || !al(rep, 4) || !al(seg, 4) || !al(ys, 4)) return DDZ_EINVAL;
@@ -4438,7 +4415,7 @@ int ddz_q_roles_features_rows(int device, const float* face, int64_t n_tables, i
 }
 int ddz_q_roles_fc1_rows_k(int device, int n_nets, const float* y, int64_t k, const int32_t* seg, const float* w2k, float* g,
                            int64_t row_capacity, void* stream) {
-  if (!roles_ok(n_nets) || !y || !seg || !w2k || !g) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !y || !seg || !w2k || !g) return DDZ_EINVAL;
   if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
   if (n_nets * row_capacity > q_row_limit(k > QH ? k : QH)) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
@@ -4450,7 +4427,7 @@ int ddz_q_roles_fc1_rows_k(int device, int n_nets, const float* y, int64_t k, co
 }
 int ddz_q_roles_gather_h0(int device, int n_nets, const float* g, int64_t g_rows, const int32_t* rows, const int8_t* slot, int64_t n_tables,
                           const float* base, float* h0, void* stream) {
-  if (!roles_ok(n_nets) || !g || !rows || !slot || !base || !h0 || n_tables <= 0 || g_rows <= 0) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !g || !rows || !slot || !base || !h0 || n_tables <= 0 || g_rows <= 0) return DDZ_EINVAL;
   if (!al(g, 16) || !al(rows, 16) || !al(h0, 16) || !al(base, 16)) return DDZ_EINVAL;
   DeviceGuard gd(device);
   if (!gd.ok) return DDZ_ENODEV;
@@ -4459,7 +4436,7 @@ int ddz_q_roles_gather_h0(int device, int n_nets, const float* g, int64_t g_rows
   return check_launch();
 }
 int64_t ddz_q_roles_need_ws_bytes(int64_t shared_row_capacity, int n_nets) {
-  if (!roles_ok(n_nets)) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets)) return DDZ_EINVAL;
   const int64_t one = ddz_q_shared_need_ws_bytes(shared_row_capacity);
   return one < 0 ? one : n_nets * one;                             // dslot [N][scap][4] | cnt [N][tiles] | base [N][tiles]
 }
@@ -4467,7 +4444,7 @@ int ddz_q_roles_need(ddz_env_t* e, int n_nets, const int32_t* row_index, const i
                      int64_t shared_row_capacity, void* ws, int64_t ws_bytes, int64_t row_capacity, int32_t* row_index2, int32_t* drep,
                      int32_t* dseg, uint8_t* row_cnt, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
-  if (!roles_ok(n_nets) || !row_index || !rows || !sseg || !ws || !row_index2 || !drep || !dseg || !row_cnt) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !row_index || !rows || !sseg || !ws || !row_index2 || !drep || !dseg || !row_cnt) return DDZ_EINVAL;
   if (!al(row_index, 4) || !al(rows, 4) || !al(sseg, 4) || !al(ws, 16) || !al(row_index2, 4) || !al(drep, 4) || !al(dseg, 4)) return DDZ_EINVAL;
   if (shared_row_capacity <= 0 || shared_row_capacity % FC_M || n_nets * shared_row_capacity > ((int64_t)1 << 28)) return DDZ_ECAP;
   if (ws_bytes < ddz_q_roles_need_ws_bytes(shared_row_capacity, n_nets)) return DDZ_ECAP;
@@ -4493,7 +4470,7 @@ int ddz_q_roles_need(ddz_env_t* e, int n_nets, const int32_t* row_index, const i
 int ddz_q_roles_features_drows(int device, const float* face, int64_t n_tables, int planes, int n_nets, const float* wf, const float* bias,
                                const float* acnt, const int32_t* rep, int64_t shared_row_capacity, const int32_t* drep, const int32_t* dseg,
                                float* dy, int64_t row_capacity, void* stream) {
-  if (!roles_ok(n_nets) || !wf || !bias || !acnt || !rep || !drep || !dseg || !dy) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !wf || !bias || !acnt || !rep || !drep || !dseg || !dy) return DDZ_EINVAL;
   if (row_capacity < FC_M || row_capacity % FC_M || n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
     const int rc = ddz_q_features_drows(device, face, n_tables, planes, wf + (int64_t)s * planes * 4 * 4 * QH, bias + s * 4 * QH,
@@ -4505,7 +4482,7 @@ int ddz_q_roles_features_drows(int device, const float* face, int64_t n_tables, 
 }
 int ddz_q_roles_fc1_rows(int device, int n_nets, const float* dy, const int32_t* seg, const uint8_t* row_cnt, const float* w2, const float* z,
                          float* d, int64_t row_capacity, void* stream) {
-  if (!roles_ok(n_nets) || !dy || !seg || !row_cnt || !w2 || !z || !d) return DDZ_EINVAL;
+  if (!n_nets_ok(n_nets) || !dy || !seg || !row_cnt || !w2 || !z || !d) return DDZ_EINVAL;
   if (row_capacity < FC_M || row_capacity % FC_M) return DDZ_EINVAL;
   if (n_nets * row_capacity > q_row_limit()) return DDZ_ECAP;
   for (int s = 0; s < n_nets; ++s) {
@@ -4521,7 +4498,7 @@ int ddz_q_roles_slab(ddz_env_t* e, int n_nets, const int8_t* slot, const float* 
   if (!good(e)) return DDZ_EHANDLE;
   if (!al(h0, 16) || !al(d, 16) || !al(w2, 16) || !al(b2, 4) || !al(counts, 4) || !al(rows, 16) || !al(q, 4) || !al(row_index, 4))
     return DDZ_EINVAL;
-  if (!roles_ok(n_nets) || !slot || !h0 || !d || !w2 || !b2 || !counts || !rows || !q || !row_index || hidden != QH || stride < 1 || d_rows < 1)
+  if (!n_nets_ok(n_nets) || !slot || !h0 || !d || !w2 || !b2 || !counts || !rows || !q || !row_index || hidden != QH || stride < 1 || d_rows < 1)
     return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;

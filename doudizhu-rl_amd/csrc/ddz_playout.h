@@ -1,9 +1,9 @@
 // ddz_playout.h -- k_playout / k_playout_choose: win counts of uniformly random playouts for every legal move of every
 // running table ("playout spec v1"; the reference's Monte-Carlo player: server/mcts/interface.py:15-45 with
 // default_policy.py:4-10 and the reward of tree.py:71-81, as flat Monte Carlo over perfect information).
-// Included by ddz_engine.hip behind ddz_ply.h, inside its anonymous namespace.  The root decode, the hidden-hand domain, the
-// redeal and every piece of a ply (ply_list, ply_entry, ply_apply, ply_draw) are ddz_ply.h's, shared with k_search and k_cfr;
-// this header holds the playout loop with its probe pass, and the choice.
+// Included by ddz_engine.hip behind ddz_ply.h, inside its anonymous namespace.  The entry into a table (table_enter,
+// root_hands), the hidden-hand domain, the redeal and every piece of a ply (ply_list, ply_entry, ply_apply, ply_draw) are
+// ddz_ply.h's, shared with k_search, k_cfr and k_solve; this header holds the playout loop with its probe pass, and the choice.
 //
 // One wavefront per WORK ITEM (table t, chunk c).  With n = the size of t's legal list and K playouts per move, the n * K
 // playouts of a table are numbered w = j * K + k (move index j, playout number k); chunk c of `chunks` runs w = c, c + chunks,
@@ -26,7 +26,7 @@
 // same K worlds), the pool is ranked by (key, c) through LDS as deal_wave_lds ranks a deal -- the wave's staging list is dead
 // between two playouts, its first 64 words hold the keys -- and two ballots give the hands (unseen_pool and redeal_wave of
 // ddz_ply.h).  The ply loop is the open one; everything of the hidden form stands under `if constexpr (HIDDEN)`.
-struct PlayoutArgs {
+struct PlayoutArgs {   // PlyArgs' six fields by name, not as a base: derived, the ply loop was 0.8 % slower (profiles/r18_notes.md 3)
   const uint8_t* state;
   int64_t T;
   uint32_t k0, k1;          // Philox key: (seed_lo ^ salt, seed_hi)
@@ -37,8 +37,8 @@ struct PlayoutArgs {
   int32_t* wins;
   unsigned long long* totals;  // {moves applied, playouts run, playouts stopped unfinished, -} or null
   int32_t* status;
+  uint32_t roles;           // bit r: tables whose actor is role r take part (the others are idle); 7 in the open form
   // hidden form only
-  uint32_t roles;           // bit r: tables whose actor is role r take part (the others are idle)
   uint8_t* worlds;          // null, or [T][K][2][16]: the worlds alone (ddz_playout_worlds), no playout runs
 };
 
@@ -54,34 +54,27 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
   const int64_t item = (int64_t)blockIdx.x * PLAYOUT_WAVES + wv;
   const int64_t t = item / a.chunks;
   const uint32_t chunk = (uint32_t)(item - t * a.chunks);
-  uint4 R = make_uint4(0, 0, 0, 0);
-  if (t < a.T && lane < DDZ_NFIELDS) R = ((const uint4*)(a.state + t * STATE_ROW_BYTES))[lane];
-  hot_fill<PLAYOUT_WAVES * 64>(hot);
-  __syncthreads();   // the block's only barrier: a wave may leave behind it
-  if (t >= a.T) return;
+  uint4 R;
+  if (!table_enter<PLAYOUT_WAVES>(a, t, lane, hot, R)) return;
   uint64_t* stage = s_stage[wv];
   uint16_t* svl = s_svl[wv];
-  const PlayRoot root = play_root_decode(R);
-  if (!root.running) return;  // not dealt, or done: nothing runs, wins stay as they are
+  // the decode and the `roles` gate, in both forms.  (What root_hands<false> derives from the opponents' hand rows -- hn0, hp0,
+  // n_next, n_prev -- the hidden instance discards unread: the compiler drops those reads, the count bytes are never read.)
+  const RootHands rh = root_hands<false>(R, a.roles, lane);
+  if (rh.kind == ROOT_IDLE) return;   // not dealt, done, or not this call's seat: nothing runs, wins stay as they are
+  const PlayRoot& root = rh.root;
   const int role0 = root.role0;
-  uint64_t hn0 = 0, hp0 = 0;
-  if constexpr (!HIDDEN) {
-    hn0 = rl64(root.P, DDZ_F_HAND0 + role_next(role0));
-    hp0 = rl64(root.P, DDZ_F_HAND0 + role_prev(role0));
-  }
+  const uint64_t hn0 = HIDDEN ? 0 : rh.hn0, hp0 = HIDDEN ? 0 : rh.hp0;
   const uint64_t gid = a.gid_base + (uint64_t)t;
-  // hidden form: the pool of unseen cards and the opponents' hand sizes, the domain checked once
   bool pool = false;
-  int n_next = 0;
+  int n_next = 0, n_prev = 0;
   uint32_t world_k = 0xFFFFFFFFu;   // the playout number the world below was dealt for (K < 2^23: none yet)
   uint64_t wn = 0, wp = 0;
-  if constexpr (HIDDEN) {
-    if (!((a.roles >> role0) & 1u)) return;   // not this call's seat: idle
-    int n_prev;
-    uint64_t unseen;
-    if (!unseen_pool(root, lane, n_next, n_prev, unseen, pool)) {
+  if constexpr (HIDDEN) {   // the pool of unseen cards and the opponents' hand sizes, the domain checked once -- called here, not
+    uint64_t unseen;        // through root_hands<true>: so built, the hidden rows ran 0.3 .. 0.6 % slower (profiles/r18_notes.md 3)
+    if (!unseen_pool(root, lane, n_next, n_prev, unseen, pool)) {   // outside the domain: nothing runs, wins stay as they are
       if (lane == 0 && chunk == 0) atomicOr(a.status, 64);
-      return;   // outside the domain: nothing runs, wins stay as they are
+      return;
     }
     if (a.worlds) {   // ddz_playout_worlds: row 0 = the next player's counts and size, row 1 = the previous player's
       for (uint32_t k = chunk; k < a.K; k += a.chunks) {
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
     }
     s_playouts += 1;
     if (winner < 0) s_unfinished += 1;
-    else if ((winner == 1) == (role0 == 1)) win_j += 1;   // tree.py:71-81: the lord alone, or either farmer
+    else if (same_side(winner, role0)) win_j += 1;
   }
   if (lane == 0) {
     if (win_j > 0) atomicAdd(wins + cur_j, win_j);

@@ -1,8 +1,14 @@
-// ddz_ply.h -- what k_playout (ddz_playout.h), k_search (ddz_search.h) and k_cfr (ddz_cfr.h) share, each piece stated once:
+// ddz_ply.h -- what k_playout (ddz_playout.h), k_search (ddz_search.h), k_cfr (ddz_cfr.h) and k_solve (ddz_solve.h) share, each
+// piece stated once:
+//   PlyArgs           the six fields every evaluator's arguments hold BY NAME (state, T, k0, k1, gid_base, status): a base of
+//                     SearchArgs, CfrArgs and SolveArgs; PlayoutArgs spells them out in its own order (ddz_playout.h)
+//   table_enter       a wave enters its table: the 176-byte row load, the hot table's fill, the block's one barrier, the leave
 //   play_root_decode  the 176-byte root as wave-uniform values: running, role, ply, the actor's hand, the combo to beat with
 //                     the passes since it was played
 //   unseen_pool       the hidden-hand domain (playout spec v2): what the actor has not seen, the opponents' hand
 //                     sizes, this lane's bit of the 54-lane pool mask
+//   root_hands        the decode, the `roles` gate, the opponents' hands (open: the hand rows; hidden: unseen_pool), the hand
+//                     sizes, and idle / outside the domain / inside.  No status bit, no output: those are the callers'
 //   redeal_wave       world k of a table: the pool dealt to the two opponents
 //   ply_list          the legal list of (hand, combo to beat): the closed-form round's legal lanes as a mask (never emitted),
 //                     the planner's tail staged into the wave's LDS list.  THE RANK-MASK CHAIN BELOW IS THE STATEMENT OF THE
@@ -10,9 +16,10 @@
 //   ply_entry         entry idx of that list: from the round by lane number, or from the staged tail
 //   ply_apply         the packed apply: the mover's hand, the combo to beat, passes, ply (ply_play), the turn (ply_turn)
 //   ply_draw          the Philox call of the playout loops' 64-draw refill (each loop keeps its refill bookkeeping)
-//   sld / sst / search_fence   relaxed wavefront-scope atomic accesses and the fence that orders them (ddz_search.h, MEMORY
-//                     ORDERING), for the workspaces one wavefront writes and reads
-// Included by ddz_engine.hip behind k_rollout and ahead of the three headers, inside its anonymous namespace: built from
+//   same_side         two roles play on one side (the lord alone, or either farmer)
+//   rfl64 / sld / sst / search_fence   a 64-bit value made wave-uniform; relaxed wavefront-scope atomic accesses and the fence
+//                     that orders them (ddz_search.h, MEMORY ORDERING), for the workspaces one wavefront writes and reads
+// Included by ddz_engine.hip behind k_rollout and ahead of the four headers, inside its anonymous namespace: built from
 // k_rollout's device functions (round_pre / round_src / round_entry, plan_scan_t<EM_STAGE>, deal ranking through LDS), none of
 // which it changes.  The two playout loops (k_playout's with the probe pass, k_search's with the child's n) stay where they are
 // and call these.
@@ -27,8 +34,30 @@ __device__ __forceinline__ void search_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32); }
+
 __device__ __forceinline__ int role_next(int role) { return role == 2 ? 0 : role + 1; }
 __device__ __forceinline__ int role_prev(int role) { return role == 0 ? 2 : role - 1; }
+__device__ __forceinline__ bool same_side(int a, int b) { return (a == 1) == (b == 1); }   // tree.py:71-81: the lord alone, or either farmer
+
+struct PlyArgs {
+  const uint8_t* state;
+  int64_t T;
+  uint32_t k0, k1;          // Philox key: (seed_lo ^ salt, seed_hi)
+  uint64_t gid_base;
+  int32_t* status;
+};
+
+// a wave of a block of WAVES enters table t: lanes < DDZ_NFIELDS load the table's rows into R, the block fills the hot table
+// and meets at its only barrier.  false: there is no table t, the wave leaves (behind the barrier).
+template <int WAVES, typename Args>
+__device__ __forceinline__ bool table_enter(const Args& a, int64_t t, int lane, HotTabT<false>& hot, uint4& R) {
+  R = make_uint4(0, 0, 0, 0);
+  if (t < a.T && lane < DDZ_NFIELDS) R = ((const uint4*)(a.state + t * STATE_ROW_BYTES))[lane];
+  hot_fill<WAVES * 64>(hot);
+  __syncthreads();
+  return t < a.T;
+}
 
 // the root of a table, decoded once (as k_rollout decodes a table): row f < 10 as 15 nibbles in lane f of P, byte 15 of row f
 // in lane f of aux, the meta row's words as scalars.  Every field is wave-uniform.
@@ -82,6 +111,37 @@ __device__ __forceinline__ bool unseen_pool(const PlayRoot& r, int lane, int& n_
   const int cnt = (int)((unseen >> (4 * (rank & 15))) & 15);
   pool = lane < 52 ? (lane & 3) < cnt : (lane < 54 && cnt == 1);
   return true;
+}
+
+// the root with its hands.  IDLE: not dealt, done, or the actor is not in `roles` (nothing else is set).  Open form: hn0 / hp0
+// are the next and the previous player's hand rows and the table is INSIDE.  Hidden form: unseen_pool decides, n_next / n_prev
+// are set either way, hn0 / hp0 wait for redeal_wave.  n_me < 1 is left to the callers that care.
+enum RootKind { ROOT_IDLE, ROOT_OUTSIDE, ROOT_INSIDE };
+struct RootHands {
+  PlayRoot root;
+  RootKind kind;
+  uint64_t hn0, hp0;
+  int n_me, n_next, n_prev;
+  uint64_t unseen;   // hidden form: deck - own hand - taken
+  bool pool;         // hidden form: this lane's card is unseen
+};
+template <bool HIDDEN>
+__device__ __forceinline__ RootHands root_hands(const uint4& R, uint32_t roles, int lane) {
+  RootHands h = {};
+  h.root = play_root_decode(R);
+  h.kind = ROOT_IDLE;
+  if (!h.root.running || !((roles >> h.root.role0) & 1u)) return h;
+  h.n_me = nib_sum(h.root.hc0);
+  if constexpr (HIDDEN) {
+    h.kind = unseen_pool(h.root, lane, h.n_next, h.n_prev, h.unseen, h.pool) ? ROOT_INSIDE : ROOT_OUTSIDE;
+  } else {
+    h.hn0 = rl64(h.root.P, DDZ_F_HAND0 + role_next(h.root.role0));
+    h.hp0 = rl64(h.root.P, DDZ_F_HAND0 + role_prev(h.root.role0));
+    h.n_next = nib_sum(h.hn0);
+    h.n_prev = nib_sum(h.hp0);
+    h.kind = ROOT_INSIDE;
+  }
+  return h;
 }
 
 // world k of a table (playout spec v2): the hands of the next and of the previous player as nibble words.  Lane c draws the key
@@ -183,8 +243,7 @@ __device__ __forceinline__ void ply_entry(uint64_t okm, int n0, int idx, uint32_
     else round_entry<false>(round_src<false>((uint32_t)okm, round_pre((uint32_t)okm), idx), (uint32_t)lc0, snib, scat, svlv, ncards);
   } else {         // from the staged tail (idx - n0 < n - n0 <= STAGE_CAP): LDS broadcast reads
     const uint64_t e = stage[idx - n0];
-    const uint64_t anib = e & 0x0FFFFFFFFFFFFFFFull;
-    snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
+    snib = rfl64(e & 0x0FFFFFFFFFFFFFFFull);
     scat = rfl((uint32_t)(e >> 60));
     svlv = rfl((uint32_t)svl[idx - n0]);
   }

@@ -1,8 +1,8 @@
 // ddz_search.h -- k_search / k_search_choose: UCT tree search around the playouts ("search spec v1 (UCT)"; the
 // reference's MCTS player: server/mcts/interface.py:37-43 with tree_policy / get_bestchild.py / tree.py:33-51 / backup.py).
-// Included by ddz_engine.hip behind ddz_ply.h and ddz_playout.h, inside its anonymous namespace.  The root decode, the
-// hidden-hand domain, the redeal, every piece of a ply (ply_list, ply_entry, ply_apply, ply_draw) and the wavefront-scope
-// accesses to the tree (sld / sst / search_fence) are ddz_ply.h's, shared with k_playout and k_cfr; this header holds the tree.
+// Included by ddz_engine.hip behind ddz_ply.h and ddz_playout.h, inside its anonymous namespace.  The entry into a table
+// (table_enter, root_hands: the root, its hands, the hidden-hand domain), the redeal, every piece of a ply and the wavefront-scope
+// accesses to the tree (sld / sst / search_fence) are ddz_ply.h's, shared with the other three; this header holds the tree.
 //
 // One wavefront per WORK ITEM (table t, tree c).  The wave decodes the root once into wave-uniform values (as k_playout), then
 // runs `budget` iterations of {descent, expansion, playout, backup} on its own tree.  The descent RE-APPLIES stored moves from
@@ -30,19 +30,14 @@
 // ever reads the tree, so nothing has to become visible at workgroup or agent scope before the kernel ends.  Every access to
 // the tree is a relaxed wavefront-scope atomic load / store: these are vector instructions, never scalar-cache loads (the
 // scalar cache is not coherent with vector stores).  The root statistics leave through 32-bit atomicAdd, the totals through 64-bit.
-struct SearchArgs {
-  const uint8_t* state;
-  int64_t T;
-  uint32_t k0, k1;          // Philox key: (seed_lo ^ salt, seed_hi)
-  uint64_t gid_base;
+struct SearchArgs : PlyArgs {
   uint32_t budget, trees, mode;
   float c;
   int64_t stride;           // visits / wins are [T][stride]
   int32_t* visits;
   int32_t* wins;
   unsigned long long* totals;  // {moves applied, iterations run, iterations scored unfinished, nodes created} or null
-  int32_t* status;
-  uint32_t roles;           // hidden form: bit r = tables whose actor is role r take part
+  uint32_t roles;           // bit r = tables whose actor is role r take part; 7 in the open form
   uint8_t* work;
   uint64_t tree_bytes;
   uint32_t hash_log;
@@ -110,34 +105,23 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   const int64_t item = (int64_t)blockIdx.x * SEARCH_WAVES + wv;
   const int64_t t = item / a.trees;
   const uint32_t tree = (uint32_t)(item - t * a.trees);
-  uint4 R = make_uint4(0, 0, 0, 0);
-  if (t < a.T && lane < DDZ_NFIELDS) R = ((const uint4*)(a.state + t * STATE_ROW_BYTES))[lane];
-  hot_fill<SEARCH_WAVES * 64>(hot);
-  __syncthreads();   // the block's only barrier: a wave may leave behind it
-  if (t >= a.T) return;
+  uint4 R;
+  if (!table_enter<SEARCH_WAVES>(a, t, lane, hot, R)) return;
   uint64_t* stage = s_stage[wv];
   uint16_t* svl = s_svl[wv];
   uint16_t* path = s_path[wv];
-  const PlayRoot root = play_root_decode(R);
-  if (!root.running) return;  // not dealt, or done: nothing runs
-  const int role0 = root.role0;
-  uint64_t hn0 = 0, hp0 = 0;
-  const uint64_t gid = a.gid_base + (uint64_t)t;
-  if constexpr (!HIDDEN) {
-    hn0 = rl64(root.P, DDZ_F_HAND0 + role_next(role0));
-    hp0 = rl64(root.P, DDZ_F_HAND0 + role_prev(role0));
-  } else {   // tree c plays on world k = c of playout spec v2: the same pool, the same domain, the same deal
-    if (!((a.roles >> role0) & 1u)) return;
-    int n_next, n_prev;
-    uint64_t unseen;
-    bool pool;
-    if (!unseen_pool(root, lane, n_next, n_prev, unseen, pool)) {
-      if (lane == 0 && tree == 0) atomicOr(a.status, 64);
-      return;   // outside the domain: nothing runs, the workspace is not touched
-    }
-    redeal_wave(gid, tree, a.k0, a.k1, lane, pool, n_next, stage, hn0, hp0);
+  const RootHands rh = root_hands<HIDDEN>(R, a.roles, lane);
+  if (rh.kind == ROOT_IDLE) return;   // not dealt, done, or not this call's seat: nothing runs
+  if (rh.kind == ROOT_OUTSIDE) {      // outside the domain: nothing runs, the workspace is not touched
+    if (lane == 0 && tree == 0) atomicOr(a.status, 64);
+    return;
   }
-  const bool root_lord = role0 == 1;
+  const PlayRoot& root = rh.root;
+  const int role0 = root.role0;
+  uint64_t hn0 = rh.hn0, hp0 = rh.hp0;
+  const uint64_t gid = a.gid_base + (uint64_t)t;
+  // hidden form: tree c plays on world k = c of playout spec v2: the same pool, the same domain, the same deal
+  if constexpr (HIDDEN) redeal_wave(gid, tree, a.k0, a.k1, lane, rh.pool, rh.n_next, stage, hn0, hp0);
   const uint32_t hlog = a.hash_log;
   uint8_t* const base = a.work + (uint64_t)item * a.tree_bytes;
   uint8_t* const nodes = base;
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       // ---- selection at a fully expanded node (get_bestchild.py:20-32)
       const uint32_t N = rfl(sld32((const uint32_t*)(nr + 8)));
       const float two_ln = 2.0f * a.ln[N <= (uint32_t)DDZ_SEARCH_MAX_BUDGET ? N : (uint32_t)DDZ_SEARCH_MAX_BUDGET];
-      const bool own = a.mode == (uint32_t)DDZ_SEARCH_SIDES ? ((role == 1) == root_lord) : (role == role0);
+      const bool own = a.mode == (uint32_t)DDZ_SEARCH_SIDES ? same_side(role, role0) : (role == role0);
       const bool take_max = own || a.mode == (uint32_t)DDZ_SEARCH_SIDES;
       uint32_t best = 0, at = SEARCH_NONE, bchild = SEARCH_NONE;
       for (int b = 0; b < n; b += 64) {
@@ -290,8 +274,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       const uint8_t* cr = nodes + (uint64_t)child * NODE_BYTES;
       const uint64_t mv = sld64((const uint64_t*)cr);
       const uint32_t cmeta = sld32((const uint32_t*)(cr + 16));
-      const uint64_t anib = mv & 0x0FFFFFFFFFFFFFFFull;
-      const uint64_t snib = (uint64_t)rfl((uint32_t)anib) | ((uint64_t)rfl((uint32_t)(anib >> 32)) << 32);
+      const uint64_t snib = rfl64(mv & 0x0FFFFFFFFFFFFFFFull);
       const uint32_t scat = rfl((uint32_t)(mv >> 60)), svlv = rfl(cmeta & 0xFFFFu);
       s_moves += 1;
       ply_turn(ply_play(snib, scat, svlv, hc, trick, passes, ply), hc, hn, hp, role);   // (an emptied hand: the child is terminal, the next trip scores it)
@@ -300,7 +283,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       if (lane == 0) path[depth] = (uint16_t)child;
     }
     // ---- backup: V += 1, W += score on every node of the path; the new node's record is written whole
-    const uint32_t score = (winner >= 0 && ((winner == 1) == root_lord)) ? 1u : 0u;
+    const uint32_t score = (winner >= 0 && same_side(winner, role0)) ? 1u : 0u;
     if (winner < 0) s_unfinished += 1;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();   // the path is written

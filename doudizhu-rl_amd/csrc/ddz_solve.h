@@ -1,9 +1,9 @@
 // ddz_solve.h -- k_solve / k_solve_choose: the exact endgame solver ("Solve spec v1"): open-hand minimax of the
 // two-sided win / lose game (the lord against the two farmers) for every root move of every table that is an endgame.
-// Included by ddz_engine.hip behind ddz_ply.h, inside its anonymous namespace.  The root decode (play_root_decode), the
-// hidden-hand domain and deal (unseen_pool, redeal_wave), the legal lists (ply_list / ply_entry: the device keeps one statement
-// of the rules), the packed apply (ply_play / ply_turn) and the wavefront-scope accesses (sld / sst / search_fence) are
-// ddz_ply.h's, shared with k_playout, k_search and k_cfr; this header holds the depth-first search and its table.
+// Included by ddz_engine.hip behind ddz_ply.h, inside its anonymous namespace.  The entry into a table (table_enter,
+// root_hands: the root, its hands, the hidden-hand domain), the deal (redeal_wave), the legal lists (ply_list / ply_entry: the
+// device keeps one statement of the rules), the packed apply (ply_play / ply_turn), same_side and the wavefront-scope accesses
+// (rfl64 / sld / sst / search_fence) are ddz_ply.h's, shared with the other three; this header holds the search and its table.
 //
 // One wavefront per WORK ITEM (table t, world k, chunk c), item = (t * worlds + k) * chunks + c.  Chunk c solves the root moves
 // j = c, c + chunks, ... of its table in ascending order, each with a node budget of its own and no cut among them.
@@ -44,18 +44,13 @@
 // MEMORY ORDERING.  As ddz_search.h: a table is written and read by ONE wavefront through relaxed wavefront-scope atomic loads
 // / stores (vector instructions) with search_fence() behind every store.  n leaves through a plain store of the table's
 // first wave, wins / unknown through 32-bit atomic adds (the worlds of a table add up), the totals through 64-bit ones.
-struct SolveArgs {
-  const uint8_t* state;
-  int64_t T;
-  uint32_t k0, k1;          // Philox key of the worlds: (seed_lo ^ salt, seed_hi)
-  uint64_t gid_base;
+struct SolveArgs : PlyArgs {   // (the key: of the worlds)
   uint32_t budget, max_cards, worlds, chunks, roles, tt_entries;
   int64_t stride;           // wins / unknown are [T][stride]
   int32_t* n;
   int32_t* wins;
   int32_t* unknown;
   unsigned long long* totals;  // {nodes, table hits, root moves solved, root moves unknown} or null
-  int32_t* status;
   uint8_t* work;            // items x tt_entries x 32 bytes
 };
 
@@ -65,8 +60,6 @@ constexpr uint64_t SOLVE_USED = 1ull << 63, SOLVE_WON = 1ull << 60, SOLVE_HAND =
 constexpr uint32_t SOLVE_ENTRY_BYTES = 32;
 static_assert(DDZ_SOLVE_MAX_DEPTH == 3 * DDZ_SOLVE_MAX_CARDS, "at most two passes around every card played");
 
-__device__ __forceinline__ uint64_t solve_rfl64(uint64_t v) { return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32); }
-
 // the slot of a key (before the mask): four odd multipliers, one xor-shift-multiply round, the high half folded in
 __device__ __forceinline__ uint32_t solve_slot(uint64_t x, uint64_t y, uint64_t z, uint64_t w) {
   uint64_t h = (x * 0x9E3779B97F4A7C15ull) ^ (y * 0xC2B2AE3D27D4EB4Full) ^ (z * 0x165667B19E3779F9ull) ^ (w * 0x85EBCA77C2B2AE63ull);
@@ -75,8 +68,6 @@ __device__ __forceinline__ uint32_t solve_slot(uint64_t x, uint64_t y, uint64_t 
   h ^= h >> 32;
   return (uint32_t)h;
 }
-
-__device__ __forceinline__ bool solve_same_side(int a, int b) { return (a == 1) == (b == 1); }
 
 template <bool HIDDEN>
 __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
@@ -91,48 +82,34 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
   const int64_t t = item / per;
   const uint32_t world = (uint32_t)((item - t * per) / a.chunks);
   const uint32_t chunk = (uint32_t)(item - t * per - (int64_t)world * a.chunks);
-  uint4 R = make_uint4(0, 0, 0, 0);
-  if (t < a.T && lane < DDZ_NFIELDS) R = ((const uint4*)(a.state + t * STATE_ROW_BYTES))[lane];
-  hot_fill<SOLVE_WAVES * 64>(hot);
-  __syncthreads();   // the block's only barrier: a wave may leave behind it
-  if (t >= a.T) return;
+  uint4 R;
+  if (!table_enter<SOLVE_WAVES>(a, t, lane, hot, R)) return;
   uint64_t* stage = s_stage[wv];
   uint16_t* svl = s_svl[wv];
   uint64_t* frame = s_frame[wv];
   const bool first = world == 0 && chunk == 0 && lane == 0;   // the lane that writes n[t] and the table's status bits
   // ---- decode and domain
-  const PlayRoot root = play_root_decode(R);
-  const int role0 = root.role0;
-  if (!root.running || !((a.roles >> role0) & 1u)) {   // idle
+  const RootHands rh = root_hands<HIDDEN>(R, a.roles, lane);
+  if (rh.kind == ROOT_IDLE) {
     if (first) a.n[t] = 0;
     return;
   }
+  const PlayRoot& root = rh.root;
+  const int role0 = root.role0;
   const uint64_t hc0 = root.hc0;
-  uint64_t hn0 = 0, hp0 = 0;
-  int n_next, n_prev;
-  bool inside = true, pool = false;
-  if constexpr (HIDDEN) {
-    uint64_t unseen;
-    inside = unseen_pool(root, lane, n_next, n_prev, unseen, pool);
-  } else {
-    hn0 = rl64(root.P, DDZ_F_HAND0 + role_next(role0));
-    hp0 = rl64(root.P, DDZ_F_HAND0 + role_prev(role0));
-    n_next = nib_sum(hn0);
-    n_prev = nib_sum(hp0);
-  }
-  const int n_me = nib_sum(hc0);
-  if (n_me + n_next + n_prev > (int)a.max_cards) {   // not an endgame: what a dispatcher tests
+  uint64_t hn0 = rh.hn0, hp0 = rh.hp0;
+  if (rh.n_me + rh.n_next + rh.n_prev > (int)a.max_cards) {   // not an endgame: what a dispatcher tests
     if (first) a.n[t] = -1;
     return;
   }
-  if (HIDDEN && (!inside || n_me < 1)) {
+  if (HIDDEN && (rh.kind == ROOT_OUTSIDE || rh.n_me < 1)) {
     if (first) { a.n[t] = -1; atomicOr(a.status, 64); }
     return;
   }
-  if constexpr (HIDDEN) redeal_wave(a.gid_base + (uint64_t)t, world, a.k0, a.k1, lane, pool, n_next, stage, hn0, hp0);
+  if constexpr (HIDDEN) redeal_wave(a.gid_base + (uint64_t)t, world, a.k0, a.k1, lane, rh.pool, rh.n_next, stage, hn0, hp0);
   // the cards of the combination to beat, as play_root_decode picks its info word
   const uint64_t r1 = rl64(root.P, DDZ_F_RECENT0 + role_prev(role0)), r2 = rl64(root.P, DDZ_F_RECENT0 + role_next(role0));
-  const uint64_t tnib0 = solve_rfl64(r1 ? r1 : r2);
+  const uint64_t tnib0 = rfl64(r1 ? r1 : r2);
   const uint32_t trick0 = rfl(root.trick0);
   const uint32_t info0 = ply_info(trick0, root.passes0);
   int n_root;
@@ -187,8 +164,8 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
             kx = hc | ((uint64_t)role << 60);
             kw = lead ? 0ull : (tnib | ((uint64_t)passes << 60));
             const uint64_t* e = tt + 4ull * (solve_slot(kx, hn, hp, kw) & tmask);
-            const uint64_t e0 = solve_rfl64(sld64(e)), e1 = solve_rfl64(sld64(e + 1));
-            const uint64_t e2 = solve_rfl64(sld64(e + 2)), e3 = solve_rfl64(sld64(e + 3));
+            const uint64_t e0 = rfl64(sld64(e)), e1 = rfl64(sld64(e + 1));
+            const uint64_t e2 = rfl64(sld64(e + 2)), e3 = rfl64(sld64(e + 3));
             if (e0 == (kx | SOLVE_USED) && (e1 & ~SOLVE_WON) == hn && e2 == hp && e3 == kw) {
               s_hits += 1;
               ret = (e1 & SOLVE_WON) != 0;
@@ -241,8 +218,8 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
           // ---- RETURN: `ret` goes to the parent, whose frame undoes the move
           if (depth == 0) break;
           depth -= 1;
-          const uint64_t f0 = solve_rfl64(frame[3 * depth + 0]), f1 = solve_rfl64(frame[3 * depth + 1]);
-          const uint64_t f2 = solve_rfl64(frame[3 * depth + 2]);
+          const uint64_t f0 = rfl64(frame[3 * depth + 0]), f1 = rfl64(frame[3 * depth + 1]);
+          const uint64_t f2 = rfl64(frame[3 * depth + 2]);
           const int child_role = role;
           role = role_prev(role);
           {
@@ -259,7 +236,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
             kx = hc | ((uint64_t)role << 60);
             kw = lead ? 0ull : (tnib | ((uint64_t)passes << 60));
           }
-          const bool mine = solve_same_side(child_role, role) ? ret : !ret;
+          const bool mine = same_side(child_role, role) ? ret : !ret;
           if (mine || idx >= n) {   // the cut, or the last child lost: the parent is finished; it returns on the next trip
             ret = mine;
             if (lane == 0) {
@@ -279,7 +256,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
           phase = CHILD;
         }
         if (over && lane == 0) atomicOr(a.status, 256);
-        if (!unk) won = solve_same_side(role, role0) ? ret : !ret;   // (depth 0: `role` moves behind move j)
+        if (!unk) won = same_side(role, role0) ? ret : !ret;   // (depth 0: `role` moves behind move j)
         s_nodes += nodes;
       }
     }

@@ -69,6 +69,10 @@ def _roles_mask(roles, hidden=True, name="roles"):
     return roles
 
 
+def _salt(salt):
+    return int(salt) & 0xFFFFFFFF
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -179,6 +183,28 @@ class BatchedEnv:
         if x is None:
             return torch.empty(self.T * self.slab_stride, dtype=torch.int32, device=self.device)
         return self._arg(x, name, torch.int32, numel=self.T * self.slab_stride)
+
+    def _slab_lists(self, what=None):
+        """the slab lists are those of the current state: entry [t, j] of a verb's result is read against them.  what
+        ("playouts need"): the verb needs the full stride, and says so"""
+        if what and self.slab_stride < MAX_LEGAL_PER_TABLE:
+            raise ValueError(f"{what} row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        if not self._slab_fresh:
+            self.legal_slab()
+
+    def _workspace(self, attr, need):
+        """a byte buffer of at least `need` bytes cached on the env as `attr`: it only grows"""
+        if need < 0:
+            raise ValueError("no workspace size for these arguments")
+        work = getattr(self, attr, None)
+        if work is None or work.numel() < need:
+            work = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            setattr(self, attr, work)
+        return work
+
+    def _need_ids(self, what):
+        if self.ids is None:
+            raise ValueError(f"{what} needs the action ids of the lists (want_ids=True)")
 
     def _q_slab_arg(self, q):
         if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
@@ -416,8 +442,7 @@ class BatchedEnv:
     def _check_q_slab(self, n_nets, h0, d, row_index, w2, b2, out, slot=None):
         """the argument checks of q_slab_needed (n_nets None: one network, and `out` may be None and is then made) and q_roles_slab
         (+ slot), behind a fresh legal_slab(); returns (hidden, out)"""
-        if not self._slab_fresh:
-            self.legal_slab()
+        self._slab_lists()
         H, N = int(h0.shape[-1]), 1 if n_nets is None else int(n_nets)
         self._arg(h0, "h0", torch.float32, shape=(self.T, H))
         self._arg(d, "d", torch.float32, shape=(d.shape[0], H))
@@ -525,8 +550,7 @@ class BatchedEnv:
         table's slab list; STEP_ROWS: int8[T,16]; STEP_RANDOM: engine RNG) to the lists legal_slab() /
         the previous step_slab() left in the buffers, then overwrite them with the lists of the new
         states (game.py:95-106 + envi.py:98-116).  Returns (done, r, illegal) like step()."""
-        if not self._slab_fresh:
-            self.legal_slab()
+        self._slab_lists()
         self._traj(traj)
         pinned = sel is not None and sel.device.type == "cpu" and sel.is_pinned()   # (pinned host memory is device-readable)
         if mode in (STEP_CHOICE, STEP_IDS):
@@ -555,8 +579,7 @@ class BatchedEnv:
         arg-max of q [T, stride] over each table's slab list (= select_slab), apply it (= step_slab), write the new
         lists and, with face_variant, the `face` [T,P,15,4] of the new states (= observe).  Returns (done, r, illegal,
         face | None); bit-identical to the three separate calls."""
-        if not self._slab_fresh:
-            self.legal_slab()
+        self._slab_lists()
         self._traj(traj)
         self._arg(choice_out, "choice_out", torch.int32, numel=self.T, none_ok=True)
         face = None if face_variant is None else self._face_out(face_out, face_variant, "face_out")
@@ -575,8 +598,7 @@ class BatchedEnv:
         returns and a ragged NN forward consumes -- by two small launches; list indices are the same in both layouts, so
         select(q_csr) feeds step_slab(CHOICE).  cap = T * rows_per_table rows (mean list: 5.6 rows under a random
         policy; the first lead of a game: ~73): a fuller list raises status bit 1 and is truncated."""
-        if not self._slab_fresh:
-            self.legal_slab()
+        self._slab_lists()
         cap = self.T * int(rows_per_table)
         if getattr(self, "_csr_cap", 0) != cap:
             self.csr_rows = torch.empty((cap, ROW), dtype=torch.int8, device=self.device)
@@ -616,10 +638,7 @@ class BatchedEnv:
         only): bit r set = tables whose actor is role r take part, the others are idle."""
         roles = _roles_mask(roles, hidden)
         st = self.slab_stride
-        if st < MAX_LEGAL_PER_TABLE:
-            raise ValueError(f"playouts need row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
-        if not self._slab_fresh:        # wins[t, j] is read against the lists of the current state (the check step_slab makes)
-            self.legal_slab()
+        self._slab_lists("playouts need")
         n_playouts = int(n_playouts)
         if not 1 <= n_playouts < (1 << 23):
             raise ValueError("n_playouts must be in [1, 2^23)")
@@ -634,10 +653,10 @@ class BatchedEnv:
         self._totals(totals)
         wins.zero_()                   # (an enqueued memset of the whole buffer)
         if hidden:
-            check(self.lib.ddz_playout_hidden(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, roles, _p(wins),
+            check(self.lib.ddz_playout_hidden(self._h, n_playouts, _salt(salt), int(chunks), st, roles, _p(wins),
                                               _p(totals), _stream(self.device)))
         else:
-            check(self.lib.ddz_playout(self._h, n_playouts, int(salt) & 0xFFFFFFFF, int(chunks), st, _p(wins), _p(totals),
+            check(self.lib.ddz_playout(self._h, n_playouts, _salt(salt), int(chunks), st, _p(wins), _p(totals),
                                        _stream(self.device)))
         return wins.view(self.T, st)
 
@@ -655,7 +674,7 @@ class BatchedEnv:
             out = torch.zeros((self.T, n_worlds, 2, ROW), dtype=torch.uint8, device=self.device)
         else:
             self._arg(out, "out", torch.uint8, numel=self.T * n_worlds * 2 * ROW, why=" ([T, n_worlds, 2, 16])")
-        check(self.lib.ddz_playout_worlds(self._h, n_worlds, int(salt) & 0xFFFFFFFF, roles, _p(out), _stream(self.device)))
+        check(self.lib.ddz_playout_worlds(self._h, n_worlds, _salt(salt), roles, _p(out), _stream(self.device)))
         return out.view(self.T, n_worlds, 2, ROW)
 
     def playout_choose(self, n_playouts, salt=0, out=None, chunks=None, hidden=False, roles=0b111):
@@ -663,8 +682,7 @@ class BatchedEnv:
         counts over each table's list (ties to the lowest index), -1 for idle tables.  Feed them to
         step_slab(mode=STEP_IDS).  hidden / roles: as playout() -- a table that the hidden form leaves out (its actor not in
         `roles`, or outside the domain) has all-zero counts and so gets the first move of its list: mask the ids by role."""
-        if self.ids is None:
-            raise ValueError("playout_choose needs the action ids of the lists (want_ids=True)")
+        self._need_ids("playout_choose")
         out = self._ids_out(out)
         self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None),
                                           hidden=hidden, roles=roles)
@@ -695,8 +713,7 @@ class BatchedEnv:
         if mode not in self.SEARCH_MODES:
             raise ValueError('mode is "reference" or "sides"')
         st = self.slab_stride
-        if st < MAX_LEGAL_PER_TABLE:
-            raise ValueError(f"search needs row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        self._slab_lists("search needs")
         budget = int(budget)
         if not 1 <= budget <= self.SEARCH_MAX_BUDGET:
             raise ValueError(f"budget must be in [1, {self.SEARCH_MAX_BUDGET}]")
@@ -708,19 +725,12 @@ class BatchedEnv:
         trees = int(trees)
         if not 1 <= trees <= 65536:
             raise ValueError("trees must be in [1, 65536]")
-        if not self._slab_fresh:        # entry [t, j] is read against the lists of the current state
-            self.legal_slab()
         visits, wins = self._slab_counts(visits, "visits"), self._slab_counts(wins, "wins")
         self._totals(totals)
-        need = int(self.lib.ddz_search_work_bytes(self.T, budget, trees))
-        if need < 0:
-            raise ValueError("no workspace size for these arguments")
-        work = getattr(self, "_search_work", None)
-        if work is None or work.numel() < need:
-            self._search_work = work = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        work = self._workspace("_search_work", int(self.lib.ddz_search_work_bytes(self.T, budget, trees)))
         visits.zero_()
         wins.zero_()
-        check(self.lib.ddz_search(self._h, budget, trees, self.SEARCH_MODES[mode], c, int(salt) & 0xFFFFFFFF, int(bool(hidden)),
+        check(self.lib.ddz_search(self._h, budget, trees, self.SEARCH_MODES[mode], c, _salt(salt), int(bool(hidden)),
                                   roles, st, _p(visits), _p(wins), _p(totals), _p(work), work.numel(), _stream(self.device)))
         return visits.view(self.T, st), wins.view(self.T, st)
 
@@ -728,8 +738,7 @@ class BatchedEnv:
         """The UCT move of every table: int32 [T] canonical action ids, the first maximum of wins / visits over the visited
         root moves of search() (get_bestchild_: the win ratio alone; ties to the lowest index), -1 where nothing was visited
         (idle tables, tables the hidden form leaves out).  Feed them to step_slab(mode=STEP_IDS)."""
-        if self.ids is None:
-            raise ValueError("search_choose needs the action ids of the lists (want_ids=True)")
+        self._need_ids("search_choose")
         out = self._ids_out(out)
         v, w = self.search(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles,
                            visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
@@ -778,9 +787,7 @@ class BatchedEnv:
                    torch.empty(self.T, dtype=torch.float64, device=self.device))
         n, ids, sigma, value = self._cfr_tensors(out, "out")
         self._arg(value, "value", torch.float64, numel=self.T, why=" (of out)")
-        work = getattr(self, "_cfr_work", None)
-        if work is None or work.numel() < need:
-            self._cfr_work = work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        work = self._workspace("_cfr_work", need)     # (at least the 256 bytes of its head)
         check(self.lib.ddz_cfr(self._h, iterations, roles, slots, _p(work), work.numel(), _p(n), _p(ids), _p(sigma), _p(value),
                                _p(totals), _stream(self.device)))
         return n, ids, sigma, value
@@ -795,7 +802,7 @@ class BatchedEnv:
             solved = self.cfr(iterations, roles=roles, slots=slots, out=getattr(self, "_cfr_out", None))
             self._cfr_out = solved
         n, ids, sigma, _ = self._cfr_tensors(solved, "solved")
-        check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), int(salt) & 0xFFFFFFFF, int(bool(greedy)), _p(out),
+        check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), _salt(salt), int(bool(greedy)), _p(out),
                                       _stream(self.device)))
         return out
 
@@ -835,8 +842,7 @@ class BatchedEnv:
         hidden = bool(hidden)
         roles = _roles_mask(roles, hidden)
         st = self.slab_stride
-        if st < MAX_LEGAL_PER_TABLE:
-            raise ValueError(f"solve needs row_capacity >= {MAX_LEGAL_PER_TABLE} * n_tables")
+        self._slab_lists("solve needs")
         budget, max_cards, worlds, chunks, tt_entries = int(budget), int(max_cards), int(worlds), int(chunks), int(tt_entries)
         if not 1 <= budget <= self.SOLVE_MAX_BUDGET:
             raise ValueError(f"budget must be in [1, {self.SOLVE_MAX_BUDGET}]")
@@ -848,23 +854,16 @@ class BatchedEnv:
             raise ValueError("chunks must be in [1, 65536]")
         if not 1 <= tt_entries <= self.SOLVE_MAX_TT or tt_entries & (tt_entries - 1):
             raise ValueError(f"tt_entries must be a power of two in [1, {self.SOLVE_MAX_TT}]")
-        if not self._slab_fresh:        # entry [t, j] is read against the lists of the current state
-            self.legal_slab()
         self._totals(totals)
         if out is None:
             out = (torch.empty(self.T, dtype=torch.int32, device=self.device),
                    torch.empty(self.T * st, dtype=torch.int32, device=self.device),
                    torch.empty(self.T * st, dtype=torch.int32, device=self.device))
         n, wins, unknown = self._solve_tensors(out, "out")
-        need = int(self.lib.ddz_solve_work_bytes(self.T, worlds, chunks, tt_entries))
-        if need < 0:
-            raise ValueError("no workspace size for these arguments")
-        work = getattr(self, "_solve_work", None)
-        if work is None or work.numel() < need:
-            self._solve_work = work = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        work = self._workspace("_solve_work", int(self.lib.ddz_solve_work_bytes(self.T, worlds, chunks, tt_entries)))
         wins.zero_()
         unknown.zero_()
-        check(self.lib.ddz_solve(self._h, budget, max_cards, worlds, int(hidden), roles, int(salt) & 0xFFFFFFFF, chunks, tt_entries,
+        check(self.lib.ddz_solve(self._h, budget, max_cards, worlds, int(hidden), roles, _salt(salt), chunks, tt_entries,
                                  st, _p(n), _p(wins), _p(unknown), _p(totals), _p(work), work.numel(), _stream(self.device)))
         return n, wins.view(self.T, st), unknown.view(self.T, st)
 
@@ -876,8 +875,7 @@ class BatchedEnv:
         every move is proven losing, else -1.  A running table that solve() left out (n = -1) has all-zero counts and so gets
         the first move of its list and value 0: mask by n.  solved: the (n, wins, unknown) of an earlier solve() call with
         the same `worlds` to choose from (no solve)."""
-        if self.ids is None:
-            raise ValueError("solve_choose needs the action ids of the lists (want_ids=True)")
+        self._need_ids("solve_choose")
         out = self._ids_out(out)
         if value is None:
             value = torch.empty(self.T, dtype=torch.int32, device=self.device)
@@ -909,8 +907,7 @@ class BatchedEnv:
         if batch:
             batch = int(min(batch, max(1, n_iters)))
             need = self.lib.ddz_rollout_csr_staging_bytes(self.T, batch, int(self.ids is not None))
-            if getattr(self, "_staging", None) is None or self._staging.numel() < need:
-                self._staging = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._workspace("_staging", need)
             check(self.lib.ddz_rollout_random_csr_staged(self._h, int(n_iters), batch, _p(self._staging), self._staging.numel(),
                                                          _p(self.offsets), _p(self.rows), _p(self.ids), self.cap, _p(traj),
                                                          _stream(self.device)))

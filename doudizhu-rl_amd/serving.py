@@ -151,6 +151,31 @@ def state_to_full_payloads(state):
     return out
 
 
+def _payload_env(payloads, hidden, device, seed):
+    """-> (env, dev): the requests as the tables of a fresh env with full slab lists -- the plain serving payloads packed by
+    payloads_to_playout_state (hidden) or the full ones, with hand_card, by full_payloads_to_state"""
+    n, dev = len(payloads), torch.device(device)
+    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
+    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
+    env.state_import(torch.from_numpy(st).view(-1))
+    return env, dev
+
+
+def _check_domain(env, what):
+    """ValueError where a table raised status bit 6 (what: the domain's name; None: nothing is asked); -> the status word"""
+    status = env.status() if what else 0
+    if status & 64:
+        raise ValueError(f"a payload is outside the {what} domain: cur_cards, history and left do not add up to a deck")
+    return status
+
+
+def _id_cards(ids, device):
+    """canonical action ids -> rank lists 3..17 ([] = pass), None for -1 (no move)"""
+    table = action_table(device).cpu().numpy()
+    ranks = np.arange(3, 18)
+    return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+
+
 def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=False):
     """The reference's mcts(payload) (server/mcts/interface.py:15-45) as flat Monte Carlo, for a batch of requests: every
     legal move of every request is followed by n_playouts uniformly random playouts over the three known hands
@@ -158,19 +183,12 @@ def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=Fa
     of rank values 3..17 ([] = pass), or None where the request has no move (a finished game).
     hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and the playouts
     run on hands dealt from the cards the requester has not seen (playout spec v2)."""
-    n = len(payloads)
-    if n == 0:
+    if not payloads:
         return []
-    dev = torch.device(device)
-    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
-    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
-    env.state_import(torch.from_numpy(st).view(-1))
+    env, dev = _payload_env(payloads, hidden, device, seed)
     ids = env.playout_choose(n_playouts, salt=salt, hidden=hidden).cpu().numpy()
-    if hidden and env.status() & 64:
-        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
-    table = action_table(dev).cpu().numpy()
-    ranks = np.arange(3, 18)
-    return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+    _check_domain(env, "hidden-hand" if hidden else None)
+    return _id_cards(ids, dev)
 
 
 def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, trees=None, mode="reference", c=0.7):
@@ -180,26 +198,12 @@ def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, 
     pass), or None where the request has no move (a finished game).
     hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and tree c
     searches world c of the hands dealt from the cards the requester has not seen (`trees` determinizations)."""
-    n = len(payloads)
-    if n == 0:
+    if not payloads:
         return []
-    dev = torch.device(device)
-    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
-    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
-    env.state_import(torch.from_numpy(st).view(-1))
+    env, dev = _payload_env(payloads, hidden, device, seed)
     ids = env.search_choose(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden).cpu().numpy()
-    if hidden and env.status() & 64:
-        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
-    table = action_table(dev).cpu().numpy()
-    ranks = np.arange(3, 18)
-    return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
-
-
-def _id_cards(ids, device):
-    """canonical action ids -> rank lists 3..17 ([] = pass)"""
-    table = action_table(device).cpu().numpy()
-    ranks = np.arange(3, 18)
-    return [[int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
+    _check_domain(env, "hidden-hand" if hidden else None)
+    return _id_cards(ids, dev)
 
 
 def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=False):
@@ -211,18 +215,12 @@ def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=Fals
     3..17, [] for a pass.  ValueError where a request is no endgame (more than 6 cards in the three hands, or a finished
     game), where cur_cards, history and left do not add up to a deck (status bit 6), or where the solver's capacities do not
     hold it (status bit 7)."""
-    n = len(payloads)
-    if n == 0:
+    if not payloads:
         return []
-    dev = torch.device(device)
-    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
-    env.state_import(torch.from_numpy(payloads_to_playout_state(payloads)).view(-1))
-    solved = env.cfr(iterations, slots=n)
+    env, dev = _payload_env(payloads, True, device, seed)
+    solved = env.cfr(iterations, slots=len(payloads))
     ids = env.cfr_choose(salt=salt, greedy=greedy, solved=solved).cpu().numpy()
-    status = env.status()
-    if status & 64:
-        raise ValueError("a payload is outside the endgame domain: cur_cards, history and left do not add up to a deck")
-    if status & 128:
+    if _check_domain(env, "endgame") & 128:
         raise ValueError("an endgame exceeds the solver's capacities")
     if (ids < 0).any():
         raise ValueError("a payload is no endgame: more than 6 cards are left, or the game is over")
@@ -241,18 +239,13 @@ def solve_act(payloads, budget=65536, max_cards=12, worlds=1, device="cuda:0", s
     requester has not seen are solved and the move that wins in the most of them is returned (perfect-information Monte
     Carlo).  ValueError where a request is no endgame (more than max_cards cards in the three hands, or a finished game)
     or, hidden form, where cur_cards, history and left do not add up to a deck (status bit 6)."""
-    n = len(payloads)
-    if n == 0:
+    if not payloads:
         return ([], []) if want_value else []
-    dev = torch.device(device)
-    env = BatchedEnv(n, seed=seed, device=dev, row_capacity=512 * n)
-    st = payloads_to_playout_state(payloads) if hidden else full_payloads_to_state(payloads)
-    env.state_import(torch.from_numpy(st).view(-1))
+    env, dev = _payload_env(payloads, hidden, device, seed)
     solved = env.solve(budget, max_cards, worlds if hidden else 1, hidden, salt=salt, chunks=chunks, tt_entries=tt_entries)
     ids, value = env.solve_choose(worlds=worlds if hidden else 1, solved=solved)
     ids, value, size = ids.cpu().numpy(), value.cpu().numpy(), solved[0].cpu().numpy()
-    if hidden and env.status() & 64:
-        raise ValueError("a payload is outside the hidden-hand domain: cur_cards, history and left do not add up to a deck")
+    _check_domain(env, "hidden-hand" if hidden else None)
     if (size <= 0).any():
         raise ValueError(f"a payload is no endgame: more than {int(max_cards)} cards are left, or the game is over")
     moves = _id_cards(ids, dev)
