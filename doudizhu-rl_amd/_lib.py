@@ -64,6 +64,9 @@ SYMBOLS = {
     "ddz_search": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_search_choose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ddz_ismcts_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "ddz_ismcts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int64,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_cfr_work_bytes": (C.c_int64, [C.c_int64]),
     "ddz_cfr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -10,10 +10,12 @@
 //             (table, chunk), the root in registers, no list stored.
 //   k_search  (ddz_search.h; ddz_search) UCT tree search around those playouts: one wavefront per (table, tree), the tree in a
 //             caller-provided workspace, the descent re-applies stored moves.
+//   k_ismcts  (ddz_ismcts.h; ddz_ismcts) information-set MCTS: one wavefront per (table, tree), ONE tree over a fresh world per
+//             iteration, a list at every level of the descent, children keyed by (parent, count word).
 //   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
 //   k_solve   (ddz_solve.h; ddz_solve) the exact endgame solver: one wavefront per (table, world, chunk), a depth-first search
 //             with its transposition table in the caller's workspace.
-//             These four share ddz_ply.h: the entry into a table, the root with its hands and the hidden-hand domain, the
+//             These five share ddz_ply.h: the entry into a table, the root with its hands and the hidden-hand domain, the
 //             redeal, and a ply (list, entry, apply, draw) built from k_rollout's device functions -- each stated once.
 //   k_table   ONE WAVEFRONT PER TABLE, one lock-step iteration per launch (the API a policy drives) on CSR lists; with
 //             F_SLAB the lists of the current state alone, in the slab layout (stepping on slab lists is k_slab's):
@@ -1382,6 +1384,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 #include "ddz_ply.h"      // the entry into a table, the root with its hands and a ply, shared by the four kernels below
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
+#include "ddz_ismcts.h"   // k_ismcts: information-set MCTS, one tree per (table, tree) over all its sampled worlds
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
 #include "ddz_solve.h"    // k_solve / k_solve_choose: exact open-hand minimax per root move, one wavefront per (table, world, chunk)
 
@@ -2846,7 +2849,7 @@ int ensure_counts(ddz_env* e, hipStream_t st) {
   return launch_table<F_COUNT, 0>(e, Io{}, st);
 }
 
-// ---- the four move evaluators (k_playout, k_search, k_cfr, k_solve): what their entry points share, stated once ----
+// ---- the move evaluators (k_playout, k_search, k_ismcts, k_cfr, k_solve): what their entry points share, stated once ----
 // PlyArgs' six fields (ddz_ply.h) of an evaluator's arguments; k_cfr draws nothing and does not read the key
 template <typename Args>
 void ply_args(Args& a, const ddz_env* e, uint64_t salt) {
@@ -2871,6 +2874,36 @@ int launch_hidden(bool hidden, int64_t blocks, void* stream, const A& a) {
   if (hidden) hipLaunchKernelGGL(HIDDEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(OPEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
   return check_launch();
+}
+// what ddz_search and ddz_ismcts do alike: the argument checks in their order, SearchArgs, the launch of one wavefront per
+// (table, tree).  tree_bytes: the workspace of one tree at this budget (asked only once the budget is known to be in range)
+template <auto OPEN, auto HIDDEN>
+int search_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int64_t budget, int64_t trees, int mode, float c, uint64_t salt,
+                  bool hidden, int roles, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
+                  int64_t work_bytes, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!visits || !wins || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
+  if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return DDZ_EINVAL;
+  if (mode != DDZ_SEARCH_REFERENCE && mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
+  if (!(c >= 0.0f) || !(c <= 3.0e38f)) return DDZ_EINVAL;   // (finite and not negative: values order as their bit patterns)
+  if (!roles_ok(roles, hidden)) return DDZ_EINVAL;
+  if (const int rc = slab_args_ok(e, stride)) return rc;
+  if (work_bytes < (int64_t)tree_bytes(budget) * e->T * trees) return DDZ_ECAP;
+  int64_t blocks;
+  if (grid_of(e->T * trees, SEARCH_WAVES, &blocks)) return DDZ_ECAP;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  SearchArgs a;
+  ply_args(a, e, salt);
+  a.budget = (uint32_t)budget; a.trees = (uint32_t)trees; a.mode = (uint32_t)mode; a.c = c;
+  a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals;
+  a.roles = (uint32_t)roles; a.work = (uint8_t*)work; a.tree_bytes = tree_bytes(budget); a.hash_log = search_hash_log(budget);
+  void* ln = nullptr;
+  const hipError_t r = hipGetSymbolAddress(&ln, HIP_SYMBOL(g_search_ln));
+  if (r != hipSuccess) return hip_fail(r);
+  a.ln = (const float*)ln;
+  if (blocks == 0) return DDZ_OK;
+  return launch_hidden<OPEN, HIDDEN, SEARCH_WAVES>(hidden, blocks, stream, a);
 }
 // a *_choose kernel over the env's tables, `per` tables to a block of BLOCK threads
 template <auto K, typename... Q>
@@ -3533,29 +3566,20 @@ int64_t ddz_search_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
 
 int ddz_search(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles, int64_t stride,
                int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
-  if (!good(e)) return DDZ_EHANDLE;
-  if (!visits || !wins || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
-  if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return DDZ_EINVAL;
-  if (mode != DDZ_SEARCH_REFERENCE && mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
-  if (!(c >= 0.0f) || !(c <= 3.0e38f)) return DDZ_EINVAL;   // (finite and not negative: values order as their bit patterns)
-  if (!roles_ok(roles, hidden)) return DDZ_EINVAL;
-  if (const int rc = slab_args_ok(e, stride)) return rc;
-  if (work_bytes < ddz_search_work_bytes(e->T, budget, trees)) return DDZ_ECAP;
-  int64_t blocks;
-  if (grid_of(e->T * trees, SEARCH_WAVES, &blocks)) return DDZ_ECAP;
-  DeviceGuard g(e->device);
-  if (!g.ok) return DDZ_ENODEV;
-  SearchArgs a;
-  ply_args(a, e, salt);
-  a.budget = (uint32_t)budget; a.trees = (uint32_t)trees; a.mode = (uint32_t)mode; a.c = c;
-  a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals;
-  a.roles = (uint32_t)roles; a.work = (uint8_t*)work; a.tree_bytes = search_tree_bytes(budget); a.hash_log = search_hash_log(budget);
-  void* ln = nullptr;
-  const hipError_t r = hipGetSymbolAddress(&ln, HIP_SYMBOL(g_search_ln));
-  if (r != hipSuccess) return hip_fail(r);
-  a.ln = (const float*)ln;
-  if (blocks == 0) return DDZ_OK;
-  return launch_hidden<k_search<false>, k_search<true>, SEARCH_WAVES>(hidden, blocks, stream, a);
+  return search_launch<k_search<false>, k_search<true>>(e, search_tree_bytes, budget, trees, mode, c, salt, hidden != 0, roles, stride,
+                                                        visits, wins, totals, work, work_bytes, stream);
+}
+
+// ddz_ismcts: one launch of k_ismcts, one wavefront per (table, tree), always the hidden form; ddz_search's checks and codes
+int64_t ddz_ismcts_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
+  if (n_tables < 0 || budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return -1;
+  return (int64_t)ismcts_tree_bytes(budget) * n_tables * trees;
+}
+
+int ddz_ismcts(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+               int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+  return search_launch<k_ismcts, k_ismcts>(e, ismcts_tree_bytes, budget, trees, mode, c, salt, true, roles, stride, visits, wins,
+                                           totals, work, work_bytes, stream);
 }
 
 int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,

@@ -1,5 +1,5 @@
-// ddz_ply.h -- what k_playout (ddz_playout.h), k_search (ddz_search.h), k_cfr (ddz_cfr.h) and k_solve (ddz_solve.h) share, each
-// piece stated once:
+// ddz_ply.h -- what k_playout (ddz_playout.h), k_search (ddz_search.h), k_ismcts (ddz_ismcts.h), k_cfr (ddz_cfr.h) and k_solve
+// (ddz_solve.h) share, each piece stated once:
 //   PlyArgs           the six fields every evaluator's arguments hold BY NAME (state, T, k0, k1, gid_base, status): a base of
 //                     SearchArgs, CfrArgs and SolveArgs; PlayoutArgs spells them out in its own order (ddz_playout.h)
 //   table_enter       a wave enters its table: the 176-byte row load, the hot table's fill, the block's one barrier, the leave

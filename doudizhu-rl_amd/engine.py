@@ -710,10 +710,20 @@ class BatchedEnv:
         int64 [4] on the device, += {moves applied, iterations run, iterations scored unfinished, nodes created}.  The
         trees live in a workspace of ddz_search_work_bytes(T, budget, trees) bytes cached on the env."""
         roles = _roles_mask(roles, hidden)
+        budget, trees, c, visits, wins = self._search_args("search needs", budget, trees, mode, c, visits, wins, totals)
+        st = self.slab_stride
+        work = self._workspace("_search_work", int(self.lib.ddz_search_work_bytes(self.T, budget, trees)))
+        visits.zero_()
+        wins.zero_()
+        check(self.lib.ddz_search(self._h, budget, trees, self.SEARCH_MODES[mode], c, _salt(salt), int(bool(hidden)),
+                                  roles, st, _p(visits), _p(wins), _p(totals), _p(work), work.numel(), _stream(self.device)))
+        return visits.view(self.T, st), wins.view(self.T, st)
+
+    def _search_args(self, what, budget, trees, mode, c, visits, wins, totals):
+        """the arguments search() and ismcts() share, checked; the slab lists made current -> (budget, trees, c, visits, wins)"""
         if mode not in self.SEARCH_MODES:
             raise ValueError('mode is "reference" or "sides"')
-        st = self.slab_stride
-        self._slab_lists("search needs")
+        self._slab_lists(what)
         budget = int(budget)
         if not 1 <= budget <= self.SEARCH_MAX_BUDGET:
             raise ValueError(f"budget must be in [1, {self.SEARCH_MAX_BUDGET}]")
@@ -727,12 +737,7 @@ class BatchedEnv:
             raise ValueError("trees must be in [1, 65536]")
         visits, wins = self._slab_counts(visits, "visits"), self._slab_counts(wins, "wins")
         self._totals(totals)
-        work = self._workspace("_search_work", int(self.lib.ddz_search_work_bytes(self.T, budget, trees)))
-        visits.zero_()
-        wins.zero_()
-        check(self.lib.ddz_search(self._h, budget, trees, self.SEARCH_MODES[mode], c, _salt(salt), int(bool(hidden)),
-                                  roles, st, _p(visits), _p(wins), _p(totals), _p(work), work.numel(), _stream(self.device)))
-        return visits.view(self.T, st), wins.view(self.T, st)
+        return budget, trees, c, visits, wins
 
     def search_choose(self, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111, out=None):
         """The UCT move of every table: int32 [T] canonical action ids, the first maximum of wins / visits over the visited
@@ -741,6 +746,39 @@ class BatchedEnv:
         self._need_ids("search_choose")
         out = self._ids_out(out)
         v, w = self.search(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles,
+                           visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
+        self._search_visits, self._search_wins = v.view(-1), w.view(-1)
+        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
+                                         _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
+        return out
+
+    # ---- information-set MCTS: one tree over all sampled worlds (search spec v2) ----
+    def ismcts(self, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111, visits=None, wins=None, totals=None):
+        """Single-observer information-set MCTS on every running table (search spec v2; Whitehouse, Powley,
+        Cowling, CIG 2011; Cowling, Powley, Whitehouse, TCIAIG 2012): where search(hidden=True) builds tree c on world c alone,
+        every tree here is built over ALL of its worlds -- iteration i of tree c plays on world c * budget + i of
+        playout(hidden=True) (playout_worlds(trees * budget) lists them), each step of the descent sees the moves legal in
+        that world, and the UCB bonus uses the child's availability count.  No tree is built with full knowledge of one deal,
+        and one tree gets the whole budget.  -> (visits, wins) as search(); mode, c, salt, roles, visits / wins / totals:
+        as search(hidden=True).  The opponents' count bytes are never read; a table outside the domain runs nothing and raises
+        status bit 6.  The env is only read.  Two memsets + one launch on the current stream: capturable.  The trees live in a
+        workspace of ddz_ismcts_work_bytes(T, budget, trees) bytes cached on the env."""
+        roles = _roles_mask(roles)
+        budget, trees, c, visits, wins = self._search_args("ismcts needs", budget, trees, mode, c, visits, wins, totals)
+        st = self.slab_stride
+        work = self._workspace("_ismcts_work", int(self.lib.ddz_ismcts_work_bytes(self.T, budget, trees)))
+        visits.zero_()
+        wins.zero_()
+        check(self.lib.ddz_ismcts(self._h, budget, trees, self.SEARCH_MODES[mode], c, _salt(salt), roles, st, _p(visits),
+                                  _p(wins), _p(totals), _p(work), work.numel(), _stream(self.device)))
+        return visits.view(self.T, st), wins.view(self.T, st)
+
+    def ismcts_choose(self, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111, out=None):
+        """The ISMCTS move of every table: int32 [T] canonical action ids, search_choose()'s rule on ismcts()'s root
+        statistics; -1 where nothing was visited.  Feed them to step_slab(mode=STEP_IDS)."""
+        self._need_ids("ismcts_choose")
+        out = self._ids_out(out)
+        v, w = self.ismcts(budget, trees=trees, mode=mode, c=c, salt=salt, roles=roles,
                            visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
         self._search_visits, self._search_wins = v.view(-1), w.view(-1)
         check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,

@@ -6,6 +6,7 @@ them.  Prints both win rates from env.stats().
 
   python examples/flat_mc.py [--tables 1024] [--playouts 16] [--iterations 400] [--seed 0] [--hidden] [--match]
   python examples/flat_mc.py --search BUDGET [--trees 1] [--mode reference] [--tables 256] [--iterations 200]
+  python examples/flat_mc.py --ismcts BUDGET [--trees 1] [--uct-trees 16] [--mode reference] [--tables 256] [--iterations 200]
 
 --hidden: the playouts do not read the farmers' hands; they run on hands dealt anew, per playout number, from the cards the
 lord has not seen (playout spec v2, BatchedEnv.playout_choose(hidden=True, roles=0b010): only the lord's tables are
@@ -18,6 +19,11 @@ prints has not been measured anywhere in this repository's notes: quote it only 
 Monte-Carlo farmers at an EQUAL number of playouts per decision -- the farmers' playouts per move are BUDGET * trees divided by
 the mean size of their lists on that iteration -- and, as the yardstick, the same match with a flat Monte-Carlo lord given the
 same number.  Both seats see all three hands.  Printed as the lord's win rate in both matches.
+
+--ismcts BUDGET: an information-set MCTS lord (BatchedEnv.ismcts_choose: --trees trees of BUDGET iterations, every iteration
+on a fresh deal of the cards the lord has not seen, search spec v2) against the RULE farmers (env.auto_choose(0b101)) -- beside
+a determinized-UCT lord (search_choose(hidden=True)) with the same total iterations per move split over --uct-trees worlds, for
+example 1 x 1024 against 16 x 64.  Neither lord reads the farmers' hands; only the lord's tables are searched (roles=0b010).
 
 The playouts are computed for every table on every iteration and used where the lord is to move (the other tables take -1 =
 the engine's random move): simple, and three times the work a loop that asks only for the lord's tables would do.
@@ -60,6 +66,23 @@ def seat_match(pkg, a, dev, uct):
     return env.stats()
 
 
+def hidden_match(pkg, a, dev, ismcts):
+    """the lord by ISMCTS (ismcts=True: trees x budget) or by determinized UCT (uct_trees x the same total / uct_trees), both
+    on sampled hands; the farmers by the rule agent"""
+    env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
+    env.reset()
+    lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    uct_budget = max(1, a.ismcts * a.trees // a.uct_trees)
+    for it in range(a.iterations):
+        if ismcts:
+            env.ismcts_choose(a.ismcts, trees=a.trees, mode=a.mode, salt=it, roles=0b010, out=lord)
+        else:
+            env.search_choose(uct_budget, trees=a.uct_trees, mode=a.mode, salt=it, hidden=True, roles=0b010, out=lord)
+        env.step_slab(torch.where(env.role == 1, lord, env.auto_choose(0b101)), pkg.STEP_IDS, auto_reset=True)
+    assert env.status() == 0
+    return env.stats()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", type=int, default=1024)
@@ -69,11 +92,24 @@ def main():
     ap.add_argument("--hidden", action="store_true", help="sample the farmers' hands per playout instead of reading them")
     ap.add_argument("--match", action="store_true", help="a hidden-playout lord against the rule farmers")
     ap.add_argument("--search", type=int, default=0, metavar="BUDGET", help="a UCT lord against flat Monte-Carlo farmers")
-    ap.add_argument("--trees", type=int, default=1, help="--search: trees per table")
-    ap.add_argument("--mode", default="reference", choices=("reference", "sides"), help="--search: the selection rule")
+    ap.add_argument("--ismcts", type=int, default=0, metavar="BUDGET", help="an ISMCTS lord against the rule farmers")
+    ap.add_argument("--trees", type=int, default=1, help="--search / --ismcts: trees per table")
+    ap.add_argument("--uct-trees", type=int, default=16, help="--ismcts: worlds of the determinized-UCT lord beside it")
+    ap.add_argument("--mode", default="reference", choices=("reference", "sides"), help="--search / --ismcts: the selection rule")
     a = ap.parse_args()
     pkg = importlib.import_module("doudizhu-rl_amd")
     dev = torch.device("cuda:0")
+    if a.ismcts:
+        t0 = time.perf_counter()
+        ism = hidden_match(pkg, a, dev, True)
+        t1 = time.perf_counter()
+        uct = hidden_match(pkg, a, dev, False)
+        t2 = time.perf_counter()
+        print(f"ISMCTS lord ({a.trees} x {a.ismcts} iterations, mode {a.mode}) vs rule farmers: {rates(ism)}  "
+              f"[{(t1 - t0) / a.iterations * 1e3:.2f} ms per iteration at {a.tables} tables]")
+        print(f"determinized-UCT lord ({a.uct_trees} x {max(1, a.ismcts * a.trees // a.uct_trees)} iterations) vs the same "
+              f"farmers: {rates(uct)}  [{(t2 - t1) / a.iterations * 1e3:.2f} ms per iteration]")
+        return
     if a.search:
         t0 = time.perf_counter()
         uct = seat_match(pkg, a, dev, True)

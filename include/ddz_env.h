@@ -378,6 +378,36 @@ int ddz_search(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c,
 int ddz_search_choose(ddz_env_t* env, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,
                       const int32_t* wins, int32_t* choice, void* stream);
 
+/* Information-set MCTS over the sampled worlds: "search spec v2 (ISMCTS)" (DESIGN.md 4), the single-observer ISMCTS of
+ * Whitehouse, Powley, Cowling (CIG 2011) and Cowling, Powley, Whitehouse (IEEE TCIAIG 4(2), 2012).  Where ddz_search(hidden)
+ * builds tree c on world c alone, ddz_ismcts builds ONE tree per (table t, tree c) over all of its worlds.  Always the hidden
+ * form: domain, `roles` mask, idle tables and status bit 6 are ddz_search(hidden != 0)'s; the opponents' count bytes are
+ * never read.
+ *   Worlds and draws: iteration i < budget of tree c plays on world k = c * budget + i of playout spec v2 (domain 5, keyed by
+ *     (gid, k)): ddz_playout_worlds(trees * budget) lists exactly these worlds.  The expansion draw (domain 6) and the playout
+ *     draws (domain 7) are spec v1's, on the counter (gid, c << 16 | i, ..).
+ *   Node: (parent, the move into it), the move being its canonical action = its count row.  It carries V, W, the
+ *     availability count A, terminal and winner (hand sizes are public: terminal is a function of the path).  It has no list
+ *     size and no count of children created.
+ *   Descent: at a non-terminal node less than DDZ_SEARCH_MAX_DEPTH moves below the root take the list L of the state in THIS
+ *     world, in slab (ascending canonical id) order.  An empty list ends the iteration unfinished.  With U = the entries of L
+ *     without a child, ascending: if U is not empty, create the ((draw_e * |U|) >> 32)-th entry of U with A = 1, raise A of
+ *     every child that exists and whose move is in L by 1, and run spec v1's playout from the new child.  Otherwise select
+ *     among the children whose moves are in L: value = W / V + c * sqrt((2 * LN[A]) / V) with the child's OWN A in place of the
+ *     parent's N -- the five fp32 operations, the LN table and both modes are spec v1's -- ties to the lowest index of L, on
+ *     the counts of before this iteration; then every child whose move is in L gets A += 1, the selected one included.
+ *     Children whose moves are not in L take no part and keep their A.
+ *   Backup, score, totals and the root outputs are spec v1's; the root actor's own list is the same in every world, so
+ *     visits / wins stay aligned with the slab list.
+ *   work: >= ddz_ismcts_work_bytes(T, budget, trees) bytes, 16-byte aligned; a smaller buffer is DDZ_ECAP from the host.  Per
+ *     tree: budget + 1 node records of 32 bytes and an open-addressing table of the power of two >= 2 * (budget + 1) entries
+ *     keyed by (parent, count row) and compared in full.  Nothing in it has to be initialised, nothing in it is an output.
+ * Arguments, checks and error codes are ddz_search's.  The env is only read; one launch on `stream`, nothing on the host
+ * (capturable).  ddz_search_choose picks the move from visits / wins. */
+int64_t ddz_ismcts_work_bytes(int64_t n_tables, int64_t budget, int64_t trees);
+int ddz_ismcts(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+               int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream);
+
 /* The CFR endgame solver: the reference's final_card (server/CFR.py: deal / initiate_game / VanillaCFR.run(8)), the engine
  * its predictor uses when the three hands hold 6 cards or fewer (server/core.py:88), batched.  "CFR spec v1" (DESIGN.md 4):
  * the reference's computation with everything it leaves to chance pinned.  Seats are the reference's player numbers, 0 lord /
