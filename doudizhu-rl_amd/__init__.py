@@ -9,6 +9,8 @@ from .engine import (BatchedEnv, FACE_PLANES, NUM_ACTIONS, STEP_CHOICE, STEP_IDS
                      pack_trajectory, q_features, q_features_needed, q_first_fwd, q_first_bwd, q_stage_fwd, q_stage_bwd, q_fc1_dense, q_fc1_rows, q_fc1_rows_k,
                      q_features_rows, q_features_drows, q_gather_h0, q_shared_ws_bytes, q_shared_need_ws_bytes,
                      q_roles_ws_bytes, q_roles_need_ws_bytes, rows_to_onehot, state_prob, observe_states, tr_ws_bytes,
-                     tr_ring_bytes, tr_ring_layout)
-from .dqn_glue import PackedBatch, RoleQ, SeatLoop, TrainLoop, TransitionRecorder, compete, train  # noqa: F401
+                     tr_ring_bytes, tr_ring_layout, mc_ws_bytes, mc_ws_layout, mc_ring_bytes,
+                     mc_ring_layout)
+from .dqn_glue import (PackedBatch, ReturnBatch, ReturnRecorder, RoleQ, SeatLoop, TrainLoop, TransitionRecorder,  # noqa: F401
+                       compete, mc_step, train)
 from .envi import Env, EnvComplicated, EnvCooperation, EnvCooperationSimplify  # noqa: F401

@@ -46,6 +46,13 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ddz_tr_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_void_p,
                                C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "ddz_mc_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "ddz_mc_ws_layout": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "ddz_mc_ring_bytes": (C.c_int64, [C.c_int64]),
+    "ddz_mc_ring_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "ddz_mc_before": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ddz_mc_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_void_p]),
     "ddz_state_prob": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_rows_to_onehot": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_observe_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

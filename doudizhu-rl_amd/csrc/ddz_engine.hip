@@ -2604,6 +2604,7 @@ __global__ __launch_bounds__(BLOCK) void k_onehot(const uint8_t* __restrict__ ro
 }
 
 #include "ddz_replay.h"
+#include "ddz_returns.h"  // (after ddz_replay.h: its block scan and its overflow rule)
 #include "ddz_qtrain.h"   // (after face_cell: the learner's stage stages its x tile from packed state rows too)
 
 // ------------------------------------------------------------------------------------
@@ -3357,6 +3358,71 @@ int ddz_tr_after(ddz_env_t* e, void* ws, int64_t ws_bytes, void* const* rings, i
   if (!done || !r || !reward) return DDZ_EINVAL;
   const TrAfter af{{reward[0], reward[1], reward[2]}, replicate_reference_quirk ? 1 : 0};
   return tr_launch<true>(e, ws, rg, done, 0, nullptr, nullptr, r, af, (hipStream_t)stream);
+}
+
+int64_t ddz_mc_ws_bytes(int64_t T, int log_cap) {
+  if (T <= 0 || log_cap < 1 || log_cap > 255 || T * log_cap > ((int64_t)1 << 30)) return DDZ_EINVAL;
+  return mc_ws_layout(T, log_cap).bytes;
+}
+int ddz_mc_ws_layout(int64_t T, int log_cap, int64_t* offsets) {
+  if (!offsets || ddz_mc_ws_bytes(T, log_cap) < 0) return DDZ_EINVAL;
+  const McWsLayout l = mc_ws_layout(T, log_cap);
+  const int64_t off[8] = {l.rows, l.act, l.who, l.cnt, l.lost, l.rank, l.blk, l.hdr};
+  for (int k = 0; k < 8; ++k) offsets[k] = off[k];
+  return DDZ_OK;
+}
+int64_t ddz_mc_ring_bytes(int64_t capacity) {
+  return capacity <= 0 || capacity > ((int64_t)1 << 30) ? DDZ_EINVAL : mc_ring_layout(capacity, nullptr);
+}
+int ddz_mc_ring_layout(int64_t capacity, int64_t* offsets) {
+  if (!offsets || ddz_mc_ring_bytes(capacity) < 0) return DDZ_EINVAL;
+  mc_ring_layout(capacity, offsets);
+  return DDZ_OK;
+}
+
+int ddz_mc_before(ddz_env_t* e, void* ws, int64_t ws_bytes, int log_cap, const int32_t* chosen, const uint8_t* active,
+                  int trained_roles, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  const int64_t need = ddz_mc_ws_bytes(e->T, log_cap);
+  if (!ws || !al(ws, 16) || need < 0 || ws_bytes < need) return DDZ_EINVAL;
+  if (!chosen || !al(chosen, 4) || (trained_roles & ~7)) return DDZ_EINVAL;
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const McWs w = mc_bind(ws, mc_ws_layout(e->T, log_cap));
+  hipLaunchKernelGGL(k_mc_append, dim3((unsigned)((e->T * 16 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     (const uint8_t*)e->state, e->T, w, log_cap, chosen, active, trained_roles);
+  return check_launch();
+}
+
+int ddz_mc_after(ddz_env_t* e, void* ws, int64_t ws_bytes, int log_cap, void* const* rings, int64_t ring_bytes, int64_t capacity,
+                 const uint8_t* done, const int8_t* r, const float* reward, float gamma, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  const int64_t need = ddz_mc_ws_bytes(e->T, log_cap), rb = ddz_mc_ring_bytes(capacity);
+  if (!ws || !rings || !al(ws, 16) || need < 0 || ws_bytes < need || rb < 0 || ring_bytes < rb) return DDZ_EINVAL;
+  if (!done || !r || !reward) return DDZ_EINVAL;
+  McRings rg;
+  TrRings counts{};                 // what k_tr_scan reads of a ring: its count and the capacity
+  rg.cap = counts.cap = capacity;
+  for (int k = 0; k < 3; ++k) {
+    if (!al(rings[k], 16)) return DDZ_EINVAL;
+    rg.r[k] = mc_ring_bind(rings[k], capacity);
+    counts.r[k].count = rg.r[k].count;
+  }
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const McWsLayout l = mc_ws_layout(e->T, log_cap);
+  const McWs w = mc_bind(ws, l);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mc_mark, dim3((unsigned)l.nb), dim3(TR_BT), 0, st, e->T, w, log_cap, done);
+  int rc = check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, counts);
+  rc = check_launch();
+  if (rc) return rc;
+  const McAfter af{{reward[0], reward[1], reward[2]}, gamma};
+  hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((e->T + MC_BT - 1) / MC_BT)), dim3(BLOCK), 0, st, e->T, w, log_cap, rg, done,
+                     r, af);
+  return check_launch();
 }
 
 int ddz_state_prob(int device, const uint8_t* known60, const int32_t* sizes, int64_t n, float* out, void* stream) {

@@ -105,6 +105,72 @@ class TransitionAssembler:
         return out
 
 
+class ReturnAssembler:
+    """Return spec v1 (include/ddz_env.h: ddz_mc_before / ddz_mc_after) in plain torch ops on any device: the host
+    statement the device recorder (ReturnRecorder, csrc/ddz_returns.h) is tested against.  A table keeps an episode log of at
+    most log_cap decisions (state row u8 [176], action id, role, the role's decision ordinal), a decision counter per role and
+    a cumulative `lost` counter; when the table finishes, log entry (role k, ordinal j) becomes the target
+        ret = (+reward[k] if k's side won else -reward[k]) * gamma^togo,   togo = c[k] - 1 - j,
+    by togo f32 multiplications (not pow: the device gives the same bits).  With gamma = 1 that is the Deep Monte Carlo target;
+    with the reference's gamma it is what y_i = r_i + (1 - done_i) * gamma * y_{i+1} gives along the role's own transitions."""
+
+    def __init__(self, n_tables, log_cap, device="cpu", reward_dict=None, trained_roles=(True, True, True), gamma=1.0):
+        rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
+        self.T, self.L, self.device = int(n_tables), int(log_cap), torch.device(device)
+        if not 1 <= self.L <= 255:
+            raise ValueError("log_cap must be in 1 .. 255")
+        dev = self.device
+        self.reward = torch.tensor([float(rd.get(k) or 0.0) for k in ("up", "lord", "down")], dtype=torch.float32, device=dev)
+        self.trained = torch.tensor([bool(x) for x in trained_roles], dtype=torch.bool, device=dev)
+        self.gamma = torch.tensor(float(gamma), dtype=torch.float32, device=dev)
+        self.rows = torch.zeros((self.T, self.L, 176), dtype=torch.uint8, device=dev)
+        self.act = torch.zeros((self.T, self.L), dtype=torch.int32, device=dev)
+        self.who = torch.zeros((self.T, self.L, 2), dtype=torch.int64, device=dev)     # {role, ordinal}
+        self.n = torch.zeros(self.T, dtype=torch.int64, device=dev)
+        self.c = torch.zeros((self.T, 3), dtype=torch.int64, device=dev)               # (u8 on the device: saturates at 255)
+        self.lost = torch.zeros(self.T, dtype=torch.int64, device=dev)                 # (u32 on the device: saturates)
+
+    def before(self, role, rows, chosen, active=None):
+        """role int [T] the actor of each table (its state row's role byte), rows u8 [T,176] the state rows now, chosen int32 [T]
+        the action ids about to be played, active bool [T] (None: all).  Appends to the logs; returns nothing."""
+        dev = self.device
+        role = role.to(dev).long()
+        ok = role <= 2
+        if active is not None:
+            ok = ok & active.to(dev).bool()
+        ok = ok & self.trained[role.clamp(max=2)]
+        t = ok.nonzero(as_tuple=True)[0]
+        k = role[t]
+        room = self.n[t] < self.L
+        tr, kr = t[room], k[room]
+        p = self.n[tr]
+        self.rows[tr, p] = rows.to(dev).view(self.T, 176)[tr]
+        self.act[tr, p] = chosen.to(dev).to(torch.int32)[tr]
+        self.who[tr, p, 0], self.who[tr, p, 1] = kr, self.c[tr, kr]
+        self.n[tr] += 1
+        self.lost[t[~room]] = (self.lost[t[~room]] + 1).clamp(max=2 ** 32 - 1)
+        self.c[t, k] = (self.c[t, k] + 1).clamp(max=255)
+
+    def after(self, done, r):
+        """done u8 [T], r i8 [T] as the step wrote them (r < 0: the lord won).  Returns the emits of the call in emit order
+        (ascending table, then ascending log position): {"s0" u8 [m,176], "a0" int32 [m], "ret" f32 [m], "table" int64 [m],
+        "togo" int64 [m], "role" int64 [m]}; the logs and decision counters of the finished tables are empty afterwards."""
+        dev = self.device
+        done = done.to(dev).bool()
+        live = torch.arange(self.L, device=dev)[None, :] < self.n[:, None]
+        t, p = (live & done[:, None]).nonzero(as_tuple=True)
+        k, j = self.who[t, p, 0], self.who[t, p, 1]
+        togo = self.c[t, k] - 1 - j
+        lord_won = r.to(dev)[t] < 0
+        ret = torch.where(lord_won == (k == 1), self.reward[k], -self.reward[k])
+        for i in range(int(togo.max()) if togo.numel() else 0):
+            ret = torch.where(togo > i, ret * self.gamma, ret)
+        out = {"s0": self.rows[t, p].clone(), "a0": self.act[t, p].clone(), "ret": ret, "table": t, "togo": togo, "role": k}
+        self.n[done] = 0
+        self.c[done] = 0
+        return out
+
+
 def td_target(transitions, q_next, gamma=0.95):
     """y = r + (1 - done) * gamma * Q_target(s1, a1)  (dqn.py:40-41, config.py:8 GAMMA)."""
     return transitions["reward"] + (~transitions["done"]).float() * gamma * q_next.view(-1)
@@ -304,6 +370,18 @@ class PackedBatch:
         return int(self.index.numel())
 
 
+class ReturnBatch(PackedBatch):
+    """A batch of return targets that stays packed (ReturnRecorder.sample_packed): side 0 of a PackedBatch -- the ring views s0
+    u8 [capacity,176] and a0 int32 [capacity], the drawn entries, the action table, the variant -- with ret f32 [capacity] and
+    togo u8 [capacity] in place of a second side: s1, a1, reward and done are None, and QNet.forward_packed(batch, 1) is a
+    ValueError."""
+    __slots__ = ("ret", "togo")
+
+    def __init__(self, s0, a0, ret, togo, index, table, variant):
+        super().__init__(s0, None, a0, None, None, None, index, table, variant)
+        self.ret, self.togo = ret, togo
+
+
 class QNet(nn.Module):
     """The reference's Q-network family (net.py:66-150: NetComplicated 5 input planes, NetMoreComplicated 8,
     NetCooperation 10, NetCooperationSimplify 7), same parameter names and shapes (state_dict-compatible); forward is
@@ -389,6 +467,8 @@ class QNet(nn.Module):
         if FACE_PLANES[batch.variant] != self.planes:
             raise ValueError(f"the network takes {self.planes} planes, face variant {batch.variant} has {FACE_PLANES[batch.variant]}")
         states, ids = (batch.s0, batch.a0) if side == 0 else (batch.s1, batch.a1)
+        if states is None:
+            raise ValueError("a batch of return targets (ReturnBatch) has no side 1")
         h = self._stage(states=states, ids=ids, index=batch.index, table=batch.table, variant=batch.variant)
         return self.fc2(F.relu(self.fc1(self.drop(h))))
 
@@ -1259,6 +1339,28 @@ def td_step(policy, target, optimizer, batch, gamma=0.95, fused=False):
     return loss.detach()
 
 
+def mc_step(policy, optimizer, batch, fused=False):
+    """One update onto Monte-Carlo return targets: MSE of Q_policy(s0, a0) against the batch's `ret` (ReturnRecorder.sample /
+    ReturnAssembler), one optimizer step -- td_step without the target pass.  Returns the loss (a tensor: no host sync).  fused
+    as in td_step: False the literal forward, True QNet.forward_fused, "stage" QNet.forward_stage; a ReturnBatch
+    (ReturnRecorder.sample_packed) goes through QNet.forward_packed whatever `fused` says."""
+    if isinstance(batch, ReturnBatch):
+        q, ret = policy.forward_packed(batch, 0), batch.ret[batch.index]
+    else:
+        if isinstance(fused, str):
+            if fused != "stage":
+                raise ValueError('fused: False, True or "stage"')
+            q_policy = policy.forward_stage
+        else:
+            q_policy = policy.forward_fused if fused else policy
+        q, ret = q_policy(batch["s0"], batch["a0"]), batch["ret"]
+    loss = F.mse_loss(q.view(-1), ret)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
+
+
 # ------------------------------------------------------------------------------------------------
 # The same bookkeeping on the device (csrc/ddz_replay.h): TransitionAssembler + one Replay per role as three launches per call,
 # transitions kept packed (two 176-byte state rows, two action ids, reward, done, table) and decoded into faces / thermometers
@@ -1286,6 +1388,17 @@ class TransitionRecorder:
 
     def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), replicate_reference_quirk=False):
         from . import engine as E
+        self._setup(env, capacity, reward_dict, trained_roles)
+        self.quirk = bool(replicate_reference_quirk)
+        self.ws = torch.zeros(E.tr_ws_bytes(self.T), dtype=torch.uint8, device=self.device)
+        self._make_rings(E.tr_ring_bytes(self.capacity), E.tr_ring_layout(self.capacity),
+                         (("s0", torch.uint8, 176), ("s1", torch.uint8, 176), ("a0", torch.int32, 1), ("a1", torch.int32, 1),
+                          ("reward", torch.float32, 1), ("table", torch.int32, 1), ("done", torch.uint8, 1)))
+
+    def _setup(self, env, capacity, reward_dict, trained_roles):
+        """what every recorder of env's tables keeps, whatever its rings hold: the device, the rewards and trained roles in role
+        order, the action table and the host-known counts"""
+        from . import engine as E
         self.device = E._require_gpu(env.device)          # (DdzError without a GPU, as BatchedEnv)
         rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
         self.env, self.T, self.capacity = env, int(env.T), int(capacity)
@@ -1296,22 +1409,23 @@ class TransitionRecorder:
         if len(self.trained) != 3:
             raise ValueError("trained_roles: (up, lord, down)")
         self.trained_mask = sum(1 << k for k in range(3) if self.trained[k])
-        self.quirk = bool(replicate_reference_quirk)
-        dev = self.device
-        self.ws = torch.zeros(E.tr_ws_bytes(self.T), dtype=torch.uint8, device=dev)
-        nbytes, off = E.tr_ring_bytes(self.capacity), E.tr_ring_layout(self.capacity)
-        self.rings = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) if t else None for t in self.trained]
+        self._rows = E.action_table(self.device, env.native_joker_kickers)   # [n_actions, 16] int8: id -> count row
+        self.known = [0, 0, 0]                                               # host-known lower bounds of the counts (note_counts)
+
+    def _make_rings(self, nbytes, off, fields):
+        """one zero-filled ring of nbytes per trained role (None for the others) and, per ring, views of its count and of its
+        fields ((name, dtype, elements per entry), ...) at the offsets `off`"""
         cap = self.capacity
+        self.rings = [torch.zeros(nbytes, dtype=torch.uint8, device=self.device) if t else None for t in self.trained]
 
         def views(ring):
-            f = lambda name, n, dt: ring[off[name]: off[name] + n].view(dt)   # noqa: E731
-            return {"count": f("count", 8, torch.int64), "s0": f("s0", cap * 176, torch.uint8).view(cap, 176),
-                    "s1": f("s1", cap * 176, torch.uint8).view(cap, 176), "a0": f("a0", cap * 4, torch.int32),
-                    "a1": f("a1", cap * 4, torch.int32), "reward": f("reward", cap * 4, torch.float32),
-                    "table": f("table", cap * 4, torch.int32), "done": f("done", cap, torch.uint8)}
+            out = {"count": ring[off["count"]: off["count"] + 8].view(torch.int64)}
+            for name, dt, width in fields:
+                size = torch.empty((), dtype=dt).element_size() * width * cap
+                v = ring[off[name]: off[name] + size].view(dt)
+                out[name] = v.view(cap, width) if width > 1 else v
+            return out
         self.fields = [None if r is None else views(r) for r in self.rings]
-        self._rows = E.action_table(dev, env.native_joker_kickers)       # [n_actions, 16] int8: id -> count row
-        self.known = [0, 0, 0]                                           # host-known lower bounds of the counts (note_counts)
 
     @property
     def ws_bytes_per_table(self):
@@ -1384,15 +1498,78 @@ class TransitionRecorder:
         return self.packed(role, self.draw(role, k, at_least), variant)
 
 
+MAX_DECISIONS_PER_ROLE = 54   # the longest game has 162 plies and the three roles take turns: a role acts at most 162 / 3 times
+
+
+class ReturnRecorder(TransitionRecorder):
+    """ReturnAssembler + one ring per trained role on the device (csrc/ddz_returns.h, return spec v1), for env's tables: before() /
+    after() around the step of a lock-step iteration (ddz_mc_before / ddz_mc_after), nothing on the host, capturable.  A ring
+    entry is (state row, action id, ret = +/-reward[role] * gamma^togo, table, togo): 189 bytes, about half a transition;
+    count / note_counts / draw / sample / sample_packed are TransitionRecorder's.  log_cap: log entries per table (1..255);
+    None = MAX_DECISIONS_PER_ROLE per trained role, which no game overflows.  The workspace is about 182 bytes per log entry:
+    121 MB at 4,096 tables with three trained roles, 1.9 GB at 65,536.  A log that does overflow loses the later decisions
+    (workspace counter `lost`), never the discount of the logged ones."""
+
+    def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), gamma=1.0, log_cap=None):
+        from . import engine as E
+        self._setup(env, capacity, reward_dict, trained_roles)
+        self.gamma = float(gamma)
+        self.log_cap = int(log_cap) if log_cap is not None else MAX_DECISIONS_PER_ROLE * max(1, sum(self.trained))
+        T, L = self.T, self.log_cap
+        self.ws = torch.zeros(E.mc_ws_bytes(T, L), dtype=torch.uint8, device=self.device)
+        self._cnt = self.ws[E.mc_ws_layout(T, L)["cnt"]:][:T * 4].view(T, 4)         # {n, c[3]} per table: what clear() zeroes
+        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity),
+                         (("s0", torch.uint8, 176), ("a0", torch.int32, 1), ("ret", torch.float32, 1), ("table", torch.int32, 1),
+                          ("togo", torch.uint8, 1)))
+
+    def before(self, chosen_ids, active=None):
+        """before the step: chosen_ids int32 [T] canonical ids of what every table plays, active u8 / bool [T] the tables that
+        move by a network (None: all)"""
+        self.env.mc_before(self.ws, self.log_cap, chosen_ids, active, self.trained_mask)
+
+    def after(self, done, r):
+        """after step(auto_reset=False), before the re-deal: done u8 [T], r i8 [T] as the step returned them"""
+        self.env.mc_after(self.ws, self.log_cap, self.rings, self.capacity, done, r, self.reward, self.gamma)
+
+    def clear(self, mask=None):
+        """forget the logs (entries and decision counters; `lost` stays) of the tables of mask (bool / u8 [T]; None: all) that the
+        caller re-deals itself before they finish.  No host sync."""
+        if mask is None:
+            self._cnt.zero_()
+        else:
+            self._cnt.masked_fill_(mask.to(device=self.device).bool().view(self.T, 1), 0)
+
+    def decode(self, role, index, variant):
+        """{"s0" f32 [n,P,15,4], "a0" f32 [n,15,4], "ret" f32 [n], "togo" u8 [n]} of the ring entries index (int64 [n] device
+        tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
+        from . import engine as E
+        f = self._ring(role)
+        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
+        ids = f["a0"][index].clamp(0, self._rows.shape[0] - 1).long()
+        return {"s0": E.observe_states(f["s0"], index, variant), "a0": E.rows_to_onehot(self._rows[ids]),
+                "ret": f["ret"][index], "togo": f["togo"][index]}
+
+    def packed(self, role, index, variant):
+        """the ReturnBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
+        ring, nothing decoded, nothing copied but the index.  No host sync."""
+        f = self._ring(role)
+        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
+        return ReturnBatch(f["s0"], f["a0"], f["ret"], f["togo"], index, self._rows, variant)
+
+
 class TrainLoop:
     """One iteration of Game.train's inner loop (game.py:90-167) for T tables, nothing on the host: SeatLoop.act() ->
     recorder.before on the network tables -> step_slab(STEP_IDS, no auto-reset) -> recorder.after -> re-deal of the finished
     tables -> the next lists and faces.  nets / epsilon as SeatLoop's; train_dict {"lord" | "down" | "up": bool} (default:
     every role with a network trains): a network role that does not train plays greedy and records nothing (game.py:95-104).
-    capture(n) records n iterations as one graph at the epsilon of the moment."""
+    capture(n) records n iterations as one graph at the epsilon of the moment.  targets: "td" -- the recorder is a
+    TransitionRecorder (one-step targets, td_step) -- or "mc" -- a ReturnRecorder(gamma, log_cap) (the episode's return,
+    mc_step): no greedy id is gathered, since no a1 is recorded."""
 
     def __init__(self, env, nets, face_variant, capacity=REPLAY_SIZE, epsilon=0.0, train_dict=None, reward_dict=None,
-                 replicate_reference_quirk=False):
+                 replicate_reference_quirk=False, targets="td", gamma=None, log_cap=None):
+        if targets not in ("td", "mc"):
+            raise ValueError('targets: "td" or "mc"')
         self.seat = SeatLoop(env, nets, face_variant, 0.0, auto_reset=False)
         nr = self.seat.rq.net_of_role
         td = {r: True for r in ROLE_ORDER} if train_dict is None else train_dict
@@ -1401,9 +1578,13 @@ class TrainLoop:
             raise ValueError(f"unknown role(s) {sorted(bad)} in train_dict")
         self.trained = tuple(nr[k] >= 0 and bool(td.get(r)) for k, r in enumerate(ROLE_ORDER))
         self.env, self.variant = env, int(face_variant)
-        self.rec = TransitionRecorder(env, capacity, reward_dict, self.trained, replicate_reference_quirk)
+        self.targets = targets
+        if targets == "mc":
+            self.rec = ReturnRecorder(env, capacity, reward_dict, self.trained, 1.0 if gamma is None else gamma, log_cap)
+        else:
+            self.rec = TransitionRecorder(env, capacity, reward_dict, self.trained, replicate_reference_quirk)
+            self._greedy_ids = torch.empty(env.T, dtype=torch.int32, device=env.device)
         self.set_epsilon(epsilon)
-        self._greedy_ids = torch.empty(env.T, dtype=torch.int32, device=env.device)
         self._active = torch.empty(env.T, dtype=torch.uint8, device=env.device)
 
     def set_epsilon(self, epsilon):
@@ -1419,9 +1600,13 @@ class TrainLoop:
         from .engine import STEP_IDS
         s, env = self.seat, self.env
         ids = s.act()
-        self._greedy_ids.copy_(env.slab_ids().gather(1, s.greedy.clamp(min=0).long()[:, None])[:, 0])
-        self._active.copy_(s.slot >= 0)
-        self.rec.before(ids, self._greedy_ids, self._active)
+        if self.targets == "mc":
+            self._active.copy_(s.slot >= 0)
+            self.rec.before(ids, self._active)
+        else:
+            self._greedy_ids.copy_(env.slab_ids().gather(1, s.greedy.clamp(min=0).long()[:, None])[:, 0])
+            self._active.copy_(s.slot >= 0)
+            self.rec.before(ids, self._greedy_ids, self._active)
         done, r, illegal = env.step_slab(ids, STEP_IDS, auto_reset=False)
         self.rec.after(done, r)
         env.reset(mask=done)
@@ -1440,7 +1625,7 @@ class TrainLoop:
 
 def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, tables=4096, seed=0, log_every=100,
           model_every=1000, book=None, model_dir=None, win_dir=None, device="cuda:0", check_every=8, capacity=REPLAY_SIZE,
-          begin=None, log=None, fused=False, batch_size=BATCH_SIZE):
+          begin=None, log=None, fused=False, batch_size=BATCH_SIZE, targets="td", gamma=None):
     """Game.train (game.py:183-238) on the batched engine, the counterpart of compete(): nets {"lord" | "down" | "up": QNet |
     None (the rule agent)}, train_dict which network roles keep training (default: all of them), reward_dict as REWARD_DICT.
     Lock-step iterations of TrainLoop over `tables` tables until `episodes` episodes have finished; every iteration each
@@ -1453,7 +1638,9 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     model_dir, the win rates under win_dir) -- `episode` being the multiple of the interval that was crossed, since the tables
     finish episodes in bulk.  The policy networks learn in train() mode (dropout on, dqn.py:41), the targets are evaluated
     without dropout.  Returns {"lord", "down", "up": wins, "episodes", "iterations", "loss": {role: last loss | None},
-    "checkpoints": [paths]}."""
+    "checkpoints": [paths]}.  targets="mc": the roles learn from Monte-Carlo return targets instead (ReturnRecorder, one mc_step
+    per ready role and iteration, gamma None = 1.0 = Deep Monte Carlo): no target network exists and none is copied; everything
+    else, the returned keys included, is the same."""
     import copy
     import time
     from . import metrics
@@ -1463,6 +1650,9 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
         raise ValueError("batch_size must be positive")
     if isinstance(fused, str) and fused not in ("stage", "packed"):
         raise ValueError('fused: False, True, "stage" or "packed"')
+    if targets not in ("td", "mc"):
+        raise ValueError('targets: "td" or "mc"')
+    mc = targets == "mc"
     nets = {r: v for r, v in nets.items()}
     for r, v in nets.items():
         if v is not None:
@@ -1471,7 +1661,7 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     env.reset()
     env.legal_slab()
     loop = TrainLoop(env, nets, face_variant, capacity=capacity, epsilon=epsilon_schedule(0), train_dict=train_dict,
-                     reward_dict=reward_dict)
+                     reward_dict=reward_dict, targets=targets, gamma=gamma)
     roles = [r for k, r in enumerate(ROLE_ORDER) if loop.trained[k]]
     if not roles:
         env.close()
@@ -1480,7 +1670,7 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     target, opt = {}, {}
     for r in roles:                                                  # (roles that share a network object share the learner)
         same = [o for o in target if policy[o] is policy[r]]
-        target[r] = target[same[0]] if same else copy.deepcopy(policy[r]).eval()
+        target[r] = None if mc else target[same[0]] if same else copy.deepcopy(policy[r]).eval()
         opt[r] = opt[same[0]] if same else torch.optim.Adam(policy[r].parameters(), LEARNING_RATE)
         policy[r].train()
     book = book if book is not None else metrics.WinRateBook(begin)
@@ -1497,7 +1687,10 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
                 if ready[r]:
                     packed = isinstance(fused, str) and fused == "packed"
                     batch = (loop.rec.sample_packed if packed else loop.rec.sample)(r, batch_size, face_variant)
-                    loss[r] = td_step(policy[r], target[r], opt[r], batch, GAMMA, fused=fused)
+                    if mc:
+                        loss[r] = mc_step(policy[r], opt[r], batch, fused=False if packed else fused)
+                    else:
+                        loss[r] = td_step(policy[r], target[r], opt[r], batch, GAMMA, fused=fused)
         it += int(check_every)
         s1 = env.stats()                                             # the host sync of the interval
         known = loop.rec.note_counts()
@@ -1508,7 +1701,7 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
         for r in roles:
             if loss[r] is not None:
                 book.add_loss(r, float(loss[r]))
-        if eps_done // UPDATE_TARGET_EVERY > prev // UPDATE_TARGET_EVERY:
+        if not mc and eps_done // UPDATE_TARGET_EVERY > prev // UPDATE_TARGET_EVERY:
             for r in roles:
                 target[r].load_state_dict(policy[r].state_dict())
         if eps_done // int(log_every) > prev // int(log_every):

@@ -370,6 +370,42 @@ class BatchedEnv:
                                     (C.c_float * 3)(*[float(x) for x in reward]), int(bool(replicate_reference_quirk)),
                                     _stream(self.device)))
 
+    # ---- Monte-Carlo return targets (csrc/ddz_returns.h; dqn_glue.ReturnRecorder) ----
+    def _check_mc(self, ws, log_cap, rings=None, capacity=None):
+        self._arg(ws, "ws", torch.uint8, at_least=mc_ws_bytes(self.T, log_cap), why=" (mc_ws_bytes(T, log_cap) bytes)")
+        if rings is None:
+            return None, 0
+        if len(rings) != 3:
+            raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
+        nbytes = mc_ring_bytes(capacity)
+        for k, ring in enumerate(rings):
+            self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (mc_ring_bytes(capacity) bytes)", none_ok=True)
+        return (C.c_void_p * 3)(*[None if x is None else x.data_ptr() for x in rings]), nbytes
+
+    def mc_before(self, ws, log_cap, chosen, active=None, trained_roles=0b111):
+        """ddz_mc_before: the episode log of every active table whose actor is a trained role takes (state row now, chosen[t])
+        (call it before the step).  chosen int32 [T] canonical action ids, active u8 / bool [T] or None (all tables),
+        trained_roles: bit r = role r.  No host sync."""
+        trained_roles = _roles_mask(trained_roles, name="trained_roles")
+        self._check_mc(ws, log_cap)
+        self._arg(chosen, "chosen", torch.int32, numel=self.T)
+        if active is not None:
+            active = self._u8_arg(active, "active")
+        check(self.lib.ddz_mc_before(self._h, _p(ws), ws.numel(), int(log_cap), _p(chosen), _p(active), trained_roles,
+                                     _stream(self.device)))
+
+    def mc_after(self, ws, log_cap, rings, capacity, done, r, reward, gamma=1.0):
+        """ddz_mc_after: the logs of the finished tables become ring entries (s0, a0, ret = +/-reward[role] * gamma^togo, table,
+        togo) and empty (call it after step(auto_reset=False), before the re-deal).  rings: one uint8 tensor of
+        mc_ring_bytes(capacity) bytes (or None: that role's entries are dropped) per role; done u8 [T], r i8 [T] as the step wrote
+        them, reward: three floats in role order up, lord, down."""
+        ptrs, nbytes = self._check_mc(ws, log_cap, rings, capacity)
+        done, r = self._u8_arg(done, "done"), self._arg(r, "r", torch.int8, numel=self.T)
+        if len(reward) != 3:
+            raise ValueError("reward: three floats in role order up, lord, down")
+        check(self.lib.ddz_mc_after(self._h, _p(ws), ws.numel(), int(log_cap), ptrs, nbytes, int(capacity), _p(done), _p(r),
+                                    (C.c_float * 3)(*[float(x) for x in reward]), float(gamma), _stream(self.device)))
+
     def select(self, q, epsilon=0.0, out=None):
         """greedy / epsilon-greedy choice per table from per-row values q (f32, CSR order of
         the current legal list; dqn.py:50-71).  Returns int32[T] indices for step(STEP_CHOICE)."""
@@ -1051,6 +1087,49 @@ def tr_ring_layout(capacity):
     if _lib.lib().ddz_tr_ring_layout(int(capacity), off) != 0:
         raise ValueError("capacity must be in 1 .. 2^30")
     return dict(zip(TR_RING_FIELDS, [int(x) for x in off]))
+
+
+def mc_ws_bytes(n_tables, log_cap):
+    """bytes of the return recorder's workspace for n_tables tables with log_cap log entries each (ddz_mc_ws_bytes; zero-filled
+    by the caller; about 182 bytes per log entry)"""
+    if not 1 <= int(log_cap) <= 255:
+        raise ValueError("log_cap must be in 1 .. 255")
+    n = int(_lib.lib().ddz_mc_ws_bytes(int(n_tables), int(log_cap)))
+    if n < 0:
+        raise ValueError("n_tables must be positive and n_tables * log_cap at most 2^30")
+    return n
+
+
+MC_WS_REGIONS = ("rows", "act", "who", "cnt", "lost", "rank", "blk", "hdr")
+
+
+def mc_ws_layout(n_tables, log_cap):
+    """{region: byte offset} of the return recorder's workspace (ddz_mc_ws_layout): rows u8 [T,L,176], act int32 [T,L], who u8
+    [T,L,2] = {role, ordinal}, cnt u8 [T,4] = {n, c[3]}, lost uint32 [T], rank int32 [T,4], blk int32 [nb,4], hdr int64 [8]"""
+    off = (C.c_int64 * 8)()
+    if _lib.lib().ddz_mc_ws_layout(int(n_tables), int(log_cap), off) != 0:
+        raise ValueError("log_cap must be in 1 .. 255, n_tables positive and n_tables * log_cap at most 2^30")
+    return dict(zip(MC_WS_REGIONS, [int(x) for x in off]))
+
+
+def mc_ring_bytes(capacity):
+    """bytes of one role's ring of `capacity` return entries (ddz_mc_ring_bytes; zero-filled by the caller)"""
+    n = int(_lib.lib().ddz_mc_ring_bytes(int(capacity)))
+    if n < 0:
+        raise ValueError("capacity must be in 1 .. 2^30")
+    return n
+
+
+MC_RING_FIELDS = ("count", "s0", "a0", "ret", "table", "togo")
+
+
+def mc_ring_layout(capacity):
+    """{field: byte offset} of a return ring (ddz_mc_ring_layout): count int64, s0 u8 [capacity,176], a0 int32, ret f32, table
+    int32, togo u8"""
+    off = (C.c_int64 * 6)()
+    if _lib.lib().ddz_mc_ring_layout(int(capacity), off) != 0:
+        raise ValueError("capacity must be in 1 .. 2^30")
+    return dict(zip(MC_RING_FIELDS, [int(x) for x in off]))
 
 
 def state_prob(known60, size1, size2, device="cuda:0"):

@@ -7,11 +7,14 @@ reference's progress lines, the total wins and the checkpoints written.
 
   python examples/train.py [--lord-vs-rule] [--tables 4096] [--episodes 20000] [--log-every 5000] [--model-every 10000]
                            [--model-dir models] [--win-dir outs/win_rates] [--fused | --packed] [--batch-size 256]
+                           [--mc [--gamma 1.0]]
 
 Default: lord, down and up all train (three networks).  --lord-vs-rule: the reference's train.py as it stands -- the lord trains
 against the rule-based farmers (reward_dict {'lord': 100}).  --fused: td_step through QNet.forward_fused (the first layer by the
 engine's forward / backward kernels, csrc/ddz_qtrain.h); --packed: batches stay packed replay rows and both passes of td_step run
 QNet.forward_packed (two stage launches per pass, no face, no library convolution); --batch-size: transitions per td_step (the reference's 256).
+--mc: Monte-Carlo return targets instead of one-step TD targets -- the device-side return recorder of csrc/ddz_returns.h, one mc_step
+per trained role per iteration, no target network; --gamma: the discount of the returns (default 1.0: Deep Monte Carlo).
 """
 import argparse
 import importlib
@@ -39,7 +42,11 @@ def main():
     ap.add_argument("--fused", action="store_true")
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--mc", action="store_true")
+    ap.add_argument("--gamma", type=float, default=None)
     a = ap.parse_args()
+    if a.gamma is not None and not a.mc:
+        ap.error("--gamma is the discount of --mc's returns")
     glue = importlib.import_module("doudizhu-rl_amd.dqn_glue")
     metrics = importlib.import_module("doudizhu-rl_amd.metrics")
     engine = importlib.import_module("doudizhu-rl_amd.engine")
@@ -56,7 +63,8 @@ def main():
     res = glue.train(FACE_VARIANT, nets, a.episodes, train_dict=train_dict, reward_dict=reward_dict, tables=a.tables,
                      seed=a.seed, log_every=a.log_every, model_every=a.model_every, book=book, model_dir=a.model_dir,
                      win_dir=a.win_dir, log=lambda m: print(m, end=""), fused="packed" if a.packed else a.fused,
-                     batch_size=glue.BATCH_SIZE if a.batch_size is None else a.batch_size)
+                     batch_size=glue.BATCH_SIZE if a.batch_size is None else a.batch_size,
+                     targets="mc" if a.mc else "td", gamma=a.gamma)
     dt = time.perf_counter() - t0
     eps = max(1, res["episodes"])
     print("Total wins: lord {} ({:.2%}), down {} ({:.2%}), up {} ({:.2%}) over {} episodes".format(
@@ -65,7 +73,7 @@ def main():
     for p in res["checkpoints"]:
         print("saved", p)
     print(f"tables={a.tables} iterations={res['iterations']}: {dt / max(1, res['iterations']) * 1e3:.2f} ms/iteration "
-          f"(wall clock, td_step and first-call allocation included)")
+          f"(wall clock, {'mc_step' if a.mc else 'td_step'} and first-call allocation included)")
 
 
 if __name__ == "__main__":

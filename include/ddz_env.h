@@ -218,6 +218,50 @@ int ddz_tr_before(ddz_env_t* env, void* ws, int64_t ws_bytes, void* const* rings
 int ddz_tr_after(ddz_env_t* env, void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity,
                  const uint8_t* done, const int8_t* r, const float* reward, int replicate_reference_quirk, void* stream);
 
+/* Monte-Carlo return targets (return spec v1; doudizhu-rl_amd/csrc/ddz_returns.h; dqn_glue.ReturnAssembler is the
+ * host statement): a decision is regressed onto its own episode's return instead of r + gamma * Q_target(s1, a1).  Two calls
+ * around the step of a lock-step iteration, used exactly as ddz_tr_before / ddz_tr_after are: on the caller's stream, nothing
+ * on the host, no atomics, capturable in a graph, deterministic.
+ *   ws: caller-owned, 16-byte aligned, ZERO-FILLED before the first call, ddz_mc_ws_bytes(T, log_cap) bytes (a multiple of
+ *     256; log_cap in 1..255 entries per table, T * log_cap <= 2^30; about 182 bytes per log entry).  Per table: an episode
+ *     log of log_cap entries (state row uint4[11], a0 int32, role u8, ordinal u8), the count n of its entries, a decision
+ *     counter per role c[3] (u8, saturating) and a cumulative counter `lost` (u32, saturating) of the decisions that were not
+ *     logged because the log was full; then the per-call scratch of the scan and hdr int64[8] with the meaning
+ *     ddz_replay.h gives it: [k] the sequence number of ring k's emit 0, [4 + k] the emits dropped in front.
+ *     ddz_mc_ws_layout writes the byte offsets of the regions into offsets[8] (HOST): rows u8[T][log_cap][176], act
+ *     int32[T][log_cap], who u8[T][log_cap][2] = {role, ordinal}, cnt u8[T][4] = {n, c[3]}, lost uint32[T], rank int32[T][4],
+ *     blk int32[nb][4], hdr int64[8] (what a caller needs to forget the logs of tables it re-deals itself: zero their cnt).
+ *   rings: HOST array of three device pointers in role order (0 up, 1 lord, 2 down), each ddz_mc_ring_bytes(capacity) bytes
+ *     (ring_bytes = the size of each), 16-byte aligned, zero-filled; NULL = that role's emits are dropped (and counted in
+ *     hdr[4 + k]).  Fields at the byte offsets ddz_mc_ring_layout writes into offsets[6] (HOST), each 256-aligned: count
+ *     int64 (total ever written), s0 u8[capacity][176], a0 int32[capacity], ret f32[capacity], table int32[capacity], togo
+ *     u8[capacity].  The entry with sequence number s is entry s % capacity.
+ *   ddz_mc_before (call it BEFORE the step, on the states the actors chose on): for every table whose role byte is <= 2, that
+ *     is active (active u8[T], NULL = all) and whose role is in trained_roles (bit r = role r): if n < log_cap the log takes
+ *     (the state row now, chosen[t], role, ordinal = c[role]) at position n and n goes up, otherwise lost goes up; in both
+ *     cases c[role] goes up.  A role byte above 2 takes no part, as in ddz_tr_before.  chosen: int32[T] canonical action ids.
+ *   ddz_mc_after (call it AFTER the step, before the re-deal: no auto-reset): for every table with done[t] != 0, every log
+ *     entry in ascending position, with role k and ordinal j, emits into ring k: s0 = the logged row, a0 = the logged action,
+ *     table = t, togo = c[k] - 1 - j, ret = g after togo steps of g <- g * gamma in f32 from g = +reward[k] if role k's side
+ *     won, else -reward[k] (r i8[T] as ddz_step writes it, < 0: the lord won; the two farmers are one side -- exactly as
+ *     ddz_tr_after decides it; reward: HOST float[3] in role order).  Repeated f32 multiplication, not powf: a host
+ *     reproduces ret bit for bit.  Then n and c of the table return to zero; lost stays.
+ *   Order of a call's emits into a ring: ascending table, within a table ascending log position; emit g gets sequence number
+ *     count + g.  Overflow as ddz_tr_after: a call that emits E > capacity into one ring writes its last `capacity` only, the
+ *     earlier ones take no sequence number and are counted in hdr[4 + k].  No two lanes store to one entry.  Entries that take
+ *     no emit, and the padding between the fields, keep their bytes.
+ *   When the log overflowed: togo counts the role's later decisions whether or not they were logged, so with the reference's
+ *     gamma ret is what the reference's own chain of transitions gives the decision under y_i = r_i + (1 - done_i) * gamma *
+ *     y_{i+1}; with gamma = 1 it is the Deep Monte Carlo target.                       (tests/test_gpu_return_recorder.py) */
+int64_t ddz_mc_ws_bytes(int64_t n_tables, int log_cap);
+int ddz_mc_ws_layout(int64_t n_tables, int log_cap, int64_t* offsets);
+int64_t ddz_mc_ring_bytes(int64_t capacity);
+int ddz_mc_ring_layout(int64_t capacity, int64_t* offsets);
+int ddz_mc_before(ddz_env_t* env, void* ws, int64_t ws_bytes, int log_cap, const int32_t* chosen, const uint8_t* active,
+                  int trained_roles, void* stream);
+int ddz_mc_after(ddz_env_t* env, void* ws, int64_t ws_bytes, int log_cap, void* const* rings, int64_t ring_bytes,
+                 int64_t capacity, const uint8_t* done, const int8_t* r, const float* reward, float gamma, void* stream);
+
 /* Replaces the native get_state_prob_manual(known60, size1, size2) (server/core.py:26-33; Env.get_state_prob(),
  * envi.py:94, is the same function of the live table): known60 u8[n][60] = thermometer of the cards the actor can see
  * (own hand + everything played), sizes int32[n][2] = cards left of the next and the next-but-one player;
