@@ -74,6 +74,15 @@ SYMBOLS = {
     "ddz_ismcts_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "ddz_ismcts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int64,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_guided_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "ddz_guided_open": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_guided_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_guided_close": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_guided_values": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p]),
     "ddz_cfr_work_bytes": (C.c_int64, [C.c_int64]),
     "ddz_cfr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -10,6 +10,8 @@
 //             (table, chunk), the root in registers, no list stored.
 //   k_search  (ddz_search.h; ddz_search) UCT tree search around those playouts: one wavefront per (table, tree), the tree in a
 //             caller-provided workspace, the descent re-applies stored moves.
+//   k_guided  (ddz_guided.h; ddz_guided_open / _step / _close) k_search's tree with leaf values from outside the kernel: one
+//             iteration of every (table, tree) per launch, the new leaf's state row out, its value in with the next launch.
 //   k_ismcts  (ddz_ismcts.h; ddz_ismcts) information-set MCTS: one wavefront per (table, tree), ONE tree over a fresh world per
 //             iteration, a list at every level of the descent, children keyed by (parent, count word).
 //   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
@@ -1384,6 +1386,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 #include "ddz_ply.h"      // the entry into a table, the root with its hands and a ply, shared by the four kernels below
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
+#include "ddz_guided.h"   // k_guided / k_guided_value: UCT with leaf values from outside the kernel, one iteration per launch
 #include "ddz_ismcts.h"   // k_ismcts: information-set MCTS, one tree per (table, tree) over all its sampled worlds
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
 #include "ddz_solve.h"    // k_solve / k_solve_choose: exact open-hand minimax per root move, one wavefront per (table, world, chunk)
@@ -2876,14 +2879,17 @@ int launch_hidden(bool hidden, int64_t blocks, void* stream, const A& a) {
   else hipLaunchKernelGGL(OPEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
   return check_launch();
 }
-// what ddz_search and ddz_ismcts do alike: the argument checks in their order, SearchArgs, the launch of one wavefront per
-// (table, tree).  tree_bytes: the workspace of one tree at this budget (asked only once the budget is known to be in range)
-template <auto OPEN, auto HIDDEN>
+// what ddz_search, ddz_ismcts and the three ddz_guided_* launches do alike: the argument checks in their order, SearchArgs,
+// the launch of one wavefront per (table, tree).  tree_bytes: the workspace of one tree at this budget (asked only once the
+// budget is known to be in range).  A: the kernels' argument struct, SearchArgs or one derived from it whose own fields
+// `fill` sets; outs: the call writes visits / wins (they must be there)
+struct SearchNoFill { void operator()(SearchArgs&) const {} };
+template <auto OPEN, auto HIDDEN, typename A = SearchArgs, typename Fill = SearchNoFill>
 int search_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int64_t budget, int64_t trees, int mode, float c, uint64_t salt,
                   bool hidden, int roles, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
-                  int64_t work_bytes, void* stream) {
+                  int64_t work_bytes, void* stream, bool outs = true, Fill fill = {}) {
   if (!good(e)) return DDZ_EHANDLE;
-  if (!visits || !wins || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
+  if ((outs && (!visits || !wins)) || !work || !al(visits, 4) || !al(wins, 4) || !al(totals, 8) || !al(work, 16)) return DDZ_EINVAL;
   if (budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return DDZ_EINVAL;
   if (mode != DDZ_SEARCH_REFERENCE && mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
   if (!(c >= 0.0f) || !(c <= 3.0e38f)) return DDZ_EINVAL;   // (finite and not negative: values order as their bit patterns)
@@ -2894,17 +2900,31 @@ int search_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int64_t budget, i
   if (grid_of(e->T * trees, SEARCH_WAVES, &blocks)) return DDZ_ECAP;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
-  SearchArgs a;
+  A a;
   ply_args(a, e, salt);
   a.budget = (uint32_t)budget; a.trees = (uint32_t)trees; a.mode = (uint32_t)mode; a.c = c;
   a.stride = stride; a.visits = visits; a.wins = wins; a.totals = (unsigned long long*)totals;
   a.roles = (uint32_t)roles; a.work = (uint8_t*)work; a.tree_bytes = tree_bytes(budget); a.hash_log = search_hash_log(budget);
+  fill(a);
   void* ln = nullptr;
   const hipError_t r = hipGetSymbolAddress(&ln, HIP_SYMBOL(g_search_ln));
   if (r != hipSuccess) return hip_fail(r);
   a.ln = (const float*)ln;
   if (blocks == 0) return DDZ_OK;
   return launch_hidden<OPEN, HIDDEN, SEARCH_WAVES>(hidden, blocks, stream, a);
+}
+// a launch of k_guided in `phase`: ddz_search's checks, then the unit's bound and the phase's own buffers
+int guided_launch(ddz_env* e, int phase, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, bool hidden, int roles,
+                  int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need, int32_t* visits, int32_t* wins,
+                  int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!al(values, 4) || !al(leaf_rows, 16) || !al(need, 4)) return DDZ_EINVAL;
+  if (phase == GUIDED_STEP && (!leaf_rows || !need)) return DDZ_EINVAL;
+  if (budget >= 1 && trees >= 1 && budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return DDZ_EINVAL;   // the int32 root sums
+  const auto fill = [=](GuidedArgs& a) { a.phase = phase; a.values = values; a.leaf_rows = leaf_rows; a.need = need; };
+  return search_launch<k_guided<false>, k_guided<true>, GuidedArgs>(e, guided_tree_bytes, budget, trees, mode, c, salt, hidden, roles,
+                                                                    stride, visits, wins, totals, work, work_bytes, stream,
+                                                                    phase == GUIDED_CLOSE, fill);
 }
 // a *_choose kernel over the env's tables, `per` tables to a block of BLOCK threads
 template <auto K, typename... Q>
@@ -3646,6 +3666,51 @@ int ddz_ismcts(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, u
                int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
   return search_launch<k_ismcts, k_ismcts>(e, ismcts_tree_bytes, budget, trees, mode, c, salt, true, roles, stride, visits, wins,
                                            totals, work, work_bytes, stream);
+}
+
+// ddz_guided_*: k_guided<hidden> in its three phases, one wavefront per (table, tree), one iteration per step
+int64_t ddz_guided_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
+  if (n_tables < 0 || budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return -1;
+  if (budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return -1;
+  return (int64_t)guided_tree_bytes(budget) * n_tables * trees;
+}
+
+int ddz_guided_open(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                    int64_t stride, void* work, int64_t work_bytes, void* stream) {
+  return guided_launch(e, GUIDED_OPEN, budget, trees, mode, c, salt, hidden != 0, roles, stride, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_guided_step(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                    int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need, void* work, int64_t work_bytes,
+                    void* stream) {
+  return guided_launch(e, GUIDED_STEP, budget, trees, mode, c, salt, hidden != 0, roles, stride, values, leaf_rows, need, nullptr,
+                       nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_guided_close(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                     const int32_t* values, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
+                     int64_t work_bytes, void* stream) {
+  return guided_launch(e, GUIDED_CLOSE, budget, trees, mode, c, salt, hidden != 0, roles, stride, values, nullptr, nullptr, visits,
+                       wins, totals, work, work_bytes, stream);
+}
+
+int ddz_guided_values(int device, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
+                      const float* inv_reward, int net_roles, int32_t* values, void* stream) {
+  if (!al(rows, 16) || !al(counts, 4) || !al(q, 4) || !al(values, 4)) return DDZ_EINVAL;
+  if (n < 0 || stride < 1 || net_roles < 0 || net_roles > 7 || !inv_reward) return DDZ_EINVAL;
+  if (n > 0 && (!rows || !counts || !q || !values)) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (n > 0x7FFFFFFF || n * stride > ((int64_t)1 << 40)) return DDZ_ECAP;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+  GuidedValueArgs a;
+  a.rows = rows; a.counts = counts; a.q = q; a.stride = stride; a.n_leaves = n;
+  for (int r = 0; r < 3; ++r) a.inv_reward[r] = inv_reward[r];
+  a.net_roles = (uint32_t)net_roles; a.values = values;
+  constexpr int per = BLOCK / 64;
+  hipLaunchKernelGGL(k_guided_value, dim3((unsigned)((n + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  return check_launch();
 }
 
 int ddz_search_choose(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* visits,

@@ -83,15 +83,70 @@ __device__ __forceinline__ void search_insert(uint64_t* tab, uint32_t hlog, uint
   }
 }
 
-// value = W / V + c * sqrt((2 * LN[N]) / V): five correctly rounded fp32 operations, nothing fused (get_bestchild.py:9-18)
+// value = W / V + c * sqrt((2 * LN[N]) / V): five correctly rounded fp32 operations, nothing fused (get_bestchild.py:9-18).
+// ONE: the unit W is counted in (1 here; DDZ_GUIDED_ONE in ddz_guided.h, whose mean is scaled by the exact 1 / ONE)
+template <uint32_t ONE = 1>
 __device__ __forceinline__ float search_value(uint32_t w, uint32_t v, float two_ln, float c) {
 #pragma clang fp contract(off)
   const float fv = (float)v;
-  const float mean = (float)w / fv;
+  float mean = (float)w / fv;
+  if constexpr (ONE != 1) mean = mean * (1.0f / (float)ONE);
   const float q = two_ln / fv;
   const float r = __builtin_sqrtf(q);
   const float bonus = c * r;
   return mean + bonus;
+}
+
+// the expansion's list index at a node with n entries of which nchild have a child: the r-th untried one, ascending
+// (r < n - nchild, wave-uniform); -1 where there is none (cannot happen)
+__device__ __forceinline__ int search_untried(const uint64_t* tab, uint32_t hlog, uint32_t node, int n, uint32_t nchild, uint32_t r,
+                                              int lane) {
+  if (nchild == 0) return (int)r;
+  for (int b = 0; b < n; b += 64) {
+    const int j = b + lane;
+    bool untried = false;
+    if (j < n) untried = search_find(tab, hlog, node * 512u + (uint32_t)j + 1u) == SEARCH_NONE;
+    const uint64_t um = __ballot(untried);
+    const uint32_t cnt = (uint32_t)__builtin_popcountll(um);
+    if (r < cnt) {
+      const uint64_t below = um & ((1ull << lane) - 1ull);
+      const uint64_t hit = __ballot(untried && (uint32_t)__builtin_popcountll(below) == r);
+      return b + (int)__builtin_ctzll(hit);
+    }
+    r -= cnt;
+  }
+  return -1;
+}
+
+// selection at a fully expanded node with n entries (get_bestchild.py:20-32): the child with the maximum (take_max) or the
+// minimum value, ties to the lowest list index; SEARCH_NONE where no child was visited (cannot happen).  own: the node's
+// actor counts W as it stands; otherwise `sides` counts V * ONE - W.  Wave-uniform result.
+template <uint32_t ONE = 1>
+__device__ __forceinline__ uint32_t search_select(const uint8_t* nodes, const uint64_t* tab, uint32_t hlog, uint32_t node, int n,
+                                                  uint32_t nnodes, float two_ln, float c, bool own, bool sides, int lane) {
+  const bool take_max = own || sides;
+  uint32_t best = 0, at = SEARCH_NONE, bchild = SEARCH_NONE;
+  for (int b = 0; b < n; b += 64) {
+    const int j = b + lane;
+    if (j < n) {
+      const uint32_t ch = search_find(tab, hlog, node * 512u + (uint32_t)j + 1u);
+      if (ch != SEARCH_NONE && ch < nnodes) {
+        const uint64_t vw = sld64((const uint64_t*)(nodes + (uint64_t)ch * NODE_BYTES + 8));
+        const uint32_t V = (uint32_t)vw, W = (uint32_t)(vw >> 32);
+        if (V > 0) {
+          // (values are non-negative floats: their bit patterns order as they do)
+          const uint32_t bits = __float_as_uint(search_value<ONE>(own ? W : (sides ? V * ONE - W : W), V, two_ln, c));
+          if (at == SEARCH_NONE || (take_max ? bits > best : bits < best)) { best = bits; at = (uint32_t)j; bchild = ch; }
+        }
+      }
+    }
+  }
+  uint32_t m;
+  if (take_max) m = (uint32_t)wave_max_i32(at == SEARCH_NONE ? (int)0x80000000 : (int)best);
+  else m = wave_min_u32(at == SEARCH_NONE ? 0xFFFFFFFFu : best);
+  const uint32_t first = wave_min_u32((at != SEARCH_NONE && best == m) ? at : SEARCH_NONE);   // ties: the lowest index
+  if (first == SEARCH_NONE) return SEARCH_NONE;
+  return rl(bchild, (int)(first & 63u));
 }
 
 template <bool HIDDEN>
@@ -178,25 +233,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
         if (nn != n) break;   // (cannot happen: the state of a node is a function of its path)
         const uint32_t u = (uint32_t)n - nchild;
         const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
-        uint32_t r = rfl(__umulhi(de, u));
-        int idx = -1;
-        if (nchild == 0) idx = (int)r;
-        else {
-          for (int b = 0; b < n; b += 64) {
-            const int j = b + lane;
-            bool untried = false;
-            if (j < n) untried = search_find(tab, hlog, node * 512u + (uint32_t)j + 1u) == SEARCH_NONE;
-            const uint64_t um = __ballot(untried);
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(um);
-            if (r < cnt) {
-              const uint64_t below = um & ((1ull << lane) - 1ull);
-              const uint64_t hit = __ballot(untried && (uint32_t)__builtin_popcountll(below) == r);
-              idx = b + (int)__builtin_ctzll(hit);
-              break;
-            }
-            r -= cnt;
-          }
-        }
+        const int idx = search_untried(tab, hlog, node, n, nchild, rfl(__umulhi(de, u)), lane);
         if (idx < 0 || idx >= n) break;   // (cannot happen: u untried indices exist)
         uint64_t snib; uint32_t scat, svlv;
         ply_entry(okm, n0, idx, info, stage, svl, snib, scat, svlv);
@@ -248,29 +285,8 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
       const uint32_t N = rfl(sld32((const uint32_t*)(nr + 8)));
       const float two_ln = 2.0f * a.ln[N <= (uint32_t)DDZ_SEARCH_MAX_BUDGET ? N : (uint32_t)DDZ_SEARCH_MAX_BUDGET];
       const bool own = a.mode == (uint32_t)DDZ_SEARCH_SIDES ? same_side(role, role0) : (role == role0);
-      const bool take_max = own || a.mode == (uint32_t)DDZ_SEARCH_SIDES;
-      uint32_t best = 0, at = SEARCH_NONE, bchild = SEARCH_NONE;
-      for (int b = 0; b < n; b += 64) {
-        const int j = b + lane;
-        if (j < n) {
-          const uint32_t ch = search_find(tab, hlog, node * 512u + (uint32_t)j + 1u);
-          if (ch != SEARCH_NONE && ch < nnodes) {
-            const uint64_t vw = sld64((const uint64_t*)(nodes + (uint64_t)ch * NODE_BYTES + 8));
-            const uint32_t V = (uint32_t)vw, W = (uint32_t)(vw >> 32);
-            if (V > 0) {
-              // (values are non-negative floats: their bit patterns order as they do)
-              const uint32_t bits = __float_as_uint(search_value(own ? W : (a.mode == (uint32_t)DDZ_SEARCH_SIDES ? V - W : W), V, two_ln, a.c));
-              if (at == SEARCH_NONE || (take_max ? bits > best : bits < best)) { best = bits; at = (uint32_t)j; bchild = ch; }
-            }
-          }
-        }
-      }
-      uint32_t m;
-      if (take_max) m = (uint32_t)wave_max_i32(at == SEARCH_NONE ? (int)0x80000000 : (int)best);
-      else m = wave_min_u32(at == SEARCH_NONE ? 0xFFFFFFFFu : best);
-      const uint32_t first = wave_min_u32((at != SEARCH_NONE && best == m) ? at : SEARCH_NONE);   // ties: the lowest index
-      if (first == SEARCH_NONE) break;   // (cannot happen: a fully expanded node has n visited children)
-      const uint32_t child = rl(bchild, (int)(first & 63u));
+      const uint32_t child = search_select(nodes, tab, hlog, node, n, nnodes, two_ln, a.c, own, a.mode == (uint32_t)DDZ_SEARCH_SIDES, lane);
+      if (child == SEARCH_NONE) break;   // (cannot happen: a fully expanded node has n visited children)
       const uint8_t* cr = nodes + (uint64_t)child * NODE_BYTES;
       const uint64_t mv = sld64((const uint64_t*)cr);
       const uint32_t cmeta = sld32((const uint32_t*)(cr + 16));

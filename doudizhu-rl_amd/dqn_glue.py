@@ -1223,6 +1223,51 @@ class SeatLoop:
         return PolicyLoop.capture(self, n)
 
 
+class QLeaf:
+    """A leaf evaluator for engine.GuidedSearch.run (search spec v3): the value of a leaf is its actor's best Q.  The leaf rows
+    are imported into a scratch BatchedEnv of one table per item (made once), q of every legal move comes from the
+    shared-rows pass keyed by network slot (SeatLoop.q_values: the leaves of a search are near-duplicates, which is where
+    that pass is at its best), and ddz_guided_values turns the maximum into 1024ths: p = qmax / reward[role] is the expected
+    outcome in [-1, 1] for the actor's side, value = rint((p + 1) * 512) clamped.  nets: {"lord" | "down" | "up": QNet | None};
+    leaves whose actor has no network are left to `fallback` (another evaluator, e.g. engine.PlayoutLeaf), which is called
+    first; without one every role needs a network."""
+
+    def __init__(self, nets, face_variant, reward_dict=None, fallback=None):
+        _, self.net_of_role = role_slots(nets, face_variant)
+        if fallback is None and min(self.net_of_role) < 0:
+            missing = [r for r, s in zip(ROLE_ORDER, self.net_of_role) if s < 0]
+            raise ValueError(f"no network for {missing} and no fallback evaluator for their leaves")
+        rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
+        self.inv_reward = [1.0 / float(rd[r]) for r in ROLE_ORDER]
+        self.net_roles = sum(1 << k for k in range(3) if self.net_of_role[k] >= 0)
+        self.nets, self.variant, self.fallback = nets, int(face_variant), fallback
+        self.loop = None
+
+    def scratch(self, search):
+        from .engine import BatchedEnv
+        if self.loop is None or self.loop.env.T != search.n_items or self.loop.env.device != search.env.device:
+            env = BatchedEnv(search.n_items, seed=search.env.seed, device=search.env.device,
+                             native_joker_kickers=search.env.native_joker_kickers)
+            self.loop = SeatLoop(env, self.nets, self.variant, auto_reset=False)
+        return self.loop
+
+    def q_values(self, search):
+        """q f32 [n_items, stride] of the leaves' lists (valid where the leaf's actor has a network) and the scratch env"""
+        loop = self.scratch(search)
+        env = loop.env
+        env.state_import(search.leaves)
+        env.legal_slab()
+        env.observe(self.variant, out=loop.face)
+        return loop.q_values(), env
+
+    def __call__(self, search):
+        from .engine import guided_values
+        if self.fallback is not None:
+            self.fallback(search)
+        q, env = self.q_values(search)
+        return guided_values(search.leaves, env.counts, q, self.inv_reward, net_roles=self.net_roles, out=search.values)
+
+
 def _compete_net(x, face_variant, device, cache):
     """a compete() role entry: None, a QNet, or the path of a reference state dict (loaded weights_only)"""
     if x is None or isinstance(x, nn.Module):

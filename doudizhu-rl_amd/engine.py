@@ -821,6 +821,32 @@ class BatchedEnv:
                                          _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
         return out
 
+    # ---- UCT with leaf values from outside the kernel (search spec v3) ----
+    GUIDED_ONE = 1024
+
+    def guided(self, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111):
+        """Opens a guided UCT search on every running table (search spec v3): search()'s trees, but the score of
+        a new non-terminal leaf is a value the caller hands in instead of a playout's result, and one launch runs one
+        iteration of every (table, tree).  -> a GuidedSearch: step() it `budget` times, filling .values for the leaves
+        .need marks from the rows in .leaves between the steps, then close() it for (visits, wins); or run(evaluator).
+        Arguments as search(); budget * trees * 1024 must stay below 2^31.  THE ENVIRONMENT MUST NOT BE STEPPED, RESET OR
+        IMPORTED INTO BETWEEN guided() AND close(): every launch re-reads the root from the state.  One search at a time
+        per environment (they share the cached workspace): a second guided() before close() raises RuntimeError."""
+        if getattr(self, "_guided_pending", None) is not None:
+            raise RuntimeError("a guided search is open on this environment's workspace: close() it first")
+        return GuidedSearch(self, budget, trees, mode, c, salt, hidden, roles)
+
+    def guided_choose(self, evaluator, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111, out=None):
+        """The guided-UCT move of every table: int32 [T] canonical action ids, search_choose()'s rule (ddz_search_choose: the
+        first maximum of wins / visits, compared exactly) on guided(...).run(evaluator)'s root statistics; -1 where nothing
+        was visited.  Feed them to step_slab(mode=STEP_IDS)."""
+        self._need_ids("guided_choose")
+        out = self._ids_out(out)
+        v, w = self.guided(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles).run(evaluator)
+        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, _p(v), _p(w), _p(out),
+                                         _stream(self.device)))
+        return out
+
     # ---- the CFR endgame solver (CFR spec v1, DESIGN.md 4) ----
     CFR_STRIDE = 16
     CFR_MAX_ITERATIONS = 64
@@ -1023,6 +1049,130 @@ class BatchedEnv:
         self.state.copy_(state.to(self.device).view(-1))
         check(self.lib.ddz_invalidate(self._h))
         self._legal_fresh = self._slab_fresh = self._csr_fresh = False
+
+
+class GuidedSearch:
+    """One open guided UCT search of a BatchedEnv (search spec v3; BatchedEnv.guided makes it).  Item k =
+    t * trees + c is tree c of table t.
+      leaves  uint8 [T * trees, 11, 16]: after step(), the state row of every item's pending leaf (an all-zero row, dealt = 0,
+              where the item waits for nothing: a leaf environment that imports them freezes those)
+      need    int32 [T * trees]: 1 where the item waits for a value
+      values  int32 [T * trees], CALLER-FILLED between the steps: the chance in 1024ths that the side of the leaf's ACTOR
+              wins (clamped into [0, 1024] by the kernel; entries with need = 0 are not read)
+    step() backs up the previous step's leaves with `values` and runs one iteration; close() backs up the last ones and
+    returns (visits, wins) int32 [T, stride], wins in 1024ths.  Every call is one launch on the current stream, nothing on
+    the host: a whole run can be captured in a graph.  The environment must not change between guided() and close().
+    step() after close(), or a second close(), raises RuntimeError without touching the device."""
+
+    def __init__(self, env, budget, trees, mode, c, salt, hidden, roles):
+        self.env = env
+        self.roles = _roles_mask(roles, hidden)
+        self.hidden = bool(hidden)
+        self.budget, self.trees, self.c, self._visits, self._wins = env._search_args("guided needs", budget, trees, mode, c, None, None,
+                                                                                    None)
+        if self.budget * self.trees * env.GUIDED_ONE >= 1 << 31:
+            raise ValueError("budget * trees * 1024 must stay below 2^31 (the int32 root sums)")
+        self.mode, self.salt = env.SEARCH_MODES[mode], _salt(salt)
+        n = env.T * self.trees
+        self.n_items = n
+        self.leaves = torch.zeros((n, NFIELDS, ROW), dtype=torch.uint8, device=env.device)
+        self.need = torch.zeros(n, dtype=torch.int32, device=env.device)
+        self.values = torch.zeros(n, dtype=torch.int32, device=env.device)
+        self.steps = 0
+        self.closed = False
+        self._work = env._workspace("_guided_work", int(env.lib.ddz_guided_work_bytes(env.T, self.budget, self.trees)))
+        check(env.lib.ddz_guided_open(env._h, *self._common(), env.slab_stride, _p(self._work), self._work.numel(),
+                                      _stream(env.device)))
+        env._guided_pending = self
+
+    def _common(self):
+        return self.budget, self.trees, self.mode, self.c, self.salt, int(self.hidden), self.roles
+
+    def _values(self):
+        return self.env._arg(self.values, "values", torch.int32, numel=self.n_items)
+
+    def step(self):
+        """back up the pending leaves with .values, then one iteration of every item -> (leaves, need)"""
+        if self.closed:
+            raise RuntimeError("step() on a closed guided search")
+        env = self.env
+        values = self._values()
+        env._arg(self.leaves, "leaves", torch.uint8, numel=self.n_items * NFIELDS * ROW)
+        env._arg(self.need, "need", torch.int32, numel=self.n_items)
+        check(env.lib.ddz_guided_step(env._h, *self._common(), env.slab_stride, _p(values) if self.steps else None,
+                                      _p(self.leaves), _p(self.need), _p(self._work), self._work.numel(), _stream(env.device)))
+        self.steps += 1
+        return self.leaves, self.need
+
+    def close(self, totals=None):
+        """back up the last pending leaves -> (visits, wins) int32 [T, stride]; totals: int64 [4] on the device, +=
+        {moves applied, iterations run, iterations scored unfinished, nodes created}"""
+        if self.closed:
+            raise RuntimeError("close() on a closed guided search")
+        env = self.env
+        values = self._values()
+        env._totals(totals)
+        self._visits.zero_()
+        self._wins.zero_()
+        check(env.lib.ddz_guided_close(env._h, *self._common(), _p(values) if self.steps else None, env.slab_stride,
+                                       _p(self._visits), _p(self._wins), _p(totals), _p(self._work), self._work.numel(),
+                                       _stream(env.device)))
+        self.closed = True
+        env._guided_pending = None
+        return self._visits.view(env.T, env.slab_stride), self._wins.view(env.T, env.slab_stride)
+
+    def run(self, evaluator, totals=None):
+        """`budget` steps with evaluator(self) between them (it fills .values from .leaves / .need), then close()"""
+        for _ in range(self.budget):
+            self.step()
+            evaluator(self)
+        return self.close(totals)
+
+
+class PlayoutLeaf:
+    """A leaf evaluator for GuidedSearch.run: flat Monte Carlo from the leaf.  The leaf rows are imported into a scratch
+    BatchedEnv of one table per item (made once, with the searched environment's seed and table_id_base 0), playout(K) runs
+    there, and value = (max_j wins_j * 1024) // K: the best move's win rate for the leaf's actor, in integers.  No network."""
+
+    def __init__(self, n_playouts, salt=0, chunks=None):
+        self.K, self.salt, self.chunks = int(n_playouts), salt, chunks
+        self.env = None
+
+    def scratch(self, search):
+        if self.env is None or self.env.T != search.n_items or self.env.device != search.env.device:
+            self.env = BatchedEnv(search.n_items, seed=search.env.seed, device=search.env.device,
+                                  native_joker_kickers=search.env.native_joker_kickers)
+        return self.env
+
+    def __call__(self, search):
+        env = self.scratch(search)
+        env.state_import(search.leaves)
+        wins = env.playout(self.K, salt=self.salt, chunks=self.chunks, wins=getattr(env, "_playout_wins", None))
+        env._playout_wins = wins.view(-1)
+        search.values.copy_(torch.div(wins.amax(dim=1) * BatchedEnv.GUIDED_ONE, self.K, rounding_mode="floor"))
+        return search.values
+
+
+def guided_values(rows, counts, q, inv_reward, net_roles=0b111, out=None):
+    """ddz_guided_values: leaf values from a q slab.  rows uint8 [n, 176] leaf rows, counts int32 [n] list sizes, q f32
+    [n, stride]; for every running row whose actor's role is in net_roles, out[i] = clamp((int)rintf((max q[i, :counts[i]] *
+    inv_reward[role] + 1) * 512), 0, 1024) -- 512 for an empty list or a NaN -- and every other entry of `out` (int32 [n], made
+    zero-filled if None) stays as it is.  No host sync."""
+    dev = _require_gpu(rows.device)
+    n = counts.numel()
+    _chk(rows, "rows", torch.uint8, dev, numel=n * NFIELDS * ROW, why=" (176-byte rows)")
+    _chk(counts, "counts", torch.int32, dev, shape=(n,))
+    stride = q.numel() // n if n else 1
+    _chk(q, "q", torch.float32, dev, numel=n * stride, why=" ([n, stride])")
+    if out is None:
+        out = torch.zeros(n, dtype=torch.int32, device=dev)
+    else:
+        _chk(out, "out", torch.int32, dev, numel=n)
+    inv = (C.c_float * 3)(*[float(x) for x in inv_reward])
+    if n:
+        check(_lib.lib().ddz_guided_values(dev.index, _p(rows), _p(counts), _p(q), stride, n, inv, _roles_mask(net_roles, name="net_roles"),
+                                           _p(out), _stream(dev)))
+    return out
 
 
 def rows_to_onehot(rows):

@@ -220,6 +220,21 @@ def ismcts_act(payloads, budget, device="cuda:0", salt=0, seed=0, trees=None, mo
     return _id_cards(ids, dev)
 
 
+def guided_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, trees=None, mode="reference", c=0.7):
+    """Guided UCT for a batch of PLAIN serving payloads (no hand_card; one that is there is not read): every request is packed
+    by payloads_to_playout_state and searched by BatchedEnv.guided_choose in the hidden form (search spec v3: tree c on world
+    c of the cards the requester has not seen, `budget` iterations of one launch each, every new leaf judged by `evaluator`
+    -- engine.PlayoutLeaf, dqn_glue.QLeaf or any callable that fills search.values), and the root move with the best value
+    for the requester's side is returned -- per request a list of rank values 3..17 ([] = pass), or None where the request
+    has no move (a finished game).  ValueError where cur_cards, history and left do not add up to a deck."""
+    if not payloads:
+        return []
+    env, dev = _payload_env(payloads, True, device, seed)
+    ids = env.guided_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt, hidden=True).cpu().numpy()
+    _check_domain(env, "hidden-hand")
+    return _id_cards(ids, dev)
+
+
 def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=False):
     """The reference's final_card(payload) (server/CFR.py:520-538) for a batch of PLAIN serving payloads (no hand_card): every
     request is packed by payloads_to_playout_state, solved by BatchedEnv.cfr (CFR spec v1: `iterations` iterations of

@@ -7,6 +7,7 @@ them.  Prints both win rates from env.stats().
   python examples/flat_mc.py [--tables 1024] [--playouts 16] [--iterations 400] [--seed 0] [--hidden] [--match]
   python examples/flat_mc.py --search BUDGET [--trees 1] [--mode reference] [--tables 256] [--iterations 200]
   python examples/flat_mc.py --ismcts BUDGET [--trees 1] [--uct-trees 16] [--mode reference] [--tables 256] [--iterations 200]
+  python examples/flat_mc.py --guided BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 4] [--tables 256] [--iterations 200]
 
 --hidden: the playouts do not read the farmers' hands; they run on hands dealt anew, per playout number, from the cards the
 lord has not seen (playout spec v2, BatchedEnv.playout_choose(hidden=True, roles=0b010): only the lord's tables are
@@ -24,6 +25,12 @@ same number.  Both seats see all three hands.  Printed as the lord's win rate in
 on a fresh deal of the cards the lord has not seen, search spec v2) against the RULE farmers (env.auto_choose(0b101)) -- beside
 a determinized-UCT lord (search_choose(hidden=True)) with the same total iterations per move split over --uct-trees worlds, for
 example 1 x 1024 against 16 x 64.  Neither lord reads the farmers' hands; only the lord's tables are searched (roles=0b010).
+
+--guided BUDGET: a guided-UCT lord (BatchedEnv.guided_choose, search spec v3: --trees trees of BUDGET iterations on sampled
+hands, one launch per iteration, every new leaf judged by --leaf: `playout` = engine.PlayoutLeaf(--leaf-playouts), `q` =
+dqn_glue.QLeaf on an UNTRAINED network of face variant 3 for every role, which is not expected to win) against the RULE farmers
+-- beside the determinized-UCT lord of search_choose(hidden=True) at the same budget and trees against the same farmers.  The
+win rates are printed with their game counts; nothing in this repository's notes has measured them.
 
 The playouts are computed for every table on every iteration and used where the lord is to move (the other tables take -1 =
 the engine's random move): simple, and three times the work a loop that asks only for the lord's tables would do.
@@ -83,6 +90,29 @@ def hidden_match(pkg, a, dev, ismcts):
     return env.stats()
 
 
+def guided_match(pkg, a, dev, guided):
+    """the lord by guided UCT (guided=True) or by determinized UCT at the same budget and trees, both on sampled hands; the
+    farmers by the rule agent"""
+    env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
+    env.reset()
+    lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    if a.leaf == "q":
+        torch.manual_seed(a.seed)
+        net = pkg.dqn_glue.QNet(pkg.FACE_PLANES[3]).to(dev).eval()
+        leaf = pkg.QLeaf({"lord": net, "down": net, "up": net}, 3)
+    else:
+        leaf = pkg.PlayoutLeaf(a.leaf_playouts)
+    for it in range(a.iterations):
+        if guided:
+            leaf.salt = it
+            env.guided_choose(leaf, a.guided, trees=a.trees, mode=a.mode, salt=it, hidden=True, roles=0b010, out=lord)
+        else:
+            env.search_choose(a.guided, trees=a.trees, mode=a.mode, salt=it, hidden=True, roles=0b010, out=lord)
+        env.step_slab(torch.where(env.role == 1, lord, env.auto_choose(0b101)), pkg.STEP_IDS, auto_reset=True)
+    assert env.status() == 0
+    return env.stats()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", type=int, default=1024)
@@ -93,12 +123,26 @@ def main():
     ap.add_argument("--match", action="store_true", help="a hidden-playout lord against the rule farmers")
     ap.add_argument("--search", type=int, default=0, metavar="BUDGET", help="a UCT lord against flat Monte-Carlo farmers")
     ap.add_argument("--ismcts", type=int, default=0, metavar="BUDGET", help="an ISMCTS lord against the rule farmers")
-    ap.add_argument("--trees", type=int, default=1, help="--search / --ismcts: trees per table")
+    ap.add_argument("--guided", type=int, default=0, metavar="BUDGET", help="a guided-UCT lord against the rule farmers")
+    ap.add_argument("--leaf", default="playout", choices=("playout", "q"), help="--guided: the leaf evaluator")
+    ap.add_argument("--leaf-playouts", type=int, default=4, help="--guided --leaf playout: playouts per move of a leaf")
+    ap.add_argument("--trees", type=int, default=1, help="--search / --ismcts / --guided: trees per table")
     ap.add_argument("--uct-trees", type=int, default=16, help="--ismcts: worlds of the determinized-UCT lord beside it")
     ap.add_argument("--mode", default="reference", choices=("reference", "sides"), help="--search / --ismcts: the selection rule")
     a = ap.parse_args()
     pkg = importlib.import_module("doudizhu-rl_amd")
     dev = torch.device("cuda:0")
+    if a.guided:
+        t0 = time.perf_counter()
+        gd = guided_match(pkg, a, dev, True)
+        t1 = time.perf_counter()
+        uct = guided_match(pkg, a, dev, False)
+        t2 = time.perf_counter()
+        print(f"guided-UCT lord ({a.trees} x {a.guided} iterations, leaf {a.leaf}, mode {a.mode}) vs rule farmers: {rates(gd)}  "
+              f"[{(t1 - t0) / a.iterations * 1e3:.2f} ms per iteration at {a.tables} tables]")
+        print(f"determinized-UCT lord ({a.trees} x {a.guided} iterations) vs the same farmers: {rates(uct)}  "
+              f"[{(t2 - t1) / a.iterations * 1e3:.2f} ms per iteration]")
+        return
     if a.ismcts:
         t0 = time.perf_counter()
         ism = hidden_match(pkg, a, dev, True)

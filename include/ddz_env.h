@@ -452,6 +452,50 @@ int64_t ddz_ismcts_work_bytes(int64_t n_tables, int64_t budget, int64_t trees);
 int ddz_ismcts(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
                int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream);
 
+/* UCT with leaf values from outside the kernel: "search spec v3 (guided UCT)" (DESIGN.md 4).  Spec v1 with the playout lifted
+ * out: the score of a new non-terminal leaf is a value the caller hands in, so a network (or anything else) can judge the
+ * position.  Everything not named here is ddz_search's: nodes, n, budget and depth limits, both modes, ties, the LN table,
+ * the expansion draw (domain 6), root parallelism, `roles`, the hidden form on world c with status bit 6, status bit 1.
+ *   Unit: W counts in DDZ_GUIDED_ONE = 1024ths, V counts visits.  budget * trees * 1024 must stay below 2^31 (the int32 root
+ *     sums): a call that breaks this is DDZ_EINVAL, nothing launched.  Selection: mean = ((float)W / (float)V) * 2^-10, then
+ *     spec v1's operations; DDZ_SEARCH_SIDES uses V * 1024 - W where v1 uses V - W.
+ *   One launch = one iteration of every (table, tree).  Descend as in v1.  A node with untried indices: expand one child; if
+ *     the move empties a hand the child is terminal, scores 1024 when the winner is on the root actor's side, else 0, and is
+ *     backed up in the same launch; otherwise the child is a PENDING LEAF: its n is the size of its state's list, its state
+ *     row is written to leaf_rows[item], need[item] = 1, and the iteration waits.  A terminal node reached by selection is
+ *     scored and backed up at once.  A non-terminal node with n = 0, or DDZ_SEARCH_MAX_DEPTH below the root: score 0, unfinished.
+ *   Leaf value: values[item] (item = t * trees + c), the chance in 1024ths that the side of the LEAF's actor wins, clamped
+ *     into [0, 1024]; the score is v where the leaf's actor is on the root actor's side, else 1024 - v.  Backup (V += 1,
+ *     W += score on the path, the new node's record written whole) happens at the start of the next launch, or in close.
+ *   Leaf row: the 176 bytes ddz_step (no auto-reset) would hold after the path's moves: hands with their count bytes (the
+ *     world's for the opponents in the hidden form), histories, recent rows with category bytes, taken, meta (role, done 0,
+ *     winner 0xFF, last r 0, ply, the root's bytes 6..15).  Items that are idle, outside the domain, finished at once or past
+ *     their budget get an all-zero row (dealt = 0) and need 0.
+ *   ddz_guided_open: sizes the root list, zeroes table and header, writes node 0.  ddz_guided_step: values may be NULL on
+ *     the first step only; leaf_rows uint8 [T * trees][176], 16-byte aligned; need int32 [T * trees].  ddz_guided_close: backs
+ *     up the last pending leaf, then visits / wins [T * stride] += the V / W (1024ths) of the root's children summed over
+ *     trees, totals += {moves applied, iterations run, unfinished, nodes created}.  ddz_search_choose serves as the chooser.
+ *   work: >= ddz_guided_work_bytes(T, budget, trees) bytes, 16-byte aligned, the same buffer for open, every step and close;
+ *     per tree spec v1's nodes and table, a 64-byte header and the stored path.  The env is only read but must not change
+ *     between open and close (the root is re-read by every launch).  Argument checks and codes are ddz_search's; one launch
+ *     per call on `stream`, nothing on the host (capturable).
+ * ddz_guided_values: leaf values from a q slab, one wavefront per leaf: for every row of rows [n][176] that is running and
+ *   whose actor's role is in net_roles, values[i] = clamp((int)rintf((qmax * inv_reward[role] + 1) * 512), 0, 1024), qmax = the
+ *   maximum of q[i * stride .. + counts[i]), single fp32 operations; counts[i] = 0 or a NaN among them gives 512.  Other
+ *   entries of values are left as they are.  inv_reward: HOST float[3] in role order. */
+#define DDZ_GUIDED_ONE 1024
+int64_t ddz_guided_work_bytes(int64_t n_tables, int64_t budget, int64_t trees);
+int ddz_guided_open(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                    int64_t stride, void* work, int64_t work_bytes, void* stream);
+int ddz_guided_step(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                    int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need, void* work, int64_t work_bytes,
+                    void* stream);
+int ddz_guided_close(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                     const int32_t* values, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
+                     int64_t work_bytes, void* stream);
+int ddz_guided_values(int device_id, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
+                      const float* inv_reward, int net_roles, int32_t* values, void* stream);
+
 /* The CFR endgame solver: the reference's final_card (server/CFR.py: deal / initiate_game / VanillaCFR.run(8)), the engine
  * its predictor uses when the three hands hold 6 cards or fewer (server/core.py:88), batched.  "CFR spec v1" (DESIGN.md 4):
  * the reference's computation with everything it leaves to chance pinned.  Seats are the reference's player numbers, 0 lord /
