@@ -53,6 +53,11 @@ SYMBOLS = {
     "ddz_mc_before": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ddz_mc_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_void_p,
                                C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_void_p]),
+    "ddz_teach_ws_bytes": (C.c_int64, [C.c_int64]),
+    "ddz_teach_ws_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "ddz_teach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                            C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int64, C.c_int64,
+                            C.POINTER(C.c_float), C.c_void_p]),
     "ddz_state_prob": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_rows_to_onehot": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ddz_observe_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

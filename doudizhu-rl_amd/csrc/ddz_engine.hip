@@ -2608,6 +2608,7 @@ __global__ __launch_bounds__(BLOCK) void k_onehot(const uint8_t* __restrict__ ro
 
 #include "ddz_replay.h"
 #include "ddz_returns.h"  // (after ddz_replay.h: its block scan and its overflow rule)
+#include "ddz_teach.h"    // (after ddz_returns.h: its rings)
 #include "ddz_qtrain.h"   // (after face_cell: the learner's stage stages its x tile from packed state rows too)
 
 // ------------------------------------------------------------------------------------
@@ -3442,6 +3443,54 @@ int ddz_mc_after(ddz_env_t* e, void* ws, int64_t ws_bytes, int log_cap, void* co
   const McAfter af{{reward[0], reward[1], reward[2]}, gamma};
   hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((e->T + MC_BT - 1) / MC_BT)), dim3(BLOCK), 0, st, e->T, w, log_cap, rg, done,
                      r, af);
+  return check_launch();
+}
+
+int64_t ddz_teach_ws_bytes(int64_t T) { return T <= 0 || T > ((int64_t)1 << 30) ? DDZ_EINVAL : teach_ws_layout(T).bytes; }
+int ddz_teach_ws_layout(int64_t T, int64_t* offsets) {
+  if (!offsets || ddz_teach_ws_bytes(T) < 0) return DDZ_EINVAL;
+  const TeachWsLayout l = teach_ws_layout(T);
+  offsets[0] = l.rank; offsets[1] = l.blk; offsets[2] = l.hdr;
+  return DDZ_OK;
+}
+
+int ddz_teach(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t stride, const int32_t* num, const int32_t* den,
+              int32_t den_const, const int32_t* unknown, int32_t scale, int32_t min_den, const uint8_t* active, int trained_roles,
+              void* ws, int64_t ws_bytes, void* const* rings, int64_t ring_bytes, int64_t capacity, const float* reward,
+              void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!counts || !ids || !num || !ws || !rings || !reward) return DDZ_EINVAL;
+  if (!al(counts, 4) || !al(ids, 4) || !al(num, 4) || !al(den, 4) || !al(unknown, 4) || !al(ws, 16)) return DDZ_EINVAL;
+  if (stride < 1 || scale < 1 || scale > 1024 || min_den < 1 || (!den && den_const < 1) || (trained_roles & ~7)) return DDZ_EINVAL;
+  if (e->T * stride >= ((int64_t)1 << 31)) return DDZ_ECAP;
+  const int64_t rb = ddz_mc_ring_bytes(capacity);
+  if (rb < 0 || ring_bytes < rb) return DDZ_EINVAL;
+  if (ws_bytes < ddz_teach_ws_bytes(e->T)) return DDZ_ECAP;
+  McRings rg;
+  TrRings ring_counts{};            // what k_tr_scan reads of a ring: its count and the capacity
+  rg.cap = ring_counts.cap = capacity;
+  for (int k = 0; k < 3; ++k) {
+    if (!al(rings[k], 16)) return DDZ_EINVAL;
+    rg.r[k] = mc_ring_bind(rings[k], capacity);
+    ring_counts.r[k].count = rg.r[k].count;
+  }
+  DeviceGuard g(e->device);
+  if (!g.ok) return DDZ_ENODEV;
+  const TeachWsLayout l = teach_ws_layout(e->T);
+  uint8_t* p = (uint8_t*)ws;
+  const TeachWs w{(int32_t*)(p + l.rank), (int32_t*)(p + l.blk), (int64_t*)(p + l.hdr)};
+  const TeachArgs a{counts, ids, num, den, unknown, active, stride, den_const, scale, min_den, trained_roles,
+                    {reward[0], reward[1], reward[2]}};
+  const uint8_t* state = (const uint8_t*)e->state;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_teach_mark, dim3((unsigned)l.nb), dim3(TEACH_MARK_THREADS), 0, st, state, e->T, w, a);
+  int rc = check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, ring_counts);
+  rc = check_launch();
+  if (rc) return rc;
+  constexpr int TPB = BLOCK / 64;   // tables per block of k_teach_emit: a wavefront each
+  hipLaunchKernelGGL(k_teach_emit, dim3((unsigned)((e->T + TPB - 1) / TPB)), dim3(BLOCK), 0, st, state, e->T, w, rg, a);
   return check_launch();
 }
 

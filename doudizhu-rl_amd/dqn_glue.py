@@ -171,6 +171,56 @@ class ReturnAssembler:
         return out
 
 
+class TeacherAssembler:
+    """Teacher spec v1 (include/ddz_env.h: ddz_teach) on the host, as plain Python loops over the tables and the
+    moves of their lists: the statement the device pass (TeacherRecorder, csrc/ddz_teach.h) is tested against.  Move j of table
+    t's list becomes the target
+        ret = reward[k] * ((2 num - p) / p),   p = (den - unknown) * scale,   k = the table's role,
+    where the table is selected and den - unknown >= min_den: +reward[k] for a move that always wins, -reward[k] for one that
+    never does.  (2 num - p) and p are converted to f32 (round to nearest), divided in f32 and multiplied by the f32 reward."""
+
+    def __init__(self, reward_dict=None, trained_roles=(True, True, True)):
+        rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
+        self.reward = torch.tensor([float(rd.get(k) or 0.0) for k in ("up", "lord", "down")], dtype=torch.float32)
+        self.trained = [bool(x) for x in trained_roles]
+        if len(self.trained) != 3:
+            raise ValueError("trained_roles: (up, lord, down)")
+
+    def label(self, rows, counts, ids, num, den=None, den_const=None, unknown=None, scale=1, min_den=1, active=None):
+        """rows u8 [T,176] the state rows, counts int [T], ids / num / den / unknown int [T, stride] (den None: den_const for
+        every entry; unknown None: nothing subtracted), active bool [T] (None: all).  Returns the emits of the call in emit
+        order (ascending table, then ascending j; a ring takes those of its role in this order): {"s0" u8 [m,176], "a0" int32
+        [m], "ret" f32 [m], "table" int64 [m], "togo" int64 [m] (zeros), "role" int64 [m]}."""
+        scale, min_den = int(scale), int(min_den)
+        if not 1 <= scale <= 1024 or min_den < 1:
+            raise ValueError("scale must be in [1, 1024] and min_den at least 1")
+        if den is None and (den_const is None or int(den_const) < 1):
+            raise ValueError("den_const must be at least 1 where no den array is given")
+        rows = rows.cpu().view(-1, 176)
+        T = rows.shape[0]
+        counts = counts.cpu().view(T).tolist()
+        table = lambda x: None if x is None else x.cpu().view(T, -1).tolist()   # noqa: E731
+        ids, num, den, unknown = table(ids), table(num), table(den), table(unknown)
+        stride = len(num[0])
+        act = None if active is None else active.cpu().view(T).tolist()
+        role_byte = rows[:, 10 * 16].tolist()
+        ts, js, ks, top, bottom = [], [], [], [], []
+        for t in range(T):
+            k = role_byte[t]
+            if k > 2 or (act is not None and not act[t]) or not self.trained[k] or counts[t] <= 0:
+                continue
+            for j in range(min(counts[t], stride)):
+                d = (den[t][j] if den is not None else int(den_const)) - (unknown[t][j] if unknown is not None else 0)
+                if d < min_den:
+                    continue
+                p = d * scale
+                ts.append(t), js.append(j), ks.append(k), top.append(2 * num[t][j] - p), bottom.append(p)
+        t, k = torch.tensor(ts, dtype=torch.int64), torch.tensor(ks, dtype=torch.int64)
+        value = torch.tensor(top, dtype=torch.int64).to(torch.float32) / torch.tensor(bottom, dtype=torch.int64).to(torch.float32)
+        return {"s0": rows[t].clone(), "a0": torch.tensor([ids[a][b] for a, b in zip(ts, js)], dtype=torch.int32),
+                "ret": self.reward[k] * value, "table": t, "togo": torch.zeros_like(t), "role": k}
+
+
 def td_target(transitions, q_next, gamma=0.95):
     """y = r + (1 - done) * gamma * Q_target(s1, a1)  (dqn.py:40-41, config.py:8 GAMMA)."""
     return transitions["reward"] + (~transitions["done"]).float() * gamma * q_next.view(-1)
@@ -1602,6 +1652,42 @@ class ReturnRecorder(TransitionRecorder):
         return ReturnBatch(f["s0"], f["a0"], f["ret"], f["togo"], index, self._rows, variant)
 
 
+class TeacherRecorder(TransitionRecorder):
+    """TeacherAssembler + one return ring per trained role on the device (csrc/ddz_teach.h, teacher spec v1), for env's tables:
+    label(stats) turns the root statistics of one evaluator run (engine.Teacher.evaluate) into ring entries (state row, action
+    id, ret = reward[role] * (2 wins / visits - 1), table, togo 0) -- one per move of every selected table whose denominator
+    reaches min_den, not only the move that is played.  Nothing on the host, capturable.  The rings are ReturnRecorder's
+    (189 bytes an entry), and count / note_counts / draw / sample / sample_packed / decode / packed are its own: mc_step takes
+    the batches unchanged.  One call at many tables emits more than a small ring holds (a list has 1 to 497 moves): the ring
+    then takes the last `capacity` emits of the call, as both other recorders do."""
+
+    def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), min_den=1):
+        from . import engine as E
+        self._setup(env, capacity, reward_dict, trained_roles)
+        self.min_den = int(min_den)
+        if self.min_den < 1:
+            raise ValueError("min_den must be at least 1")
+        self.ws = torch.zeros(E.teach_ws_bytes(self.T), dtype=torch.uint8, device=self.device)     # (per-call scratch)
+        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity),
+                         (("s0", torch.uint8, 176), ("a0", torch.int32, 1), ("ret", torch.float32, 1), ("table", torch.int32, 1),
+                          ("togo", torch.uint8, 1)))
+
+    def before(self, *args, **kwargs):
+        raise TypeError("a TeacherRecorder has no before / after pair around the step: label(stats) is its one call")
+
+    after = before
+    decode, packed = ReturnRecorder.decode, ReturnRecorder.packed
+
+    def label(self, stats, active=None):
+        """on the states the evaluator ran on (before the step): stats = Teacher.evaluate(env)'s TeacherStats, active u8 / bool
+        [T] the tables to label (None: all).  Only roles that are trained here AND that the evaluator took are labelled."""
+        env = self.env
+        env._need_ids("TeacherRecorder.label")
+        env.teach(self.ws, self.rings, self.capacity, stats.num, stats.den, stats.den_const, stats.unknown, stats.scale,
+                  self.min_den, active, self.trained_mask & stats.roles, self.reward, counts=stats.counts, ids=env.ids,
+                  stride=env.slab_stride)
+
+
 class TrainLoop:
     """One iteration of Game.train's inner loop (game.py:90-167) for T tables, nothing on the host: SeatLoop.act() ->
     recorder.before on the network tables -> step_slab(STEP_IDS, no auto-reset) -> recorder.after -> re-deal of the finished
@@ -1609,12 +1695,24 @@ class TrainLoop:
     every role with a network trains): a network role that does not train plays greedy and records nothing (game.py:95-104).
     capture(n) records n iterations as one graph at the epsilon of the moment.  targets: "td" -- the recorder is a
     TransitionRecorder (one-step targets, td_step) -- or "mc" -- a ReturnRecorder(gamma, log_cap) (the episode's return,
-    mc_step): no greedy id is gathered, since no a1 is recorded."""
+    mc_step): no greedy id is gathered, since no a1 is recorded.
+    targets="teacher" (teacher spec v1): the recorder is a TeacherRecorder(min_den) and every label_every-th
+    iteration runs SeatLoop.act() -> stats = teacher.evaluate(env) -> rec.label(stats, active = the network tables) -- a target
+    for EVERY legal move of every network table of a trained role -- and, with act="teacher" (expert iteration), the ids of
+    the labelled tables are replaced by teacher.choose(env, stats) where it is >= 0 (the same statistics: no second search);
+    then the step, the re-deal, the lists and the faces as in the other modes.  No before / after pair, no greedy-id gather,
+    no target network; batches go to mc_step.  teacher: an engine.Teacher; whether it reads the opponents' hands (hidden) is
+    the caller's choice -- open-hand labels are legitimate for training, not for serving.  One label() at many tables emits
+    more than a small ring holds; the ring then takes the last `capacity` emits of the call, as both other recorders do.
+    capture(n) records the n iterations with their labelling pattern unrolled, so n must be a multiple of label_every."""
 
     def __init__(self, env, nets, face_variant, capacity=REPLAY_SIZE, epsilon=0.0, train_dict=None, reward_dict=None,
-                 replicate_reference_quirk=False, targets="td", gamma=None, log_cap=None):
-        if targets not in ("td", "mc"):
-            raise ValueError('targets: "td" or "mc"')
+                 replicate_reference_quirk=False, targets="td", gamma=None, log_cap=None, teacher=None, label_every=1, min_den=1,
+                 act="net"):
+        if targets not in ("td", "mc", "teacher"):
+            raise ValueError('targets: "td", "mc" or "teacher"')
+        _teacher_args(targets, teacher, label_every, min_den, act)
+        self.teacher, self.label_every, self.act, self._it = teacher, int(label_every), act, 0
         self.seat = SeatLoop(env, nets, face_variant, 0.0, auto_reset=False)
         nr = self.seat.rq.net_of_role
         td = {r: True for r in ROLE_ORDER} if train_dict is None else train_dict
@@ -1624,7 +1722,11 @@ class TrainLoop:
         self.trained = tuple(nr[k] >= 0 and bool(td.get(r)) for k, r in enumerate(ROLE_ORDER))
         self.env, self.variant = env, int(face_variant)
         self.targets = targets
-        if targets == "mc":
+        if targets == "teacher":
+            self.rec = TeacherRecorder(env, capacity, reward_dict, self.trained, min_den)
+            self._trained_of_role = torch.tensor(self.trained, dtype=torch.bool, device=env.device)
+            self._teacher_ids = torch.empty(env.T, dtype=torch.int32, device=env.device)
+        elif targets == "mc":
             self.rec = ReturnRecorder(env, capacity, reward_dict, self.trained, 1.0 if gamma is None else gamma, log_cap)
         else:
             self.rec = TransitionRecorder(env, capacity, reward_dict, self.trained, replicate_reference_quirk)
@@ -1645,7 +1747,17 @@ class TrainLoop:
         from .engine import STEP_IDS
         s, env = self.seat, self.env
         ids = s.act()
-        if self.targets == "mc":
+        if self.targets == "teacher":
+            if self._it % self.label_every == 0:
+                self._active.copy_(s.slot >= 0)
+                stats = self.teacher.evaluate(env)
+                self.rec.label(stats, self._active)
+                if self.act == "teacher":
+                    move = self.teacher.choose(env, stats, out=self._teacher_ids)
+                    labelled = self._active.bool() & self._trained_of_role[env.role.clamp(max=2).long()] & (env.role <= 2)
+                    ids.copy_(torch.where(labelled & (move >= 0), move, ids))
+            self._it += 1
+        elif self.targets == "mc":
             self._active.copy_(s.slot >= 0)
             self.rec.before(ids, self._active)
         else:
@@ -1653,7 +1765,8 @@ class TrainLoop:
             self._active.copy_(s.slot >= 0)
             self.rec.before(ids, self._greedy_ids, self._active)
         done, r, illegal = env.step_slab(ids, STEP_IDS, auto_reset=False)
-        self.rec.after(done, r)
+        if self.targets != "teacher":
+            self.rec.after(done, r)
         env.reset(mask=done)
         env.legal_slab()
         env.observe(self.variant, out=s.face)
@@ -1664,13 +1777,32 @@ class TrainLoop:
             self.step()
 
     def capture(self, n=1):
-        """n iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first)."""
+        """n iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first).  targets="teacher": the
+        labelling pattern of the n iterations is part of the graph, so n is a multiple of label_every."""
+        if self.targets == "teacher" and int(n) % self.label_every:
+            raise ValueError("capture(n) unrolls the labelling pattern: n must be a multiple of label_every")
         return PolicyLoop.capture(self, n)
+
+
+def _teacher_args(targets, teacher, label_every, min_den, act):
+    """the arguments of targets="teacher" (TrainLoop, train), checked before anything touches the device"""
+    from .engine import Teacher
+    if act not in ("net", "teacher"):
+        raise ValueError('act: "net" or "teacher"')
+    if targets != "teacher":
+        if teacher is not None or act != "net":
+            raise ValueError('teacher= and act="teacher" go with targets="teacher"')
+        return
+    if not isinstance(teacher, Teacher):
+        raise ValueError('targets="teacher" needs teacher=engine.Teacher(kind, ...)')
+    if int(label_every) < 1 or int(min_den) < 1:
+        raise ValueError("label_every and min_den must be at least 1")
 
 
 def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, tables=4096, seed=0, log_every=100,
           model_every=1000, book=None, model_dir=None, win_dir=None, device="cuda:0", check_every=8, capacity=REPLAY_SIZE,
-          begin=None, log=None, fused=False, batch_size=BATCH_SIZE, targets="td", gamma=None):
+          begin=None, log=None, fused=False, batch_size=BATCH_SIZE, targets="td", gamma=None, teacher=None, label_every=1,
+          min_den=1, act="net"):
     """Game.train (game.py:183-238) on the batched engine, the counterpart of compete(): nets {"lord" | "down" | "up": QNet |
     None (the rule agent)}, train_dict which network roles keep training (default: all of them), reward_dict as REWARD_DICT.
     Lock-step iterations of TrainLoop over `tables` tables until `episodes` episodes have finished; every iteration each
@@ -1685,7 +1817,10 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     without dropout.  Returns {"lord", "down", "up": wins, "episodes", "iterations", "loss": {role: last loss | None},
     "checkpoints": [paths]}.  targets="mc": the roles learn from Monte-Carlo return targets instead (ReturnRecorder, one mc_step
     per ready role and iteration, gamma None = 1.0 = Deep Monte Carlo): no target network exists and none is copied; everything
-    else, the returned keys included, is the same."""
+    else, the returned keys included, is the same.  targets="teacher": the roles learn from the root statistics of a search
+    (TrainLoop(targets="teacher", teacher=engine.Teacher(...), label_every, min_den, act): a target for every legal move of the
+    labelled tables; act="teacher" also plays the teacher's move there), again one mc_step per ready role and iteration and no
+    target network; the same returned keys."""
     import copy
     import time
     from . import metrics
@@ -1695,9 +1830,10 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
         raise ValueError("batch_size must be positive")
     if isinstance(fused, str) and fused not in ("stage", "packed"):
         raise ValueError('fused: False, True, "stage" or "packed"')
-    if targets not in ("td", "mc"):
-        raise ValueError('targets: "td" or "mc"')
-    mc = targets == "mc"
+    if targets not in ("td", "mc", "teacher"):
+        raise ValueError('targets: "td", "mc" or "teacher"')
+    _teacher_args(targets, teacher, label_every, min_den, act)
+    mc = targets != "td"                                             # (return rings and mc_step, no target network)
     nets = {r: v for r, v in nets.items()}
     for r, v in nets.items():
         if v is not None:
@@ -1706,7 +1842,8 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     env.reset()
     env.legal_slab()
     loop = TrainLoop(env, nets, face_variant, capacity=capacity, epsilon=epsilon_schedule(0), train_dict=train_dict,
-                     reward_dict=reward_dict, targets=targets, gamma=gamma)
+                     reward_dict=reward_dict, targets=targets, gamma=gamma, teacher=teacher, label_every=label_every,
+                     min_den=min_den, act=act)
     roles = [r for k, r in enumerate(ROLE_ORDER) if loop.trained[k]]
     if not roles:
         env.close()

@@ -5,6 +5,7 @@ PyTorch owns every buffer (state, scratch, CSR list, outputs); the HIP library
 (csrc/, C ABI include/ddz_env.h) is handed raw device pointers and the current stream.
 Nothing here computes game logic on the CPU, and nothing falls back to it.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -405,6 +406,56 @@ class BatchedEnv:
             raise ValueError("reward: three floats in role order up, lord, down")
         check(self.lib.ddz_mc_after(self._h, _p(ws), ws.numel(), int(log_cap), ptrs, nbytes, int(capacity), _p(done), _p(r),
                                     (C.c_float * 3)(*[float(x) for x in reward]), float(gamma), _stream(self.device)))
+
+    # ---- teacher targets (csrc/ddz_teach.h; dqn_glue.TeacherRecorder, Teacher below) ----
+    TEACH_REWARD = (50.0, 100.0, 50.0)       # dqn_glue.REWARD_DICT in role order
+
+    def teach(self, ws, rings, capacity, num, den=None, den_const=None, unknown=None, scale=1, min_den=1, active=None,
+              trained_roles=0b111, reward=TEACH_REWARD, counts=None, ids=None, stride=None):
+        """ddz_teach (teacher spec v1): every move j of every selected table's list whose denominator d = (den[t, j]
+        or den_const) - unknown[t, j] is at least min_den becomes an entry (state row, ids[t, j], ret = reward[role] *
+        (2 num[t, j] - d scale) / (d scale), table, togo 0) of the role's return ring -- the rings of mc_after, which
+        ReturnRecorder.sample / mc_step consume.  num / den / unknown int32 [T * stride] (den None: den_const for every entry;
+        unknown None: nothing subtracted), scale 1 or GUIDED_ONE for guided wins, active u8 / bool [T] or None (all tables),
+        trained_roles: bit r = role r.  ws: uint8, teach_ws_bytes(T) bytes of per-call scratch (nothing to initialise).
+        counts / ids / stride: the lists the statistics belong to (default: the env's own slab lists, which the caller made
+        current; stride goes with them).  Three launches on the current stream, nothing on the host: capturable."""
+        trained_roles = _roles_mask(trained_roles, name="trained_roles")
+        if (counts is None) != (ids is None) or (counts is None and stride is not None):
+            raise ValueError("counts, ids and stride describe one list layout: give all of them or none")
+        if counts is None:
+            self._need_ids("teach")
+            counts, ids, stride = self.counts, self.ids, self.slab_stride
+        stride = self.slab_stride if stride is None else int(stride)
+        if stride < 1 or self.T * stride > 0x7FFFFFFF:
+            raise ValueError("stride must be at least 1 and T * stride below 2^31")
+        scale, min_den = int(scale), int(min_den)
+        if not 1 <= scale <= 1024:
+            raise ValueError("scale must be in [1, 1024]")
+        if not 1 <= min_den <= 0x7FFFFFFF:
+            raise ValueError("min_den must be in [1, 2^31)")
+        if den is None and (den_const is None or not 1 <= int(den_const) <= 0x7FFFFFFF):
+            raise ValueError("den_const must be in [1, 2^31) where no den array is given")
+        n = self.T * stride
+        self._arg(counts, "counts", torch.int32, numel=self.T, pinned=self.host_mirror)
+        self._arg(ids, "ids", torch.int32, at_least=n)
+        self._arg(num, "num", torch.int32, numel=n, why=" ([T * stride])")
+        self._arg(den, "den", torch.int32, numel=n, why=" ([T * stride])", none_ok=True)
+        self._arg(unknown, "unknown", torch.int32, numel=n, why=" ([T * stride])", none_ok=True)
+        self._arg(ws, "ws", torch.uint8, at_least=teach_ws_bytes(self.T), why=" (teach_ws_bytes(T) bytes)")
+        if len(rings) != 3:
+            raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
+        nbytes = mc_ring_bytes(capacity)
+        for k, ring in enumerate(rings):
+            self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (mc_ring_bytes(capacity) bytes)", none_ok=True)
+        ptrs = (C.c_void_p * 3)(*[None if x is None else x.data_ptr() for x in rings])
+        if active is not None:
+            active = self._u8_arg(active, "active")
+        if len(reward) != 3:
+            raise ValueError("reward: three floats in role order up, lord, down")
+        check(self.lib.ddz_teach(self._h, _p(counts), _p(ids), stride, _p(num), _p(den), int(den_const or 0), _p(unknown), scale,
+                                 min_den, _p(active), trained_roles, _p(ws), ws.numel(), ptrs, nbytes, int(capacity),
+                                 (C.c_float * 3)(*[float(x) for x in reward]), _stream(self.device)))
 
     def select(self, q, epsilon=0.0, out=None):
         """greedy / epsilon-greedy choice per table from per-row values q (f32, CSR order of
@@ -1280,6 +1331,109 @@ def mc_ring_layout(capacity):
     if _lib.lib().ddz_mc_ring_layout(int(capacity), off) != 0:
         raise ValueError("capacity must be in 1 .. 2^30")
     return dict(zip(MC_RING_FIELDS, [int(x) for x in off]))
+
+
+def teach_ws_bytes(n_tables):
+    """bytes of ddz_teach's per-call scratch for n_tables tables (ddz_teach_ws_bytes; nothing in it has to be initialised)"""
+    n = int(_lib.lib().ddz_teach_ws_bytes(int(n_tables)))
+    if n < 0:
+        raise ValueError("n_tables must be in 1 .. 2^30")
+    return n
+
+
+TEACH_WS_REGIONS = ("rank", "blk", "hdr")
+
+
+def teach_ws_layout(n_tables):
+    """{region: byte offset} of ddz_teach's scratch (ddz_teach_ws_layout): rank int32 [T,4], blk int32 [nb,4], hdr int64 [8]"""
+    off = (C.c_int64 * 3)()
+    if _lib.lib().ddz_teach_ws_layout(int(n_tables), off) != 0:
+        raise ValueError("n_tables must be in 1 .. 2^30")
+    return dict(zip(TEACH_WS_REGIONS, [int(x) for x in off]))
+
+
+TeacherStats = collections.namedtuple("TeacherStats", "counts num den den_const unknown scale roles", defaults=(0b111,))
+TeacherStats.__doc__ = """What Teacher.evaluate hands BatchedEnv.teach (teacher spec v1): counts int32 [T] the list sizes the
+statistics belong to, num int32 [T * stride] the wins of the root actor's side per move, den int32 [T * stride] the visits per
+move or None with den_const the total per table, unknown int32 [T * stride] or None, scale the unit of num; roles: the mask of
+the roles whose tables the evaluator took (the others' statistics are all zero and must not be labelled).  Views of buffers
+cached on the env: the next evaluate() overwrites them."""
+
+
+class Teacher:
+    """One of the evaluators as a source of training targets and of moves (teacher spec v1): kind "playout"
+    (BatchedEnv.playout), "search", "ismcts", "guided" (BatchedEnv.guided(...).run(evaluator); needs evaluator=, e.g.
+    PlayoutLeaf or dqn_glue.QLeaf) or "solve"; the keyword arguments are the evaluator's own (n_playouts, budget, trees,
+    hidden, roles, salt, ...) and are passed through.  evaluate(env) runs the evaluator once on env's current states and
+    returns TeacherStats; choose(env, stats) turns THE SAME statistics into moves with the evaluator's own rule
+    (ddz_playout_choose / ddz_search_choose / ddz_solve_choose): no second search.  Nothing here touches the host, so both
+    can be captured.  hidden is the caller's choice: labels from open hands (hidden=False, what playout / search / solve
+    default to) are legitimate for training a network that only sees its own face, not for serving moves to a seat."""
+    KINDS = {"playout": ("playout", ("n_playouts",)), "search": ("search", ("budget",)), "ismcts": ("ismcts", ("budget",)),
+             "guided": ("guided", ("budget",)), "solve": ("solve", ())}
+    _BUFFERS = ("self", "wins", "visits", "totals", "out")
+
+    def __init__(self, kind, evaluator=None, **kwargs):
+        import inspect
+        if kind not in self.KINDS:
+            raise ValueError(f"kind is one of {', '.join(self.KINDS)}")
+        method, required = self.KINDS[kind]
+        allowed = [p for p in inspect.signature(getattr(BatchedEnv, method)).parameters if p not in self._BUFFERS]
+        bad = sorted(set(kwargs) - set(allowed))
+        if bad:
+            raise ValueError(f"{kind} takes {', '.join(allowed)}; not {', '.join(bad)}")
+        missing = [p for p in required if p not in kwargs]
+        if missing:
+            raise ValueError(f"{kind} needs {', '.join(missing)}")
+        if (kind == "guided") != (evaluator is not None):
+            raise ValueError("evaluator= is the leaf evaluator of kind \"guided\", and of no other kind")
+        self.kind, self.evaluator, self.kwargs = kind, evaluator, dict(kwargs)
+        hidden = kind == "ismcts" or bool(kwargs.get("hidden", False))
+        self.roles = _roles_mask(kwargs.get("roles", 0b111), hidden)
+
+    def evaluate(self, env):
+        """run the evaluator on env's current states -> TeacherStats (the slab lists are made current by the evaluator)"""
+        kw, kind = self.kwargs, self.kind
+        if kind == "playout":
+            wins = env.playout(wins=getattr(env, "_playout_wins", None), **kw)
+            env._playout_wins = wins
+            return TeacherStats(env.counts, wins.view(-1), None, int(kw["n_playouts"]), None, 1, self.roles)
+        if kind == "solve":
+            solved = env.solve(out=getattr(env, "_solve_out", None), **kw)
+            env._solve_out = n, wins, unknown = tuple(x.view(-1) for x in solved)
+            # its own n as the list sizes: a table that is no endgame (n <= 0) emits nothing
+            return TeacherStats(n, wins, None, int(kw.get("worlds", 1)), unknown, 1, self.roles)
+        if kind == "guided":
+            v, w = env.guided(**kw).run(self.evaluator)
+            return TeacherStats(env.counts, w.view(-1), v.view(-1), None, None, BatchedEnv.GUIDED_ONE, self.roles)
+        run = env.search if kind == "search" else env.ismcts
+        v, w = run(visits=getattr(env, "_search_visits", None), wins=getattr(env, "_search_wins", None), **kw)
+        env._search_visits, env._search_wins = v.view(-1), w.view(-1)
+        return TeacherStats(env.counts, env._search_wins, env._search_visits, None, None, 1, self.roles)
+
+    def choose(self, env, stats, out=None):
+        """the evaluator's move of every table from stats (evaluate()'s, of env's current states): int32 [T] canonical action
+        ids, -1 where the teacher has none -- idle tables, nothing visited, and the tables the evaluator left out (a role
+        outside `roles`, or for "solve" a table that is no endgame).  Feed them to step_slab(mode=STEP_IDS) where >= 0."""
+        env._need_ids("Teacher.choose")
+        out = env._ids_out(out)
+        h, counts, ids, st, s = env._h, env._pp["counts"], env._pp["ids"], env.slab_stride, _stream(env.device)
+        if self.kind == "playout":
+            check(env.lib.ddz_playout_choose(h, counts, ids, st, _p(stats.num), _p(out), s))
+        elif self.kind == "solve":
+            value = getattr(env, "_teach_value", None)
+            if value is None:
+                value = env._teach_value = torch.empty(env.T, dtype=torch.int32, device=env.device)
+            check(env.lib.ddz_solve_choose(h, counts, ids, st, int(stats.den_const), _p(stats.num), _p(stats.unknown), _p(out),
+                                           _p(value), s))
+            out.copy_(torch.where(stats.counts > 0, out, -1))
+        else:
+            check(env.lib.ddz_search_choose(h, counts, ids, st, _p(stats.den), _p(stats.num), _p(out), s))
+        if stats.roles != 0b111:
+            role = env.role.clamp(max=2).int()
+            taken = (torch.full_like(role, stats.roles) >> role) & 1
+            out.copy_(torch.where(taken.bool(), out, -1))
+        return out
 
 
 def state_prob(known60, size1, size2, device="cuda:0"):
