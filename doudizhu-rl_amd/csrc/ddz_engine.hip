@@ -3340,6 +3340,32 @@ int tr_args(const ddz_env* e, void* ws, int64_t ws_bytes, void* const* rings, in
   return DDZ_OK;
 }
 
+// the chain every recorder call ends in, a launch check after each link: mark() leaves the emits of each 256-block in w.blk,
+// k_tr_scan turns them into places behind the rings' counts (`counts`: all it reads of a ring), emit() stores the entries
+template <class Mark, class Emit>
+int mark_scan_emit(hipStream_t st, const TrWs& w, int64_t nb, const TrRings& counts, Mark mark, Emit emit) {
+  mark();
+  int rc = check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, w, nb, counts);
+  rc = check_launch();
+  if (rc) return rc;
+  emit();
+  return check_launch();
+}
+
+// binds the three return rings (null: that role's entries are dropped) and what k_tr_scan reads of them; false: one is misaligned
+bool mc_rings_bind(void* const* rings, int64_t capacity, McRings* rg, TrRings* counts) {
+  *counts = TrRings{};
+  rg->cap = counts->cap = capacity;
+  for (int k = 0; k < 3; ++k) {
+    if (!al(rings[k], 16)) return false;
+    rg->r[k] = mc_ring_bind(rings[k], capacity);
+    counts->r[k].count = rg->r[k].count;
+  }
+  return true;
+}
+
 template <bool AFTER>
 int tr_launch(ddz_env* e, void* ws, const TrRings& rings, const uint8_t* gate, int trained, const int32_t* chosen,
               const int32_t* greedy, const int8_t* r, TrAfter af, hipStream_t st) {
@@ -3348,15 +3374,12 @@ int tr_launch(ddz_env* e, void* ws, const TrRings& rings, const uint8_t* gate, i
   const TrWsLayout l = tr_ws_layout(e->T);
   const TrWs w = tr_bind(ws, l);
   const uint8_t* state = (const uint8_t*)e->state;
-  hipLaunchKernelGGL((k_tr_mark<AFTER>), dim3((unsigned)l.nb), dim3(TR_BT), 0, st, state, e->T, w, gate, trained);
-  int rc = check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, w, l.nb, rings);
-  rc = check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_tr_emit<AFTER>), dim3((unsigned)((e->T * 16 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, e->T, w,
-                     rings, chosen, greedy, r, af);
-  return check_launch();
+  return mark_scan_emit(st, w, l.nb, rings, [&] {
+    hipLaunchKernelGGL((k_tr_mark<AFTER>), dim3((unsigned)l.nb), dim3(TR_BT), 0, st, state, e->T, w, gate, trained);
+  }, [&] {
+    hipLaunchKernelGGL((k_tr_emit<AFTER>), dim3((unsigned)((e->T * 16 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, state, e->T, w,
+                       rings, chosen, greedy, r, af);
+  });
 }
 }  // namespace
 
@@ -3422,28 +3445,20 @@ int ddz_mc_after(ddz_env_t* e, void* ws, int64_t ws_bytes, int log_cap, void* co
   if (!ws || !rings || !al(ws, 16) || need < 0 || ws_bytes < need || rb < 0 || ring_bytes < rb) return DDZ_EINVAL;
   if (!done || !r || !reward) return DDZ_EINVAL;
   McRings rg;
-  TrRings counts{};                 // what k_tr_scan reads of a ring: its count and the capacity
-  rg.cap = counts.cap = capacity;
-  for (int k = 0; k < 3; ++k) {
-    if (!al(rings[k], 16)) return DDZ_EINVAL;
-    rg.r[k] = mc_ring_bind(rings[k], capacity);
-    counts.r[k].count = rg.r[k].count;
-  }
+  TrRings counts;
+  if (!mc_rings_bind(rings, capacity, &rg, &counts)) return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   const McWsLayout l = mc_ws_layout(e->T, log_cap);
   const McWs w = mc_bind(ws, l);
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_mc_mark, dim3((unsigned)l.nb), dim3(TR_BT), 0, st, e->T, w, log_cap, done);
-  int rc = check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, counts);
-  rc = check_launch();
-  if (rc) return rc;
   const McAfter af{{reward[0], reward[1], reward[2]}, gamma};
-  hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((e->T + MC_BT - 1) / MC_BT)), dim3(BLOCK), 0, st, e->T, w, log_cap, rg, done,
-                     r, af);
-  return check_launch();
+  return mark_scan_emit(st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, counts, [&] {
+    hipLaunchKernelGGL(k_mc_mark, dim3((unsigned)l.nb), dim3(TR_BT), 0, st, e->T, w, log_cap, done);
+  }, [&] {
+    hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((e->T + MC_BT - 1) / MC_BT)), dim3(BLOCK), 0, st, e->T, w, log_cap, rg, done,
+                       r, af);
+  });
 }
 
 int64_t ddz_teach_ws_bytes(int64_t T) { return T <= 0 || T > ((int64_t)1 << 30) ? DDZ_EINVAL : teach_ws_layout(T).bytes; }
@@ -3467,13 +3482,8 @@ int ddz_teach(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t s
   if (rb < 0 || ring_bytes < rb) return DDZ_EINVAL;
   if (ws_bytes < ddz_teach_ws_bytes(e->T)) return DDZ_ECAP;
   McRings rg;
-  TrRings ring_counts{};            // what k_tr_scan reads of a ring: its count and the capacity
-  rg.cap = ring_counts.cap = capacity;
-  for (int k = 0; k < 3; ++k) {
-    if (!al(rings[k], 16)) return DDZ_EINVAL;
-    rg.r[k] = mc_ring_bind(rings[k], capacity);
-    ring_counts.r[k].count = rg.r[k].count;
-  }
+  TrRings ring_counts;
+  if (!mc_rings_bind(rings, capacity, &rg, &ring_counts)) return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
   const TeachWsLayout l = teach_ws_layout(e->T);
@@ -3483,15 +3493,12 @@ int ddz_teach(ddz_env_t* e, const int32_t* counts, const int32_t* ids, int64_t s
                     {reward[0], reward[1], reward[2]}};
   const uint8_t* state = (const uint8_t*)e->state;
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_teach_mark, dim3((unsigned)l.nb), dim3(TEACH_MARK_THREADS), 0, st, state, e->T, w, a);
-  int rc = check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(TR_BT), 0, st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, ring_counts);
-  rc = check_launch();
-  if (rc) return rc;
   constexpr int TPB = BLOCK / 64;   // tables per block of k_teach_emit: a wavefront each
-  hipLaunchKernelGGL(k_teach_emit, dim3((unsigned)((e->T + TPB - 1) / TPB)), dim3(BLOCK), 0, st, state, e->T, w, rg, a);
-  return check_launch();
+  return mark_scan_emit(st, TrWs{nullptr, nullptr, nullptr, w.blk, w.hdr}, l.nb, ring_counts, [&] {
+    hipLaunchKernelGGL(k_teach_mark, dim3((unsigned)l.nb), dim3(TEACH_MARK_THREADS), 0, st, state, e->T, w, a);
+  }, [&] {
+    hipLaunchKernelGGL(k_teach_emit, dim3((unsigned)((e->T + TPB - 1) / TPB)), dim3(BLOCK), 0, st, state, e->T, w, rg, a);
+  });
 }
 
 int ddz_state_prob(int device, const uint8_t* known60, const int32_t* sizes, int64_t n, float* out, void* stream) {

@@ -863,7 +863,32 @@ def ragged_q(net, face, rows, offsets):
     return fq.q_csr(fq.tables(face), rows, offsets)
 
 
-class PolicyLoop:
+class _Loop:
+    """run(n) and capture(n) of a loop that has step(), env and no host synchronisation in an iteration"""
+
+    def run(self, n):
+        for _ in range(int(n)):
+            self.step()
+
+    def capture(self, n=1):
+        """n lock-step iterations as ONE hipGraph (the loop has no host synchronisation and no size-dependent shape):
+        returns the torch.cuda.CUDAGraph; every .replay() runs the n iterations on the state the previous ones left (states,
+        faces, choices, q values: bit for bit what n eager step() calls give -- tests/test_gpu_qnet.py).  Call step() a few
+        times first (workspaces allocated, libraries warm).  An iteration is ~30 short launches: the replay removes the host's
+        share of the gaps between them."""
+        dev = self.env.device
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                self.run(n)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        return g
+
+
+class PolicyLoop(_Loop):
     """game.py:95-104 for T tables with a Q-network on every seat, one lock-step iteration per step(), no per-table work on
     the host:
         face -> Q of every legal move of every table (slab layout) -> ddz_policy_step_slab (epsilon-greedy arg-max + apply +
@@ -922,27 +947,6 @@ class PolicyLoop:
         done, r, illegal, _ = self.env.policy_step_slab(q, self.epsilon, face_variant=self.variant, face_out=self.face,
                                                         choice_out=self.choice, auto_reset=self.auto_reset, traj=traj)
         return done, r, illegal
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-
-    def capture(self, n=1):
-        """n lock-step iterations as ONE hipGraph (the loop has no host synchronisation and no size-dependent shape):
-        returns the torch.cuda.CUDAGraph; every .replay() runs the n iterations on the state the previous ones left (states,
-        faces, choices, q values: bit for bit what n eager step() calls give -- tests/test_gpu_qnet.py).  Call step() a few
-        times first (workspaces allocated, libraries warm).  An iteration is ~30 short launches: the replay removes the host's
-        share of the gaps between them."""
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self.run(n)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        return g
 
     def profile(self, n=10):
         """Per-stage device time of n iterations: FactorisedQ.needed itself, issued through its stage hook with HIP events on the
@@ -1178,7 +1182,7 @@ class RolesU:
         self.h0, self.d, self.row_index, self.seg, self.slot = h0, d, row_index, seg, slot
 
 
-class SeatLoop:
+class SeatLoop(_Loop):
     """game.py:95-106 for T tables with a network or the rule agent per role, one lock-step iteration per step():
         act():   RoleQ's pass over the network tables -> greedy choice (ddz_select_slab) and, with epsilon per role, the
                  epsilon-greedy choice (trained roles explore, game.py:95-104) -> the rule agent's move for the roles mapped to
@@ -1190,13 +1194,7 @@ class SeatLoop:
 
     def __init__(self, env, nets, face_variant, epsilon=0.0, auto_reset=True):
         self.rq = RoleQ(nets, face_variant)
-        if isinstance(epsilon, dict):
-            bad = set(epsilon) - set(ROLE_ORDER)
-            if bad:
-                raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
-            eps = [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
-        else:
-            eps = [float(epsilon)] * 3
+        eps = self._eps_arg(epsilon)
         self.env, self.variant, self.auto_reset = env, int(face_variant), bool(auto_reset)
         nr = self.rq.net_of_role
         self.eps = [e if nr[k] >= 0 else 0.0 for k, e in enumerate(eps)]
@@ -1212,6 +1210,16 @@ class SeatLoop:
         self.slot = None
         if not env._slab_fresh:
             env.legal_slab()
+
+    @staticmethod
+    def _eps_arg(epsilon):
+        """a float for every role, or {"lord" | "down" | "up": float}, in role order"""
+        if not isinstance(epsilon, dict):
+            return [float(epsilon)] * 3
+        bad = set(epsilon) - set(ROLE_ORDER)
+        if bad:
+            raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
+        return [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
 
     def q_values(self):
         """q [T, stride] of the current lists for the network tables (valid in [t, :counts[t]] where slot[t] >= 0)"""
@@ -1239,13 +1247,7 @@ class SeatLoop:
     def set_epsilon(self, epsilon):
         """new exploration rates (a float for every network role, or {"lord" | "down" | "up": float}) for the next act(); a host
         value, as in __init__: a captured graph keeps the rates it was captured with"""
-        if isinstance(epsilon, dict):
-            bad = set(epsilon) - set(ROLE_ORDER)
-            if bad:
-                raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
-            eps = [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
-        else:
-            eps = [float(epsilon)] * 3
+        eps = self._eps_arg(epsilon)
         nr = self.rq.net_of_role
         self.eps = [e if nr[k] >= 0 else 0.0 for k, e in enumerate(eps)]
         self._eps_of_role.copy_(torch.tensor(self.eps, dtype=torch.float32))
@@ -1264,13 +1266,6 @@ class SeatLoop:
         self.act()
         return self.apply(traj)
 
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
-
-    def capture(self, n=1):
-        """n lock-step iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first)."""
-        return PolicyLoop.capture(self, n)
 
 
 class QLeaf:
@@ -1473,26 +1468,13 @@ def _role_id(role):
     return int(role)
 
 
-class TransitionRecorder:
-    """TransitionAssembler + one Replay per role (dqn.py:14) on the device, for env's tables: before() / after() around the
-    step of a lock-step iteration (ddz_tr_before / ddz_tr_after: same semantics as before_step / after_step, the `fresh` rule,
-    trained_roles, the active mask and replicate_reference_quirk included), nothing on the host, capturable.  A role's ring
-    holds `capacity` packed transitions (369 bytes each: any face variant is rebuilt from them, bit for bit, by decode());
-    the transition with sequence number s is entry s % capacity, in the order Replay.push would have stored the same calls
-    (per call: ascending table).  trained_roles: (up, lord, down); only they get a ring."""
-
-    def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), replicate_reference_quirk=False):
-        from . import engine as E
-        self._setup(env, capacity, reward_dict, trained_roles)
-        self.quirk = bool(replicate_reference_quirk)
-        self.ws = torch.zeros(E.tr_ws_bytes(self.T), dtype=torch.uint8, device=self.device)
-        self._make_rings(E.tr_ring_bytes(self.capacity), E.tr_ring_layout(self.capacity),
-                         (("s0", torch.uint8, 176), ("s1", torch.uint8, 176), ("a0", torch.int32, 1), ("a1", torch.int32, 1),
-                          ("reward", torch.float32, 1), ("table", torch.int32, 1), ("done", torch.uint8, 1)))
+class _Recorder:
+    """What every recorder of env's tables shares, whatever its rings hold: the device, the rewards and trained roles in role
+    order, the action table, a ring per trained role, the host-known counts, the draws.  A recorder adds its workspace `ws`,
+    decode / packed of its entries and around_step(loop, ids, step): what a TrainLoop does with it around step() -> its result."""
+    target_network = False     # whether its batches are learnt against a target network (td_step) or alone (mc_step)
 
     def _setup(self, env, capacity, reward_dict, trained_roles):
-        """what every recorder of env's tables keeps, whatever its rings hold: the device, the rewards and trained roles in role
-        order, the action table and the host-known counts"""
         from . import engine as E
         self.device = E._require_gpu(env.device)          # (DdzError without a GPU, as BatchedEnv)
         rd = dict(REWARD_DICT if reward_dict is None else reward_dict)
@@ -1526,20 +1508,15 @@ class TransitionRecorder:
     def ws_bytes_per_table(self):
         return self.ws.numel() / self.T
 
-    def before(self, chosen_ids, greedy_ids, active=None):
-        """before the step: chosen_ids / greedy_ids int32 [T] canonical ids of what every table plays and of its greedy action
-        (a1 of the closing transition), active u8 / bool [T] the tables that move by a network (None: all)"""
-        self.env.tr_before(self.ws, self.rings, self.capacity, chosen_ids, greedy_ids, active, self.trained_mask)
-
-    def after(self, done, r):
-        """after step(auto_reset=False), before the re-deal: done u8 [T], r i8 [T] as the step returned them"""
-        self.env.tr_after(self.ws, self.rings, self.capacity, done, r, self.reward, self.quirk)
-
     def _ring(self, role):
         f = self.fields[_role_id(role)]
         if f is None:
             raise ValueError(f"role {role!r} is not trained: it has no ring")
         return f
+
+    def _index(self, index):
+        """ring entries as an int64 [n] device tensor, clamped into the ring"""
+        return index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
 
     def count(self, role):
         """transitions ever written into the role's ring: a 0-dim int64 DEVICE tensor (a view: it moves with the recorder)"""
@@ -1551,18 +1528,6 @@ class TransitionRecorder:
                          for f in self.fields]).tolist()
         self.known = [int(x) for x in c]
         return self.known
-
-    def decode(self, role, index, variant):
-        """the dict Replay.sample returns -- s0, s1 f32 [n,P,15,4], a0, a1 f32 [n,15,4], reward f32 [n], done bool [n] -- of
-        the ring entries index (int64 [n] device tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
-        from . import engine as E
-        f = self._ring(role)
-        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
-        na = self._rows.shape[0]
-        thermo = lambda ids: E.rows_to_onehot(self._rows[ids[index].clamp(0, na - 1).long()])   # noqa: E731
-        return {"s0": E.observe_states(f["s0"], index, variant), "a0": thermo(f["a0"]),
-                "s1": E.observe_states(f["s1"], index, variant), "a1": thermo(f["a1"]),
-                "reward": f["reward"][index], "done": f["done"][index].bool()}
 
     def draw(self, role, k, at_least=None):
         """int64 [k] device tensor: k entries drawn uniformly (with replacement, as Replay.sample) from the role's
@@ -1581,26 +1546,94 @@ class TransitionRecorder:
         """decode() of draw(role, k, at_least): the batch as faces and thermometers"""
         return self.decode(role, self.draw(role, k, at_least), variant)
 
-    def packed(self, role, index, variant):
-        """the PackedBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
-        ring, nothing decoded, nothing copied but the index.  No host sync."""
-        f = self._ring(role)
-        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
-        return PackedBatch(f["s0"], f["s1"], f["a0"], f["a1"], f["reward"], f["done"], index, self._rows, variant)
-
     def sample_packed(self, role, k, variant, at_least=None):
         """packed() of draw(role, k, at_least): the batch sample() would decode for the same RNG state, left packed"""
         return self.packed(role, self.draw(role, k, at_least), variant)
 
 
+class TransitionRecorder(_Recorder):
+    """TransitionAssembler + one Replay per role (dqn.py:14) on the device, for env's tables: before() / after() around the
+    step of a lock-step iteration (ddz_tr_before / ddz_tr_after: same semantics as before_step / after_step, the `fresh` rule,
+    trained_roles, the active mask and replicate_reference_quirk included), nothing on the host, capturable.  A role's ring
+    holds `capacity` packed transitions (369 bytes each: any face variant is rebuilt from them, bit for bit, by decode());
+    the transition with sequence number s is entry s % capacity, in the order Replay.push would have stored the same calls
+    (per call: ascending table).  trained_roles: (up, lord, down); only they get a ring."""
+    target_network = True
+
+    def __init__(self, env, capacity, reward_dict=None, trained_roles=(True, True, True), replicate_reference_quirk=False):
+        from . import engine as E
+        self._setup(env, capacity, reward_dict, trained_roles)
+        self.quirk = bool(replicate_reference_quirk)
+        self.ws = torch.zeros(E.tr_ws_bytes(self.T), dtype=torch.uint8, device=self.device)
+        self._make_rings(E.tr_ring_bytes(self.capacity), E.tr_ring_layout(self.capacity),
+                         (("s0", torch.uint8, 176), ("s1", torch.uint8, 176), ("a0", torch.int32, 1), ("a1", torch.int32, 1),
+                          ("reward", torch.float32, 1), ("table", torch.int32, 1), ("done", torch.uint8, 1)))
+
+    def before(self, chosen_ids, greedy_ids, active=None):
+        """before the step: chosen_ids / greedy_ids int32 [T] canonical ids of what every table plays and of its greedy action
+        (a1 of the closing transition), active u8 / bool [T] the tables that move by a network (None: all)"""
+        self.env.tr_before(self.ws, self.rings, self.capacity, chosen_ids, greedy_ids, active, self.trained_mask)
+
+    def after(self, done, r):
+        """after step(auto_reset=False), before the re-deal: done u8 [T], r i8 [T] as the step returned them"""
+        self.env.tr_after(self.ws, self.rings, self.capacity, done, r, self.reward, self.quirk)
+
+    def around_step(self, loop, ids, step):
+        """the greedy ids of the network tables gathered into loop._greedy_ids, before(), the step, after()"""
+        loop._greedy_ids.copy_(self.env.slab_ids().gather(1, loop.seat.greedy.clamp(min=0).long()[:, None])[:, 0])
+        loop._active.copy_(loop.seat.slot >= 0)
+        self.before(ids, loop._greedy_ids, loop._active)
+        done, r, illegal = step()
+        self.after(done, r)
+        return done, r, illegal
+
+    def decode(self, role, index, variant):
+        """the dict Replay.sample returns -- s0, s1 f32 [n,P,15,4], a0, a1 f32 [n,15,4], reward f32 [n], done bool [n] -- of
+        the ring entries index (int64 [n] device tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
+        from . import engine as E
+        f, index = self._ring(role), self._index(index)
+        na = self._rows.shape[0]
+        thermo = lambda ids: E.rows_to_onehot(self._rows[ids[index].clamp(0, na - 1).long()])   # noqa: E731
+        return {"s0": E.observe_states(f["s0"], index, variant), "a0": thermo(f["a0"]),
+                "s1": E.observe_states(f["s1"], index, variant), "a1": thermo(f["a1"]),
+                "reward": f["reward"][index], "done": f["done"][index].bool()}
+
+    def packed(self, role, index, variant):
+        """the PackedBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
+        ring, nothing decoded, nothing copied but the index.  No host sync."""
+        f = self._ring(role)
+        return PackedBatch(f["s0"], f["s1"], f["a0"], f["a1"], f["reward"], f["done"], self._index(index), self._rows, variant)
+
+
 MAX_DECISIONS_PER_ROLE = 54   # the longest game has 162 plies and the three roles take turns: a role acts at most 162 / 3 times
 
 
-class ReturnRecorder(TransitionRecorder):
+class _ReturnRings(_Recorder):
+    """a recorder whose rings hold return entries (csrc/ddz_returns.h's McRing): mc_step takes its batches"""
+    RING_FIELDS = (("s0", torch.uint8, 176), ("a0", torch.int32, 1), ("ret", torch.float32, 1), ("table", torch.int32, 1),
+                   ("togo", torch.uint8, 1))
+
+    def decode(self, role, index, variant):
+        """{"s0" f32 [n,P,15,4], "a0" f32 [n,15,4], "ret" f32 [n], "togo" u8 [n]} of the ring entries index (int64 [n] device
+        tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
+        from . import engine as E
+        f, index = self._ring(role), self._index(index)
+        ids = f["a0"][index].clamp(0, self._rows.shape[0] - 1).long()
+        return {"s0": E.observe_states(f["s0"], index, variant), "a0": E.rows_to_onehot(self._rows[ids]),
+                "ret": f["ret"][index], "togo": f["togo"][index]}
+
+    def packed(self, role, index, variant):
+        """the ReturnBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
+        ring, nothing decoded, nothing copied but the index.  No host sync."""
+        f = self._ring(role)
+        return ReturnBatch(f["s0"], f["a0"], f["ret"], f["togo"], self._index(index), self._rows, variant)
+
+
+class ReturnRecorder(_ReturnRings):
     """ReturnAssembler + one ring per trained role on the device (csrc/ddz_returns.h, return spec v1), for env's tables: before() /
     after() around the step of a lock-step iteration (ddz_mc_before / ddz_mc_after), nothing on the host, capturable.  A ring
     entry is (state row, action id, ret = +/-reward[role] * gamma^togo, table, togo): 189 bytes, about half a transition;
-    count / note_counts / draw / sample / sample_packed are TransitionRecorder's.  log_cap: log entries per table (1..255);
+    count / note_counts / draw / sample / sample_packed are every recorder's.  log_cap: log entries per table (1..255);
     None = MAX_DECISIONS_PER_ROLE per trained role, which no game overflows.  The workspace is about 182 bytes per log entry:
     121 MB at 4,096 tables with three trained roles, 1.9 GB at 65,536.  A log that does overflow loses the later decisions
     (workspace counter `lost`), never the discount of the logged ones."""
@@ -1613,9 +1646,7 @@ class ReturnRecorder(TransitionRecorder):
         T, L = self.T, self.log_cap
         self.ws = torch.zeros(E.mc_ws_bytes(T, L), dtype=torch.uint8, device=self.device)
         self._cnt = self.ws[E.mc_ws_layout(T, L)["cnt"]:][:T * 4].view(T, 4)         # {n, c[3]} per table: what clear() zeroes
-        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity),
-                         (("s0", torch.uint8, 176), ("a0", torch.int32, 1), ("ret", torch.float32, 1), ("table", torch.int32, 1),
-                          ("togo", torch.uint8, 1)))
+        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity), self.RING_FIELDS)
 
     def before(self, chosen_ids, active=None):
         """before the step: chosen_ids int32 [T] canonical ids of what every table plays, active u8 / bool [T] the tables that
@@ -1626,6 +1657,14 @@ class ReturnRecorder(TransitionRecorder):
         """after step(auto_reset=False), before the re-deal: done u8 [T], r i8 [T] as the step returned them"""
         self.env.mc_after(self.ws, self.log_cap, self.rings, self.capacity, done, r, self.reward, self.gamma)
 
+    def around_step(self, loop, ids, step):
+        """before() on the network tables, the step, after(): no greedy id is gathered, since no a1 is recorded"""
+        loop._active.copy_(loop.seat.slot >= 0)
+        self.before(ids, loop._active)
+        done, r, illegal = step()
+        self.after(done, r)
+        return done, r, illegal
+
     def clear(self, mask=None):
         """forget the logs (entries and decision counters; `lost` stays) of the tables of mask (bool / u8 [T]; None: all) that the
         caller re-deals itself before they finish.  No host sync."""
@@ -1634,25 +1673,8 @@ class ReturnRecorder(TransitionRecorder):
         else:
             self._cnt.masked_fill_(mask.to(device=self.device).bool().view(self.T, 1), 0)
 
-    def decode(self, role, index, variant):
-        """{"s0" f32 [n,P,15,4], "a0" f32 [n,15,4], "ret" f32 [n], "togo" u8 [n]} of the ring entries index (int64 [n] device
-        tensor; clamped into the ring) in the faces of `variant`.  No host sync."""
-        from . import engine as E
-        f = self._ring(role)
-        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
-        ids = f["a0"][index].clamp(0, self._rows.shape[0] - 1).long()
-        return {"s0": E.observe_states(f["s0"], index, variant), "a0": E.rows_to_onehot(self._rows[ids]),
-                "ret": f["ret"][index], "togo": f["togo"][index]}
 
-    def packed(self, role, index, variant):
-        """the ReturnBatch of the ring entries index (int64 [n] device tensor; clamped into the ring as decode does): views of the
-        ring, nothing decoded, nothing copied but the index.  No host sync."""
-        f = self._ring(role)
-        index = index.to(device=self.device, dtype=torch.int64).clamp(0, self.capacity - 1).contiguous()
-        return ReturnBatch(f["s0"], f["a0"], f["ret"], f["togo"], index, self._rows, variant)
-
-
-class TeacherRecorder(TransitionRecorder):
+class TeacherRecorder(_ReturnRings):
     """TeacherAssembler + one return ring per trained role on the device (csrc/ddz_teach.h, teacher spec v1), for env's tables:
     label(stats) turns the root statistics of one evaluator run (engine.Teacher.evaluate) into ring entries (state row, action
     id, ret = reward[role] * (2 wins / visits - 1), table, togo 0) -- one per move of every selected table whose denominator
@@ -1668,15 +1690,12 @@ class TeacherRecorder(TransitionRecorder):
         if self.min_den < 1:
             raise ValueError("min_den must be at least 1")
         self.ws = torch.zeros(E.teach_ws_bytes(self.T), dtype=torch.uint8, device=self.device)     # (per-call scratch)
-        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity),
-                         (("s0", torch.uint8, 176), ("a0", torch.int32, 1), ("ret", torch.float32, 1), ("table", torch.int32, 1),
-                          ("togo", torch.uint8, 1)))
+        self._make_rings(E.mc_ring_bytes(self.capacity), E.mc_ring_layout(self.capacity), self.RING_FIELDS)
 
     def before(self, *args, **kwargs):
         raise TypeError("a TeacherRecorder has no before / after pair around the step: label(stats) is its one call")
 
     after = before
-    decode, packed = ReturnRecorder.decode, ReturnRecorder.packed
 
     def label(self, stats, active=None):
         """on the states the evaluator ran on (before the step): stats = Teacher.evaluate(env)'s TeacherStats, active u8 / bool
@@ -1687,8 +1706,22 @@ class TeacherRecorder(TransitionRecorder):
                   self.min_den, active, self.trained_mask & stats.roles, self.reward, counts=stats.counts, ids=env.ids,
                   stride=env.slab_stride)
 
+    def around_step(self, loop, ids, step):
+        """every label_every-th iteration: evaluate, label() of the network tables, act="teacher": its moves into ids; the step"""
+        if loop._it % loop.label_every == 0:
+            env = self.env
+            loop._active.copy_(loop.seat.slot >= 0)
+            stats = loop.teacher.evaluate(env)
+            self.label(stats, loop._active)
+            if loop.act == "teacher":
+                move = loop.teacher.choose(env, stats, out=loop._teacher_ids)
+                labelled = loop._active.bool() & loop._trained_of_role[env.role.clamp(max=2).long()] & (env.role <= 2)
+                ids.copy_(torch.where(labelled & (move >= 0), move, ids))
+        loop._it += 1
+        return step()
 
-class TrainLoop:
+
+class TrainLoop(_Loop):
     """One iteration of Game.train's inner loop (game.py:90-167) for T tables, nothing on the host: SeatLoop.act() ->
     recorder.before on the network tables -> step_slab(STEP_IDS, no auto-reset) -> recorder.after -> re-deal of the finished
     tables -> the next lists and faces.  nets / epsilon as SeatLoop's; train_dict {"lord" | "down" | "up": bool} (default:
@@ -1709,8 +1742,6 @@ class TrainLoop:
     def __init__(self, env, nets, face_variant, capacity=REPLAY_SIZE, epsilon=0.0, train_dict=None, reward_dict=None,
                  replicate_reference_quirk=False, targets="td", gamma=None, log_cap=None, teacher=None, label_every=1, min_den=1,
                  act="net"):
-        if targets not in ("td", "mc", "teacher"):
-            raise ValueError('targets: "td", "mc" or "teacher"')
         _teacher_args(targets, teacher, label_every, min_den, act)
         self.teacher, self.label_every, self.act, self._it = teacher, int(label_every), act, 0
         self.seat = SeatLoop(env, nets, face_variant, 0.0, auto_reset=False)
@@ -1720,8 +1751,7 @@ class TrainLoop:
         if bad:
             raise ValueError(f"unknown role(s) {sorted(bad)} in train_dict")
         self.trained = tuple(nr[k] >= 0 and bool(td.get(r)) for k, r in enumerate(ROLE_ORDER))
-        self.env, self.variant = env, int(face_variant)
-        self.targets = targets
+        self.env, self.variant, self.targets = env, int(face_variant), targets
         if targets == "teacher":
             self.rec = TeacherRecorder(env, capacity, reward_dict, self.trained, min_den)
             self._trained_of_role = torch.tensor(self.trained, dtype=torch.bool, device=env.device)
@@ -1745,48 +1775,27 @@ class TrainLoop:
 
     def step(self):
         from .engine import STEP_IDS
-        s, env = self.seat, self.env
-        ids = s.act()
-        if self.targets == "teacher":
-            if self._it % self.label_every == 0:
-                self._active.copy_(s.slot >= 0)
-                stats = self.teacher.evaluate(env)
-                self.rec.label(stats, self._active)
-                if self.act == "teacher":
-                    move = self.teacher.choose(env, stats, out=self._teacher_ids)
-                    labelled = self._active.bool() & self._trained_of_role[env.role.clamp(max=2).long()] & (env.role <= 2)
-                    ids.copy_(torch.where(labelled & (move >= 0), move, ids))
-            self._it += 1
-        elif self.targets == "mc":
-            self._active.copy_(s.slot >= 0)
-            self.rec.before(ids, self._active)
-        else:
-            self._greedy_ids.copy_(env.slab_ids().gather(1, s.greedy.clamp(min=0).long()[:, None])[:, 0])
-            self._active.copy_(s.slot >= 0)
-            self.rec.before(ids, self._greedy_ids, self._active)
-        done, r, illegal = env.step_slab(ids, STEP_IDS, auto_reset=False)
-        if self.targets != "teacher":
-            self.rec.after(done, r)
+        env = self.env
+        ids = self.seat.act()
+        done, r, illegal = self.rec.around_step(self, ids, lambda: env.step_slab(ids, STEP_IDS, auto_reset=False))
         env.reset(mask=done)
         env.legal_slab()
-        env.observe(self.variant, out=s.face)
+        env.observe(self.variant, out=self.seat.face)
         return done, r, illegal
-
-    def run(self, n):
-        for _ in range(int(n)):
-            self.step()
 
     def capture(self, n=1):
         """n iterations as ONE hipGraph, as PolicyLoop.capture (call step() a few times first).  targets="teacher": the
         labelling pattern of the n iterations is part of the graph, so n is a multiple of label_every."""
         if self.targets == "teacher" and int(n) % self.label_every:
             raise ValueError("capture(n) unrolls the labelling pattern: n must be a multiple of label_every")
-        return PolicyLoop.capture(self, n)
+        return super().capture(n)
 
 
 def _teacher_args(targets, teacher, label_every, min_den, act):
-    """the arguments of targets="teacher" (TrainLoop, train), checked before anything touches the device"""
+    """targets and the arguments of targets="teacher" (TrainLoop, train), checked before anything touches the device"""
     from .engine import Teacher
+    if targets not in ("td", "mc", "teacher"):
+        raise ValueError('targets: "td", "mc" or "teacher"')
     if act not in ("net", "teacher"):
         raise ValueError('act: "net" or "teacher"')
     if targets != "teacher":
@@ -1830,10 +1839,7 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
         raise ValueError("batch_size must be positive")
     if isinstance(fused, str) and fused not in ("stage", "packed"):
         raise ValueError('fused: False, True, "stage" or "packed"')
-    if targets not in ("td", "mc", "teacher"):
-        raise ValueError('targets: "td", "mc" or "teacher"')
     _teacher_args(targets, teacher, label_every, min_den, act)
-    mc = targets != "td"                                             # (return rings and mc_step, no target network)
     nets = {r: v for r, v in nets.items()}
     for r, v in nets.items():
         if v is not None:
@@ -1844,6 +1850,7 @@ def train(face_variant, nets, episodes, train_dict=None, reward_dict=None, table
     loop = TrainLoop(env, nets, face_variant, capacity=capacity, epsilon=epsilon_schedule(0), train_dict=train_dict,
                      reward_dict=reward_dict, targets=targets, gamma=gamma, teacher=teacher, label_every=label_every,
                      min_den=min_den, act=act)
+    mc = not loop.rec.target_network                                 # (return rings and mc_step, no target network)
     roles = [r for k, r in enumerate(ROLE_ORDER) if loop.trained[k]]
     if not roles:
         env.close()

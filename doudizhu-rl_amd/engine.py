@@ -74,6 +74,12 @@ def _salt(salt):
     return int(salt) & 0xFFFFFFFF
 
 
+def _reward3(reward):
+    if len(reward) != 3:
+        raise ValueError("reward: three floats in role order up, lord, down")
+    return (C.c_float * 3)(*[float(x) for x in reward])
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -207,6 +213,61 @@ class BatchedEnv:
         if self.ids is None:
             raise ValueError(f"{what} needs the action ids of the lists (want_ids=True)")
 
+    # ---- the statistic buffers an env keeps for the choose verbs, PlayoutLeaf and Teacher, by what they hold: the one place they
+    # live.  verb: (what its buffers hold, how it takes them back); search() and ismcts() write the same pair
+    _KEPT = {"playout": ("playout wins", lambda k: {"wins": k[0]}),
+             "search": ("search visits, wins", lambda k: {"visits": k[0], "wins": k[1]}),
+             "ismcts": ("search visits, wins", lambda k: {"visits": k[0], "wins": k[1]}),
+             "solve": ("solve out", lambda k: {"out": k}),
+             "cfr": ("cfr out", lambda k: {"out": k})}
+
+    def _kept(self, key, make=None):
+        """the buffers kept under `key` (a tuple of flat tensors), or None; make: what makes them where there are none"""
+        kept = self.__dict__.setdefault("_kept_stats", {})
+        if make is not None and key not in kept:
+            kept[key] = make()
+        return kept.get(key)
+
+    def _run_kept(self, verb, *args, **kw):
+        """the evaluator `verb` writing into the buffers kept for it (the first run makes them) -> its statistics, each flat"""
+        key, give = self._KEPT[verb]
+        kept = self.__dict__.setdefault("_kept_stats", {}).get(key)
+        if kept is not None:                # (the verb hands back views of what it is given: the kept tuple stays the result)
+            getattr(self, verb)(*args, **kw, **give(kept))
+            return kept
+        got = getattr(self, verb)(*args, **kw)
+        self._kept_stats[key] = kept = tuple(x.view(-1) for x in (got if isinstance(got, tuple) else (got,)))
+        return kept
+
+    # ---- the choose rules: statistics of the current slab lists -> one canonical action id per table, in `out` ----
+    def _choose_out(self, what, out):
+        """the int32 [T] a choose verb writes, checked before anything runs"""
+        self._need_ids(what)
+        return self._ids_out(out)
+
+    def _choose_wins(self, wins, out):
+        """the first maximum of wins (ddz_playout_choose)"""
+        check(self.lib.ddz_playout_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, _p(wins), _p(out),
+                                          _stream(self.device)))
+        return out
+
+    def _choose_ratio(self, visits, wins, out):
+        """the first maximum of wins / visits over the visited moves, compared exactly (ddz_search_choose)"""
+        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, _p(visits), _p(wins), _p(out),
+                                         _stream(self.device)))
+        return out
+
+    def _choose_solved(self, worlds, wins, unknown, out, value):
+        """the solver's rule and the chosen move's `value` (ddz_solve_choose)"""
+        check(self.lib.ddz_solve_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, worlds, _p(wins), _p(unknown),
+                                        _p(out), _p(value), _stream(self.device)))
+        return out
+
+    def _choose_sigma(self, n, ids, sigma, salt, greedy, out):
+        """cfr's rule: sampled from sigma, or its first maximum (ddz_cfr_choose)"""
+        check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), _salt(salt), int(bool(greedy)), _p(out), _stream(self.device)))
+        return out
+
     def _q_slab_arg(self, q):
         if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
             q = q.to(device=self.device, dtype=torch.float32).contiguous()
@@ -331,67 +392,54 @@ class BatchedEnv:
         return out
 
     # ---- the transition recorder (csrc/ddz_replay.h; dqn_glue.TransitionRecorder) ----
-    def _check_tr(self, ws, rings, capacity, need):
-        self._arg(ws, "ws", torch.uint8, at_least=tr_ws_bytes(self.T), why=" (tr_ws_bytes(T) bytes)")
+    def _rings_arg(self, rings, ring_bytes, capacity, need=0):
+        """the three rings of a recorder verb, one uint8 tensor of ring_bytes(capacity) bytes (or None) per role; bit k of `need`:
+        role k must have one -> (their addresses, the bytes of one)"""
         if len(rings) != 3:
             raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
-        nbytes = tr_ring_bytes(capacity)
+        nbytes, why = ring_bytes(capacity), f" ({ring_bytes.__name__}(capacity) bytes)"
         for k, ring in enumerate(rings):
-            if ring is None:
-                if (need >> k) & 1:
-                    raise ValueError("a trained role needs a ring")
-            else:
-                self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (tr_ring_bytes(capacity) bytes)")
+            if ring is not None:
+                self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=why)
+            elif (need >> k) & 1:
+                raise ValueError("a trained role needs a ring")
         return (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rings]), nbytes
 
-    def _u8_arg(self, x, name):
-        """uint8 [T]; a bool [T] is converted"""
-        return self._arg(x.to(torch.uint8) if x.dtype == torch.bool else x, name, torch.uint8, numel=self.T)
+    def _u8_arg(self, x, name, none_ok=False):
+        """uint8 [T]; a bool [T] is converted; none_ok (`active`: None = all tables): None passes as None"""
+        return self._arg(x.to(torch.uint8) if x is not None and x.dtype == torch.bool else x, name, torch.uint8, numel=self.T,
+                         none_ok=none_ok)
 
     def tr_before(self, ws, rings, capacity, chosen, greedy, active=None, trained_roles=0b111):
         """ddz_tr_before: close and open transitions on the CURRENT states (call it before the step).  chosen / greedy int32 [T]
         canonical action ids, active u8 / bool [T] or None (all tables), trained_roles: bit r = role r.  No host sync."""
         trained_roles = _roles_mask(trained_roles, name="trained_roles")
-        ptrs, nbytes = self._check_tr(ws, rings, capacity, trained_roles)
+        self._arg(ws, "ws", torch.uint8, at_least=tr_ws_bytes(self.T), why=" (tr_ws_bytes(T) bytes)")
+        ptrs, nbytes = self._rings_arg(rings, tr_ring_bytes, capacity, trained_roles)
         self._arg(chosen, "chosen", torch.int32, numel=self.T)
         self._arg(greedy, "greedy", torch.int32, numel=self.T)
-        if active is not None:
-            active = self._u8_arg(active, "active")
+        active = self._u8_arg(active, "active", none_ok=True)
         check(self.lib.ddz_tr_before(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(chosen), _p(greedy), _p(active),
                                      trained_roles, _stream(self.device)))
 
     def tr_after(self, ws, rings, capacity, done, r, reward, replicate_reference_quirk=False):
         """ddz_tr_after: the terminal transitions of the finished tables (call it after step(auto_reset=False), before the
         re-deal).  done u8 [T], r i8 [T] as the step wrote them, reward: three floats in role order up, lord, down."""
-        ptrs, nbytes = self._check_tr(ws, rings, capacity, 0)
+        self._arg(ws, "ws", torch.uint8, at_least=tr_ws_bytes(self.T), why=" (tr_ws_bytes(T) bytes)")
+        ptrs, nbytes = self._rings_arg(rings, tr_ring_bytes, capacity)
         done, r = self._u8_arg(done, "done"), self._arg(r, "r", torch.int8, numel=self.T)
-        if len(reward) != 3:
-            raise ValueError("reward: three floats in role order up, lord, down")
         check(self.lib.ddz_tr_after(self._h, _p(ws), ws.numel(), ptrs, nbytes, int(capacity), _p(done), _p(r),
-                                    (C.c_float * 3)(*[float(x) for x in reward]), int(bool(replicate_reference_quirk)),
-                                    _stream(self.device)))
+                                    _reward3(reward), int(bool(replicate_reference_quirk)), _stream(self.device)))
 
     # ---- Monte-Carlo return targets (csrc/ddz_returns.h; dqn_glue.ReturnRecorder) ----
-    def _check_mc(self, ws, log_cap, rings=None, capacity=None):
-        self._arg(ws, "ws", torch.uint8, at_least=mc_ws_bytes(self.T, log_cap), why=" (mc_ws_bytes(T, log_cap) bytes)")
-        if rings is None:
-            return None, 0
-        if len(rings) != 3:
-            raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
-        nbytes = mc_ring_bytes(capacity)
-        for k, ring in enumerate(rings):
-            self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (mc_ring_bytes(capacity) bytes)", none_ok=True)
-        return (C.c_void_p * 3)(*[None if x is None else x.data_ptr() for x in rings]), nbytes
-
     def mc_before(self, ws, log_cap, chosen, active=None, trained_roles=0b111):
         """ddz_mc_before: the episode log of every active table whose actor is a trained role takes (state row now, chosen[t])
         (call it before the step).  chosen int32 [T] canonical action ids, active u8 / bool [T] or None (all tables),
         trained_roles: bit r = role r.  No host sync."""
         trained_roles = _roles_mask(trained_roles, name="trained_roles")
-        self._check_mc(ws, log_cap)
+        self._arg(ws, "ws", torch.uint8, at_least=mc_ws_bytes(self.T, log_cap), why=" (mc_ws_bytes(T, log_cap) bytes)")
         self._arg(chosen, "chosen", torch.int32, numel=self.T)
-        if active is not None:
-            active = self._u8_arg(active, "active")
+        active = self._u8_arg(active, "active", none_ok=True)
         check(self.lib.ddz_mc_before(self._h, _p(ws), ws.numel(), int(log_cap), _p(chosen), _p(active), trained_roles,
                                      _stream(self.device)))
 
@@ -400,12 +448,11 @@ class BatchedEnv:
         togo) and empty (call it after step(auto_reset=False), before the re-deal).  rings: one uint8 tensor of
         mc_ring_bytes(capacity) bytes (or None: that role's entries are dropped) per role; done u8 [T], r i8 [T] as the step wrote
         them, reward: three floats in role order up, lord, down."""
-        ptrs, nbytes = self._check_mc(ws, log_cap, rings, capacity)
+        self._arg(ws, "ws", torch.uint8, at_least=mc_ws_bytes(self.T, log_cap), why=" (mc_ws_bytes(T, log_cap) bytes)")
+        ptrs, nbytes = (None, 0) if rings is None else self._rings_arg(rings, mc_ring_bytes, capacity)   # (None: the library's error)
         done, r = self._u8_arg(done, "done"), self._arg(r, "r", torch.int8, numel=self.T)
-        if len(reward) != 3:
-            raise ValueError("reward: three floats in role order up, lord, down")
         check(self.lib.ddz_mc_after(self._h, _p(ws), ws.numel(), int(log_cap), ptrs, nbytes, int(capacity), _p(done), _p(r),
-                                    (C.c_float * 3)(*[float(x) for x in reward]), float(gamma), _stream(self.device)))
+                                    _reward3(reward), float(gamma), _stream(self.device)))
 
     # ---- teacher targets (csrc/ddz_teach.h; dqn_glue.TeacherRecorder, Teacher below) ----
     TEACH_REWARD = (50.0, 100.0, 50.0)       # dqn_glue.REWARD_DICT in role order
@@ -443,19 +490,11 @@ class BatchedEnv:
         self._arg(den, "den", torch.int32, numel=n, why=" ([T * stride])", none_ok=True)
         self._arg(unknown, "unknown", torch.int32, numel=n, why=" ([T * stride])", none_ok=True)
         self._arg(ws, "ws", torch.uint8, at_least=teach_ws_bytes(self.T), why=" (teach_ws_bytes(T) bytes)")
-        if len(rings) != 3:
-            raise ValueError("rings: one tensor (or None) per role, in role order up, lord, down")
-        nbytes = mc_ring_bytes(capacity)
-        for k, ring in enumerate(rings):
-            self._arg(ring, f"rings[{k}]", torch.uint8, numel=nbytes, why=" (mc_ring_bytes(capacity) bytes)", none_ok=True)
-        ptrs = (C.c_void_p * 3)(*[None if x is None else x.data_ptr() for x in rings])
-        if active is not None:
-            active = self._u8_arg(active, "active")
-        if len(reward) != 3:
-            raise ValueError("reward: three floats in role order up, lord, down")
+        ptrs, nbytes = self._rings_arg(rings, mc_ring_bytes, capacity)
+        active = self._u8_arg(active, "active", none_ok=True)
         check(self.lib.ddz_teach(self._h, _p(counts), _p(ids), stride, _p(num), _p(den), int(den_const or 0), _p(unknown), scale,
                                  min_den, _p(active), trained_roles, _p(ws), ws.numel(), ptrs, nbytes, int(capacity),
-                                 (C.c_float * 3)(*[float(x) for x in reward]), _stream(self.device)))
+                                 _reward3(reward), _stream(self.device)))
 
     def select(self, q, epsilon=0.0, out=None):
         """greedy / epsilon-greedy choice per table from per-row values q (f32, CSR order of
@@ -769,13 +808,8 @@ class BatchedEnv:
         counts over each table's list (ties to the lowest index), -1 for idle tables.  Feed them to
         step_slab(mode=STEP_IDS).  hidden / roles: as playout() -- a table that the hidden form leaves out (its actor not in
         `roles`, or outside the domain) has all-zero counts and so gets the first move of its list: mask the ids by role."""
-        self._need_ids("playout_choose")
-        out = self._ids_out(out)
-        self._playout_wins = self.playout(n_playouts, salt=salt, chunks=chunks, wins=getattr(self, "_playout_wins", None),
-                                          hidden=hidden, roles=roles)
-        check(self.lib.ddz_playout_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
-                                          _p(self._playout_wins), _p(out), _stream(self.device)))
-        return out
+        out = self._choose_out("playout_choose", out)
+        return self._choose_wins(*self._run_kept("playout", n_playouts, salt=salt, chunks=chunks, hidden=hidden, roles=roles), out)
 
     # ---- UCT tree search around the playouts (search spec v1, DESIGN.md 4) ----
     SEARCH_MODES = {"reference": 0, "sides": 1}
@@ -830,14 +864,9 @@ class BatchedEnv:
         """The UCT move of every table: int32 [T] canonical action ids, the first maximum of wins / visits over the visited
         root moves of search() (get_bestchild_: the win ratio alone; ties to the lowest index), -1 where nothing was visited
         (idle tables, tables the hidden form leaves out).  Feed them to step_slab(mode=STEP_IDS)."""
-        self._need_ids("search_choose")
-        out = self._ids_out(out)
-        v, w = self.search(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles,
-                           visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
-        self._search_visits, self._search_wins = v.view(-1), w.view(-1)
-        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
-                                         _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
-        return out
+        out = self._choose_out("search_choose", out)
+        return self._choose_ratio(*self._run_kept("search", budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles),
+                                  out)
 
     # ---- information-set MCTS: one tree over all sampled worlds (search spec v2, DESIGN.md 4) ----
     def ismcts(self, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111, visits=None, wins=None, totals=None):
@@ -863,14 +892,8 @@ class BatchedEnv:
     def ismcts_choose(self, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111, out=None):
         """The ISMCTS move of every table: int32 [T] canonical action ids, search_choose()'s rule on ismcts()'s root
         statistics; -1 where nothing was visited.  Feed them to step_slab(mode=STEP_IDS)."""
-        self._need_ids("ismcts_choose")
-        out = self._ids_out(out)
-        v, w = self.ismcts(budget, trees=trees, mode=mode, c=c, salt=salt, roles=roles,
-                           visits=getattr(self, "_search_visits", None), wins=getattr(self, "_search_wins", None))
-        self._search_visits, self._search_wins = v.view(-1), w.view(-1)
-        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride,
-                                         _p(self._search_visits), _p(self._search_wins), _p(out), _stream(self.device)))
-        return out
+        out = self._choose_out("ismcts_choose", out)
+        return self._choose_ratio(*self._run_kept("ismcts", budget, trees=trees, mode=mode, c=c, salt=salt, roles=roles), out)
 
     # ---- UCT with leaf values from outside the kernel (search spec v3, DESIGN.md 4) ----
     GUIDED_ONE = 1024
@@ -891,12 +914,9 @@ class BatchedEnv:
         """The guided-UCT move of every table: int32 [T] canonical action ids, search_choose()'s rule (ddz_search_choose: the
         first maximum of wins / visits, compared exactly) on guided(...).run(evaluator)'s root statistics; -1 where nothing
         was visited.  Feed them to step_slab(mode=STEP_IDS)."""
-        self._need_ids("guided_choose")
-        out = self._ids_out(out)
-        v, w = self.guided(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles).run(evaluator)
-        check(self.lib.ddz_search_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, _p(v), _p(w), _p(out),
-                                         _stream(self.device)))
-        return out
+        out = self._choose_out("guided_choose", out)
+        return self._choose_ratio(*self.guided(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles).run(evaluator),
+                                  out)
 
     # ---- the CFR endgame solver (CFR spec v1, DESIGN.md 4) ----
     CFR_STRIDE = 16
@@ -950,12 +970,9 @@ class BatchedEnv:
         solved: the (n, ids, sigma, value) of an earlier cfr() call to choose from (no solve)."""
         out = self._ids_out(out)
         if solved is None:
-            solved = self.cfr(iterations, roles=roles, slots=slots, out=getattr(self, "_cfr_out", None))
-            self._cfr_out = solved
+            solved = self._run_kept("cfr", iterations, roles=roles, slots=slots)
         n, ids, sigma, _ = self._cfr_tensors(solved, "solved")
-        check(self.lib.ddz_cfr_choose(self._h, _p(n), _p(ids), _p(sigma), _salt(salt), int(bool(greedy)), _p(out),
-                                      _stream(self.device)))
-        return out
+        return self._choose_sigma(n, ids, sigma, salt, greedy, out)
 
     # ---- the exact endgame solver (solve spec v1, DESIGN.md 4) ----
     SOLVE_MAX_CARDS = 20
@@ -1026,8 +1043,7 @@ class BatchedEnv:
         every move is proven losing, else -1.  A running table that solve() left out (n = -1) has all-zero counts and so gets
         the first move of its list and value 0: mask by n.  solved: the (n, wins, unknown) of an earlier solve() call with
         the same `worlds` to choose from (no solve)."""
-        self._need_ids("solve_choose")
-        out = self._ids_out(out)
+        out = self._choose_out("solve_choose", out)
         if value is None:
             value = torch.empty(self.T, dtype=torch.int32, device=self.device)
         self._arg(value, "value", torch.int32, numel=self.T)
@@ -1035,12 +1051,9 @@ class BatchedEnv:
         if not 1 <= worlds <= 65536:
             raise ValueError("worlds must be in [1, 65536]")
         if solved is None:
-            solved = self.solve(budget, max_cards, worlds, hidden, roles, salt, chunks, tt_entries, out=getattr(self, "_solve_out", None))
-            self._solve_out = tuple(x.view(-1) for x in solved)
+            solved = self._run_kept("solve", budget, max_cards, worlds, hidden, roles, salt, chunks, tt_entries)
         _, wins, unknown = self._solve_tensors(tuple(x.view(-1) if x is not None and x.is_contiguous() else x for x in solved), "solved")
-        check(self.lib.ddz_solve_choose(self._h, self._pp["counts"], self._pp["ids"], self.slab_stride, worlds, _p(wins), _p(unknown),
-                                        _p(out), _p(value), _stream(self.device)))
-        return out, value
+        return self._choose_solved(worlds, wins, unknown, out, value), value
 
     def rollout_random_csr(self, n_iters, traj=None, batch=None):
         """The same loop with packed CSR lists (offsets/rows/ids as legal() returns them: afterwards they hold the lists
@@ -1198,9 +1211,8 @@ class PlayoutLeaf:
     def __call__(self, search):
         env = self.scratch(search)
         env.state_import(search.leaves)
-        wins = env.playout(self.K, salt=self.salt, chunks=self.chunks, wins=getattr(env, "_playout_wins", None))
-        env._playout_wins = wins.view(-1)
-        search.values.copy_(torch.div(wins.amax(dim=1) * BatchedEnv.GUIDED_ONE, self.K, rounding_mode="floor"))
+        wins, = env._run_kept("playout", self.K, salt=self.salt, chunks=self.chunks)
+        search.values.copy_(torch.div(wins.view(env.T, -1).amax(dim=1) * BatchedEnv.GUIDED_ONE, self.K, rounding_mode="floor"))
         return search.values
 
 
@@ -1262,20 +1274,30 @@ def observe_states(states, index=None, variant=3, out=None):
     return out
 
 
+def _size_query(symbol, args, error):
+    """the library's answer to a `*_bytes` query, or ValueError(error) where it refuses the arguments"""
+    n = int(getattr(_lib.lib(), symbol)(*map(int, args)))
+    if n < 0:
+        raise ValueError(error)
+    return n
+
+
+def _layout_query(symbol, args, names, error):
+    """{name: byte offset} from the library's `*_layout` query, or ValueError(error) where it refuses the arguments"""
+    off = (C.c_int64 * len(names))()
+    if getattr(_lib.lib(), symbol)(*map(int, args), off) != 0:
+        raise ValueError(error)
+    return dict(zip(names, [int(x) for x in off]))
+
+
 def tr_ws_bytes(n_tables):
     """bytes of the transition recorder's workspace for n_tables tables (ddz_tr_ws_bytes; zero-filled by the caller)"""
-    n = int(_lib.lib().ddz_tr_ws_bytes(int(n_tables)))
-    if n < 0:
-        raise ValueError("n_tables must be in 1 .. 2^30")
-    return n
+    return _size_query("ddz_tr_ws_bytes", (n_tables,), "n_tables must be in 1 .. 2^30")
 
 
 def tr_ring_bytes(capacity):
     """bytes of one role's ring of `capacity` packed transitions (ddz_tr_ring_bytes; zero-filled by the caller)"""
-    n = int(_lib.lib().ddz_tr_ring_bytes(int(capacity)))
-    if n < 0:
-        raise ValueError("capacity must be in 1 .. 2^30")
-    return n
+    return _size_query("ddz_tr_ring_bytes", (capacity,), "capacity must be in 1 .. 2^30")
 
 
 TR_RING_FIELDS = ("count", "s0", "s1", "a0", "a1", "reward", "table", "done")
@@ -1284,10 +1306,7 @@ TR_RING_FIELDS = ("count", "s0", "s1", "a0", "a1", "reward", "table", "done")
 def tr_ring_layout(capacity):
     """{field: byte offset} of a ring (ddz_tr_ring_layout): count int64, s0 / s1 u8 [capacity,176], a0 / a1 int32, reward f32,
     table int32, done u8"""
-    off = (C.c_int64 * 8)()
-    if _lib.lib().ddz_tr_ring_layout(int(capacity), off) != 0:
-        raise ValueError("capacity must be in 1 .. 2^30")
-    return dict(zip(TR_RING_FIELDS, [int(x) for x in off]))
+    return _layout_query("ddz_tr_ring_layout", (capacity,), TR_RING_FIELDS, "capacity must be in 1 .. 2^30")
 
 
 def mc_ws_bytes(n_tables, log_cap):
@@ -1295,10 +1314,7 @@ def mc_ws_bytes(n_tables, log_cap):
     by the caller; about 182 bytes per log entry)"""
     if not 1 <= int(log_cap) <= 255:
         raise ValueError("log_cap must be in 1 .. 255")
-    n = int(_lib.lib().ddz_mc_ws_bytes(int(n_tables), int(log_cap)))
-    if n < 0:
-        raise ValueError("n_tables must be positive and n_tables * log_cap at most 2^30")
-    return n
+    return _size_query("ddz_mc_ws_bytes", (n_tables, log_cap), "n_tables must be positive and n_tables * log_cap at most 2^30")
 
 
 MC_WS_REGIONS = ("rows", "act", "who", "cnt", "lost", "rank", "blk", "hdr")
@@ -1307,18 +1323,13 @@ MC_WS_REGIONS = ("rows", "act", "who", "cnt", "lost", "rank", "blk", "hdr")
 def mc_ws_layout(n_tables, log_cap):
     """{region: byte offset} of the return recorder's workspace (ddz_mc_ws_layout): rows u8 [T,L,176], act int32 [T,L], who u8
     [T,L,2] = {role, ordinal}, cnt u8 [T,4] = {n, c[3]}, lost uint32 [T], rank int32 [T,4], blk int32 [nb,4], hdr int64 [8]"""
-    off = (C.c_int64 * 8)()
-    if _lib.lib().ddz_mc_ws_layout(int(n_tables), int(log_cap), off) != 0:
-        raise ValueError("log_cap must be in 1 .. 255, n_tables positive and n_tables * log_cap at most 2^30")
-    return dict(zip(MC_WS_REGIONS, [int(x) for x in off]))
+    return _layout_query("ddz_mc_ws_layout", (n_tables, log_cap), MC_WS_REGIONS,
+                         "log_cap must be in 1 .. 255, n_tables positive and n_tables * log_cap at most 2^30")
 
 
 def mc_ring_bytes(capacity):
     """bytes of one role's ring of `capacity` return entries (ddz_mc_ring_bytes; zero-filled by the caller)"""
-    n = int(_lib.lib().ddz_mc_ring_bytes(int(capacity)))
-    if n < 0:
-        raise ValueError("capacity must be in 1 .. 2^30")
-    return n
+    return _size_query("ddz_mc_ring_bytes", (capacity,), "capacity must be in 1 .. 2^30")
 
 
 MC_RING_FIELDS = ("count", "s0", "a0", "ret", "table", "togo")
@@ -1327,18 +1338,12 @@ MC_RING_FIELDS = ("count", "s0", "a0", "ret", "table", "togo")
 def mc_ring_layout(capacity):
     """{field: byte offset} of a return ring (ddz_mc_ring_layout): count int64, s0 u8 [capacity,176], a0 int32, ret f32, table
     int32, togo u8"""
-    off = (C.c_int64 * 6)()
-    if _lib.lib().ddz_mc_ring_layout(int(capacity), off) != 0:
-        raise ValueError("capacity must be in 1 .. 2^30")
-    return dict(zip(MC_RING_FIELDS, [int(x) for x in off]))
+    return _layout_query("ddz_mc_ring_layout", (capacity,), MC_RING_FIELDS, "capacity must be in 1 .. 2^30")
 
 
 def teach_ws_bytes(n_tables):
     """bytes of ddz_teach's per-call scratch for n_tables tables (ddz_teach_ws_bytes; nothing in it has to be initialised)"""
-    n = int(_lib.lib().ddz_teach_ws_bytes(int(n_tables)))
-    if n < 0:
-        raise ValueError("n_tables must be in 1 .. 2^30")
-    return n
+    return _size_query("ddz_teach_ws_bytes", (n_tables,), "n_tables must be in 1 .. 2^30")
 
 
 TEACH_WS_REGIONS = ("rank", "blk", "hdr")
@@ -1346,10 +1351,7 @@ TEACH_WS_REGIONS = ("rank", "blk", "hdr")
 
 def teach_ws_layout(n_tables):
     """{region: byte offset} of ddz_teach's scratch (ddz_teach_ws_layout): rank int32 [T,4], blk int32 [nb,4], hdr int64 [8]"""
-    off = (C.c_int64 * 3)()
-    if _lib.lib().ddz_teach_ws_layout(int(n_tables), off) != 0:
-        raise ValueError("n_tables must be in 1 .. 2^30")
-    return dict(zip(TEACH_WS_REGIONS, [int(x) for x in off]))
+    return _layout_query("ddz_teach_ws_layout", (n_tables,), TEACH_WS_REGIONS, "n_tables must be in 1 .. 2^30")
 
 
 TeacherStats = collections.namedtuple("TeacherStats", "counts num den den_const unknown scale roles", defaults=(0b111,))
@@ -1391,44 +1393,33 @@ class Teacher:
         hidden = kind == "ismcts" or bool(kwargs.get("hidden", False))
         self.roles = _roles_mask(kwargs.get("roles", 0b111), hidden)
 
+    # kind: the verb's statistics, each flat, as TeacherStats' (counts, num, den, den_const, unknown, scale)
+    _STATS = {"playout": lambda env, kw, wins: (env.counts, wins, None, int(kw["n_playouts"]), None, 1),
+              "search": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, 1),
+              "ismcts": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, 1),
+              "guided": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
+              # its own n as the list sizes: a table that is no endgame (n <= 0) emits nothing
+              "solve": lambda env, kw, n, wins, unknown: (n, wins, None, int(kw.get("worlds", 1)), unknown, 1)}
+
     def evaluate(self, env):
         """run the evaluator on env's current states -> TeacherStats (the slab lists are made current by the evaluator)"""
         kw, kind = self.kwargs, self.kind
-        if kind == "playout":
-            wins = env.playout(wins=getattr(env, "_playout_wins", None), **kw)
-            env._playout_wins = wins
-            return TeacherStats(env.counts, wins.view(-1), None, int(kw["n_playouts"]), None, 1, self.roles)
-        if kind == "solve":
-            solved = env.solve(out=getattr(env, "_solve_out", None), **kw)
-            env._solve_out = n, wins, unknown = tuple(x.view(-1) for x in solved)
-            # its own n as the list sizes: a table that is no endgame (n <= 0) emits nothing
-            return TeacherStats(n, wins, None, int(kw.get("worlds", 1)), unknown, 1, self.roles)
-        if kind == "guided":
-            v, w = env.guided(**kw).run(self.evaluator)
-            return TeacherStats(env.counts, w.view(-1), v.view(-1), None, None, BatchedEnv.GUIDED_ONE, self.roles)
-        run = env.search if kind == "search" else env.ismcts
-        v, w = run(visits=getattr(env, "_search_visits", None), wins=getattr(env, "_search_wins", None), **kw)
-        env._search_visits, env._search_wins = v.view(-1), w.view(-1)
-        return TeacherStats(env.counts, env._search_wins, env._search_visits, None, None, 1, self.roles)
+        got = [x.view(-1) for x in env.guided(**kw).run(self.evaluator)] if kind == "guided" else env._run_kept(kind, **kw)
+        return TeacherStats(*self._STATS[kind](env, kw, *got), self.roles)
 
     def choose(self, env, stats, out=None):
         """the evaluator's move of every table from stats (evaluate()'s, of env's current states): int32 [T] canonical action
         ids, -1 where the teacher has none -- idle tables, nothing visited, and the tables the evaluator left out (a role
         outside `roles`, or for "solve" a table that is no endgame).  Feed them to step_slab(mode=STEP_IDS) where >= 0."""
-        env._need_ids("Teacher.choose")
-        out = env._ids_out(out)
-        h, counts, ids, st, s = env._h, env._pp["counts"], env._pp["ids"], env.slab_stride, _stream(env.device)
+        out = env._choose_out("Teacher.choose", out)
         if self.kind == "playout":
-            check(env.lib.ddz_playout_choose(h, counts, ids, st, _p(stats.num), _p(out), s))
+            env._choose_wins(stats.num, out)
         elif self.kind == "solve":
-            value = getattr(env, "_teach_value", None)
-            if value is None:
-                value = env._teach_value = torch.empty(env.T, dtype=torch.int32, device=env.device)
-            check(env.lib.ddz_solve_choose(h, counts, ids, st, int(stats.den_const), _p(stats.num), _p(stats.unknown), _p(out),
-                                           _p(value), s))
+            value = env._kept("teach value", lambda: torch.empty(env.T, dtype=torch.int32, device=env.device))
+            env._choose_solved(int(stats.den_const), stats.num, stats.unknown, out, value)
             out.copy_(torch.where(stats.counts > 0, out, -1))
         else:
-            check(env.lib.ddz_search_choose(h, counts, ids, st, _p(stats.den), _p(stats.num), _p(out), s))
+            env._choose_ratio(stats.den, stats.num, out)
         if stats.roles != 0b111:
             role = env.role.clamp(max=2).int()
             taken = (torch.full_like(role, stats.roles) >> role) & 1

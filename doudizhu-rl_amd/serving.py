@@ -176,6 +176,18 @@ def _id_cards(ids, device):
     return [None if a < 0 else [int(x) for x in np.repeat(ranks, table[a, :15].astype(int))] for a in ids]
 
 
+def _act(payloads, hidden, device, seed, domain, choose):
+    """The frame of every *_act: the requests as a fresh env (_payload_env) -> choose(env), the ids or a tuple of tensors with the
+    ids first, read back -> _check_domain -> (the ids as rank lists, the status word, choose's result as numpy); none: ([], 0, ())."""
+    if not payloads:
+        return [], 0, ()
+    env, dev = _payload_env(payloads, hidden, device, seed)
+    got = choose(env)
+    host = tuple(x.cpu().numpy() for x in (got if isinstance(got, tuple) else (got,)))
+    status = _check_domain(env, domain)
+    return _id_cards(host[0], dev), status, host
+
+
 def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=False):
     """The reference's mcts(payload) (server/mcts/interface.py:15-45) as flat Monte Carlo, for a batch of requests: every
     legal move of every request is followed by n_playouts uniformly random playouts over the three known hands
@@ -183,12 +195,8 @@ def playout_act(payloads, n_playouts, device="cuda:0", salt=0, seed=0, hidden=Fa
     of rank values 3..17 ([] = pass), or None where the request has no move (a finished game).
     hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and the playouts
     run on hands dealt from the cards the requester has not seen (playout spec v2)."""
-    if not payloads:
-        return []
-    env, dev = _payload_env(payloads, hidden, device, seed)
-    ids = env.playout_choose(n_playouts, salt=salt, hidden=hidden).cpu().numpy()
-    _check_domain(env, "hidden-hand" if hidden else None)
-    return _id_cards(ids, dev)
+    return _act(payloads, hidden, device, seed, "hidden-hand" if hidden else None,
+                lambda env: env.playout_choose(n_playouts, salt=salt, hidden=hidden))[0]
 
 
 def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, trees=None, mode="reference", c=0.7):
@@ -198,12 +206,8 @@ def search_act(payloads, budget, device="cuda:0", salt=0, seed=0, hidden=False, 
     pass), or None where the request has no move (a finished game).
     hidden=True: the payloads are the PLAIN serving payloads (no hand_card; one that is there is not read) and tree c
     searches world c of the hands dealt from the cards the requester has not seen (`trees` determinizations)."""
-    if not payloads:
-        return []
-    env, dev = _payload_env(payloads, hidden, device, seed)
-    ids = env.search_choose(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden).cpu().numpy()
-    _check_domain(env, "hidden-hand" if hidden else None)
-    return _id_cards(ids, dev)
+    return _act(payloads, hidden, device, seed, "hidden-hand" if hidden else None,
+                lambda env: env.search_choose(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden))[0]
 
 
 def ismcts_act(payloads, budget, device="cuda:0", salt=0, seed=0, trees=None, mode="reference", c=0.7):
@@ -212,12 +216,8 @@ def ismcts_act(payloads, budget, device="cuda:0", salt=0, seed=0, trees=None, mo
     `budget` iterations, each iteration on a fresh deal of the cards the requester has not seen), and the root move with the
     best win ratio for the requester's side is returned -- per request a list of rank values 3..17 ([] = pass), or None where
     the request has no move (a finished game).  ValueError where cur_cards, history and left do not add up to a deck."""
-    if not payloads:
-        return []
-    env, dev = _payload_env(payloads, True, device, seed)
-    ids = env.ismcts_choose(budget, trees=trees, mode=mode, c=c, salt=salt).cpu().numpy()
-    _check_domain(env, "hidden-hand")
-    return _id_cards(ids, dev)
+    return _act(payloads, True, device, seed, "hidden-hand",
+                lambda env: env.ismcts_choose(budget, trees=trees, mode=mode, c=c, salt=salt))[0]
 
 
 def guided_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, trees=None, mode="reference", c=0.7):
@@ -227,12 +227,8 @@ def guided_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, tre
     -- engine.PlayoutLeaf, dqn_glue.QLeaf or any callable that fills search.values), and the root move with the best value
     for the requester's side is returned -- per request a list of rank values 3..17 ([] = pass), or None where the request
     has no move (a finished game).  ValueError where cur_cards, history and left do not add up to a deck."""
-    if not payloads:
-        return []
-    env, dev = _payload_env(payloads, True, device, seed)
-    ids = env.guided_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt, hidden=True).cpu().numpy()
-    _check_domain(env, "hidden-hand")
-    return _id_cards(ids, dev)
+    return _act(payloads, True, device, seed, "hidden-hand",
+                lambda env: env.guided_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt, hidden=True))[0]
 
 
 def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=False):
@@ -246,14 +242,13 @@ def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=Fals
     hold it (status bit 7)."""
     if not payloads:
         return []
-    env, dev = _payload_env(payloads, True, device, seed)
-    solved = env.cfr(iterations, slots=len(payloads))
-    ids = env.cfr_choose(salt=salt, greedy=greedy, solved=solved).cpu().numpy()
-    if _check_domain(env, "endgame") & 128:
+    moves, status, (ids,) = _act(payloads, True, device, seed, "endgame", lambda env: env.cfr_choose(
+        salt=salt, greedy=greedy, solved=env.cfr(iterations, slots=len(payloads))))
+    if status & 128:
         raise ValueError("an endgame exceeds the solver's capacities")
     if (ids < 0).any():
         raise ValueError("a payload is no endgame: more than 6 cards are left, or the game is over")
-    return _id_cards(ids, dev)
+    return moves
 
 
 def solve_act(payloads, budget=65536, max_cards=12, worlds=1, device="cuda:0", salt=0, seed=0, hidden=False, chunks=1,
@@ -270,14 +265,13 @@ def solve_act(payloads, budget=65536, max_cards=12, worlds=1, device="cuda:0", s
     or, hidden form, where cur_cards, history and left do not add up to a deck (status bit 6)."""
     if not payloads:
         return ([], []) if want_value else []
-    env, dev = _payload_env(payloads, hidden, device, seed)
-    solved = env.solve(budget, max_cards, worlds if hidden else 1, hidden, salt=salt, chunks=chunks, tt_entries=tt_entries)
-    ids, value = env.solve_choose(worlds=worlds if hidden else 1, solved=solved)
-    ids, value, size = ids.cpu().numpy(), value.cpu().numpy(), solved[0].cpu().numpy()
-    _check_domain(env, "hidden-hand" if hidden else None)
+    def choose(env):
+        solved = env.solve(budget, max_cards, worlds if hidden else 1, hidden, salt=salt, chunks=chunks, tt_entries=tt_entries)
+        return env.solve_choose(worlds=worlds if hidden else 1, solved=solved) + (solved[0],)
+
+    moves, _, (_, value, size) = _act(payloads, hidden, device, seed, "hidden-hand" if hidden else None, choose)
     if (size <= 0).any():
         raise ValueError(f"a payload is no endgame: more than {int(max_cards)} cards are left, or the game is over")
-    moves = _id_cards(ids, dev)
     return (moves, [int(v) for v in value]) if want_value else moves
 
 

@@ -15,6 +15,7 @@ Size classes of a parameter: "exact" (shape or numel fixed by the call), "min" (
 passes exactly the minimum), "free" (the tensor's own shape defines the sizes of the call), "bytes" (a workspace whose byte
 count travels to the library with its address: the library tests it), "size" (an input the verb converts: only its size is
 refused)."""
+import ctypes as C
 import importlib
 
 import pytest
@@ -35,17 +36,42 @@ def z(*shape, dt=f32):
 
 
 class StandIn:
-    """the library: a launch records its name and succeeds; a size query answers a positive size and is not recorded"""
+    """the library: a launch records its name (calls) and its arguments as they arrive (trace) and succeeds; a size query
+    answers a positive size and is not recorded"""
 
     def __init__(self):
-        self.calls = []
+        self.calls, self.trace = [], []
 
     def __getattr__(self, name):
         if not name.startswith("ddz_"):
             raise AttributeError(name)
         if name.endswith("_bytes") or name in SIZE_QUERIES:
             return lambda *a: SIZE_QUERIES.get(name, 64)
-        return lambda *a: self.calls.append(name) or 0
+
+        def launch(*a):
+            self.calls.append(name)
+            self.trace.append((name, a))
+            return 0
+        return launch
+
+
+def scalars(args):
+    """what a launch's arguments say apart from addresses: numbers as they are, an address as "ptr" (None: null), an array of
+    floats / ints as a list, an array of addresses as a list of "ptr" / None, anything else by its type's name"""
+    def one(a):
+        if a is None or isinstance(a, (bool, int, float)):
+            return a
+        if isinstance(a, C.c_void_p):
+            return "ptr" if a.value else None
+        if isinstance(a, C.Array):
+            return [("ptr" if x else None) if a._type_ is C.c_void_p else x for x in a]
+        return type(a).__name__
+    return [one(a) for a in args]
+
+
+def addresses(args):
+    """the addresses among a launch's arguments, in order (None: null)"""
+    return [a.value for a in args if isinstance(a, C.c_void_p)]
 
 
 @pytest.fixture()
