@@ -50,6 +50,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/ddz_env.h"
 #include "ddz_device.h"
@@ -2681,6 +2682,16 @@ inline int pick_tpw(int64_t T) {
   return (int)(v < 1 ? 1 : v > 32 ? 32 : v);
 }
 
+// a run-time value as a compile-time one: f(std::integral_constant<V>) for the V among Vs that equals v; false where none does
+template <auto V, auto... Rest, class T, class F>
+bool pick(T v, F&& f) {
+  if (v == (T)V) { f(std::integral_constant<decltype(V), V>{}); return true; }
+  if constexpr (sizeof...(Rest) > 0) return pick<Rest...>(v, f);
+  else return false;
+}
+// the planes of a face variant (ddz_face_planes; the kernels keep their own expression)
+constexpr int face_planes(int v) { return v == 0 ? 4 : v == 1 ? 7 : v == 2 ? 9 : 6; }
+
 int launch_moves(const Scratch& sc, const int8_t* hands, const int8_t* lasts, int64_t n, int32_t* offsets,
                  int8_t* rows, int32_t* ids, int64_t cap, hipStream_t st) {
   int64_t v = (n + 16383) / 16384;
@@ -2691,12 +2702,10 @@ int launch_moves(const Scratch& sc, const int8_t* hands, const int8_t* lasts, in
                      sc.counts[0], sc.local_off[0], sc.blk_tot[0], offsets, (uint4*)rows, ids, cap, sc.status);
   int rc = check_launch();
   if (rc) return rc;
-  if (ids)
-    hipLaunchKernelGGL((k_moves<true, true>), grid, block, 0, st, (const uint4*)hands, (const uint4*)lasts, n, tpw,
+  pick<false, true>(ids != nullptr, [&](auto IDS) {
+    hipLaunchKernelGGL((k_moves<true, IDS()>), grid, block, 0, st, (const uint4*)hands, (const uint4*)lasts, n, tpw,
                        sc.counts[0], sc.local_off[0], sc.blk_tot[0], offsets, (uint4*)rows, ids, cap, sc.status);
-  else
-    hipLaunchKernelGGL((k_moves<true, false>), grid, block, 0, st, (const uint4*)hands, (const uint4*)lasts, n, tpw,
-                       sc.counts[0], sc.local_off[0], sc.blk_tot[0], offsets, (uint4*)rows, ids, cap, sc.status);
+  });
   return check_launch();
 }
 
@@ -2823,11 +2832,17 @@ struct Io {  // optional buffers of one k_table launch
   int64_t stride = 0;
 };
 
+// the six-field head of TableArgs, SlabArgs and RolloutArgs (the evaluators' is ply_args below: its key is salted)
+template <typename Args>
+void head_args(Args& a, const ddz_env* e) {
+  a.state = e->state; a.T = e->T; a.tpw = e->tpw;
+  a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+}
+
 template <int FLAGS, int MODE>
 int launch_table(ddz_env* e, const Io& io, hipStream_t st) {
   TableArgs a;
-  a.state = e->state; a.T = e->T; a.tpw = e->tpw;
-  a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  head_args(a, e);
   a.auto_reset = io.auto_reset; a.sel = io.sel;
   a.offsets = io.offsets; a.rows = (uint4*)io.rows; a.ids = io.ids; a.cap = io.cap;
   const int cur = e->parity, nxt = cur ^ 1;
@@ -2837,16 +2852,37 @@ int launch_table(ddz_env* e, const Io& io, hipStream_t st) {
   a.blk_stats = e->sc.blk_stats; a.status = e->sc.status; a.legal_rows = e->sc.legal_rows;
   a.slab_counts = io.slab_counts; a.stride = io.stride;
   const dim3 grid((unsigned)e->nblocks), block(TB);
-  if ((FLAGS & (F_ENUM | F_SLAB)) && io.ids)
-    hipLaunchKernelGGL((k_table<FLAGS, MODE, true>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((k_table<FLAGS, MODE, false>), grid, block, 0, st, a);
+  pick<false, true>((FLAGS & (F_ENUM | F_SLAB)) && io.ids, [&](auto IDS) {
+    hipLaunchKernelGGL((k_table<FLAGS, MODE, IDS()>), grid, block, 0, st, a);
+  });
   int rc = check_launch();
   if (rc == DDZ_OK && !(FLAGS & F_SLAB) && (FLAGS & (F_STEP | F_RESET | F_COUNT))) {
     e->parity = nxt;
     e->counts_valid = true;
   }
   return rc;
+}
+
+// SlabArgs as ddz_step_slab passes them; ddz_policy_step_slab then sets the four fields of the fused policy iteration
+SlabArgs slab_args(const ddz_env* e, const void* sel, int32_t* counts, int8_t* rows, int32_t* ids, int64_t stride, int auto_reset,
+                   uint8_t* done, int8_t* reward, uint8_t* illegal, uint8_t* traj) {
+  SlabArgs a;
+  head_args(a, e);
+  a.auto_reset = auto_reset ? 1 : 0; a.sel = sel; a.counts = counts; a.rows = (uint4*)rows; a.ids = ids; a.stride = stride;
+  a.done = done; a.reward = reward; a.illegal = illegal; a.traj = (uint4*)traj;
+  a.wave_stats = e->sc.blk_stats; a.status = e->sc.status;
+  a.thr = 0; a.choice_out = nullptr; a.face = nullptr; a.face_variant = 0;
+  a.coop = e->slab_coop; a.lpt = e->slab_lpt; a.team = e->slab_team;
+  return a;
+}
+template <int MODE>
+int launch_slab(ddz_env* e, const SlabArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)e->nblocks), block(TB);
+  pick<false, true>(a.coop != 0, [&](auto COOP) {
+    pick<false, true>(a.ids != nullptr, [&](auto IDS) { hipLaunchKernelGGL((k_slab<MODE, IDS(), COOP()>), grid, block, 0, st, a); });
+  });
+  e->counts_valid = false;  // the state moved on without refreshing the CSR scan buffers
+  return check_launch();
 }
 
 int ensure_counts(ddz_env* e, hipStream_t st) {
@@ -3003,14 +3039,10 @@ static int launch_q_features(int device, const float* face, int64_t n_tables, in
   const dim3 grid((unsigned)((n_tables + QF_TILE - 1) / QF_TILE)), block(QH);
   hipStream_t st = (hipStream_t)stream;
   const float4* f = (const float4*)face;
-  switch (planes) {
-    case 4: hipLaunchKernelGGL(k_q_feat<4>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
-    case 6: hipLaunchKernelGGL(k_q_feat<6>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
-    case 7: hipLaunchKernelGGL(k_q_feat<7>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
-    case 9: hipLaunchKernelGGL(k_q_feat<9>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride); break;
-    default: return DDZ_EINVAL;
-  }
-  return check_launch();
+  const bool known = pick<4, 6, 7, 9>(planes, [&](auto P) {
+    hipLaunchKernelGGL(k_q_feat<P()>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y, y_row_stride);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 // ---- host chains of the Q forward that more than one entry point issues (ddz_qnet.h sections 4-7) ----
@@ -3069,10 +3101,7 @@ int ddz_last_hip_error(void) { return g_last_hip; }
 
 int64_t ddz_state_bytes(int64_t T) { return T < 0 ? DDZ_EINVAL : T * DDZ_NFIELDS * DDZ_ROW; }
 int64_t ddz_scratch_bytes(int64_t T) { return T < 0 ? DDZ_EINVAL : make_layout(T).bytes; }
-int ddz_face_planes(int v) {
-  static const int p[4] = {4, 7, 9, 6};
-  return v >= 0 && v < 4 ? p[v] : DDZ_EINVAL;
-}
+int ddz_face_planes(int v) { return v >= 0 && v < 4 ? face_planes(v) : DDZ_EINVAL; }
 
 int ddz_create(ddz_env_t** out, int64_t T, uint64_t seed, uint64_t gid_base, int device, void* state,
                int64_t state_bytes, void* scratch, int64_t scratch_bytes) {
@@ -3153,13 +3182,11 @@ int ddz_step(ddz_env_t* e, int mode, const void* sel, const int32_t* offsets, co
   Io io;
   io.sel = sel; io.offsets = (int32_t*)offsets; io.rows = (int8_t*)rows; io.cap = e->legal_cap;
   io.auto_reset = auto_reset ? 1 : 0; io.done = done; io.reward = reward; io.illegal = illegal; io.traj = traj;
-  hipStream_t st = (hipStream_t)stream;
-  switch (mode) {
-    case DDZ_STEP_RANDOM: return launch_table<F_STEP, DDZ_STEP_RANDOM>(e, io, st);
-    case DDZ_STEP_CHOICE: return launch_table<F_STEP, DDZ_STEP_CHOICE>(e, io, st);
-    case DDZ_STEP_IDS: return launch_table<F_STEP, DDZ_STEP_IDS>(e, io, st);
-    default: return launch_table<F_STEP, DDZ_STEP_ROWS>(e, io, st);
-  }
+  int rc = DDZ_EINVAL;   // (unreachable: the mode is checked above)
+  pick<DDZ_STEP_RANDOM, DDZ_STEP_CHOICE, DDZ_STEP_ROWS, DDZ_STEP_IDS>(mode, [&](auto MODE) {
+    rc = launch_table<F_STEP, MODE()>(e, io, (hipStream_t)stream);
+  });
+  return rc;
 }
 
 int ddz_legal_slab(ddz_env_t* e, int32_t* counts, int8_t* rows, int32_t* ids, int64_t stride, void* stream) {
@@ -3181,35 +3208,12 @@ int ddz_step_slab(ddz_env_t* e, int mode, const void* sel, int32_t* counts, int8
   if (mode != DDZ_STEP_RANDOM && !sel) return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
-  SlabArgs a;
-  a.state = e->state; a.T = e->T; a.tpw = e->tpw;
-  a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
-  a.auto_reset = auto_reset ? 1 : 0; a.sel = sel; a.counts = counts; a.rows = (uint4*)rows; a.ids = ids; a.stride = stride;
-  a.done = done; a.reward = reward; a.illegal = illegal; a.traj = (uint4*)traj;
-  a.wave_stats = e->sc.blk_stats; a.status = e->sc.status;
-  a.thr = 0; a.choice_out = nullptr; a.face = nullptr; a.face_variant = 0;
-  a.coop = e->slab_coop; a.lpt = e->slab_lpt; a.team = e->slab_team;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)e->nblocks), block(TB);
-#define DDZ_LAUNCH_SLAB(M)                                                                    \
-  do {                                                                                        \
-    if (a.coop) {                                                                             \
-      if (ids) hipLaunchKernelGGL((k_slab<M, true, true>), grid, block, 0, st, a);            \
-      else hipLaunchKernelGGL((k_slab<M, false, true>), grid, block, 0, st, a);               \
-    } else {                                                                                  \
-      if (ids) hipLaunchKernelGGL((k_slab<M, true, false>), grid, block, 0, st, a);           \
-      else hipLaunchKernelGGL((k_slab<M, false, false>), grid, block, 0, st, a);              \
-    }                                                                                         \
-  } while (0)
-  switch (mode) {
-    case DDZ_STEP_RANDOM: DDZ_LAUNCH_SLAB(DDZ_STEP_RANDOM); break;
-    case DDZ_STEP_CHOICE: DDZ_LAUNCH_SLAB(DDZ_STEP_CHOICE); break;
-    case DDZ_STEP_IDS: DDZ_LAUNCH_SLAB(DDZ_STEP_IDS); break;
-    default: DDZ_LAUNCH_SLAB(DDZ_STEP_ROWS); break;
-  }
-#undef DDZ_LAUNCH_SLAB
-  e->counts_valid = false;  // the state moved on without refreshing the CSR scan buffers
-  return check_launch();
+  const SlabArgs a = slab_args(e, sel, counts, rows, ids, stride, auto_reset, done, reward, illegal, traj);
+  int rc = DDZ_EINVAL;   // (unreachable: the mode is checked above)
+  pick<DDZ_STEP_RANDOM, DDZ_STEP_CHOICE, DDZ_STEP_ROWS, DDZ_STEP_IDS>(mode, [&](auto MODE) {
+    rc = launch_slab<MODE()>(e, a, (hipStream_t)stream);
+  });
+  return rc;
 }
 
 int ddz_policy_step_slab(ddz_env_t* e, const float* q, double epsilon, int32_t* counts, int8_t* rows, int32_t* ids,
@@ -3221,24 +3225,9 @@ int ddz_policy_step_slab(ddz_env_t* e, const float* q, double epsilon, int32_t* 
   if (face && ddz_face_planes(face_variant) < 0) return DDZ_EINVAL;
   DeviceGuard g(e->device);
   if (!g.ok) return DDZ_ENODEV;
-  SlabArgs a;
-  a.state = e->state; a.T = e->T; a.tpw = e->tpw;
-  a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
-  a.auto_reset = auto_reset ? 1 : 0; a.sel = q; a.counts = counts; a.rows = (uint4*)rows; a.ids = ids; a.stride = stride;
-  a.done = done; a.reward = reward; a.illegal = illegal; a.traj = (uint4*)traj;
-  a.wave_stats = e->sc.blk_stats; a.status = e->sc.status;
+  SlabArgs a = slab_args(e, q, counts, rows, ids, stride, auto_reset, done, reward, illegal, traj);
   a.thr = (uint64_t)(epsilon * 4294967296.0); a.choice_out = choice; a.face = (float4*)face; a.face_variant = face_variant;
-  a.coop = e->slab_coop; a.lpt = e->slab_lpt; a.team = e->slab_team;
-  const dim3 grid((unsigned)e->nblocks), block(TB);
-  if (a.coop) {
-    if (ids) hipLaunchKernelGGL((k_slab<STEP_Q, true, true>), grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_slab<STEP_Q, false, true>), grid, block, 0, (hipStream_t)stream, a);
-  } else {
-    if (ids) hipLaunchKernelGGL((k_slab<STEP_Q, true, false>), grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_slab<STEP_Q, false, false>), grid, block, 0, (hipStream_t)stream, a);
-  }
-  e->counts_valid = false;
-  return check_launch();
+  return launch_slab<STEP_Q>(e, a, (hipStream_t)stream);
 }
 
 int ddz_mask_words(void) { return MASK_WORDS; }
@@ -3264,13 +3253,10 @@ int ddz_observe(ddz_env_t* e, int variant, float* face, void* stream) {
   const int64_t n = e->T * P * 15;
   const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
   const uint8_t* st = (const uint8_t*)e->state;
-  switch (variant) {
-    case 0: hipLaunchKernelGGL(k_observe<0>, grid, block, 0, (hipStream_t)stream, st, e->T, (float4*)face); break;
-    case 1: hipLaunchKernelGGL(k_observe<1>, grid, block, 0, (hipStream_t)stream, st, e->T, (float4*)face); break;
-    case 2: hipLaunchKernelGGL(k_observe<2>, grid, block, 0, (hipStream_t)stream, st, e->T, (float4*)face); break;
-    default: hipLaunchKernelGGL(k_observe<3>, grid, block, 0, (hipStream_t)stream, st, e->T, (float4*)face); break;
-  }
-  return check_launch();
+  const bool known = pick<0, 1, 2, 3>(variant, [&](auto V) {
+    hipLaunchKernelGGL(k_observe<V()>, grid, block, 0, (hipStream_t)stream, st, e->T, (float4*)face);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 int ddz_rows_to_onehot(int device, const int8_t* rows, int64_t n, float* out, void* stream) {
@@ -3303,13 +3289,10 @@ int ddz_observe_states(int device, const uint8_t* states, const int64_t* index, 
   if (!g.ok) return DDZ_ENODEV;
   const int64_t m = n * P * 15;
   const dim3 grid((unsigned)((m + BLOCK - 1) / BLOCK)), block(BLOCK);
-  switch (variant) {
-    case 0: hipLaunchKernelGGL(k_observe_states<0>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
-    case 1: hipLaunchKernelGGL(k_observe_states<1>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
-    case 2: hipLaunchKernelGGL(k_observe_states<2>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
-    default: hipLaunchKernelGGL(k_observe_states<3>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face); break;
-  }
-  return check_launch();
+  const bool known = pick<0, 1, 2, 3>(variant, [&](auto V) {
+    hipLaunchKernelGGL(k_observe_states<V()>, grid, block, 0, (hipStream_t)stream, states, index, n, (float4*)face);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 int64_t ddz_tr_ws_bytes(int64_t T) { return T <= 0 || T > ((int64_t)1 << 30) ? DDZ_EINVAL : tr_ws_layout(T).bytes; }
@@ -3536,16 +3519,13 @@ int ddz_get_moves_slab(int device, const int8_t* hands, const int8_t* lasts, int
   if (!g.ok) return DDZ_ENODEV;
   int rc = ensure_table(device);
   if (rc) return rc;
-  int64_t v = (n + 4095) / 4096;
-  const int tpw = (int)(v < 1 ? 1 : v > 32 ? 32 : v);
+  const int tpw = pick_tpw(n);
   const int64_t per_block = (int64_t)WPB * tpw;
   const dim3 grid((unsigned)((n + per_block - 1) / per_block)), block(TB);
-  if (ids)
-    hipLaunchKernelGGL((k_moves_slab<true>), grid, block, 0, (hipStream_t)stream, (const uint4*)hands, (const uint4*)lasts, n,
+  pick<false, true>(ids != nullptr, [&](auto IDS) {
+    hipLaunchKernelGGL((k_moves_slab<IDS()>), grid, block, 0, (hipStream_t)stream, (const uint4*)hands, (const uint4*)lasts, n,
                        tpw, counts, (uint4*)rows, ids, stride, status);
-  else
-    hipLaunchKernelGGL((k_moves_slab<false>), grid, block, 0, (hipStream_t)stream, (const uint4*)hands, (const uint4*)lasts, n,
-                       tpw, counts, (uint4*)rows, ids, stride, status);
+  });
   return check_launch();
 }
 
@@ -3564,12 +3544,10 @@ int ddz_slab_to_csr(ddz_env_t* e, const int32_t* counts, const int8_t* rows, con
                      CsrBatch{});
   int rc = check_launch();
   if (rc) return rc;
-  if (ids_out)
-    hipLaunchKernelGGL((k_csr_copy<true>), dim3((unsigned)nb), dim3(CSR_BT), 0, st, counts, (const uint4*)rows, ids, e->T, stride,
+  pick<false, true>(ids_out != nullptr, [&](auto IDS) {
+    hipLaunchKernelGGL((k_csr_copy<IDS()>), dim3((unsigned)nb), dim3(CSR_BT), 0, st, counts, (const uint4*)rows, ids, e->T, stride,
                        e->sc.local_off[0], e->sc.blk_tot[0], offsets, (uint4*)rows_out, ids_out, row_capacity, e->sc.status, CsrBatch{});
-  else
-    hipLaunchKernelGGL((k_csr_copy<false>), dim3((unsigned)nb), dim3(CSR_BT), 0, st, counts, (const uint4*)rows, ids, e->T, stride,
-                       e->sc.local_off[0], e->sc.blk_tot[0], offsets, (uint4*)rows_out, ids_out, row_capacity, e->sc.status, CsrBatch{});
+  });
   return check_launch();
 }
 
@@ -3586,8 +3564,7 @@ int ddz_read_stats(ddz_env_t* e, int64_t* stats, void* stream) {
 static int launch_rollout(ddz_env* e, int64_t n_iters, int32_t* counts, int8_t* rows, int32_t* ids, int64_t stride,
                           uint8_t* traj, hipStream_t st, int64_t it_rows = 0, int64_t it_counts = 0) {
   RolloutArgs a;
-  a.state = e->state; a.T = e->T; a.tpw = e->tpw;
-  a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32); a.gid_base = e->gid_base;
+  head_args(a, e);
   a.counts = counts; a.rows = (uint4*)rows; a.ids = ids; a.stride = stride;
   a.it_rows = it_rows; a.it_counts = it_counts;
   a.wave_stats = e->sc.blk_stats; a.status = e->sc.status; a.legal_rows = e->sc.legal_rows;
@@ -3607,20 +3584,14 @@ static int launch_rollout(ddz_env* e, int64_t n_iters, int32_t* counts, int8_t* 
   for (int64_t done = 0; done < n_iters; done += CHUNK) {
     a.n_iters = n_iters - done < CHUNK ? n_iters - done : CHUNK;
     a.traj = traj ? (uint4*)(traj + done * e->T * DDZ_TRAJ_BYTES) : nullptr;
-    if (dense) {
-      if (it_rows && traj) hipLaunchKernelGGL((k_rollout<false, true, true, RW12>), grid12, block12, 0, st, a);
-      else if (it_rows) hipLaunchKernelGGL((k_rollout<false, false, true, RW12>), grid12, block12, 0, st, a);
-      else if (traj) hipLaunchKernelGGL((k_rollout<false, true, false, RW12>), grid12, block12, 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<false, false, false, RW12>), grid12, block12, 0, st, a);
-    } else if (it_rows) {
-      if (ids && traj) hipLaunchKernelGGL((k_rollout<true, true, true>), grid, block, 0, st, a);
-      else if (ids) hipLaunchKernelGGL((k_rollout<true, false, true>), grid, block, 0, st, a);
-      else if (traj) hipLaunchKernelGGL((k_rollout<false, true, true>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<false, false, true>), grid, block, 0, st, a);
-    } else if (ids && traj) hipLaunchKernelGGL((k_rollout<true, true>), grid, block, 0, st, a);
-    else if (ids) hipLaunchKernelGGL((k_rollout<true, false>), grid, block, 0, st, a);
-    else if (traj) hipLaunchKernelGGL((k_rollout<false, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_rollout<false, false>), grid, block, 0, st, a);
+    pick<false, true>(traj != nullptr, [&](auto TRAJ) {
+      pick<false, true>(it_rows != 0, [&](auto STAGED) {
+        if (dense) hipLaunchKernelGGL((k_rollout<false, TRAJ(), STAGED(), RW12>), grid12, block12, 0, st, a);   // (dense: no ids)
+        else pick<false, true>(ids != nullptr, [&](auto IDS) {
+          hipLaunchKernelGGL((k_rollout<IDS(), TRAJ(), STAGED()>), grid, block, 0, st, a);
+        });
+      });
+    });
   }
   e->counts_valid = false;  // the state moved on without refreshing the CSR scan buffers
   return check_launch();
@@ -3932,12 +3903,10 @@ int ddz_rollout_random_csr_staged(ddz_env_t* e, int64_t n_iters, int batch, void
     CsrBatch bt = bt0;
     bt.first = first;
     const dim3 grid((unsigned)nb, (unsigned)count);
-    if (ids)
-      hipLaunchKernelGGL((k_csr_copy<true>), grid, dim3(CSR_BT), 0, st, (const int32_t*)s_counts, (const uint4*)s_rows, (const int32_t*)s_ids,
+    pick<false, true>(ids != nullptr, [&](auto IDS) {
+      hipLaunchKernelGGL((k_csr_copy<IDS()>), grid, dim3(CSR_BT), 0, st, (const int32_t*)s_counts, (const uint4*)s_rows, (const int32_t*)s_ids,
                          T, S, (const int32_t*)s_local, (const int32_t*)s_blk, offsets, (uint4*)rows, ids, cap, e->sc.status, bt);
-    else
-      hipLaunchKernelGGL((k_csr_copy<false>), grid, dim3(CSR_BT), 0, st, (const int32_t*)s_counts, (const uint4*)s_rows, (const int32_t*)s_ids,
-                         T, S, (const int32_t*)s_local, (const int32_t*)s_blk, offsets, (uint4*)rows, ids, cap, e->sc.status, bt);
+    });
   };
   for (int64_t done = 0; done < n_iters; done += batch) {
     const int b = (int)(n_iters - done < batch ? n_iters - done : batch);
@@ -4146,19 +4115,17 @@ int ddz_q_features(int device, const float* face, int64_t n_tables, int planes, 
 // ---- the learner's first layer and its whole pre-fc1 stage, forward and backward (ddz_qtrain.h) ----
 static bool qt_planes(int planes) { return planes == 4 || planes == 6 || planes == 7 || planes == 9; }
 
-// one switch over the instances: key = planes (faces) or 16 + variant (rows)
-#define QT_INSTANCES(CALL)                                                                                                       \
-  switch (key) {                                                                                                                 \
-    case 4: CALL(4, -1); break;                                                                                                  \
-    case 6: CALL(6, -1); break;                                                                                                  \
-    case 7: CALL(7, -1); break;                                                                                                  \
-    case 9: CALL(9, -1); break;                                                                                                  \
-    case 16: CALL(4, 0); break;                                                                                                  \
-    case 17: CALL(7, 1); break;                                                                                                  \
-    case 18: CALL(9, 2); break;                                                                                                  \
-    case 19: CALL(6, 3); break;                                                                                                  \
-    default: return DDZ_EINVAL;                                                                                                  \
-  }
+}  // extern "C"
+
+// one choice over the stage's instances, f(P, V): key (qt_source) = planes (faces: V = -1) or 16 + variant (rows: P = the
+// variant's planes).  (A template: outside the extern "C" block.)
+template <class F>
+static bool qt_pick(int key, F&& f) {
+  if (key < 16) return pick<4, 6, 7, 9>(key, [&](auto P) { f(P, std::integral_constant<int, -1>{}); });
+  return pick<0, 1, 2, 3>(key - 16, [&](auto V) { f(std::integral_constant<int, face_planes(V())>{}, V); });
+}
+
+extern "C" {
 
 static QtSrc qt_faces(const float* face, const float* action) {
   QtSrc s = {};
@@ -4182,13 +4149,10 @@ int ddz_q_first_fwd(int device, const float* face, const float* action, int64_t 
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
   const QtSrc src = qt_faces(face, action);
-  switch (planes) {
-    case 4: qt_launch_fwd<4, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
-    case 6: qt_launch_fwd<6, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
-    case 7: qt_launch_fwd<7, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
-    default: qt_launch_fwd<9, -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream); break;
-  }
-  return check_launch();
+  const bool known = pick<4, 6, 7, 9>(planes, [&](auto P) {
+    qt_launch_fwd<P(), -1, true>(src, n, p, nullptr, nullptr, y, arg, (hipStream_t)stream);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 int64_t ddz_q_first_bwd_ws_bytes(int64_t n, int planes) {
@@ -4213,13 +4177,10 @@ int ddz_q_first_bwd(int device, const float* face, const float* action, int64_t 
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
   const QtSrc src = qt_faces(face, action);
-  switch (planes) {
-    case 4: qt_launch_bwd<4, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
-    case 6: qt_launch_bwd<6, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
-    case 7: qt_launch_bwd<7, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
-    default: qt_launch_bwd<9, -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream); break;
-  }
-  return check_launch();
+  const bool known = pick<4, 6, 7, 9>(planes, [&](auto P) {
+    qt_launch_bwd<P(), -1, true>(src, n, gy, arg, q, nullptr, nullptr, (float*)ws, (hipStream_t)stream);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 static bool qt_source_known(const ddz_q_src_t* d) {
@@ -4269,10 +4230,10 @@ int ddz_q_stage_fwd(int device, const ddz_q_src_t* source, int64_t n, const floa
   if (n > ((int64_t)1 << 30)) return DDZ_ECAP;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
-#define QT_CALL(P, V) qt_launch_fwd<P, V, false>(src, n, p, w[4], b[4], h, arg, (hipStream_t)stream)
-  QT_INSTANCES(QT_CALL)
-#undef QT_CALL
-  return check_launch();
+  const bool known = qt_pick(key, [&](auto P, auto V) {
+    qt_launch_fwd<P(), V(), false>(src, n, p, w[4], b[4], h, arg, (hipStream_t)stream);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 int64_t ddz_q_stage_bwd_ws_bytes(int64_t n, int planes) {
@@ -4301,10 +4262,10 @@ int ddz_q_stage_bwd(int device, const ddz_q_src_t* source, int64_t n, const floa
   if (ws_bytes < qs_ws_bytes(n, planes)) return DDZ_EINVAL;
   DeviceGuard g(device);
   if (!g.ok) return DDZ_ENODEV;
-#define QT_CALL(P, V) qt_launch_bwd<P, V, false>(src, n, gh, arg, q, gw[4], gb[4], (float*)ws, (hipStream_t)stream)
-  QT_INSTANCES(QT_CALL)
-#undef QT_CALL
-  return check_launch();
+  const bool known = qt_pick(key, [&](auto P, auto V) {
+    qt_launch_bwd<P(), V(), false>(src, n, gh, arg, q, gw[4], gb[4], (float*)ws, (hipStream_t)stream);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 // ---- the "needed rows" form of the ragged Q forward (ddz_qnet.h) ----
@@ -4346,14 +4307,10 @@ int ddz_q_features_needed(int device, const float* face, int64_t n_tables, int p
   const dim3 grid((unsigned)((n_tables + QF_TILE - 1) / QF_TILE)), block(QH);
   hipStream_t st = (hipStream_t)stream;
   const float4* f = (const float4*)face;
-  switch (planes) {
-    case 4: hipLaunchKernelGGL(k_q_feat_needed<4>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y0, dy, row_capacity, row_index); break;
-    case 6: hipLaunchKernelGGL(k_q_feat_needed<6>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y0, dy, row_capacity, row_index); break;
-    case 7: hipLaunchKernelGGL(k_q_feat_needed<7>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y0, dy, row_capacity, row_index); break;
-    case 9: hipLaunchKernelGGL(k_q_feat_needed<9>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y0, dy, row_capacity, row_index); break;
-    default: return DDZ_EINVAL;
-  }
-  return check_launch();
+  const bool known = pick<4, 6, 7, 9>(planes, [&](auto P) {
+    hipLaunchKernelGGL(k_q_feat_needed<P()>, grid, block, 0, st, f, n_tables, wf, bias, acnt, y0, dy, row_capacity, row_index);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 
 int ddz_q_fc1_dense(int device, const float* a, int64_t n_rows, int64_t k, const float* w, float* c, void* stream) {
@@ -4426,10 +4383,10 @@ int ddz_q_shared_rows_hashed(ddz_env_t* e, int variant, void* ws, int64_t ws_byt
   if (hipMemsetAsync(keys, 0, (size_t)15 * R * 12, st) != hipSuccess) return DDZ_EHIP;   // keys and values: one clear
   if (hipMemsetAsync(rep, 0xFF, (size_t)row_capacity * 4, st) != hipSuccess) return DDZ_EHIP;
   const unsigned nb = (unsigned)((e->T * 16 + 255) / 256);
-  if (variant == 1)
-    hipLaunchKernelGGL(k_qs_hmark<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
-  else
-    hipLaunchKernelGGL(k_qs_hmark<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
+  const bool known = pick<1, 2>(variant, [&](auto V) {
+    hipLaunchKernelGGL(k_qs_hmark<V()>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, keys, vals, R, rows);
+  });
+  if (!known) return DDZ_EINVAL;   // (unreachable: the variant is checked above)
   launch_qs_number<false>(st, vals, cnt, base, R, cpr, seg, rep, row_capacity);
   hipLaunchKernelGGL(k_qs_rows<false>, dim3(nb), dim3(256), 0, st, (const int32_t*)vals, e->T, rows, 15 * R);
   return check_launch();
@@ -4450,12 +4407,10 @@ int ddz_q_features_rows(int device, const float* face, int64_t n_tables, int pla
   const dim3 grid((unsigned)(row_capacity / QR_TILE)), block(QH);
   hipStream_t st = (hipStream_t)stream;
   const float4* f4 = (const float4*)face;
-  switch (planes) {
-    case 6: hipLaunchKernelGGL(k_q_feat_rows<6>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
-    case 7: hipLaunchKernelGGL(k_q_feat_rows<7>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
-    default: hipLaunchKernelGGL(k_q_feat_rows<9>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g); break;
-  }
-  return check_launch();
+  const bool known = pick<6, 7, 9>(planes, [&](auto P) {
+    hipLaunchKernelGGL(k_q_feat_rows<P()>, grid, block, 0, st, f4, n_tables, wf, bias, rep, seg, ys, (int)ys_ld, mz, g);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 // the needed rows D shared as well (ddz_qnet.h section 6)
 int64_t ddz_q_shared_need_ws_bytes(int64_t shared_row_capacity) {
@@ -4499,12 +4454,10 @@ int ddz_q_features_drows(int device, const float* face, int64_t n_tables, int pl
   const dim3 grid((unsigned)(row_capacity / QR_TILE)), block(QH);
   hipStream_t st = (hipStream_t)stream;
   const float4* f4 = (const float4*)face;
-  switch (planes) {
-    case 6: hipLaunchKernelGGL(k_q_feat_drows<6>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
-    case 7: hipLaunchKernelGGL(k_q_feat_drows<7>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
-    default: hipLaunchKernelGGL(k_q_feat_drows<9>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy); break;
-  }
-  return check_launch();
+  const bool known = pick<6, 7, 9>(planes, [&](auto P) {
+    hipLaunchKernelGGL(k_q_feat_drows<P()>, grid, block, 0, st, f4, n_tables, wf, bias, acnt, rep, shared_row_capacity, drep, dseg, dy);
+  });
+  return known ? check_launch() : DDZ_EINVAL;
 }
 int ddz_q_gather_h0(int device, const float* g, int64_t g_rows, const int32_t* rows, int64_t n_tables, const float* base, float* h0,
                     void* stream) {
@@ -4597,10 +4550,10 @@ int ddz_q_roles_rows(ddz_env_t* e, int variant, const int32_t* net_of_role, int 
     int32_t* cnt = vals + (int64_t)n_nets * 15 * R;
     int32_t* base = cnt + n_nets * 15 * cpr;
     if (hipMemsetAsync(keys, 0, (size_t)n_nets * 15 * R * 12, st) != hipSuccess) return DDZ_EHIP;   // keys and values: one clear
-    if (variant == 1)
-      hipLaunchKernelGGL(k_qs_hmark_roles<1>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
-    else
-      hipLaunchKernelGGL(k_qs_hmark_roles<2>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
+    const bool known = pick<1, 2>(variant, [&](auto V) {
+      hipLaunchKernelGGL(k_qs_hmark_roles<V()>, dim3(nb), dim3(256), 0, st, (const uint8_t*)e->state, e->T, map, keys, vals, R, rows, slot);
+    });
+    if (!known) return DDZ_EINVAL;   // (unreachable: the variant is checked above)
     for (int s = 0; s < n_nets; ++s)
       launch_qs_number<false>(st, vals + (int64_t)s * 15 * R, cnt + s * 15 * cpr, base + s * 15 * cpr, R, cpr, seg + s * QN_SEG_WORDS,
                               rep + s * row_capacity, row_capacity);

@@ -497,6 +497,10 @@ def test_get_moves_slab_golden_and_csr(pkg, golden):
         goff = g["offsets"].astype(np.int64)
         want = np.concatenate([g["ids"][goff[k]:goff[k + 1]] for k in np.flatnonzero(small)]).astype(np.int32)
         assert np.array_equal(ids[take].cpu().numpy(), want)
+        counts2, rows2, ids2, status2 = pkg.get_moves_slab(h, l, want_ids=False)     # the launch without an id buffer
+        assert ids2 is None and int(status2.item()) == 0 and torch.equal(counts2, counts) and torch.equal(rows2[take], crow)
+        off2, crow2, cid2 = pkg.get_moves(h, l, want_ids=False)
+        assert cid2 is None and torch.equal(off2, off) and torch.equal(crow2, crow)
     bad_last = torch.zeros((3, 15), dtype=torch.int8); bad_last[1, 0] = 1; bad_last[1, 2] = 1     # "3 5": no combo
     hand = torch.zeros((3, 15), dtype=torch.int8); hand[:, :13] = 1; hand[2, :13] = 4; hand[2, 13:] = 1  # query 2: the full deck
     counts, rows, ids, status = pkg.get_moves_slab(hand.to(_dev()), bad_last.to(_dev()))

@@ -8,7 +8,7 @@ and last iteration.  Everything is bytes and integers against OracleEnv: every c
            (the smallest count that selects the dense 12-wave variant) and 256 tables (16-wave blocks).  With the seeds below
            2,239 of 6,144 tables (36.4 %) and 92 of 256 (35.9 %) are still in their first episode after 65 iterations; the
            oracle run asserts that there are some.  Forms: plain, with records (the last 6 iterations' records: they hold the
-           draw of ply 64), and the staged-CSR rollout (its batches are the launches).
+           draw of ply 64), and the staged-CSR rollout (its batches are the launches), without and with records.
   win      The oracle's state before the iteration of that run in which the most tables win (and some win in the one after):
            launches of 1 and of 2 iterations from it, with and without records -- win and deal on the only, the first and the
            last iteration of a launch.
@@ -88,14 +88,14 @@ def _run(oracle, T):
 
 def _lists(env, form):
     """(list sizes, the rows of all lists in table order) of the last iteration"""
-    if form == "csr":
+    if "csr" in form:
         off = _np(env.offsets).astype(np.int64)
         return np.diff(off).astype(np.int32), _np(env.rows[:int(off[-1])])
     mask = torch.arange(env.slab_stride, device=_dev())[None, :] < env.counts[:, None]
     return _np(env.counts), _np(env.slab_rows()[mask])
 
 
-@pytest.mark.parametrize("T,form", [(6144, "plain"), (256, "plain"), (6144, "records"), (6144, "csr")])
+@pytest.mark.parametrize("T,form", [(6144, "plain"), (256, "plain"), (6144, "records"), (6144, "csr"), (6144, "csr records")])
 def test_refill_inside_and_at_the_edge_of_a_launch(pkg, oracle, T, form):
     r = _run(oracle, T)
     # the precondition: episodes that run past ply 64, so the launch of 70 refills its draws in the middle of an episode
@@ -109,20 +109,20 @@ def test_refill_inside_and_at_the_edge_of_a_launch(pkg, oracle, T, form):
         assert np.array_equal(_np(env.state), r.start)
         recs = []
         for n in split:
-            traj = torch.zeros((n, T, 32), dtype=torch.uint8, device=_dev()) if form == "records" else None
-            if form == "csr":
-                env.rollout_random_csr(n)
+            traj = torch.zeros((n, T, 32), dtype=torch.uint8, device=_dev()) if "records" in form else None
+            if "csr" in form:
+                env.rollout_random_csr(n, traj=traj)
             else:
                 env.rollout_random(n, traj=traj)
             if traj is not None:
                 recs.append(traj)
         sizes, rows = _lists(env, form)
         got[name] = {"sizes": sizes, "rows": rows, "state": _np(env.state), "stats": env.stats()}
-        if form == "records":
+        if "records" in form:
             got[name]["traj"] = _np(torch.cat(recs))[ITERS - RECORDED:]
         assert env.status() == 0, name
     want = {"sizes": last["sizes"], "rows": last["rows"], "state": r.state}
-    if form == "records":
+    if "records" in form:
         want["traj"] = np.stack([s["traj"] for s in r.tail])
     for name, g in got.items():
         assert cs.differences(g, want) == [], (name, T, form)
