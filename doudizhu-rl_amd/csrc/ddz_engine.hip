@@ -14,6 +14,8 @@
 //             iteration of every (table, tree) per launch, the new leaf's state row out, its value in with the next launch.
 //   k_ismcts  (ddz_ismcts.h; ddz_ismcts) information-set MCTS: one wavefront per (table, tree), ONE tree over a fresh world per
 //             iteration, a list at every level of the descent, children keyed by (parent, count word).
+//   k_gismcts (ddz_gismcts.h; ddz_gismcts_open / _step / _close) k_ismcts's tree and descent in k_guided's phases: one iteration
+//             per launch on that iteration's world, the new leaf's state row out, its value in with the next launch.
 //   k_cfr     (ddz_cfr.h; ddz_cfr) the CFR endgame solver: one wavefront per table, the forest in a workspace slot.
 //   k_solve   (ddz_solve.h; ddz_solve) the exact endgame solver: one wavefront per (table, world, chunk), a depth-first search
 //             with its transposition table in the caller's workspace.
@@ -1389,6 +1391,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 #include "ddz_guided.h"   // k_guided / k_guided_value: UCT with leaf values from outside the kernel, one iteration per launch
 #include "ddz_ismcts.h"   // k_ismcts: information-set MCTS, one tree per (table, tree) over all its sampled worlds
+#include "ddz_gismcts.h"  // k_gismcts: k_ismcts's tree with leaf values from outside the kernel, one iteration per launch
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
 #include "ddz_solve.h"    // k_solve / k_solve_choose: exact open-hand minimax per root move, one wavefront per (table, world, chunk)
 
@@ -2916,7 +2919,7 @@ int launch_hidden(bool hidden, int64_t blocks, void* stream, const A& a) {
   else hipLaunchKernelGGL(OPEN, dim3((unsigned)blocks), dim3(WAVES * 64), 0, (hipStream_t)stream, a);
   return check_launch();
 }
-// what ddz_search, ddz_ismcts and the three ddz_guided_* launches do alike: the argument checks in their order, SearchArgs,
+// what ddz_search, ddz_ismcts and the three ddz_guided_* / ddz_gismcts_* launches do alike: the argument checks in their order, SearchArgs,
 // the launch of one wavefront per (table, tree).  tree_bytes: the workspace of one tree at this budget (asked only once the
 // budget is known to be in range).  A: the kernels' argument struct, SearchArgs or one derived from it whose own fields
 // `fill` sets; outs: the call writes visits / wins (they must be there)
@@ -2950,18 +2953,19 @@ int search_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int64_t budget, i
   if (blocks == 0) return DDZ_OK;
   return launch_hidden<OPEN, HIDDEN, SEARCH_WAVES>(hidden, blocks, stream, a);
 }
-// a launch of k_guided in `phase`: ddz_search's checks, then the unit's bound and the phase's own buffers
-int guided_launch(ddz_env* e, int phase, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, bool hidden, int roles,
-                  int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need, int32_t* visits, int32_t* wins,
-                  int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+// a launch of k_guided (OPEN / HIDDEN) or k_gismcts (both, hidden = true) in `phase`: ddz_search's checks, then the unit's
+// bound and the phase's own buffers
+template <auto OPEN, auto HIDDEN>
+int guided_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int phase, int64_t budget, int64_t trees, int mode, float c,
+                  uint64_t salt, bool hidden, int roles, int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need,
+                  int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
   if (!good(e)) return DDZ_EHANDLE;
   if (!al(values, 4) || !al(leaf_rows, 16) || !al(need, 4)) return DDZ_EINVAL;
   if (phase == GUIDED_STEP && (!leaf_rows || !need)) return DDZ_EINVAL;
   if (budget >= 1 && trees >= 1 && budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return DDZ_EINVAL;   // the int32 root sums
   const auto fill = [=](GuidedArgs& a) { a.phase = phase; a.values = values; a.leaf_rows = leaf_rows; a.need = need; };
-  return search_launch<k_guided<false>, k_guided<true>, GuidedArgs>(e, guided_tree_bytes, budget, trees, mode, c, salt, hidden, roles,
-                                                                    stride, visits, wins, totals, work, work_bytes, stream,
-                                                                    phase == GUIDED_CLOSE, fill);
+  return search_launch<OPEN, HIDDEN, GuidedArgs>(e, tree_bytes, budget, trees, mode, c, salt, hidden, roles, stride, visits, wins, totals,
+                                                 work, work_bytes, stream, phase == GUIDED_CLOSE, fill);
 }
 // a *_choose kernel over the env's tables, `per` tables to a block of BLOCK threads
 template <auto K, typename... Q>
@@ -3704,22 +3708,51 @@ int64_t ddz_guided_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
 
 int ddz_guided_open(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
                     int64_t stride, void* work, int64_t work_bytes, void* stream) {
-  return guided_launch(e, GUIDED_OPEN, budget, trees, mode, c, salt, hidden != 0, roles, stride, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, work, work_bytes, stream);
+  return guided_launch<k_guided<false>, k_guided<true>>(e, guided_tree_bytes, GUIDED_OPEN, budget, trees, mode, c, salt, hidden != 0,
+                                                        roles, stride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, work,
+                                                        work_bytes, stream);
 }
 
 int ddz_guided_step(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
                     int64_t stride, const int32_t* values, uint8_t* leaf_rows, int32_t* need, void* work, int64_t work_bytes,
                     void* stream) {
-  return guided_launch(e, GUIDED_STEP, budget, trees, mode, c, salt, hidden != 0, roles, stride, values, leaf_rows, need, nullptr,
-                       nullptr, nullptr, work, work_bytes, stream);
+  return guided_launch<k_guided<false>, k_guided<true>>(e, guided_tree_bytes, GUIDED_STEP, budget, trees, mode, c, salt, hidden != 0,
+                                                        roles, stride, values, leaf_rows, need, nullptr, nullptr, nullptr, work,
+                                                        work_bytes, stream);
 }
 
 int ddz_guided_close(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
                      const int32_t* values, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
                      int64_t work_bytes, void* stream) {
-  return guided_launch(e, GUIDED_CLOSE, budget, trees, mode, c, salt, hidden != 0, roles, stride, values, nullptr, nullptr, visits,
-                       wins, totals, work, work_bytes, stream);
+  return guided_launch<k_guided<false>, k_guided<true>>(e, guided_tree_bytes, GUIDED_CLOSE, budget, trees, mode, c, salt, hidden != 0,
+                                                        roles, stride, values, nullptr, nullptr, visits, wins, totals, work,
+                                                        work_bytes, stream);
+}
+
+// ddz_gismcts_*: k_gismcts in its three phases, always the hidden form; ddz_guided_*'s checks and codes
+int64_t ddz_gismcts_work_bytes(int64_t n_tables, int64_t budget, int64_t trees) {
+  if (n_tables < 0 || budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return -1;
+  if (budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return -1;
+  return (int64_t)gismcts_tree_bytes(budget) * n_tables * trees;
+}
+
+int ddz_gismcts_open(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+                     void* work, int64_t work_bytes, void* stream) {
+  return guided_launch<k_gismcts, k_gismcts>(e, gismcts_tree_bytes, GUIDED_OPEN, budget, trees, mode, c, salt, true, roles, stride,
+                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_gismcts_step(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+                     const int32_t* values, uint8_t* leaf_rows, int32_t* need, void* work, int64_t work_bytes, void* stream) {
+  return guided_launch<k_gismcts, k_gismcts>(e, gismcts_tree_bytes, GUIDED_STEP, budget, trees, mode, c, salt, true, roles, stride,
+                                             values, leaf_rows, need, nullptr, nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_gismcts_close(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles,
+                      const int32_t* values, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
+                      int64_t work_bytes, void* stream) {
+  return guided_launch<k_gismcts, k_gismcts>(e, gismcts_tree_bytes, GUIDED_CLOSE, budget, trees, mode, c, salt, true, roles, stride,
+                                             values, nullptr, nullptr, visits, wins, totals, work, work_bytes, stream);
 }
 
 int ddz_guided_values(int device, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,

@@ -22,7 +22,8 @@
 // look up 64 staged entries each.  Both orders ascend with the lane, so a ballot ranks the entries without a child.  Pass 1
 // counts them, keeps each lane's best selectable child and raises A of every child it finds (each child is found by one lane,
 // once per iteration: the values use the counts of before); only then the wave decides.  Expansion runs the lookups a second
-// time to find the r-th entry without a child.
+// time to find the r-th entry without a child.  Pass 1, that ranking and the selection's reduce are the functions ismcts_pass1
+// / ismcts_untried / ismcts_select below: k_gismcts (ddz_gismcts.h) calls them too, with W in 1024ths.
 //
 // LOOPS, MEMORY ORDERING: as ddz_search.h.  Every loop is counted (iterations by budget, the descent by
 // DDZ_SEARCH_MAX_DEPTH, a probe by H, the trips by n <= STAGE_CAP, the playout by DDZ_PLAYOUT_MAX_PLIES); a wave waits for no
@@ -90,6 +91,75 @@ __device__ __forceinline__ int ismcts_lane_entry(int trip, uint64_t okm, int n0,
   if (k >= n - n0) return -1;
   nib = stage[k] & NIB60;
   return n0 + k;
+}
+
+// pass 1 of a descent step at `node`, over the list ply_list left (trips = 1 + the staged trips): the child of every entry is
+// looked up; the entries without one are counted (-> untried, wave-uniform), every child found has its A raised, and each
+// lane keeps the best of its selectable children (value on the counts of BEFORE; bits, list index, child: at = SEARCH_NONE
+// where the lane has none).  ONE: the unit W is counted in (search_value's).  Shared by k_ismcts and k_gismcts.
+template <uint32_t ONE = 1>
+__device__ __forceinline__ uint32_t ismcts_pass1(uint8_t* nodes, const uint64_t* tab, uint32_t hlog, uint32_t nnodes, uint32_t node,
+                                                 int trips, uint64_t okm, int n0, int n, uint32_t info, const uint64_t* stage, int lane,
+                                                 const float* ln, float c, bool own, bool sides, uint32_t& best, uint32_t& at,
+                                                 uint32_t& bchild) {
+  const bool take_max = own || sides;
+  uint32_t untried = 0;
+  best = 0; at = SEARCH_NONE; bchild = SEARCH_NONE;
+  for (int trip = 0; trip < trips; ++trip) {
+    uint64_t nib;
+    const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
+    uint32_t ch = SEARCH_NONE;
+    if (j >= 0) ch = ismcts_find(nodes, tab, hlog, nnodes, node, nib);
+    untried += (uint32_t)__builtin_popcountll(__ballot(j >= 0 && ch == SEARCH_NONE));
+    if (ch != SEARCH_NONE) {
+      uint8_t* cr = nodes + (uint64_t)ch * INODE_BYTES;
+      const uint64_t vw = sld64((const uint64_t*)(cr + 8));
+      const uint32_t V = (uint32_t)vw, W = (uint32_t)(vw >> 32);
+      const uint32_t A = sld32((const uint32_t*)(cr + 16));
+      sst32((uint32_t*)(cr + 16), A + 1u);
+      if (V > 0) {
+        const float two_ln = 2.0f * ln[A <= (uint32_t)DDZ_SEARCH_MAX_BUDGET ? A : (uint32_t)DDZ_SEARCH_MAX_BUDGET];
+        // (values are non-negative floats: their bit patterns order as they do)
+        const uint32_t bits = __float_as_uint(search_value<ONE>(own ? W : (sides ? V * ONE - W : W), V, two_ln, c));
+        if (at == SEARCH_NONE || (take_max ? bits > best : bits < best)) { best = bits; at = (uint32_t)j; bchild = ch; }
+      }
+    }
+  }
+  return rfl(untried);
+}
+
+// the expansion's list index: the r-th entry without a child, ascending (r < untried, wave-uniform: a second run of the
+// lookups); -1 where there is none (cannot happen)
+__device__ __forceinline__ int ismcts_untried(const uint8_t* nodes, const uint64_t* tab, uint32_t hlog, uint32_t nnodes, uint32_t node,
+                                              int trips, uint64_t okm, int n0, int n, uint32_t info, const uint64_t* stage, int lane,
+                                              uint32_t untried, uint32_t r) {
+  if (untried == (uint32_t)n) return (int)r;
+  for (int trip = 0; trip < trips; ++trip) {
+    uint64_t nib;
+    const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
+    bool open = false;
+    if (j >= 0) open = ismcts_find(nodes, tab, hlog, nnodes, node, nib) == SEARCH_NONE;
+    const uint64_t um = __ballot(open);
+    const uint32_t cnt = (uint32_t)__builtin_popcountll(um);
+    if (r < cnt) {
+      const uint64_t below = um & ((1ull << lane) - 1ull);
+      const uint64_t hit = __ballot(open && (uint32_t)__builtin_popcountll(below) == r);
+      return (int)rl((uint32_t)j, (int)__builtin_ctzll(hit));
+    }
+    r -= cnt;
+  }
+  return -1;
+}
+
+// the selection among the lanes' bests of pass 1 (get_bestchild.py:20-32 with A for N): the maximum (take_max) or the minimum,
+// ties to the lowest index of the list -> that index, SEARCH_NONE where no lane holds one; child: its node (wave-uniform)
+__device__ __forceinline__ uint32_t ismcts_select(bool take_max, uint32_t best, uint32_t at, uint32_t bchild, uint32_t& child) {
+  uint32_t m;
+  if (take_max) m = (uint32_t)wave_max_i32(at == SEARCH_NONE ? (int)0x80000000 : (int)best);
+  else m = wave_min_u32(at == SEARCH_NONE ? 0xFFFFFFFFu : best);
+  const uint32_t first = wave_min_u32((at != SEARCH_NONE && best == m) ? at : SEARCH_NONE);   // ties: the lowest index
+  child = first == SEARCH_NONE ? SEARCH_NONE : rfl(wave_min_u32((at == first) ? bchild : SEARCH_NONE));
+  return first;
 }
 
 __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
@@ -165,53 +235,16 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
       if (n <= 0) break;   // outside the domain: unfinished
       const int trips = 1 + (n - n0 + 63) / 64;
       // ---- pass 1: every entry's child; the entries without one counted, the best of the others kept, their A raised
-      const bool own = a.mode == (uint32_t)DDZ_SEARCH_SIDES ? same_side(role, role0) : (role == role0);
-      const bool take_max = own || a.mode == (uint32_t)DDZ_SEARCH_SIDES;
-      uint32_t untried = 0, best = 0, at = SEARCH_NONE, bchild = SEARCH_NONE;
-      for (int trip = 0; trip < trips; ++trip) {
-        uint64_t nib;
-        const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
-        uint32_t ch = SEARCH_NONE;
-        if (j >= 0) ch = ismcts_find(nodes, tab, hlog, nnodes, node, nib);
-        untried += (uint32_t)__builtin_popcountll(__ballot(j >= 0 && ch == SEARCH_NONE));
-        if (ch != SEARCH_NONE) {
-          uint8_t* cr = nodes + (uint64_t)ch * INODE_BYTES;
-          const uint64_t vw = sld64((const uint64_t*)(cr + 8));
-          const uint32_t V = (uint32_t)vw, W = (uint32_t)(vw >> 32);
-          const uint32_t A = sld32((const uint32_t*)(cr + 16));
-          sst32((uint32_t*)(cr + 16), A + 1u);
-          if (V > 0) {
-            const float two_ln = 2.0f * a.ln[A <= (uint32_t)DDZ_SEARCH_MAX_BUDGET ? A : (uint32_t)DDZ_SEARCH_MAX_BUDGET];
-            // (values are non-negative floats: their bit patterns order as they do)
-            const uint32_t bits = __float_as_uint(search_value(own ? W : (a.mode == (uint32_t)DDZ_SEARCH_SIDES ? V - W : W), V, two_ln, a.c));
-            if (at == SEARCH_NONE || (take_max ? bits > best : bits < best)) { best = bits; at = (uint32_t)j; bchild = ch; }
-          }
-        }
-      }
-      untried = rfl(untried);
+      const bool sides = a.mode == (uint32_t)DDZ_SEARCH_SIDES;
+      const bool own = sides ? same_side(role, role0) : (role == role0);
+      uint32_t best, at, bchild;
+      const uint32_t untried = ismcts_pass1(nodes, tab, hlog, nnodes, node, trips, okm, n0, n, info, stage, lane, a.ln, a.c, own, sides,
+                                            best, at, bchild);
       if (untried > 0) {
         // ---- expansion: the (draw_e * |U|) >> 32-th entry without a child, ascending
         const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
-        uint32_t r = rfl(__umulhi(de, untried));
-        int idx = -1;
-        if (untried == (uint32_t)n) idx = (int)r;
-        else {
-          for (int trip = 0; trip < trips; ++trip) {
-            uint64_t nib;
-            const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
-            bool open = false;
-            if (j >= 0) open = ismcts_find(nodes, tab, hlog, nnodes, node, nib) == SEARCH_NONE;
-            const uint64_t um = __ballot(open);
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(um);
-            if (r < cnt) {
-              const uint64_t below = um & ((1ull << lane) - 1ull);
-              const uint64_t hit = __ballot(open && (uint32_t)__builtin_popcountll(below) == r);
-              idx = (int)rl((uint32_t)j, (int)__builtin_ctzll(hit));
-              break;
-            }
-            r -= cnt;
-          }
-        }
+        const int idx = ismcts_untried(nodes, tab, hlog, nnodes, node, trips, okm, n0, n, info, stage, lane, untried,
+                                       rfl(__umulhi(de, untried)));
         if (idx < 0 || idx >= n) break;   // (cannot happen: `untried` entries without a child exist)
         uint64_t snib; uint32_t scat, svlv;
         ply_entry(okm, n0, idx, info, stage, svl, snib, scat, svlv);
@@ -264,12 +297,9 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
         break;
       }
       // ---- selection among the children whose moves are in this world's list (get_bestchild.py:20-32 with A for N)
-      uint32_t m;
-      if (take_max) m = (uint32_t)wave_max_i32(at == SEARCH_NONE ? (int)0x80000000 : (int)best);
-      else m = wave_min_u32(at == SEARCH_NONE ? 0xFFFFFFFFu : best);
-      const uint32_t first = wave_min_u32((at != SEARCH_NONE && best == m) ? at : SEARCH_NONE);   // ties: the lowest index
+      uint32_t child;
+      const uint32_t first = ismcts_select(own || sides, best, at, bchild, child);
       if (first == SEARCH_NONE) break;   // (cannot happen: every child was backed up when it was made)
-      const uint32_t child = rfl(wave_min_u32((at == first) ? bchild : SEARCH_NONE));
       uint64_t snib; uint32_t scat, svlv;
       ply_entry(okm, n0, (int)first, info, stage, svl, snib, scat, svlv);
       s_moves += 1;

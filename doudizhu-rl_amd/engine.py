@@ -918,6 +918,26 @@ class BatchedEnv:
         return self._choose_ratio(*self.guided(budget, trees=trees, mode=mode, c=c, salt=salt, hidden=hidden, roles=roles).run(evaluator),
                                   out)
 
+    # ---- information-set MCTS with leaf values from outside the kernel (search spec v4) ----
+    def guided_ismcts(self, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111):
+        """Opens a guided ISMCTS search on every running table (search spec v4): ismcts()'s trees -- ONE tree per
+        (table, tree) over all of its worlds, iteration i of tree c on world c * budget + i, every step of the descent on the
+        list of that world, the child's availability count in the bonus -- judged as guided()'s are: the score of a new
+        non-terminal leaf is a value the caller hands in, one launch runs one iteration, and the leaf row holds that
+        iteration's world as the opponents' hands.  Always the hidden form: the search a seat can run with a network.
+        -> a GuidedSearch, used exactly as guided()'s (PlayoutLeaf and dqn_glue.QLeaf serve as they are); budget * trees *
+        1024 must stay below 2^31; the same one-open-search-per-environment rule, shared with guided()."""
+        if getattr(self, "_guided_pending", None) is not None:
+            raise RuntimeError("a guided search is open on this environment's workspace: close() it first")
+        return GuidedSearch(self, budget, trees, mode, c, salt, True, roles, ismcts=True)
+
+    def guided_ismcts_choose(self, evaluator, budget, trees=None, mode="reference", c=0.7, salt=0, roles=0b111, out=None):
+        """The guided-ISMCTS move of every table: int32 [T] canonical action ids, search_choose()'s rule on
+        guided_ismcts(...).run(evaluator)'s root statistics; -1 where nothing was visited.  Feed them to
+        step_slab(mode=STEP_IDS)."""
+        out = self._choose_out("guided_ismcts_choose", out)
+        return self._choose_ratio(*self.guided_ismcts(budget, trees=trees, mode=mode, c=c, salt=salt, roles=roles).run(evaluator), out)
+
     # ---- the CFR endgame solver (CFR spec v1, DESIGN.md 4) ----
     CFR_STRIDE = 16
     CFR_MAX_ITERATIONS = 64
@@ -1116,8 +1136,9 @@ class BatchedEnv:
 
 
 class GuidedSearch:
-    """One open guided UCT search of a BatchedEnv (search spec v3; BatchedEnv.guided makes it).  Item k =
-    t * trees + c is tree c of table t.
+    """One open guided search of a BatchedEnv: guided UCT (search spec v3; BatchedEnv.guided makes it) or guided
+    ISMCTS (search spec v4; BatchedEnv.guided_ismcts makes it: the same fields and calls, ddz_gismcts_*'s entry points and
+    workspace).  Item k = t * trees + c is tree c of table t.
       leaves  uint8 [T * trees, 11, 16]: after step(), the state row of every item's pending leaf (an all-zero row, dealt = 0,
               where the item waits for nothing: a leaf environment that imports them freezes those)
       need    int32 [T * trees]: 1 where the item waits for a value
@@ -1128,10 +1149,12 @@ class GuidedSearch:
     the host: a whole run can be captured in a graph.  The environment must not change between guided() and close().
     step() after close(), or a second close(), raises RuntimeError without touching the device."""
 
-    def __init__(self, env, budget, trees, mode, c, salt, hidden, roles):
+    def __init__(self, env, budget, trees, mode, c, salt, hidden, roles, ismcts=False):
         self.env = env
-        self.roles = _roles_mask(roles, hidden)
-        self.hidden = bool(hidden)
+        self.ismcts = bool(ismcts)
+        self.hidden = bool(hidden) or self.ismcts
+        self.roles = _roles_mask(roles, self.hidden)
+        self._verb = "ddz_gismcts" if self.ismcts else "ddz_guided"
         self.budget, self.trees, self.c, self._visits, self._wins = env._search_args("guided needs", budget, trees, mode, c, None, None,
                                                                                     None)
         if self.budget * self.trees * env.GUIDED_ONE >= 1 << 31:
@@ -1144,13 +1167,18 @@ class GuidedSearch:
         self.values = torch.zeros(n, dtype=torch.int32, device=env.device)
         self.steps = 0
         self.closed = False
-        self._work = env._workspace("_guided_work", int(env.lib.ddz_guided_work_bytes(env.T, self.budget, self.trees)))
-        check(env.lib.ddz_guided_open(env._h, *self._common(), env.slab_stride, _p(self._work), self._work.numel(),
-                                      _stream(env.device)))
+        self._work = env._workspace("_gismcts_work" if self.ismcts else "_guided_work",
+                                    int(self._fn("work_bytes")(env.T, self.budget, self.trees)))
+        check(self._fn("open")(env._h, *self._common(), env.slab_stride, _p(self._work), self._work.numel(), _stream(env.device)))
         env._guided_pending = self
 
+    def _fn(self, phase):
+        """the entry point of `phase`: ddz_guided_*'s, or ddz_gismcts_*'s (the same arguments without `hidden`)"""
+        return getattr(self.env.lib, f"{self._verb}_{phase}")
+
     def _common(self):
-        return self.budget, self.trees, self.mode, self.c, self.salt, int(self.hidden), self.roles
+        head = (self.budget, self.trees, self.mode, self.c, self.salt)
+        return head + (self.roles,) if self.ismcts else head + (int(self.hidden), self.roles)
 
     def _values(self):
         return self.env._arg(self.values, "values", torch.int32, numel=self.n_items)
@@ -1163,8 +1191,8 @@ class GuidedSearch:
         values = self._values()
         env._arg(self.leaves, "leaves", torch.uint8, numel=self.n_items * NFIELDS * ROW)
         env._arg(self.need, "need", torch.int32, numel=self.n_items)
-        check(env.lib.ddz_guided_step(env._h, *self._common(), env.slab_stride, _p(values) if self.steps else None,
-                                      _p(self.leaves), _p(self.need), _p(self._work), self._work.numel(), _stream(env.device)))
+        check(self._fn("step")(env._h, *self._common(), env.slab_stride, _p(values) if self.steps else None,
+                               _p(self.leaves), _p(self.need), _p(self._work), self._work.numel(), _stream(env.device)))
         self.steps += 1
         return self.leaves, self.need
 
@@ -1178,9 +1206,9 @@ class GuidedSearch:
         env._totals(totals)
         self._visits.zero_()
         self._wins.zero_()
-        check(env.lib.ddz_guided_close(env._h, *self._common(), _p(values) if self.steps else None, env.slab_stride,
-                                       _p(self._visits), _p(self._wins), _p(totals), _p(self._work), self._work.numel(),
-                                       _stream(env.device)))
+        check(self._fn("close")(env._h, *self._common(), _p(values) if self.steps else None, env.slab_stride,
+                                _p(self._visits), _p(self._wins), _p(totals), _p(self._work), self._work.numel(),
+                                _stream(env.device)))
         self.closed = True
         env._guided_pending = None
         return self._visits.view(env.T, env.slab_stride), self._wins.view(env.T, env.slab_stride)
@@ -1364,15 +1392,16 @@ cached on the env: the next evaluate() overwrites them."""
 
 class Teacher:
     """One of the evaluators as a source of training targets and of moves (teacher spec v1): kind "playout"
-    (BatchedEnv.playout), "search", "ismcts", "guided" (BatchedEnv.guided(...).run(evaluator); needs evaluator=, e.g.
-    PlayoutLeaf or dqn_glue.QLeaf) or "solve"; the keyword arguments are the evaluator's own (n_playouts, budget, trees,
-    hidden, roles, salt, ...) and are passed through.  evaluate(env) runs the evaluator once on env's current states and
+    (BatchedEnv.playout), "search", "ismcts", "guided" / "guided_ismcts" (BatchedEnv.guided(...) / guided_ismcts(...)
+    .run(evaluator); they need evaluator=, e.g. PlayoutLeaf or dqn_glue.QLeaf; "guided_ismcts" is always hidden) or "solve";
+    the keyword arguments are the evaluator's own (n_playouts, budget, trees, hidden, roles, salt, ...) and are passed through.  evaluate(env) runs the evaluator once on env's current states and
     returns TeacherStats; choose(env, stats) turns THE SAME statistics into moves with the evaluator's own rule
     (ddz_playout_choose / ddz_search_choose / ddz_solve_choose): no second search.  Nothing here touches the host, so both
     can be captured.  hidden is the caller's choice: labels from open hands (hidden=False, what playout / search / solve
     default to) are legitimate for training a network that only sees its own face, not for serving moves to a seat."""
     KINDS = {"playout": ("playout", ("n_playouts",)), "search": ("search", ("budget",)), "ismcts": ("ismcts", ("budget",)),
-             "guided": ("guided", ("budget",)), "solve": ("solve", ())}
+             "guided": ("guided", ("budget",)), "guided_ismcts": ("guided_ismcts", ("budget",)), "solve": ("solve", ())}
+    GUIDED = ("guided", "guided_ismcts")     # the kinds that take a leaf evaluator
     _BUFFERS = ("self", "wins", "visits", "totals", "out")
 
     def __init__(self, kind, evaluator=None, **kwargs):
@@ -1387,10 +1416,10 @@ class Teacher:
         missing = [p for p in required if p not in kwargs]
         if missing:
             raise ValueError(f"{kind} needs {', '.join(missing)}")
-        if (kind == "guided") != (evaluator is not None):
-            raise ValueError("evaluator= is the leaf evaluator of kind \"guided\", and of no other kind")
+        if (kind in self.GUIDED) != (evaluator is not None):
+            raise ValueError("evaluator= is the leaf evaluator of the kinds \"guided\" and \"guided_ismcts\", and of no other kind")
         self.kind, self.evaluator, self.kwargs = kind, evaluator, dict(kwargs)
-        hidden = kind == "ismcts" or bool(kwargs.get("hidden", False))
+        hidden = kind in ("ismcts", "guided_ismcts") or bool(kwargs.get("hidden", False))
         self.roles = _roles_mask(kwargs.get("roles", 0b111), hidden)
 
     # kind: the verb's statistics, each flat, as TeacherStats' (counts, num, den, den_const, unknown, scale)
@@ -1398,13 +1427,17 @@ class Teacher:
               "search": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, 1),
               "ismcts": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, 1),
               "guided": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
+              "guided_ismcts": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
               # its own n as the list sizes: a table that is no endgame (n <= 0) emits nothing
               "solve": lambda env, kw, n, wins, unknown: (n, wins, None, int(kw.get("worlds", 1)), unknown, 1)}
 
     def evaluate(self, env):
         """run the evaluator on env's current states -> TeacherStats (the slab lists are made current by the evaluator)"""
         kw, kind = self.kwargs, self.kind
-        got = [x.view(-1) for x in env.guided(**kw).run(self.evaluator)] if kind == "guided" else env._run_kept(kind, **kw)
+        if kind in self.GUIDED:
+            got = [x.view(-1) for x in getattr(env, kind)(**kw).run(self.evaluator)]
+        else:
+            got = env._run_kept(kind, **kw)
         return TeacherStats(*self._STATS[kind](env, kw, *got), self.roles)
 
     def choose(self, env, stats, out=None):

@@ -231,6 +231,17 @@ def guided_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, tre
                 lambda env: env.guided_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt, hidden=True))[0]
 
 
+def guided_ismcts_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, trees=None, mode="reference", c=0.7):
+    """Guided ISMCTS for a batch of PLAIN serving payloads (no hand_card; one that is there is not read): every request is
+    packed by payloads_to_playout_state and searched by BatchedEnv.guided_ismcts_choose (search spec v4: `trees` trees of
+    `budget` iterations of one launch each, every iteration on a fresh deal of the cards the requester has not seen, every
+    new leaf judged by `evaluator` as in guided_act), and the root move with the best value for the requester's side is
+    returned -- per request a list of rank values 3..17 ([] = pass), or None where the request has no move (a finished
+    game).  ValueError where cur_cards, history and left do not add up to a deck."""
+    return _act(payloads, True, device, seed, "hidden-hand",
+                lambda env: env.guided_ismcts_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt))[0]
+
+
 def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=False):
     """The reference's final_card(payload) (server/CFR.py:520-538) for a batch of PLAIN serving payloads (no hand_card): every
     request is packed by payloads_to_playout_state, solved by BatchedEnv.cfr (CFR spec v1: `iterations` iterations of

@@ -8,6 +8,7 @@ them.  Prints both win rates from env.stats().
   python examples/flat_mc.py --search BUDGET [--trees 1] [--mode reference] [--tables 256] [--iterations 200]
   python examples/flat_mc.py --ismcts BUDGET [--trees 1] [--uct-trees 16] [--mode reference] [--tables 256] [--iterations 200]
   python examples/flat_mc.py --guided BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 4] [--tables 256] [--iterations 200]
+  python examples/flat_mc.py --guided-ismcts BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 1] [--uct-trees 4] [--tables 256]
 
 --hidden: the playouts do not read the farmers' hands; they run on hands dealt anew, per playout number, from the cards the
 lord has not seen (playout spec v2, BatchedEnv.playout_choose(hidden=True, roles=0b010): only the lord's tables are
@@ -31,6 +32,12 @@ hands, one launch per iteration, every new leaf judged by --leaf: `playout` = en
 dqn_glue.QLeaf on an UNTRAINED network of face variant 3 for every role, which is not expected to win) against the RULE farmers
 -- beside the determinized-UCT lord of search_choose(hidden=True) at the same budget and trees against the same farmers.  The
 win rates are printed with their game counts; nothing in this repository's notes has measured them.
+
+--guided-ismcts BUDGET: a guided-ISMCTS lord (BatchedEnv.guided_ismcts_choose, search spec v4: --trees trees of BUDGET
+iterations, every iteration on a fresh deal of the cards the lord has not seen, one launch per iteration, every new leaf judged
+by --leaf as above) against the RULE farmers -- beside a guided-UCT lord with the same evaluator and the same total iterations
+per move split over --uct-trees worlds, and an ISMCTS lord (random playouts) at the same trees and budget, for example 1 x 256
+against 4 x 64 and 1 x 256.  Printed with their game counts; one run is an observation, not a measurement.
 
 The playouts are computed for every table on every iteration and used where the lord is to move (the other tables take -1 =
 the engine's random move): simple, and three times the work a loop that asks only for the lord's tables would do.
@@ -90,18 +97,43 @@ def hidden_match(pkg, a, dev, ismcts):
     return env.stats()
 
 
+def make_leaf(pkg, a, dev):
+    """--leaf: engine.PlayoutLeaf(--leaf-playouts), or dqn_glue.QLeaf on one untrained network for the three roles"""
+    if a.leaf == "q":
+        torch.manual_seed(a.seed)
+        net = pkg.dqn_glue.QNet(pkg.FACE_PLANES[3]).to(dev).eval()
+        return pkg.QLeaf({"lord": net, "down": net, "up": net}, 3)
+    return pkg.PlayoutLeaf(a.leaf_playouts)
+
+
+def guided_ismcts_match(pkg, a, dev, lord_kind):
+    """the lord by guided ISMCTS ("v4": trees x budget), by guided UCT ("v3": uct_trees x the same total / uct_trees, the same
+    evaluator) or by ISMCTS with its random playout ("v2": trees x budget), all on sampled hands; the farmers by the rule agent"""
+    env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
+    env.reset()
+    lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    leaf = make_leaf(pkg, a, dev)
+    uct_budget = max(1, a.guided_ismcts * a.trees // a.uct_trees)
+    for it in range(a.iterations):
+        leaf.salt = it
+        if lord_kind == "v4":
+            env.guided_ismcts_choose(leaf, a.guided_ismcts, trees=a.trees, mode=a.mode, salt=it, roles=0b010, out=lord)
+        elif lord_kind == "v3":
+            env.guided_choose(leaf, uct_budget, trees=a.uct_trees, mode=a.mode, salt=it, hidden=True, roles=0b010, out=lord)
+        else:
+            env.ismcts_choose(a.guided_ismcts, trees=a.trees, mode=a.mode, salt=it, roles=0b010, out=lord)
+        env.step_slab(torch.where(env.role == 1, lord, env.auto_choose(0b101)), pkg.STEP_IDS, auto_reset=True)
+    assert env.status() == 0
+    return env.stats()
+
+
 def guided_match(pkg, a, dev, guided):
     """the lord by guided UCT (guided=True) or by determinized UCT at the same budget and trees, both on sampled hands; the
     farmers by the rule agent"""
     env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
     env.reset()
     lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
-    if a.leaf == "q":
-        torch.manual_seed(a.seed)
-        net = pkg.dqn_glue.QNet(pkg.FACE_PLANES[3]).to(dev).eval()
-        leaf = pkg.QLeaf({"lord": net, "down": net, "up": net}, 3)
-    else:
-        leaf = pkg.PlayoutLeaf(a.leaf_playouts)
+    leaf = make_leaf(pkg, a, dev)
     for it in range(a.iterations):
         if guided:
             leaf.salt = it
@@ -124,14 +156,28 @@ def main():
     ap.add_argument("--search", type=int, default=0, metavar="BUDGET", help="a UCT lord against flat Monte-Carlo farmers")
     ap.add_argument("--ismcts", type=int, default=0, metavar="BUDGET", help="an ISMCTS lord against the rule farmers")
     ap.add_argument("--guided", type=int, default=0, metavar="BUDGET", help="a guided-UCT lord against the rule farmers")
-    ap.add_argument("--leaf", default="playout", choices=("playout", "q"), help="--guided: the leaf evaluator")
+    ap.add_argument("--guided-ismcts", type=int, default=0, metavar="BUDGET", help="a guided-ISMCTS lord against the rule farmers")
+    ap.add_argument("--leaf", default="playout", choices=("playout", "q"), help="--guided / --guided-ismcts: the leaf evaluator")
     ap.add_argument("--leaf-playouts", type=int, default=4, help="--guided --leaf playout: playouts per move of a leaf")
     ap.add_argument("--trees", type=int, default=1, help="--search / --ismcts / --guided: trees per table")
-    ap.add_argument("--uct-trees", type=int, default=16, help="--ismcts: worlds of the determinized-UCT lord beside it")
+    ap.add_argument("--uct-trees", type=int, default=None,
+                    help="--ismcts / --guided-ismcts: worlds of the UCT lord beside it (default 16 / 4)")
     ap.add_argument("--mode", default="reference", choices=("reference", "sides"), help="--search / --ismcts: the selection rule")
     a = ap.parse_args()
     pkg = importlib.import_module("doudizhu-rl_amd")
     dev = torch.device("cuda:0")
+    if a.uct_trees is None:
+        a.uct_trees = 4 if a.guided_ismcts else 16
+    if a.guided_ismcts:
+        uct_budget = max(1, a.guided_ismcts * a.trees // a.uct_trees)
+        for kind, name in (("v4", f"guided-ISMCTS lord ({a.trees} x {a.guided_ismcts} iterations, leaf {a.leaf}, mode {a.mode})"),
+                           ("v3", f"guided-UCT lord ({a.uct_trees} x {uct_budget} iterations, leaf {a.leaf})"),
+                           ("v2", f"ISMCTS lord ({a.trees} x {a.guided_ismcts} iterations, random playouts)")):
+            t0 = time.perf_counter()
+            st = guided_ismcts_match(pkg, a, dev, kind)
+            dt = time.perf_counter() - t0
+            print(f"{name} vs rule farmers: {rates(st)}  [{dt / a.iterations * 1e3:.2f} ms per iteration at {a.tables} tables]")
+        return
     if a.guided:
         t0 = time.perf_counter()
         gd = guided_match(pkg, a, dev, True)

@@ -537,6 +537,34 @@ int ddz_guided_close(ddz_env_t* env, int64_t budget, int64_t trees, int mode, fl
 int ddz_guided_values(int device_id, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
                       const float* inv_reward, int net_roles, int32_t* values, void* stream);
 
+/* Information-set MCTS with leaf values from outside the kernel: "search spec v4 (guided ISMCTS)" (DESIGN.md 4).  ddz_ismcts's
+ * tree and descent in ddz_guided_*'s phases, unit and leaf value: no tree is built with full knowledge of one deal, and a
+ * network (or anything else) judges the leaves.  Everything not named here is ddz_ismcts's for the tree (always the hidden
+ * form, the `roles` gate, the domain with status bit 6, nodes keyed by (parent, move) with V, W and the availability count A,
+ * the descent enumerating the list of the state in this iteration's world, A += 1 for every existing child in that list, the
+ * child's own A in the bonus, the expansion draw of domain 6 on (gid, c << 16 | i)) and ddz_guided_*'s for the launches (open /
+ * step / close, W in 1024ths, budget * trees * 1024 < 2^31 else DDZ_EINVAL, the clamped value scored v or 1024 - v by the leaf
+ * actor's side, the leaf row, need, the backup at the start of the next launch or in close).
+ *   The step that runs iteration i of tree c deals world c * budget + i of playout spec v2 itself; there are no playout
+ *     draws.  Selection value: ((float)W / (float)V) * 2^-10 + c * sqrt((2 * LN[A]) / V), nothing fused; DDZ_SEARCH_SIDES away
+ *     from the root's side uses V * 1024 - W.  A new child has A = 1; one whose move empties a hand is terminal, scores 1024
+ *     or 0 and is backed up in the same launch; any other is a pending leaf whose row holds this iteration's world as the two
+ *     opponents' hands (its list is not enumerated).  An empty list or DDZ_SEARCH_MAX_DEPTH below the root: score 0, unfinished.
+ *   ddz_gismcts_close: backs up the last pending leaf, then visits / wins [T * stride] += the V / W (1024ths) of the root's
+ *     children at their index of the root's own list (the same in every world), totals += {moves applied, iterations run,
+ *     unfinished, nodes created}.  ddz_search_choose serves as the chooser.
+ *   work: >= ddz_gismcts_work_bytes(T, budget, trees) bytes, 16-byte aligned, the same buffer for open, every step and close;
+ *     per tree ddz_ismcts's nodes and table, a 64-byte header and the stored path.  A launch that finds a header open did not
+ *     write runs nothing on that tree.  Argument checks and codes are ddz_guided_*'s, in their order. */
+int64_t ddz_gismcts_work_bytes(int64_t n_tables, int64_t budget, int64_t trees);
+int ddz_gismcts_open(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+                     void* work, int64_t work_bytes, void* stream);
+int ddz_gismcts_step(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles, int64_t stride,
+                     const int32_t* values, uint8_t* leaf_rows, int32_t* need, void* work, int64_t work_bytes, void* stream);
+int ddz_gismcts_close(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int roles,
+                      const int32_t* values, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
+                      int64_t work_bytes, void* stream);
+
 /* The CFR endgame solver: the reference's final_card (server/CFR.py: deal / initiate_game / VanillaCFR.run(8)), the engine
  * its predictor uses when the three hands hold 6 cards or fewer (server/core.py:88), batched.  "CFR spec v1" (DESIGN.md 4):
  * the reference's computation with everything it leaves to chance pinned.  Seats are the reference's player numbers, 0 lord /
