@@ -525,63 +525,93 @@ class QNet(nn.Module):
 
 class FactorisedQ:
     """Inference form of a QNet: the weight-only tables of the factorisation above, cached until the weights change
-    (refresh() is called automatically when a parameter's version counter moved).  Eval semantics (no dropout)."""
+    (refresh() is called automatically, by every eager call, when a parameter's version counter moved).  Eval semantics (no
+    dropout).
+    Fixed storage: every derived table (TABLES) is allocated once per object and device and WRITTEN IN PLACE by every later
+    refresh(); the workspaces of _ws are allocated once per (device, T) and survive a refresh.  A hipGraph that captured an
+    acting pass therefore reads, at every replay, the tables of the last refresh() -- the weights of that moment, defined
+    values in live memory -- and after a learner step the caller runs refresh() eagerly (no Python runs at replay) and replays.
+    A network moved to another device gets new tables there: not under a live graph.
+    What refresh() cannot see: _versions() compares (id, address, version counter) per parameter, which an optimizer step, any
+    in-place write under no_grad, load_state_dict (assign=True too) and a swapped Parameter all move; a write through `.data`
+    (p.data.mul_()) moves none of them and is unsupported unless followed by refresh(force=True)."""
+    # the derived tables: what a captured pass holds addresses of (Wd is a view of W2; W2_jok a list of two)
+    TABLES = ("Wf", "bias_f", "A", "Mz_f", "Z", "base", "W2", "W2x", "W2_main", "w2", "b2")
+
     def __init__(self, net, chunk_tables=16384):
         self.net, self.chunk = net, int(chunk_tables)
         self.two_streams = True        # needed(shared="all"): the D chain on a side stream beside the H0 chain
         self.P = net.planes
+        self.H, self.H1 = _CONV_CH, net.fc1.out_features
         self._ver = None
+        self._dev = None
         self._ws = {}
         self.refresh()
 
     def _versions(self):
-        # (id and storage address too: load_state_dict(assign=True) / a swapped Parameter can carry an equal version)
+        # (id and storage address too: load_state_dict(assign=True) / a swapped Parameter can carry an equal version; a write
+        # through p.data moves nothing here: refresh(force=True) is the caller's part then)
         return tuple((id(p), p.data_ptr(), p._version) for p in self.net.parameters()) + (next(self.net.parameters()).device,)
 
+    def _allocate(self, dev):
+        """the derived tables' storage on dev, made once: refresh() writes into it"""
+        P, H, H1 = self.P, self.H, self.H1
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        self.Wf, self.bias_f, self.A = z(P * 4, 4 * H), z(4 * H), z(5, 4, H)
+        self.Mz_f, self.Z, self.base = z(P * 60, H1), z(15, 5, H1), z(H1)
+        self.W2, self.W2x = z(15, H, H1), z(15, H + (4 * P + 15) // 16 * 16, H1)
+        self.Wd = self.W2.view(15 * H, H1)                             # the dense GEMM's right operand: K = 15 * 256, rank-major
+        self.W2_main, self.W2_jok = z(65, H, H1), [z(2, H, H1), z(2, H, H1)]
+        self.w2, self.b2 = z(H), z(1)
+        self._dev = dev
+
     @torch.no_grad()
-    def refresh(self):
-        n, P, H = self.net, self.P, _CONV_CH
-        dev, dt = n.fc1.weight.device, torch.float32
+    def refresh(self, force=False):
+        """Recompute the derived tables from the current weights, into their fixed storage, when a parameter moved (_versions)
+        or when forced; returns whether it did.  Raises RuntimeError while the current stream is capturing: a refresh is no
+        part of an iteration, and one must not be baked into a graph unnoticed (_Loop.capture refreshes before it begins)."""
+        now = self._versions()
+        if not force and now == self._ver:
+            return False
+        n, P, H, H1 = self.net, self.P, self.H, self.H1
+        dev = n.fc1.weight.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the network's weights moved (or refresh(force=True)) while the stream is capturing: call "
+                               "refresh() before the capture begins")
+        if dev != self._dev:
+            self._allocate(dev)
         C = P + 1
         convs = (n.conv1, n.conv2, n.conv3, n.conv4)
-        Wf = torch.zeros((P, 4, 4, H), dtype=dt, device=dev)           # [plane, slot j, conv k, channel]
-        A = torch.zeros((5, 4, H), dtype=dt, device=dev)               # [count, conv k, channel]
+        Wf = self.Wf.view(P, 4, 4, H)                                  # [plane, slot j, conv k, channel] (slots j > k stay 0)
+        A = self.A                                                     # [count, conv k, channel] (count 0 stays 0)
         for k, cv in enumerate(convs):
             w = cv.weight[:, :, 0, :]                                  # [H, C, k+1]
             Wf[:, : k + 1, k, :] = w[:, :P, :].permute(1, 2, 0)
             for cnt in range(1, 5):
                 A[cnt, k] = w[:, C - 1, : min(k + 1, cnt)].sum(dim=1)
-        self.Wf = Wf.reshape(P * 4, 4 * H).contiguous()
-        self.bias_f = torch.cat([cv.bias for cv in convs]).contiguous()
-        self.A = A.contiguous()
-        H1 = n.fc1.out_features
+        torch.cat([cv.bias for cv in convs], out=self.bias_f)
         W1 = n.fc1.weight
         W1y = W1[:, : 15 * H].reshape(H1, H, 15)                       # input index c * 15 + r (net.py:94 view)
         W1z = W1[:, 15 * H:].reshape(H1, H, 4)                         # input index c * 4 + w  (net.py:96)
         Ws = n.conv_shunzi.weight[:, :, :, 0]                          # [H, C, 15]
         Mz = torch.einsum("ocw,cpr->prwo", W1z, Ws)                    # [C, 15, 4, H1]: conv_shunzi then fc1, composed
-        self.Mz_f = Mz[:P].reshape(P * 60, H1).contiguous()            # face part: one GEMM per table
-        Z = torch.zeros((15, 5, H1), dtype=dt, device=dev)             # action part per (rank, count): weights only
-        Z[:, 1:] = Mz[C - 1].cumsum(dim=1)
-        self.Z = Z.contiguous()
-        self.base = (n.fc1.bias + torch.einsum("ocw,c->o", W1z, n.conv_shunzi.bias)).contiguous()
-        W2 = W1y.permute(2, 1, 0).contiguous()                         # [r, c, o]: fc1 per rank
-        self.W2 = W2
+        self.Mz_f.copy_(Mz[:P].reshape(P * 60, H1))                    # face part: one GEMM per table
+        self.Z[:, 1:] = Mz[C - 1].cumsum(dim=1)                        # action part per (rank, count): weights only
+        self.base.copy_(n.fc1.bias + torch.einsum("ocw,c->o", W1z, n.conv_shunzi.bias))
+        W2 = self.W2.copy_(W1y.permute(2, 1, 0))                       # [r, c, o]: fc1 per rank
         # fc1 per rank with the table term's rows appended (the shared-rows form, csrc/ddz_qnet.h section 5): a shared row
         # carries its 4 P column values behind its 256 first-layer values, so [fc1_r ; Mz[:, r] ; 0] (K = 256 + ceil16(4 P):
-        # 288 for P = 6 / 7, 304 for P = 9) gives Y x fc1_r + column x Mz_r in one product
-        pad = (4 * P + 15) // 16 * 16 - 4 * P
-        self.W2x = torch.cat([W2, Mz[:P].permute(1, 0, 2, 3).reshape(15, P * 4, H1),
-                              torch.zeros((15, pad, H1), dtype=dt, device=dev)], dim=1).contiguous()
-        self.Wd = W2.reshape(15 * H, H1)                               # the dense GEMM's right operand: K = 15 * 256, rank-major
+        # 288 for P = 6 / 7, 304 for P = 9) gives Y x fc1_r + column x Mz_r in one product (the padding rows stay 0)
+        self.W2x[:, :H] = W2
+        self.W2x[:, H: H + 4 * P] = Mz[:P].permute(1, 0, 2, 3).reshape(15, P * 4, H1)
         # one GEMM batch per (rank, count): ranks 3..2 have counts 0..4 (65 batches), the two jokers counts 0..1
-        self.W2_main = W2[:13, None].expand(13, 5, H, H1).reshape(65, H, H1).contiguous()
-        self.W2_jok = [W2[r, None].expand(2, H, H1).contiguous() for r in (13, 14)]
-        self.w2 = n.fc2.weight[0].contiguous()
-        self.b2 = n.fc2.bias.detach().clone()
-        self.H, self.H1 = H, H1
-        self._ver = self._versions()
-        self._ws = {}
+        self.W2_main.view(13, 5, H, H1).copy_(W2[:13, None].expand(13, 5, H, H1))
+        for k, r in enumerate((13, 14)):
+            self.W2_jok[k].copy_(W2[r, None].expand(2, H, H1))
+        self.w2.copy_(n.fc2.weight[0])
+        self.b2.copy_(n.fc2.bias)
+        self._ver = now
+        return True
 
     def _workspace(self, Tc, dev, fused):
         key = (Tc, dev, fused)
@@ -864,7 +894,7 @@ def ragged_q(net, face, rows, offsets):
 
 
 class _Loop:
-    """run(n) and capture(n) of a loop that has step(), env and no host synchronisation in an iteration"""
+    """run(n) and capture(n) of a loop that has step(), refresh(), env and no host synchronisation in an iteration"""
 
     def run(self, n):
         for _ in range(int(n)):
@@ -875,8 +905,15 @@ class _Loop:
         returns the torch.cuda.CUDAGraph; every .replay() runs the n iterations on the state the previous ones left (states,
         faces, choices, q values: bit for bit what n eager step() calls give -- tests/test_gpu_qnet.py).  Call step() a few
         times first (workspaces allocated, libraries warm).  An iteration is ~30 short launches: the replay removes the host's
-        share of the gaps between them."""
+        share of the gaps between them.
+        The weights: the graph holds the addresses of the derived tables (FactorisedQ / RoleQ: fixed storage, written in place),
+        not their values, and no Python runs at replay.  capture() refreshes them before it begins; weights that move WHILE the
+        stream captures raise (RuntimeError from refresh()).  After a learner step -- an optimizer step, load_state_dict -- call
+        loop.refresh() eagerly, then replay: the graph reads the current tables.  Without that call it plays the weights of the
+        last refresh(): defined values, never freed memory.  A write through `.data` needs refresh(force=True); moving the
+        network to another device reallocates the tables and is not allowed under a live graph."""
         dev = self.env.device
+        self.refresh()
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream(dev)
@@ -937,6 +974,11 @@ class PolicyLoop(_Loop):
                 + ") + ddz_q_fc1_rows (D = dY x fc1[rank], k_fc1 with the segment table in device memory)"
                 + " -> ddz_q_slab_needed -> ddz_policy_step_slab(greedy, face): every legal action of every table gets its Q "
                 "value each iteration; nothing crosses to the host")
+
+    def refresh(self, force=False):
+        """FactorisedQ.refresh: the derived tables brought up to date in place (eager steps do it themselves; a captured graph
+        needs it after every learner step -- _Loop.capture); returns whether anything was recomputed"""
+        return self.fq.refresh(force)
 
     def q_values(self):
         """q [T, stride] of the current lists (valid in [:, :counts[t]])"""
@@ -1097,8 +1139,11 @@ class RoleQ:
     agent (Game, game.py:11-43).  One pass over the tables whose actor has a network: the shared rows keyed by (network slot,
     rank, column) (csrc/ddz_qnet.h section 7), the per-slot GEMMs on the slot's weights, H0 / D / q of a table from its own
     network -- bit for bit what FactorisedQ(net of the table's role).needed(env, face, shared="all") + q_slab give.  Tables played
-    by the rule agent take no part (their q entries are left alone).  The stacked weight tables are rebuilt when a parameter
-    version of any network moves."""
+    by the rule agent take no part (their q entries are left alone).  The stacked weight tables (STACKED: slot s holds the
+    table of network s) follow FactorisedQ's contract: allocated once per object and device, the slots of the networks whose
+    parameter versions moved rewritten in place by refresh() -- every eager needed() calls it; a captured pass plays the tables
+    of the last refresh() until the caller refreshes eagerly; a write through `.data` needs refresh(force=True)."""
+    STACKED = ("Wf", "bias_f", "A", "W2x", "W2", "Z", "base", "w2", "b2")
 
     def __init__(self, nets, face_variant):
         self.nets, self.net_of_role = role_slots(nets, face_variant)
@@ -1106,20 +1151,38 @@ class RoleQ:
         self.fqs = [FactorisedQ(n) for n in self.nets]
         self.P = self.fqs[0].P
         self._ws = {}
-        self._stack()
+        self._ver = self._dev = None
+        self.refresh()
 
     def _versions(self):
         return tuple(fq._versions() for fq in self.fqs)
 
     @torch.no_grad()
-    def _stack(self):
+    def refresh(self, force=False):
+        """Bring the slots of the networks whose weights moved (every slot when forced) up to date, in place; returns whether
+        anything was recomputed.  Raises RuntimeError while the current stream is capturing, as FactorisedQ.refresh."""
+        now = self._versions()
+        if not force and now == self._ver:
+            return False
+        dev = self.fqs[0].net.fc1.weight.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a network's weights moved (or refresh(force=True)) while the stream is capturing: call "
+                               "refresh() before the capture begins")
         for fq in self.fqs:
-            if fq._ver != fq._versions():
-                fq.refresh()
-        st = lambda name: torch.stack([getattr(fq, name) for fq in self.fqs]).contiguous()  # noqa: E731
-        self.Wf, self.bias_f, self.A, self.W2x, self.W2, self.Z = (st(k) for k in ("Wf", "bias_f", "A", "W2x", "W2", "Z"))
-        self.base, self.w2, self.b2 = st("base"), st("w2"), torch.cat([fq.b2.view(1) for fq in self.fqs]).contiguous()
-        self._ver = self._versions()
+            fq.refresh(force)
+        stale = [force or self._ver is None or self._ver[s] != now[s] for s in range(self.N)]
+        if dev != self._dev:                                            # (one device for all: the kernels take one)
+            for name in self.STACKED:
+                t = getattr(self.fqs[0], name)
+                shape = (self.N,) if name == "b2" else (self.N,) + tuple(t.shape)
+                setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=dev))
+            self._dev, stale = dev, [True] * self.N
+        for s, fq in enumerate(self.fqs):
+            if stale[s]:
+                for name in self.STACKED:
+                    getattr(self, name)[s: s + 1].copy_(getattr(fq, name).view((1,) + tuple(getattr(self, name).shape[1:])))
+        self._ver = now
+        return True
 
     def _workspace(self, env, face):
         from . import engine as E
@@ -1149,7 +1212,7 @@ class RoleQ:
         beside the finder and the H0 chain (fork / join by events), nothing crosses to the host, every launch is capturable."""
         from . import engine as E
         if self._ver != self._versions():
-            self._stack()
+            self.refresh()
         T, P, N = face.shape[0], self.P, self.N
         if tuple(face.shape[1:]) != (P, 15, 4) or T != env.T or not face.is_cuda:
             raise ValueError(f"face must be a device tensor [T,{P},15,4] of the environment's tables")
@@ -1220,6 +1283,12 @@ class SeatLoop(_Loop):
         if bad:
             raise ValueError(f"unknown role(s) {sorted(bad)} in epsilon")
         return [float(epsilon.get(r, 0.0)) for r in ROLE_ORDER]
+
+    def refresh(self, force=False):
+        """RoleQ.refresh: the stacked tables of the networks that moved brought up to date in place (eager steps do it
+        themselves; a captured graph needs it after every learner step -- _Loop.capture); returns whether anything was
+        recomputed"""
+        return self.rq.refresh(force)
 
     def q_values(self):
         """q [T, stride] of the current lists for the network tables (valid in [t, :counts[t]] where slot[t] >= 0)"""
@@ -1295,6 +1364,11 @@ class QLeaf:
                              native_joker_kickers=search.env.native_joker_kickers)
             self.loop = SeatLoop(env, self.nets, self.variant, auto_reset=False)
         return self.loop
+
+    def refresh(self, force=False):
+        """SeatLoop.refresh of the scratch loop (False before the first search made it: a new loop is built from the current
+        weights).  An eager run refreshes itself at every leaf pass; a captured search needs the call after a learner step."""
+        return False if self.loop is None else self.loop.refresh(force)
 
     def q_values(self, search):
         """q f32 [n_items, stride] of the leaves' lists (valid where the leaf's actor has a network) and the scratch env"""
@@ -1726,7 +1800,9 @@ class TrainLoop(_Loop):
     recorder.before on the network tables -> step_slab(STEP_IDS, no auto-reset) -> recorder.after -> re-deal of the finished
     tables -> the next lists and faces.  nets / epsilon as SeatLoop's; train_dict {"lord" | "down" | "up": bool} (default:
     every role with a network trains): a network role that does not train plays greedy and records nothing (game.py:95-104).
-    capture(n) records n iterations as one graph at the epsilon of the moment.  targets: "td" -- the recorder is a
+    capture(n) records n iterations as one graph at the epsilon of the moment and on the derived tables' fixed storage: after
+    every learner step call refresh(), then replay (_Loop.capture; without it the graph plays the weights of the last
+    refresh).  targets: "td" -- the recorder is a
     TransitionRecorder (one-step targets, td_step) -- or "mc" -- a ReturnRecorder(gamma, log_cap) (the episode's return,
     mc_step): no greedy id is gathered, since no a1 is recorded.
     targets="teacher" (teacher spec v1): the recorder is a TeacherRecorder(min_den) and every label_every-th
@@ -1772,6 +1848,11 @@ class TrainLoop(_Loop):
     @property
     def face(self):
         return self.seat.face
+
+    def refresh(self, force=False):
+        """SeatLoop.refresh of the acting loop: with a captured graph, the call between a learner step (td_step / mc_step on the
+        networks this loop holds) and the next replay -- _Loop.capture; eager step() calls refresh themselves"""
+        return self.seat.refresh(force)
 
     def step(self):
         from .engine import STEP_IDS
