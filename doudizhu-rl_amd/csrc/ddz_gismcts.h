@@ -2,9 +2,14 @@
 // DESIGN.md 4).  Included by ddz_engine.hip behind ddz_ismcts.h and ddz_guided.h, inside its anonymous namespace.  Spec v2's
 // tree (a node is (parent, the move into it) with V, W and the availability count A), its hash table (ismcts_find /
 // ismcts_insert), its list in lanes (ismcts_lane_entry), pass 1, the expansion ranking and the selection (ismcts_pass1 /
-// ismcts_untried / ismcts_select) are ddz_ismcts.h's; spec v3's phases, unit (W in 1024ths, search_value<1024>), header words
-// (GH_*), GuidedArgs and the leaf row are ddz_guided.h's; the entry into a table, the redeal, every piece of a ply and the
-// wavefront-scope accesses are ddz_ply.h's.  This header holds their composition.
+// ismcts_untried / ismcts_select), a new node's record (ismcts_make_node), the selection step (ismcts_descend) and the root's
+// children leaving (ismcts_root_out) are ddz_ismcts.h's; spec v3's phases, unit (W in 1024ths, search_value<1024>), header
+// words (GH_*), GuidedArgs and the phased scaffold -- the view of a tree, OPEN, the check of a header, the pending leaf's score
+// and path, the rows a descent carries with the leaf's row, the header store and the outputs (guided_tree, guided_open,
+// guided_header_live, guided_pending_score, DescentRows, guided_leave_pending, guided_store_header, guided_emit) -- are
+// ddz_guided.h's; the backup of a path and the totals (path_backup, search_totals_out) are ddz_search.h's; the entry into a
+// table, the redeal, every piece of a ply and the wavefront-scope accesses are ddz_ply.h's.  This header holds their
+// composition: the kernel below is its prologue, node 0, and the descent loop between those calls.
 //
 // One wavefront per WORK ITEM (table t, tree c), 12-wave blocks as k_search, always the hidden form.  Phases of a launch,
 // wave-uniform, as k_guided's:
@@ -34,18 +39,6 @@
 // totals, the status word.
 inline uint64_t gismcts_tree_bytes(int64_t budget) { return GUIDED_HDR_BYTES + GUIDED_PATH_BYTES + ismcts_tree_bytes(budget); }
 
-// V += 1, W += score on path[0 .. depth] (the wave's LDS copy), the new node included
-__device__ __forceinline__ void gismcts_backup(uint8_t* nodes, const uint16_t* path, int depth, uint32_t score, int lane) {
-  for (int b = 0; b <= depth; b += 64) {
-    const int l = b + lane;
-    if (l <= depth) {
-      uint64_t* p = (uint64_t*)(nodes + (uint64_t)path[l] * INODE_BYTES + 8);
-      const uint64_t vw = sld64(p);
-      sst64(p, vw + 1ull + ((uint64_t)score << 32));
-    }
-  }
-}
-
 __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) {
   __shared__ HotTabT<false> hot;
   __shared__ uint64_t s_stage[SEARCH_WAVES][STAGE_CAP];
@@ -68,56 +61,29 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
   const RootHands rh = root_hands<true>(R, a.roles, lane);
   const PlayRoot& root = rh.root;
   const int role0 = root.role0;
-  uint8_t* const base = a.work + (uint64_t)item * a.tree_bytes;
-  uint32_t* const hdr = (uint32_t*)base;
-  uint32_t* const gpath = (uint32_t*)(base + GUIDED_HDR_BYTES);
-  uint8_t* const nodes = base + GUIDED_HDR_BYTES + GUIDED_PATH_BYTES;
-  uint64_t* const tab = (uint64_t*)(nodes + (uint64_t)(a.budget + 1) * INODE_BYTES);
+  const GuidedTree g = guided_tree(a.work, item, a.tree_bytes, a.budget, INODE_BYTES);
+  uint32_t* const hdr = g.hdr;
+  uint8_t* const nodes = g.nodes;
+  uint64_t* const tab = g.tab;
   const uint32_t hlog = a.hash_log;
   if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, 64);   // outside the domain: nothing runs
   if (rh.kind == ROOT_INSIDE && a.phase == GUIDED_OPEN) {
-    // ---- OPEN: the root actor's list is the same in every world; an empty one (or one the slab cannot hold) leaves the item dead
-    uint64_t okm; int n0;
-    int n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
-    __builtin_amdgcn_wave_barrier();
-    if (n_root > STAGE_CAP || n_root > a.stride) {
-      if (lane == 0) atomicOr(a.status, 2);
-      n_root = 0;
-    }
-    const bool live = n_root > 0;
-    if (live) {
-      for (uint32_t i = (uint32_t)lane; i < (1u << hlog); i += 64) sst64(tab + i, 0ull);
-      if (lane < 4) sst64((uint64_t*)nodes + lane, lane == 2 ? (uint64_t)SEARCH_NONE << 32 : 0ull);   // node 0: no move, no parent
-    }
-    if (lane < 16) sst32(hdr + lane, lane == GH_LIVE ? (live ? 1u : 0u) : lane == GH_NNODES ? 1u : lane == GH_PENDING ? SEARCH_NONE : 0u);
-    search_fence();
+    // ---- OPEN: the root actor's list is the same in every world
+    const bool live = guided_open(g, a, root, hot, lane, stage, svl) > 0;
+    if (live && lane < 4) sst64((uint64_t*)nodes + lane, lane == 2 ? (uint64_t)SEARCH_NONE << 32 : 0ull);   // node 0: no move, no parent
+    guided_open_header(hdr, live, lane);
     return;
   }
-  // a header OPEN did not write (a workspace of another budget, or none) is dead: every index below stays inside the tree
-  bool live = false;
-  if (rh.kind == ROOT_INSIDE && rfl(sld32(hdr + GH_LIVE)) == 1u) {
-    const uint32_t it = rfl(sld32(hdr + GH_IT)), nnodes = rfl(sld32(hdr + GH_NNODES)), pending = rfl(sld32(hdr + GH_PENDING));
-    live = it <= a.budget && nnodes >= 1u && nnodes <= it + 1u &&
-           (pending == SEARCH_NONE || (pending < nnodes && rfl(sld32(hdr + GH_PDEPTH)) <= (uint32_t)DDZ_SEARCH_MAX_DEPTH));
-  }
-  if (live) {
+  if (rh.kind == ROOT_INSIDE && guided_header_live(hdr, a.budget)) {
     uint32_t it = rfl(sld32(hdr + GH_IT)), nnodes = rfl(sld32(hdr + GH_NNODES));
     uint32_t s_unfinished = rfl(sld32(hdr + GH_UNFINISHED));
     unsigned long long s_moves = rfl64(sld64((const uint64_t*)(hdr + GH_MOVES)));
     const uint32_t pending = rfl(sld32(hdr + GH_PENDING));
     if (pending != SEARCH_NONE) {
-      // ---- the pending leaf's value: the chance in 1024ths that the LEAF actor's side wins, seen from the root's side
-      const int pdepth = (int)rfl(sld32(hdr + GH_PDEPTH));
-      int32_t v = a.values ? a.values[item] : 0;
-      v = v < 0 ? 0 : v > (int32_t)GUIDED_ONE ? (int32_t)GUIDED_ONE : v;
-      const uint32_t score = rfl(sld32(hdr + GH_PSIDE)) ? (uint32_t)v : GUIDED_ONE - (uint32_t)v;
-      for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
-        const uint32_t two = sld32(gpath + w);
-        path[2 * w] = (uint16_t)((two & 0xFFFFu) < nnodes ? two : 0u);   // (a node of this tree, whatever the words hold)
-        path[2 * w + 1] = (uint16_t)((two >> 16) < nnodes ? two >> 16 : 0u);
-      }
-      search_fence();
-      gismcts_backup(nodes, path, pdepth, score, lane);
+      // ---- the pending leaf is backed up with its path (its record is whole since it was made)
+      int pdepth;
+      const uint32_t score = guided_pending_score(g, a.values, item, nnodes, path, lane, pdepth);
+      path_backup<INODE_BYTES>(nodes, path, pdepth, score, lane);
       search_fence();
     }
     uint32_t made = SEARCH_NONE;   // the node this launch creates and, where it is not terminal, leaves pending
@@ -131,16 +97,8 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
       redeal_wave(gid, tree * a.budget + it, a.k0, a.k1, lane, rh.pool, rh.n_next, stage, hn, hp);
       uint32_t trick = root.trick0, ply = root.ply0;
       int passes = root.passes0, role = role0;
-      // the rows the hands' words do not carry, as lane f's row f (k_guided's form): history, recent + category, taken, and
-      // byte 15 of every row (a hand row's: the cards left, the same in every world)
-      uint64_t P = root.P;
-      uint32_t aux = root.aux;
-      const auto track = [&](uint64_t snib, uint32_t scat) {   // envi.py:39-43 on the packed rows, before the turn passes on
-        const int d = lane - role;
-        const uint64_t add = (d == DDZ_F_HIST0 || lane == DDZ_F_TAKEN) ? snib : 0ull;
-        P = d == DDZ_F_RECENT0 ? snib : P + add;
-        aux = d == DDZ_F_RECENT0 ? scat : d == DDZ_F_HAND0 ? aux - (uint32_t)nib_sum(snib) : aux;
-      };
+      DescentRows rows = {root.P, root.aux};   // (the cards left of a hand row are the same in every world)
+      const auto track = [&](uint64_t snib, uint32_t scat) { rows.track(snib, scat, role, lane); };   // (the mover: before the turn)
       uint32_t node = 0;
       int winner = -1;
       if (lane == 0) path[0] = 0;
@@ -180,15 +138,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
           const int mover = role;
           track(snib, scat);
           const bool over = ply_apply(snib, scat, svlv, hc, hn, hp, trick, passes, role, ply);
-          if (lane == 0) {   // the record whole (V = W = 0 until the backup, A = 1), then its table entry
-            uint64_t* q = (uint64_t*)(nodes + (uint64_t)made * INODE_BYTES);
-            sst64(q, snib | ((uint64_t)scat << 60));
-            sst64(q + 1, 0ull);
-            sst64(q + 2, 1ull | ((uint64_t)node << 32));
-            sst64(q + 3, over ? (1u << 26) | ((uint32_t)mover << 27) : 0u);
-            ismcts_insert(tab, hlog, node, snib, made);
-            path[depth + 1] = (uint16_t)made;
-          }
+          ismcts_make_node(nodes, tab, hlog, node, made, snib, scat, over, mover, path, depth, lane);
           depth += 1;
           if (over) winner = mover;
           else {   // ---- a pending leaf: its value is the caller's (its list is not enumerated: a node keeps no n)
@@ -205,41 +155,22 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
         ply_entry(okm, n0, (int)first, info, stage, svl, snib, scat, svlv);
         s_moves += 1;
         track(snib, scat);
-        const uint64_t hnew = ply_play(snib, scat, svlv, hc, trick, passes, ply);
-        __builtin_amdgcn_wave_barrier();   // the staging list is reused by the next level
-        ply_turn(hnew, hc, hn, hp, role);  // (an emptied hand: the child is terminal, the next trip scores it)
+        ismcts_descend(snib, scat, svlv, child, hc, hn, hp, trick, passes, ply, role, path, depth, lane);
         node = child;
-        depth += 1;
-        if (lane == 0) path[depth] = (uint16_t)child;
       }
       it += 1;
       search_fence();   // the path, the new record and the raised A's are written
       if (wait) {
-        // the leaf's row: the hands back by role, the meta row as ddz_step leaves it on a running table
-        const int rp1 = role_next(role), rm1 = role_prev(role);
-        const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
-        Rleaf = unpack_row(Pf, aux);
-        if (lane == DDZ_F_META) Rleaf = make_uint4((uint32_t)role | (0xFFu << 16), (my & 0xFFFF0000u) | (ply & 0xFFFFu), mz, mw);
+        Rleaf = rows.leaf_row(hc, hn, hp, role, ply, my, mz, mw, lane);
         needs = 1;
-        for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
-          const uint32_t lo = 2 * w <= depth ? path[2 * w] : 0u, hi = 2 * w + 1 <= depth ? path[2 * w + 1] : 0u;
-          sst32(gpath + w, lo | (hi << 16));
-        }
+        guided_leave_pending(g.gpath, path, depth, lane);
       } else {
         const uint32_t score = (winner >= 0 && same_side(winner, role0)) ? GUIDED_ONE : 0u;
         if (winner < 0) s_unfinished += 1;
-        gismcts_backup(nodes, path, depth, score, lane);
+        path_backup<INODE_BYTES>(nodes, path, depth, score, lane);
       }
     }
-    if (lane == 0) {
-      sst32(hdr + GH_IT, it);
-      sst32(hdr + GH_NNODES, nnodes);
-      sst32(hdr + GH_PENDING, wait ? made : SEARCH_NONE);
-      sst32(hdr + GH_PDEPTH, (uint32_t)depth);
-      sst32(hdr + GH_PSIDE, pside);
-      sst32(hdr + GH_UNFINISHED, s_unfinished);
-      sst64((uint64_t*)(hdr + GH_MOVES), s_moves);
-    }
+    guided_store_header(hdr, it, nnodes, wait ? made : SEARCH_NONE, depth, pside, s_unfinished, s_moves, lane);
     search_fence();
     if (a.phase == GUIDED_CLOSE) {
       // ---- the root's children leave: visits / wins += V / W (1024ths) at their index of the root's list
@@ -247,31 +178,9 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
       uint64_t okm; int n0;
       const int n = ply_list(root.hc0, info, hot, lane, stage, svl, okm, n0);
       __builtin_amdgcn_wave_barrier();
-      if (n > 0 && n <= STAGE_CAP) {
-        const int trips = 1 + (n - n0 + 63) / 64;
-        for (int trip = 0; trip < trips; ++trip) {
-          uint64_t nib;
-          const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
-          if (j >= 0 && j < a.stride) {
-            const uint32_t ch = ismcts_find(nodes, tab, hlog, nnodes, 0u, nib);
-            if (ch != SEARCH_NONE) {
-              const uint64_t vw = sld64((const uint64_t*)(nodes + (uint64_t)ch * INODE_BYTES + 8));
-              atomicAdd(a.visits + t * a.stride + j, (int32_t)(uint32_t)vw);
-              if ((uint32_t)(vw >> 32)) atomicAdd(a.wins + t * a.stride + j, (int32_t)(uint32_t)(vw >> 32));
-            }
-          }
-        }
-      }
-      if (lane == 0 && a.totals) {
-        atomicAdd(a.totals + 0, s_moves);
-        atomicAdd(a.totals + 1, (unsigned long long)it);
-        if (s_unfinished) atomicAdd(a.totals + 2, (unsigned long long)s_unfinished);
-        atomicAdd(a.totals + 3, (unsigned long long)(nnodes - 1u));
-      }
+      if (n > 0 && n <= STAGE_CAP) ismcts_root_out(a, t, nodes, tab, nnodes, okm, n0, n, info, stage, a.stride, lane);
+      search_totals_out(a.totals, s_moves, it, s_unfinished, nnodes, lane);
     }
   }
-  if (a.phase == GUIDED_STEP) {
-    if (lane < DDZ_NFIELDS) ((uint4*)(a.leaf_rows + (uint64_t)item * STATE_ROW_BYTES))[lane] = Rleaf;
-    if (lane == 0) a.need[item] = needs;
-  }
+  guided_emit(a, item, Rleaf, needs, lane);
 }

@@ -25,6 +25,13 @@
 // tree, its header and its path are written and read by ONE wavefront through the relaxed wavefront-scope accesses and the
 // fence of ddz_search.h (MEMORY ORDERING, there): vector instructions of one wave issued in order through one vector L1.
 // values is read, leaf_rows and need are written with plain vector accesses: no wave reads what another wrote in a launch.
+//
+// THE PHASED SCAFFOLD is stated here once, for k_guided and for k_gismcts (ddz_gismcts.h), which keeps spec v2's tree in the same
+// workspace: the view of a tree (GuidedTree, guided_tree), OPEN (guided_open, guided_open_header; node 0 is each kernel's), the
+// check of a header (guided_header_live), the pending leaf's score and path (guided_pending_score), the rows a descent carries
+// and the leaf's row (DescentRows), a leaf left pending (guided_leave_pending), the header at the end of a launch
+// (guided_store_header) and the launch's outputs (guided_emit).  The backup of a path and the totals (path_backup,
+// search_totals_out) are ddz_search.h's.  A kernel keeps its prologue, its descent loop and the order of these calls.
 constexpr uint32_t GUIDED_ONE = DDZ_GUIDED_ONE;
 constexpr int GUIDED_OPEN = 0, GUIDED_STEP = 1, GUIDED_CLOSE = 2;
 constexpr uint32_t GUIDED_HDR_BYTES = 64;
@@ -40,17 +47,127 @@ struct GuidedArgs : SearchArgs {
 
 inline uint64_t guided_tree_bytes(int64_t budget) { return GUIDED_HDR_BYTES + GUIDED_PATH_BYTES + search_tree_bytes(budget); }
 
-// V += 1, W += score on path[0 .. depth] (the wave's LDS copy) and the new node's record, written whole
+// one item's workspace.  The table starts at the first multiple of 16 behind the nodes: spec v1's 24-byte records are rounded
+// up to it, spec v2's 32-byte records end on it.
+struct GuidedTree {
+  uint32_t* hdr;     // [16]
+  uint32_t* gpath;   // [SEARCH_PATH / 2]
+  uint8_t* nodes;    // [budget + 1] records of node_stride bytes
+  uint64_t* tab;     // [1 << hash_log]
+};
+__device__ __forceinline__ GuidedTree guided_tree(uint8_t* work, int64_t item, uint64_t tree_bytes, uint32_t budget,
+                                                  uint32_t node_stride) {
+  uint8_t* const base = work + (uint64_t)item * tree_bytes;
+  uint8_t* const nodes = base + GUIDED_HDR_BYTES + GUIDED_PATH_BYTES;
+  return {(uint32_t*)base, (uint32_t*)(base + GUIDED_HDR_BYTES), nodes,
+          (uint64_t*)(nodes + (((uint64_t)(budget + 1) * node_stride + 15) & ~15ull))};
+}
+
+// OPEN: the root's list is sized -> its n, 0 where the item stays dead (an empty list, or one the slab cannot hold: status bit
+// 1); a live item's hash table is zeroed.  The kernel writes its node 0 behind this, then guided_open_header.
+__device__ __forceinline__ int guided_open(const GuidedTree& g, const GuidedArgs& a, const PlayRoot& root, const HotTabT<false>& hot,
+                                           int lane, uint64_t* stage, uint16_t* svl) {
+  uint64_t okm; int n0;
+  int n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
+  __builtin_amdgcn_wave_barrier();
+  if (n_root > STAGE_CAP || n_root > a.stride) {
+    if (lane == 0) atomicOr(a.status, 2);
+    n_root = 0;
+  }
+  if (n_root > 0)
+    for (uint32_t i = (uint32_t)lane; i < (1u << a.hash_log); i += 64) sst64(g.tab + i, 0ull);
+  return n_root;
+}
+__device__ __forceinline__ void guided_open_header(uint32_t* hdr, bool live, int lane) {
+  if (lane < 16) sst32(hdr + lane, lane == GH_LIVE ? (live ? 1u : 0u) : lane == GH_NNODES ? 1u : lane == GH_PENDING ? SEARCH_NONE : 0u);
+  search_fence();
+}
+
+// a header OPEN did not write (a workspace of another budget, or none), or one whose fields are out of range, is dead: with a
+// live one every index a STEP or a CLOSE computes stays inside the tree.  A dead item reads these header words and nothing else.
+__device__ __forceinline__ bool guided_header_live(const uint32_t* hdr, uint32_t budget) {
+  if (rfl(sld32(hdr + GH_LIVE)) != 1u) return false;
+  const uint32_t it = rfl(sld32(hdr + GH_IT)), nnodes = rfl(sld32(hdr + GH_NNODES)), pending = rfl(sld32(hdr + GH_PENDING));
+  return it <= budget && nnodes >= 1u && nnodes <= it + 1u &&
+         (pending == SEARCH_NONE || (pending < nnodes && rfl(sld32(hdr + GH_PDEPTH)) <= (uint32_t)DDZ_SEARCH_MAX_DEPTH));
+}
+
+// the pending leaf's value -> its score: the chance in 1024ths that the LEAF actor's side wins (values[item], clamped), seen
+// from the root's side.  The stored path is reloaded into LDS (every entry a node of this tree, whatever the words hold) and
+// fenced; pdepth: the leaf's depth.
+__device__ __forceinline__ uint32_t guided_pending_score(const GuidedTree& g, const int32_t* values, int64_t item, uint32_t nnodes,
+                                                         uint16_t* path, int lane, int& pdepth) {
+  pdepth = (int)rfl(sld32(g.hdr + GH_PDEPTH));
+  int32_t v = values ? values[item] : 0;
+  v = v < 0 ? 0 : v > (int32_t)GUIDED_ONE ? (int32_t)GUIDED_ONE : v;
+  const uint32_t score = rfl(sld32(g.hdr + GH_PSIDE)) ? (uint32_t)v : GUIDED_ONE - (uint32_t)v;
+  for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
+    const uint32_t two = sld32(g.gpath + w);
+    path[2 * w] = (uint16_t)((two & 0xFFFFu) < nnodes ? two : 0u);
+    path[2 * w + 1] = (uint16_t)((two >> 16) < nnodes ? two >> 16 : 0u);
+  }
+  search_fence();
+  return score;
+}
+
+// the rows the hands' words do not carry along a descent, as lane f's row f (k_rollout's form): history, recent + category,
+// taken, and byte 15 of every row (a hand row's: the cards left)
+struct DescentRows {
+  uint64_t P;
+  uint32_t aux;
+  // a move of `role` (envi.py:39-43 on the packed rows), before the turn passes on
+  __device__ __forceinline__ void track(uint64_t snib, uint32_t scat, int role, int lane) {
+    const int d = lane - role;
+    const uint64_t add = (d == DDZ_F_HIST0 || lane == DDZ_F_TAKEN) ? snib : 0ull;
+    P = d == DDZ_F_RECENT0 ? snib : P + add;
+    aux = d == DDZ_F_RECENT0 ? scat : d == DDZ_F_HAND0 ? aux - (uint32_t)nib_sum(snib) : aux;
+  }
+  // this lane's 16 bytes of the leaf's 176-byte row, as state_import reads it: the hands back by role, the meta row as ddz_step
+  // leaves it on a running table (my, mz, mw: the words of the root's meta row a leaf keeps)
+  __device__ __forceinline__ uint4 leaf_row(uint64_t hc, uint64_t hn, uint64_t hp, int role, uint32_t ply, uint32_t my, uint32_t mz,
+                                            uint32_t mw, int lane) const {
+    const int rp1 = role_next(role), rm1 = role_prev(role);
+    const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
+    uint4 r = unpack_row(Pf, aux);
+    if (lane == DDZ_F_META) r = make_uint4((uint32_t)role | (0xFFu << 16), (my & 0xFFFF0000u) | (ply & 0xFFFFu), mz, mw);
+    return r;
+  }
+};
+
+// a leaf is left pending: the path[0 .. depth] of its descent is stored, two nodes to a word
+__device__ __forceinline__ void guided_leave_pending(uint32_t* gpath, const uint16_t* path, int depth, int lane) {
+  for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
+    const uint32_t lo = 2 * w <= depth ? path[2 * w] : 0u, hi = 2 * w + 1 <= depth ? path[2 * w + 1] : 0u;
+    sst32(gpath + w, lo | (hi << 16));
+  }
+}
+
+// the header at the end of a STEP or a CLOSE (k_guided stores GH_PMETA / GH_PMOVE on top); the caller's fence stands behind it
+__device__ __forceinline__ void guided_store_header(uint32_t* hdr, uint32_t it, uint32_t nnodes, uint32_t pending, int depth,
+                                                    uint32_t pside, uint32_t unfinished, unsigned long long moves, int lane) {
+  if (lane == 0) {
+    sst32(hdr + GH_IT, it);
+    sst32(hdr + GH_NNODES, nnodes);
+    sst32(hdr + GH_PENDING, pending);
+    sst32(hdr + GH_PDEPTH, (uint32_t)depth);
+    sst32(hdr + GH_PSIDE, pside);
+    sst32(hdr + GH_UNFINISHED, unfinished);
+    sst64((uint64_t*)(hdr + GH_MOVES), moves);
+  }
+}
+
+// what a STEP leaves of every running item: its leaf's row (all zero without a pending leaf) and its need flag
+__device__ __forceinline__ void guided_emit(const GuidedArgs& a, int64_t item, const uint4& Rleaf, int32_t needs, int lane) {
+  if (a.phase == GUIDED_STEP) {
+    if (lane < DDZ_NFIELDS) ((uint4*)(a.leaf_rows + (uint64_t)item * STATE_ROW_BYTES))[lane] = Rleaf;
+    if (lane == 0) a.need[item] = needs;
+  }
+}
+
+// path_backup on path[0 .. depth] and the new node's record, written whole
 __device__ __forceinline__ void guided_backup(uint8_t* nodes, const uint16_t* path, int depth, uint32_t score, uint32_t made,
                                               uint64_t made_move, uint32_t made_meta, int lane) {
-  for (int b = 0; b <= depth; b += 64) {
-    const int l = b + lane;
-    if (l <= depth) {
-      uint64_t* p = (uint64_t*)(nodes + (uint64_t)path[l] * NODE_BYTES + 8);
-      const uint64_t vw = sld64(p);
-      sst64(p, vw + 1ull + ((uint64_t)score << 32));
-    }
-  }
+  path_backup<NODE_BYTES>(nodes, path, depth, score, lane);
   if (made != SEARCH_NONE && lane == 0) {
     uint8_t* q = nodes + (uint64_t)made * NODE_BYTES;
     sst64((uint64_t*)q, made_move);
@@ -83,60 +200,33 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
   const RootHands rh = root_hands<HIDDEN>(R, a.roles, lane);
   const PlayRoot& root = rh.root;
   const int role0 = root.role0;
-  uint8_t* const base = a.work + (uint64_t)item * a.tree_bytes;
-  uint32_t* const hdr = (uint32_t*)base;
-  uint32_t* const gpath = (uint32_t*)(base + GUIDED_HDR_BYTES);
-  uint8_t* const nodes = base + GUIDED_HDR_BYTES + GUIDED_PATH_BYTES;
-  uint64_t* const tab = (uint64_t*)(nodes + (((uint64_t)(a.budget + 1) * NODE_BYTES + 15) & ~15ull));
+  const GuidedTree g = guided_tree(a.work, item, a.tree_bytes, a.budget, NODE_BYTES);
+  uint32_t* const hdr = g.hdr;
+  uint8_t* const nodes = g.nodes;
+  uint64_t* const tab = g.tab;
   const uint32_t hlog = a.hash_log;
   if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, 64);   // outside the domain: nothing runs
   if (rh.kind == ROOT_INSIDE && a.phase == GUIDED_OPEN) {
-    // ---- OPEN: the root's list is node 0's n; an empty list (or one the slab cannot hold) leaves the item dead
-    uint64_t okm; int n0;
-    int n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
-    __builtin_amdgcn_wave_barrier();
-    if (n_root > STAGE_CAP || n_root > a.stride) {
-      if (lane == 0) atomicOr(a.status, 2);
-      n_root = 0;
+    // ---- OPEN: the root's list is node 0's n
+    const int n_root = guided_open(g, a, root, hot, lane, stage, svl);
+    if (n_root > 0 && lane == 0) {   // node 0: no move, nothing visited
+      sst64((uint64_t*)nodes, 0ull);
+      sst64((uint64_t*)(nodes + 8), 0ull);
+      sst32((uint32_t*)(nodes + 16), (uint32_t)n_root << 16);
+      sst32((uint32_t*)(nodes + 20), 0u);
     }
-    const bool live = n_root > 0;
-    if (live) {
-      for (uint32_t i = (uint32_t)lane; i < (1u << hlog); i += 64) sst64(tab + i, 0ull);
-      if (lane == 0) {   // node 0: no move, nothing visited
-        sst64((uint64_t*)nodes, 0ull);
-        sst64((uint64_t*)(nodes + 8), 0ull);
-        sst32((uint32_t*)(nodes + 16), (uint32_t)n_root << 16);
-        sst32((uint32_t*)(nodes + 20), 0u);
-      }
-    }
-    if (lane < 16) sst32(hdr + lane, lane == GH_LIVE ? (live ? 1u : 0u) : lane == GH_NNODES ? 1u : lane == GH_PENDING ? SEARCH_NONE : 0u);
-    search_fence();
+    guided_open_header(hdr, n_root > 0, lane);
     return;
   }
-  // a header OPEN did not write (a workspace of another budget, or none) is dead: every index below stays inside the tree
-  bool live = false;
-  if (rh.kind == ROOT_INSIDE && rfl(sld32(hdr + GH_LIVE)) == 1u) {
-    const uint32_t it = rfl(sld32(hdr + GH_IT)), nnodes = rfl(sld32(hdr + GH_NNODES)), pending = rfl(sld32(hdr + GH_PENDING));
-    live = it <= a.budget && nnodes >= 1u && nnodes <= it + 1u &&
-           (pending == SEARCH_NONE || (pending < nnodes && rfl(sld32(hdr + GH_PDEPTH)) <= (uint32_t)DDZ_SEARCH_MAX_DEPTH));
-  }
-  if (live) {
+  if (rh.kind == ROOT_INSIDE && guided_header_live(hdr, a.budget)) {
     uint32_t it = rfl(sld32(hdr + GH_IT)), nnodes = rfl(sld32(hdr + GH_NNODES));
     uint32_t s_unfinished = rfl(sld32(hdr + GH_UNFINISHED));
     unsigned long long s_moves = rfl64(sld64((const uint64_t*)(hdr + GH_MOVES)));
     const uint32_t pending = rfl(sld32(hdr + GH_PENDING));
     if (pending != SEARCH_NONE) {
-      // ---- the pending leaf's value: the chance in 1024ths that the LEAF actor's side wins, seen from the root's side
-      const int pdepth = (int)rfl(sld32(hdr + GH_PDEPTH));
-      int32_t v = a.values ? a.values[item] : 0;
-      v = v < 0 ? 0 : v > (int32_t)GUIDED_ONE ? (int32_t)GUIDED_ONE : v;
-      const uint32_t score = rfl(sld32(hdr + GH_PSIDE)) ? (uint32_t)v : GUIDED_ONE - (uint32_t)v;
-      for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
-        const uint32_t two = sld32(gpath + w);
-        path[2 * w] = (uint16_t)((two & 0xFFFFu) < nnodes ? two : 0u);   // (a node of this tree, whatever the words hold)
-        path[2 * w + 1] = (uint16_t)((two >> 16) < nnodes ? two >> 16 : 0u);
-      }
-      search_fence();
+      // ---- the pending leaf is backed up, its record written whole
+      int pdepth;
+      const uint32_t score = guided_pending_score(g, a.values, item, nnodes, path, lane, pdepth);
       guided_backup(nodes, path, pdepth, score, pending, sld64((const uint64_t*)(hdr + GH_PMOVE)), sld32(hdr + GH_PMETA), lane);
       search_fence();
     }
@@ -152,16 +242,8 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
       uint64_t hc = root.hc0, hn = hn0, hp = hp0;
       uint32_t trick = root.trick0, ply = root.ply0;
       int passes = root.passes0, role = role0;
-      // the rows the hands' words do not carry, as lane f's row f (k_rollout's form): history, recent + category, taken, and
-      // byte 15 of every row (a hand row's: the cards left)
-      uint64_t P = root.P;
-      uint32_t aux = root.aux;
-      const auto track = [&](uint64_t snib, uint32_t scat) {   // envi.py:39-43 on the packed rows, before the turn passes on
-        const int d = lane - role;
-        const uint64_t add = (d == DDZ_F_HIST0 || lane == DDZ_F_TAKEN) ? snib : 0ull;
-        P = d == DDZ_F_RECENT0 ? snib : P + add;
-        aux = d == DDZ_F_RECENT0 ? scat : d == DDZ_F_HAND0 ? aux - (uint32_t)nib_sum(snib) : aux;
-      };
+      DescentRows rows = {root.P, root.aux};
+      const auto track = [&](uint64_t snib, uint32_t scat) { rows.track(snib, scat, role, lane); };   // (the mover: before the turn)
       uint32_t node = 0;
       int winner = -1;
       if (lane == 0) path[0] = 0;
@@ -236,32 +318,19 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
       it += 1;
       search_fence();   // the path is written
       if (wait) {
-        // the leaf's row: the hands back by role, the meta row as ddz_step leaves it on a running table
-        const int rp1 = role_next(role), rm1 = role_prev(role);
-        const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
-        Rleaf = unpack_row(Pf, aux);
-        if (lane == DDZ_F_META) Rleaf = make_uint4((uint32_t)role | (0xFFu << 16), (my & 0xFFFF0000u) | (ply & 0xFFFFu), mz, mw);
+        Rleaf = rows.leaf_row(hc, hn, hp, role, ply, my, mz, mw, lane);
         needs = 1;
-        for (int w = lane; w < SEARCH_PATH / 2; w += 64) {
-          const uint32_t lo = 2 * w <= depth ? path[2 * w] : 0u, hi = 2 * w + 1 <= depth ? path[2 * w + 1] : 0u;
-          sst32(gpath + w, lo | (hi << 16));
-        }
+        guided_leave_pending(g.gpath, path, depth, lane);
       } else {
         const uint32_t score = (winner >= 0 && same_side(winner, role0)) ? GUIDED_ONE : 0u;
         if (winner < 0) s_unfinished += 1;
         guided_backup(nodes, path, depth, score, made, made_move, made_meta, lane);
       }
     }
-    if (lane == 0) {
-      sst32(hdr + GH_IT, it);
-      sst32(hdr + GH_NNODES, nnodes);
-      sst32(hdr + GH_PENDING, wait ? made : SEARCH_NONE);
-      sst32(hdr + GH_PDEPTH, (uint32_t)depth);
-      sst32(hdr + GH_PSIDE, pside);
-      sst32(hdr + GH_UNFINISHED, s_unfinished);
+    guided_store_header(hdr, it, nnodes, wait ? made : SEARCH_NONE, depth, pside, s_unfinished, s_moves, lane);
+    if (lane == 0) {   // the record guided_backup writes when the leaf's value is there
       sst32(hdr + GH_PMETA, made_meta);
       sst64((uint64_t*)(hdr + GH_PMOVE), made_move);
-      sst64((uint64_t*)(hdr + GH_MOVES), s_moves);
     }
     search_fence();
     if (a.phase == GUIDED_CLOSE) {
@@ -278,18 +347,10 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
           }
         }
       }
-      if (lane == 0 && a.totals) {
-        atomicAdd(a.totals + 0, s_moves);
-        atomicAdd(a.totals + 1, (unsigned long long)it);
-        if (s_unfinished) atomicAdd(a.totals + 2, (unsigned long long)s_unfinished);
-        atomicAdd(a.totals + 3, (unsigned long long)(nnodes - 1u));
-      }
+      search_totals_out(a.totals, s_moves, it, s_unfinished, nnodes, lane);
     }
   }
-  if (a.phase == GUIDED_STEP) {
-    if (lane < DDZ_NFIELDS) ((uint4*)(a.leaf_rows + (uint64_t)item * STATE_ROW_BYTES))[lane] = Rleaf;
-    if (lane == 0) a.need[item] = needs;
-  }
+  guided_emit(a, item, Rleaf, needs, lane);
 }
 
 // k_guided_value: leaf values from a q slab.  One wavefront per leaf i with a running row whose actor's role is in

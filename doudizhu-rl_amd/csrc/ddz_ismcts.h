@@ -23,7 +23,10 @@
 // counts them, keeps each lane's best selectable child and raises A of every child it finds (each child is found by one lane,
 // once per iteration: the values use the counts of before); only then the wave decides.  Expansion runs the lookups a second
 // time to find the r-th entry without a child.  Pass 1, that ranking and the selection's reduce are the functions ismcts_pass1
-// / ismcts_untried / ismcts_select below: k_gismcts (ddz_gismcts.h) calls them too, with W in 1024ths.
+// / ismcts_untried / ismcts_select below: k_gismcts (ddz_gismcts.h) calls them too, with W in 1024ths.  So it does the other
+// pieces of spec v2 a descent is made of, stated here once: a new node's record and table entry (ismcts_make_node), the
+// selection step (ismcts_descend) and the root's children leaving (ismcts_root_out).  The backup of a path and the totals
+// (path_backup<INODE_BYTES>, search_totals_out) are ddz_search.h's.
 //
 // LOOPS, MEMORY ORDERING: as ddz_search.h.  Every loop is counted (iterations by budget, the descent by
 // DDZ_SEARCH_MAX_DEPTH, a probe by H, the trips by n <= STAGE_CAP, the playout by DDZ_PLAYOUT_MAX_PLIES); a wave waits for no
@@ -162,6 +165,54 @@ __device__ __forceinline__ uint32_t ismcts_select(bool take_max, uint32_t best, 
   return first;
 }
 
+// expansion: the child `made` of `node` by the move (snib, scat) of `mover` (over: it emptied the hand).  Lane 0 writes the
+// record whole (V = W = 0 until the backup, A = 1), then its table entry, and puts it on the path below `depth`.
+__device__ __forceinline__ void ismcts_make_node(uint8_t* nodes, uint64_t* tab, uint32_t hlog, uint32_t node, uint32_t made,
+                                                 uint64_t snib, uint32_t scat, bool over, int mover, uint16_t* path, int depth, int lane) {
+  if (lane == 0) {
+    uint64_t* q = (uint64_t*)(nodes + (uint64_t)made * INODE_BYTES);
+    sst64(q, snib | ((uint64_t)scat << 60));
+    sst64(q + 1, 0ull);
+    sst64(q + 2, 1ull | ((uint64_t)node << 32));
+    sst64(q + 3, over ? (1u << 26) | ((uint32_t)mover << 27) : 0u);
+    ismcts_insert(tab, hlog, node, snib, made);
+    path[depth + 1] = (uint16_t)made;
+  }
+}
+
+// the selection step: the selected entry (snib, scat, svlv: as ply_entry gives it) is played, the turn passes on and `child`
+// goes on the path one level down.  (An emptied hand: the child is terminal, the next trip of the descent scores it.)
+__device__ __forceinline__ void ismcts_descend(uint64_t snib, uint32_t scat, uint32_t svlv, uint32_t child, uint64_t& hc, uint64_t& hn,
+                                               uint64_t& hp, uint32_t& trick, int& passes, uint32_t& ply, int& role, uint16_t* path,
+                                               int& depth, int lane) {
+  const uint64_t hnew = ply_play(snib, scat, svlv, hc, trick, passes, ply);
+  __builtin_amdgcn_wave_barrier();   // the staging list is reused by the next level
+  ply_turn(hnew, hc, hn, hp, role);
+  depth += 1;
+  if (lane == 0) path[depth] = (uint16_t)child;
+}
+
+// the root's children leave: visits / wins of table t += V / W at their index j < bound of the root's list (okm, n0, n, info:
+// as ply_list left it, the same in every world)
+template <class Bound>
+__device__ __forceinline__ void ismcts_root_out(const SearchArgs& a, int64_t t, const uint8_t* nodes, const uint64_t* tab,
+                                                uint32_t nnodes, uint64_t okm, int n0, int n, uint32_t info, const uint64_t* stage,
+                                                Bound bound, int lane) {
+  const int trips = 1 + (n - n0 + 63) / 64;
+  for (int trip = 0; trip < trips; ++trip) {
+    uint64_t nib;
+    const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
+    if (j >= 0 && j < bound) {
+      const uint32_t ch = ismcts_find(nodes, tab, a.hash_log, nnodes, 0u, nib);
+      if (ch != SEARCH_NONE) {
+        const uint64_t vw = sld64((const uint64_t*)(nodes + (uint64_t)ch * INODE_BYTES + 8));
+        atomicAdd(a.visits + t * a.stride + j, (int32_t)(uint32_t)vw);
+        if ((uint32_t)(vw >> 32)) atomicAdd(a.wins + t * a.stride + j, (int32_t)(uint32_t)(vw >> 32));
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
   __shared__ HotTabT<false> hot;
   __shared__ uint64_t s_stage[SEARCH_WAVES][STAGE_CAP];
@@ -252,15 +303,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
         s_moves += 1;
         const int mover = role;
         const bool over = ply_apply(snib, scat, svlv, hc, hn, hp, trick, passes, role, ply);
-        if (lane == 0) {   // the record whole (V = W = 0 until the backup, A = 1), then its table entry
-          uint64_t* q = (uint64_t*)(nodes + (uint64_t)made * INODE_BYTES);
-          sst64(q, snib | ((uint64_t)scat << 60));
-          sst64(q + 1, 0ull);
-          sst64(q + 2, 1ull | ((uint64_t)node << 32));
-          sst64(q + 3, over ? (1u << 26) | ((uint32_t)mover << 27) : 0u);
-          ismcts_insert(tab, hlog, node, snib, made);
-          path[depth + 1] = (uint16_t)made;
-        }
+        ismcts_make_node(nodes, tab, hlog, node, made, snib, scat, over, mover, path, depth, lane);
         depth += 1;
         if (over) {
           winner = mover;
@@ -303,25 +346,14 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
       uint64_t snib; uint32_t scat, svlv;
       ply_entry(okm, n0, (int)first, info, stage, svl, snib, scat, svlv);
       s_moves += 1;
-      const uint64_t hnew = ply_play(snib, scat, svlv, hc, trick, passes, ply);
-      __builtin_amdgcn_wave_barrier();   // the staging list is reused by the next level
-      ply_turn(hnew, hc, hn, hp, role);  // (an emptied hand: the child is terminal, the next trip scores it)
+      ismcts_descend(snib, scat, svlv, child, hc, hn, hp, trick, passes, ply, role, path, depth, lane);
       node = child;
-      depth += 1;
-      if (lane == 0) path[depth] = (uint16_t)child;
     }
     // ---- backup: V += 1, W += score on every node of the path, the new node included
     const uint32_t score = (winner >= 0 && same_side(winner, role0)) ? 1u : 0u;
     if (winner < 0) s_unfinished += 1;
     search_fence();   // the path, the new record and the raised A's are written
-    for (int b = 0; b <= depth; b += 64) {
-      const int l = b + lane;
-      if (l <= depth) {
-        uint64_t* p = (uint64_t*)(nodes + (uint64_t)path[l] * INODE_BYTES + 8);
-        const uint64_t vw = sld64(p);
-        sst64(p, vw + 1ull + ((uint64_t)score << 32));
-      }
-    }
+    path_backup<INODE_BYTES>(nodes, path, depth, score, lane);
     search_fence();
   }
   // ---- the root's children leave: visits / wins += V / W at their index of the root's list
@@ -330,24 +362,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
     uint64_t okm; int n0;
     const int n = ply_list(root.hc0, info, hot, lane, stage, svl, okm, n0);
     __builtin_amdgcn_wave_barrier();
-    const int trips = 1 + (n - n0 + 63) / 64;
-    for (int trip = 0; trip < trips; ++trip) {
-      uint64_t nib;
-      const int j = ismcts_lane_entry(trip, okm, n0, n, info, stage, lane, nib);
-      if (j >= 0 && j < n_root) {
-        const uint32_t ch = ismcts_find(nodes, tab, hlog, nnodes, 0u, nib);
-        if (ch != SEARCH_NONE) {
-          const uint64_t vw = sld64((const uint64_t*)(nodes + (uint64_t)ch * INODE_BYTES + 8));
-          atomicAdd(a.visits + t * a.stride + j, (int32_t)(uint32_t)vw);
-          if ((uint32_t)(vw >> 32)) atomicAdd(a.wins + t * a.stride + j, (int32_t)(uint32_t)(vw >> 32));
-        }
-      }
-    }
+    ismcts_root_out(a, t, nodes, tab, nnodes, okm, n0, n, info, stage, n_root, lane);
   }
-  if (lane == 0 && a.totals) {
-    atomicAdd(a.totals + 0, s_moves);
-    atomicAdd(a.totals + 1, (unsigned long long)a.budget);
-    if (s_unfinished) atomicAdd(a.totals + 2, (unsigned long long)s_unfinished);
-    atomicAdd(a.totals + 3, (unsigned long long)(nnodes - 1u));
-  }
+  search_totals_out(a.totals, s_moves, a.budget, s_unfinished, nnodes, lane);
 }

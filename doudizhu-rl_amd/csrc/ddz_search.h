@@ -149,6 +149,31 @@ __device__ __forceinline__ uint32_t search_select(const uint8_t* nodes, const ui
   return rl(bchild, (int)(first & 63u));
 }
 
+// the backup of the later specs (k_ismcts, k_guided, k_gismcts): V += 1, W += score on path[0 .. depth] (the wave's LDS copy),
+// lane l the l-th node.  The V | W word stands at byte 8 of a record of either size.  The caller's fences stand around it.
+template <uint32_t NODE_STRIDE>
+__device__ __forceinline__ void path_backup(uint8_t* nodes, const uint16_t* path, int depth, uint32_t score, int lane) {
+  for (int b = 0; b <= depth; b += 64) {
+    const int l = b + lane;
+    if (l <= depth) {
+      uint64_t* p = (uint64_t*)(nodes + (uint64_t)path[l] * NODE_STRIDE + 8);
+      const uint64_t vw = sld64(p);
+      sst64(p, vw + 1ull + ((uint64_t)score << 32));
+    }
+  }
+}
+
+// the totals of one work item leave (the same kernels'): {moves applied, iterations run, scored unfinished, nodes created}
+__device__ __forceinline__ void search_totals_out(unsigned long long* totals, unsigned long long moves, uint32_t iterations,
+                                                  uint32_t unfinished, uint32_t nnodes, int lane) {
+  if (lane == 0 && totals) {
+    atomicAdd(totals + 0, moves);
+    atomicAdd(totals + 1, (unsigned long long)iterations);
+    if (unfinished) atomicAdd(totals + 2, (unsigned long long)unfinished);
+    atomicAdd(totals + 3, (unsigned long long)(nnodes - 1u));
+  }
+}
+
 template <bool HIDDEN>
 __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   __shared__ HotTabT<false> hot;

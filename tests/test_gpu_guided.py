@@ -312,6 +312,52 @@ def test_misuse_raises_without_touching_the_device(pkg, roots):
     assert env.status() == 0
 
 
+@pytest.mark.parametrize("hidden", (False, True))
+def test_a_header_open_did_not_write_runs_nothing(pkg, roots, hidden):
+    """a step and a close on a workspace no open wrote (every byte 0x3F, then every byte 0: neither is a live header), or on
+    one whose header has a field out of range, touch nothing of it, emit all-zero rows and flags and add nothing to the root
+    sums or the totals (guided_header_live: the check k_gismcts shares, tests/test_gpu_gismcts.py)"""
+    st = roots[hidden][:gc.OUTSIDE]                # (without the table outside the domain: status stays 0)
+    env = _env(pkg, st)
+    env.legal_slab()
+    L, T, stride = env.lib, env.T, env.slab_stride
+    budget, n = 16, env.T * gc.TREES
+    nbytes = L.ddz_guided_work_bytes(T, budget, gc.TREES)
+    common = (budget, gc.TREES, 0, 0.7, 0, int(hidden), _roles(hidden))
+
+    def step_and_close(work):
+        rows = torch.full((n * 176,), FILL, dtype=torch.uint8, device=_dev())
+        need = torch.full((n,), -5, dtype=torch.int32, device=_dev())
+        vals = torch.full((n,), 700, dtype=torch.int32, device=_dev())
+        v, w = (torch.zeros(T * stride, dtype=torch.int32, device=_dev()) for _ in range(2))
+        totals = torch.zeros(4, dtype=torch.int64, device=_dev())
+        assert L.ddz_guided_step(env._h, *common, stride, vals.data_ptr(), rows.data_ptr(), need.data_ptr(), work.data_ptr(), nbytes,
+                                 None) == 0
+        assert L.ddz_guided_close(env._h, *common, vals.data_ptr(), stride, v.data_ptr(), w.data_ptr(), totals.data_ptr(),
+                                  work.data_ptr(), nbytes, None) == 0
+        torch.cuda.synchronize()
+        return not rows.any() and not need.any() and not v.any() and not w.any() and not totals.any()
+
+    for fill in (FILL, 0):
+        work = torch.full((nbytes,), fill, dtype=torch.uint8, device=_dev())
+        assert step_and_close(work) and (work == fill).all()
+    # a header open wrote, then one field out of range on every tree: iteration > budget, no node, more nodes than iterations
+    # allow, a pending node beyond the node count, a pending depth beyond DDZ_SEARCH_MAX_DEPTH (with a valid pending node)
+    per = L.ddz_guided_work_bytes(1, budget, 1)
+    for word, value, also in ((1, budget + 1, ()), (2, 0, ()), (2, 2, ()), (3, 1, ()), (4, sr.MAX_DEPTH + 1, ((3, 0),))):
+        work = torch.full((nbytes,), FILL, dtype=torch.uint8, device=_dev())
+        assert L.ddz_guided_open(env._h, *common, stride, work.data_ptr(), nbytes, None) == 0
+        hdr = work.view(n, per)[:, :64].contiguous().view(torch.int32)
+        live = [gc.TREES * t for t in (0, 1, gc.MID)]
+        assert hdr[live, 0].tolist() == [1, 1, 1] and hdr[gc.TREES * gc.NOT_DEALT, 0].item() == 0x3F3F3F3F
+        for k, x in ((word, value),) + also:
+            hdr[:, k] = x
+        work.view(n, per)[:, :64] = hdr.view(torch.uint8)
+        kept = work.clone()
+        assert step_and_close(work) and torch.equal(work, kept), (word, value)
+    assert env.status() == 0
+
+
 def test_two_runs_are_bit_identical_and_the_env_is_only_read(pkg, roots):
     st = roots[True]
     env = _env(pkg, st)
