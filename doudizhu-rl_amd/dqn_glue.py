@@ -1339,7 +1339,8 @@ class SeatLoop(_Loop):
 
 class QLeaf:
     """A leaf evaluator for engine.GuidedSearch.run (search spec v3): the value of a leaf is its actor's best Q.  The leaf rows
-    are imported into a scratch BatchedEnv of one table per item (made once), q of every legal move comes from the
+    are imported into a scratch BatchedEnv of one table per item (made once; anew when a later search has another item count,
+    device or rule set), q of every legal move comes from the
     shared-rows pass keyed by network slot (SeatLoop.q_values: the leaves of a search are near-duplicates, which is where
     that pass is at its best), and ddz_guided_values turns the maximum into 1024ths: p = qmax / reward[role] is the expected
     outcome in [-1, 1] for the actor's side, value = rint((p + 1) * 512) clamped.  nets: {"lord" | "down" | "up": QNet | None};
@@ -1359,7 +1360,8 @@ class QLeaf:
 
     def scratch(self, search):
         from .engine import BatchedEnv
-        if self.loop is None or self.loop.env.T != search.n_items or self.loop.env.device != search.env.device:
+        if (self.loop is None or self.loop.env.T != search.n_items or self.loop.env.device != search.env.device
+                or self.loop.env.native_joker_kickers != search.env.native_joker_kickers):
             env = BatchedEnv(search.n_items, seed=search.env.seed, device=search.env.device,
                              native_joker_kickers=search.env.native_joker_kickers)
             self.loop = SeatLoop(env, self.nets, self.variant, auto_reset=False)

@@ -1223,7 +1223,8 @@ class GuidedSearch:
 
 class PlayoutLeaf:
     """A leaf evaluator for GuidedSearch.run: flat Monte Carlo from the leaf.  The leaf rows are imported into a scratch
-    BatchedEnv of one table per item (made once, with the searched environment's seed and table_id_base 0), playout(K) runs
+    BatchedEnv of one table per item (made once, with the searched environment's seed, rule set and table_id_base 0; made anew
+    when a later search has another item count, device or rule set), playout(K) runs
     there, and value = (max_j wins_j * 1024) // K: the best move's win rate for the leaf's actor, in integers.  No network."""
 
     def __init__(self, n_playouts, salt=0, chunks=None):
@@ -1231,7 +1232,8 @@ class PlayoutLeaf:
         self.env = None
 
     def scratch(self, search):
-        if self.env is None or self.env.T != search.n_items or self.env.device != search.env.device:
+        if (self.env is None or self.env.T != search.n_items or self.env.device != search.env.device
+                or self.env.native_joker_kickers != search.env.native_joker_kickers):
             self.env = BatchedEnv(search.n_items, seed=search.env.seed, device=search.env.device,
                                   native_joker_kickers=search.env.native_joker_kickers)
         return self.env

@@ -55,7 +55,7 @@ def guided(oracle, states, budget, evaluator, trees=1, mode="reference", c=0.7, 
     """-> (visits int32 [T, stride], wins int32 [T, stride] in 1024ths, totals int64 [4], launches) of search spec v3 for
     `states` uint8 [T, 11, 16]; with trace=True -> (..., launches, items): items[k].iters[i] = {"path": node numbers from the
     root, "choices": the list indices applied from the root, "sel": [(depth, node, list index, took the max, tied, values)],
-    "expand": (node, list index, n of the node) or None, "terminal": the path ended in a terminal node that existed before,
+    "expand": (node, list index, n of the node) or None, "expand_id": the canonical id of its move (beside "expand"), "terminal": the path ended in a terminal node that existed before,
     "pending": the iteration waited for a value, "own": the leaf's actor is on the root actor's side, "value": the clamped
     value, "score", "moves", "winner"}, items[k].nodes"""
     assert mode in ("reference", "sides") and 1 <= budget <= MAX_BUDGET and c >= 0 and budget * trees * ONE < 2 ** 31
@@ -105,7 +105,7 @@ def guided(oracle, states, budget, evaluator, trees=1, mode="reference", c=0.7, 
         leaf_rows = np.zeros((T * trees, NFIELDS, ROW), np.uint8)
         need = np.zeros(T * trees, np.int32)
         while (phase != OVER).any():
-            off, _, _ = env.legal()
+            off, _, ids = env.legal()
             A = np.diff(off).astype(np.int64)
             done = m[:, pr.M_DONE] == 1
             sel = np.full(I, -1, np.int32)
@@ -139,6 +139,7 @@ def guided(oracle, states, budget, evaluator, trees=1, mode="reference", c=0.7, 
                     node.kids[j] = len(it.nodes)
                     it.probe.insert(cur[k], j)
                     rec[k]["expand"] = (cur[k], j, node.n)
+                    rec[k]["expand_id"] = int(ids[off[k] + j])
                     it.nodes.append(child)
                     made[k] = child
                     child.winner = role      # (used if the move empties the hand)

@@ -100,6 +100,7 @@ def search(oracle, states, budget, trees=1, mode="reference", c=0.7, seed=0, gid
     """-> (visits int32 [T, stride], wins int32 [T, stride], totals int64 [4]) of search spec v1 for `states` uint8
     [T, 11, 16]; with trace=True -> (visits, wins, totals, items): items[k].iters[i] = {"path": node numbers from the root,
     "sel": [(depth, node, list index, took the max, tied, values)], "expand": (node, list index, n of the node) or None,
+    "expand_id": the canonical id of the expansion's move (beside "expand"),
     "terminal": the path ended in a terminal node that existed before, "moves", "winner"}, items[k].nodes, .probe"""
     assert mode in ("reference", "sides") and 1 <= budget <= MAX_BUDGET and c >= 0
     states = np.asarray(states, np.uint8).reshape(-1, NFIELDS, ROW)
@@ -141,7 +142,7 @@ def search(oracle, states, budget, trees=1, mode="reference", c=0.7, seed=0, gid
         moves = np.zeros(I, np.int64)
         rec = [{"path": path[k], "sel": [], "expand": None, "terminal": False, "moves": 0, "winner": -1} for k in range(I)]
         while (phase != OVER).any():
-            off, _, _ = env.legal()
+            off, _, ids = env.legal()
             A = np.diff(off).astype(np.int64)
             ply = m[:, pr.M_PLY].astype(np.int64) | (m[:, pr.M_PLY + 1].astype(np.int64) << 8)
             done = m[:, pr.M_DONE] == 1
@@ -165,6 +166,7 @@ def search(oracle, states, budget, trees=1, mode="reference", c=0.7, seed=0, gid
                     node.kids[j] = len(it.nodes)
                     it.probe.insert(cur[k], j)
                     rec[k]["expand"] = (cur[k], j, node.n)
+                    rec[k]["expand_id"] = int(ids[off[k] + j])
                     it.nodes.append(child)
                     made[k] = child
                     child.winner = role      # (used if the move empties the hand)

@@ -99,6 +99,17 @@ def test_follow_lists_are_small(oracle):
     assert worst < 64   # a follow list is pass + same-category beats + bombs + rocket
 
 
+def test_count_vectors_are_pairwise_distinct(oracle):
+    """the premise of keying an ISMCTS child by (parent, 60-bit count word) (csrc/ddz_ismcts.h, ddz_gismcts.h) instead of by
+    canonical id: in both rule sets no two rows of the action table hold the same 15 counts, the joker-kicker rows included
+    (13,527 of 13,527 and 13,551 of 13,551), and every count fits a nibble"""
+    for jk, n in ((False, 13527), (True, 13551)):
+        with oracle.variant(jk=jk):
+            rows = oracle.action_table()[0]
+        assert len(rows) == n and rows[:, :15].min() >= 0 and rows[:, :15].max() <= 4
+        assert len(np.unique(rows[:, :15], axis=0)) == n
+
+
 def test_episode_length_bound(oracle):
     # every non-pass play removes a card and at most two passes separate plays: <= 162 plies,
     # so the u16 ply counter and the RNG's 16-bit ply field cannot wrap
