@@ -10,7 +10,9 @@ from .engine import (BatchedEnv, GuidedSearch, PlayoutLeaf, guided_values, FACE_
                      q_features_rows, q_features_drows, q_gather_h0, q_shared_ws_bytes, q_shared_need_ws_bytes,
                      q_roles_ws_bytes, q_roles_need_ws_bytes, rows_to_onehot, state_prob, observe_states, tr_ws_bytes,
                      tr_ring_bytes, tr_ring_layout, mc_ws_bytes, mc_ws_layout, mc_ring_bytes,
-                     mc_ring_layout, teach_ws_bytes, teach_ws_layout, Teacher, TeacherStats)
+                     mc_ring_layout, teach_ws_bytes, teach_ws_layout, Teacher, TeacherStats,
+                     STATUS_MISMATCH, STATUS_CAPACITY, STATUS_BAD_LAST, STATUS_AUTO_WAIT, STATUS_AUTO_DEPTH, STATUS_Q_NO_ROW,
+                     STATUS_DOMAIN, STATUS_CFR_CAPACITY, STATUS_SOLVE_DEPTH)
 from .dqn_glue import (PackedBatch, QLeaf, ReturnBatch, ReturnRecorder, RoleQ, SeatLoop, TeacherAssembler, TeacherRecorder,  # noqa: F401
                        TrainLoop, TransitionRecorder, compete, mc_step, train)
 from .envi import Env, EnvComplicated, EnvCooperation, EnvCooperationSimplify  # noqa: F401

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(TB, 4) void k_auto(AutoArgs a) {
       const uint64_t P = pack_row(R);
       const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
       role = mx & 0xFF;
-      active = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF) && role <= 2 && ((a.auto_roles >> role) & 1);
+      active = meta_dealt(my) && !meta_done(mx) && role <= 2 && ((a.auto_roles >> role) & 1);
       if (role > 2) role = 0;
       const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
       hand = rl64(P, DDZ_F_HAND0 + role);
@@ -181,12 +181,12 @@ __global__ __launch_bounds__(TB, 4) void k_auto(AutoArgs a) {
       left0 = q & 0xFF; left1 = (q >> 8) & 0xFF; left2 = (q >> 16) & 0xFF; role = (int)(q >> 24);
       active = true;
       if (linfo == INFO_INVALID || ge_mask(hand, 5) || (hand >> 60) || role > 2) {  // no combo of the action space
-        if (lane == 0 && a.status) atomicOr(a.status, 4);
+        if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_BAD_LAST);
         active = false; invalid = true;
       }
     }
     if (active && nib_sum(hand) > 20) {  // no player ever holds more than 20 cards: the search is sized for that
-      if (lane == 0 && a.status) atomicOr(a.status, 4);
+      if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_BAD_LAST);
       active = false; invalid = true;
     }
     if (!active || hand == 0) {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(TB, 4) void k_auto(AutoArgs a) {
     }
     __builtin_amdgcn_wave_barrier();
     if (n > STAGE_CAP) {  // cannot happen for a <= 20-card hand
-      if (lane == 0) { if (a.status) atomicOr(a.status, 2); a.ids[t] = DDZ_AUTO_INVALID; }
+      if (lane == 0) { if (a.status) atomicOr(a.status, DDZ_ST_CAPACITY); a.ids[t] = DDZ_AUTO_INVALID; }
       continue;
     }
     // ---- 2. per candidate: cards_value x 2, fine_mask bit, lowest rank; counting sort by lowest rank
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(TB, 4) void k_auto(AutoArgs a) {
         continue;
       }
       if (d + 1 >= AUTO_DEPTH) {  // cannot happen: at most 20 actions
-        if (lane == 0 && a.status) atomicOr(a.status, 16);
+        if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_AUTO_DEPTH);
         continue;
       }
       // ---- descend

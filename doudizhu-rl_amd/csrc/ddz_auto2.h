@@ -111,7 +111,7 @@ __device__ __forceinline__ void a2_lock(uint32_t* l, int lane, int32_t* status) 
     uint32_t spins = 0;
     while (__hip_atomic_exchange(l, 1u, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) {
       __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1u << 24)) { if (status) atomicOr(status, 8); break; }
+      if (++spins > (1u << 24)) { if (status) atomicOr(status, DDZ_ST_AUTO_WAIT); break; }
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(AO_BT) void k_auto_order(const uint8_t* __restrict_
     const uint8_t* row = state + t * STATE_ROW_BYTES;
     const uint4 meta = *(const uint4*)(row + DDZ_F_META * 16);
     const int role = meta.x & 0xFF;
-    const bool active = ((meta.y >> 16) & 0xFF) && !((meta.x >> 8) & 0xFF) && role <= 2 && ((auto_roles >> role) & 1);
+    const bool active = meta_dealt(meta.y) && !meta_done(meta.x) && role <= 2 && ((auto_roles >> role) & 1);
     if (active) {
       cls = auto_class(row + (DDZ_F_HAND0 + role) * 16);
       single = row[(DDZ_F_HAND0 + role) * 16 + 15] >= 13;  // cards left (envi.py:23)
@@ -394,12 +394,12 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
       if (own < 0) {
         if (first_helper) {     // no team to join (yet, or any more): on to the queue once the owner is through
           if (a2_peek(&s_first_done) != 0) { first_helper = false; polls = 0; continue; }
-          if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, 8); first_helper = false; continue; }
+          if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_AUTO_WAIT); first_helper = false; continue; }
           __builtin_amdgcn_s_sleep(4);
           continue;
         }
         if (a2_peek(&s_inflight) == 0) break;
-        if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, 8); break; }
+        if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_AUTO_WAIT); break; }
         __builtin_amdgcn_s_sleep(16);
         continue;
       }
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
         const uint64_t P = pack_row(R);
         const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
         role = mx & 0xFF;
-        active = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF) && role <= 2 && ((a.auto_roles >> role) & 1);
+        active = meta_dealt(my) && !meta_done(mx) && role <= 2 && ((a.auto_roles >> role) & 1);
         if (role > 2) role = 0;
         const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
         hand = rl64(P, DDZ_F_HAND0 + role);
@@ -449,12 +449,12 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
         left0 = qq & 0xFF; left1 = (qq >> 8) & 0xFF; left2 = (qq >> 16) & 0xFF; role = (int)(qq >> 24);
         active = true;
         if (linfo == INFO_INVALID || ge_mask(hand, 5) || (hand >> 60) || role > 2) {  // no combo of the action space
-          if (lane == 0 && a.status) atomicOr(a.status, 4);
+          if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_BAD_LAST);
           active = false; invalid = true;
         }
       }
       if (active && nib_sum(hand) > 20) {  // no player ever holds more than 20 cards: the search is sized for that
-        if (lane == 0 && a.status) atomicOr(a.status, 4);
+        if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_BAD_LAST);
         active = false; invalid = true;
       }
       if (!active || hand == 0) {
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
       tq_enum = __builtin_amdgcn_s_memtime();
 #endif
       if (n > A2_CAND) {  // cannot happen for a <= 20-card hand (tools/max_legal_bound.c)
-        if (lane == 0) { if (a.status) atomicOr(a.status, 2); a.ids[t] = DDZ_AUTO_INVALID; }
+        if (lane == 0) { if (a.status) atomicOr(a.status, DDZ_ST_CAPACITY); a.ids[t] = DDZ_AUTO_INVALID; }
         continue;
       }
       // per candidate (lane holds entries lane, lane + 64, ...: at most 8): value x 2, fine_mask, lowest rank, cards.
@@ -1069,7 +1069,7 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
             if (bn > 0) { A2DBG(3, nt); A2DBG(7, 1); next_item = nt; polls = 0; continue; }
             if (over) break;                // nobody holds work, nothing in the box: the search is complete
           }
-          if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, 8); break; }
+          if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_AUTO_WAIT); break; }
           __builtin_amdgcn_s_sleep(4);
           continue;
         }
@@ -1273,7 +1273,7 @@ __global__ __launch_bounds__(A2_TB, DDZ_A2_OCC) void k_auto2(AutoArgs a) {
       const int nm = (int)rfl(TM.members);
       a2_unlock(&TM.lock, lane);
       while (__hip_atomic_load(&TM.finished, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u < (uint32_t)nm) {
-        if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, 8); break; }
+        if (++polls > A2_POLL_LIMIT) { if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_AUTO_WAIT); break; }
         __builtin_amdgcn_s_sleep(2);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   // counts that are not negative, and where that holds for no rank deck - taken = unseen + hand without a borrow, so
   // `sum(deck - taken) != n_me + n_next + n_prev` is `sum(unseen) != n_next + n_prev`.  The actor's own hand is not empty.
   if (rh.kind == ROOT_OUTSIDE || n_me < 1) {
-    if (lane == 0) { a.n[t] = -1; atomicOr(a.status, 64); }
+    if (lane == 0) { a.n[t] = -1; atomicOr(a.status, DDZ_ST_DOMAIN); }
     return;
   }
   const uint64_t pool = rh.unseen + hc0;   // deck - taken
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   }
   if (over) {   // no slot, or a capacity: nothing was stored out of bounds
     if (lane < DDZ_CFR_STRIDE) out_ids[lane] = -1;
-    if (lane == 0) { a.n[t] = -2; atomicOr(a.status, 128); }
+    if (lane == 0) { a.n[t] = -2; atomicOr(a.status, DDZ_ST_CFR_CAPACITY); }
     return;
   }
   const uint32_t nlev = depth + 1;
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
   }
   if (I0 == CFR_NONE || nI0 != (uint32_t)n_root) {   // (cannot happen: the actual hand is the actor's hand of some deal)
     if (lane < DDZ_CFR_STRIDE) out_ids[lane] = -1;
-    if (lane == 0) { a.n[t] = -2; atomicOr(a.status, 128); }
+    if (lane == 0) { a.n[t] = -2; atomicOr(a.status, DDZ_ST_CFR_CAPACITY); }
     return;
   }
   if (lane < n_root) out_sigma[lane] = sldf(Sg + off0 + (uint32_t)lane);
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(CFR_WAVES * 64) void k_cfr(CfrArgs a) {
 }
 
 // ddz_cfr_choose: one lane per table.  greedy: the first maximum of sigma; else u = x * 2^-32 with x = the first word of
-// philox4x32_10((gid_lo, gid_hi, 0, 8 << 16), key) (RNG domain 8), the first j with u below the running sum of sigma in list
+// rng_draw(gid, 0, RNG_CFR_CHOOSE, 0, key), the first j with u below the running sum of sigma in list
 // order, falling back to the last j with sigma_j > 0.  -1 where n <= 0.
 __global__ __launch_bounds__(BLOCK) void k_cfr_choose(const int32_t* __restrict__ n, const int32_t* __restrict__ ids,
                                                       const double* __restrict__ sigma, uint32_t k0, uint32_t k1, uint64_t gid_base,
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(BLOCK) void k_cfr_choose(const int32_t* __restrict_
       if (pick < 0 || s[j] > best) { best = s[j]; pick = j; }
   } else {
     const uint64_t gid = gid_base + (uint64_t)t;
-    const uint32_t x = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), 0u, 8u << 16), k0, k1).x;
+    const uint32_t x = rng_draw(gid, 0u, RNG_CFR_CHOOSE, 0u, k0, k1).x;
     const double u = (double)x * (1.0 / 4294967296.0);
     double acc = 0.0;
     int last = k - 1;

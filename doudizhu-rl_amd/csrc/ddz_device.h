@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ddz_env.h"  // DDZ_F_*, DDZ_ST_*
+
 #ifndef DDZ_NATIVE_JOKER_KICKERS
 #define DDZ_NATIVE_JOKER_KICKERS 0  // 1: libddz_hip_jk.so, the rule set plus the 24 joker-kicker rows (include/ddz_env.h)
 #endif
@@ -253,6 +255,75 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
     k1 += 0xBB67AE85u;
   }
   return c;
+}
+// The domains of the engine's draws: the streams are independent because these values differ.
+enum RngDomain : uint32_t {
+  RNG_DEAL = 1,          // the deal of an episode: index = card / 4
+  RNG_STEP = 2,          // random.choice of a step or rollout: index = ply
+  RNG_EPSILON = 3,       // the epsilon-greedy draw of a Q step: index = ply
+  RNG_PLAYOUT = 4,       // a playout's plies: index = ply
+  RNG_WORLD = 5,         // the redeal of the hidden hands: index = card / 4
+  RNG_EXPAND = 6,        // a tree search's expansion
+  RNG_TREE_PLAYOUT = 7,  // a tree search's playout: index = ply
+  RNG_CFR_CHOOSE = 8     // the sample from the CFR average strategy
+};
+// the one Philox call of a draw: counter (gid_lo, gid_hi, third, domain << 16 | index), index < 2^16.  The deals
+// (deal_wave, deal_wave_lds, redeal_wave) and the tree searches' expansion draws spell the same counter themselves, with the
+// domain's name: there the call compiled to other code than the expression did (profiles/r29_notes.md)
+__device__ __forceinline__ uint4 rng_draw(uint64_t gid, uint32_t third, RngDomain domain, uint32_t index, uint32_t k0, uint32_t k1) {
+  return philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), third, ((uint32_t)domain << 16) | index), k0, k1);
+}
+
+// ---- the meta row (row DDZ_F_META of a table, include/ddz_env.h) as its four words ------------------------------------
+//   x: [0] role to move, [1] done, [2] winner's role (META_NO_WINNER: none), [3] reward code     z: the episode
+//   y: [4..5] ply, [6] dealt, [7] kept as imported                                              w: kept (zero after a deal)
+// The functions below are what a kernel calls; the constants are for the sites where a call compiled to other code than the
+// expression did (profiles/r29_notes.md), which spell the same expressions with them.
+constexpr int META_DONE_SHIFT = 8, META_WINNER_SHIFT = 16, META_REWARD_SHIFT = 24;  // in x
+constexpr int META_DEALT_SHIFT = 16;                                               // in y
+constexpr uint32_t META_BYTE = 0xFF, META_PLY_MASK = 0xFFFF, META_NO_WINNER = 0xFFu;
+__device__ __forceinline__ int meta_role(uint32_t mx) {  // never index outside the table on a corrupted import
+  const int role = mx & META_BYTE;
+  return role > 2 ? 0 : role;
+}
+__device__ __forceinline__ uint32_t meta_done(uint32_t mx) { return (mx >> META_DONE_SHIFT) & META_BYTE; }    // the bytes as
+__device__ __forceinline__ uint32_t meta_dealt(uint32_t my) { return (my >> META_DEALT_SHIFT) & META_BYTE; }  // imported: non-zero is true
+__device__ __forceinline__ uint32_t meta_ply(uint32_t my) { return my & META_PLY_MASK; }
+// a table is running where meta_dealt(my) && !meta_done(mx): written out at every site, since a function around the && is
+// compiled to one test of both bytes where the sites branch on the first
+__device__ __forceinline__ uint4 meta_fresh(uint32_t episode) {  // after a deal: the lord to move, nobody has won, ply 0
+  return make_uint4(1u | (0xFFu << 16), 1u << 16, episode, 0);
+}
+// after a ply (`ply` counts it already): bytes 6..7 stay the table's own (`my`), and so do mz and mw
+__device__ __forceinline__ uint4 meta_after_ply(int next_role, bool won, int winner_role, uint32_t reward, uint32_t my,
+                                                uint32_t ply, uint32_t mz, uint32_t mw) {
+  return make_uint4((uint32_t)next_role | (won ? 1u << META_DONE_SHIFT : 0u) |
+                        ((won ? (uint32_t)winner_role : META_NO_WINNER) << META_WINNER_SHIFT) | (reward << META_REWARD_SHIFT),
+                    (my & ~META_PLY_MASK) | (ply & META_PLY_MASK), mz, mw);
+}
+// lane f < DDZ_NFIELDS: row f of a freshly dealt table (hands of 17 / 20 / 17 cards, the lord leads).  k_table's reset calls
+// it; the deals after a won game (k_table's, k_slab's three) write the same selection out around meta_fresh
+__device__ __forceinline__ uint4 fresh_deal_row(int lane, uint64_t h0, uint64_t h1, uint64_t h2, uint32_t episode) {
+  return lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
+         : lane == DDZ_F_META ? meta_fresh(episode) : make_uint4(0, 0, 0, 0);
+}
+
+// ---- the step record (the trajectory entry's second 16 bytes; the first is the chosen row) ----------------------------
+//   x: [0] role, [1] won (frozen: done), [2] reward code, [3] flags     y: legal count | ply << 16
+//   z: episode                                                           w: index of the move in its list, TRAJ_NO_INDEX none
+constexpr int TRAJ_WON_SHIFT = 8, TRAJ_REWARD_SHIFT = 16, TRAJ_FLAGS_SHIFT = 24;  // in x
+constexpr int TRAJ_PLY_SHIFT = 16;                                               // in y
+constexpr uint32_t TRAJ_BYTE = 0xFF, TRAJ_LEGAL_MASK = 0xFFFF, TRAJ_NO_INDEX = 0xFFFFFFFFu;
+constexpr uint32_t TRAJ_ILLEGAL = 1u << TRAJ_FLAGS_SHIFT;  // the selection is not in the list: table untouched
+constexpr uint32_t TRAJ_FROZEN = 2u << TRAJ_FLAGS_SHIFT;   // empty list (done / not dealt): table untouched
+// the record starts as make_uint4(role, (n_legal & TRAJ_LEGAL_MASK) | ply << TRAJ_PLY_SHIFT, episode, TRAJ_NO_INDEX): written
+// out in the three stepping kernels (a function compiled to other code in each of them)
+__device__ __forceinline__ uint32_t traj_outcome(bool won, uint32_t reward) {  // or-ed into x
+  return (uint32_t)won << TRAJ_WON_SHIFT | reward << TRAJ_REWARD_SHIFT;
+}
+constexpr uint32_t REWARD_FARMERS = 1u, REWARD_LORD = 0xFFu;          // +1 / -1 as an int8 (rule_play.py:14)
+__device__ __forceinline__ uint32_t reward_code(bool won, int role) {  // of the ply that `role` made
+  return won ? (role == 1 ? REWARD_LORD : REWARD_FARMERS) : 0u;
 }
 
 }  // namespace ddz

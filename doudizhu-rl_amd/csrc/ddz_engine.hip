@@ -200,7 +200,9 @@ __device__ __forceinline__ uint4 row_of_id(int id) {
 __device__ uint4 g_tmp_rows[DDZ_NUM_ACTIONS];
 __device__ int32_t g_tmp_ids[DDZ_NUM_ACTIONS];
 
-// one wavefront: enumerate the full deck on lead (every action, ids 1..13526 in order)
+// one wavefront: enumerate the full deck on lead (every action, ids 1..13526 in order).  `status` is the build's own flag
+// word, not a ddz_status word: the host tests it against zero only
+constexpr int BUILD_TABLE_FAILED = 8;  // the enumerator's count or id order is not the action space's
 __global__ __launch_bounds__(64) void k_build_table(int32_t* status) {
   const int lane = threadIdx.x & 63;
   if (lane < 9) {  // lane k writes combination list k
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(64) void k_build_table(int32_t* status) {
   __threadfence();
   __syncthreads();
   if (n != DDZ_NUM_ACTIONS - 1) {
-    if (lane == 0) atomicOr(status, 8);
+    if (lane == 0) atomicOr(status, BUILD_TABLE_FAILED);
     return;
   }
   for (int p = lane; p < n + 1; p += 64) {
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(64) void k_build_table(int32_t* status) {
     if (p > 0) {
       row = g_tmp_rows[p - 1];
       id = g_tmp_ids[p - 1];
-      if (id != p) atomicOr(status, 8);
+      if (id != p) atomicOr(status, BUILD_TABLE_FAILED);
     }
     const uint64_t nib = pack_row(row);
     const uint32_t info = info_of_row(nib, (int)(row.w >> 24));
@@ -590,7 +592,7 @@ __device__ __forceinline__ uint64_t nib_from_cards(uint64_t b) {  // bit k = car
 }
 __device__ inline void deal_wave(uint64_t gid, uint32_t episode, uint32_t k0, uint32_t k1, int lane,
                                  uint64_t& o0, uint64_t& o1, uint64_t& o2) {
-  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (1u << 16) | (uint32_t)(lane >> 2)), k0, k1);
+  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (RNG_DEAL << 16) | (uint32_t)(lane >> 2)), k0, k1);
   const int w = lane & 3;
   const uint32_t key = w == 0 ? d.x : w == 1 ? d.y : w == 2 ? d.z : d.w;
   // rank by (key, card index): one 64-bit compare of (key << 6 | index) per card
@@ -609,7 +611,7 @@ __device__ inline void deal_wave(uint64_t gid, uint32_t episode, uint32_t k0, ui
 // one table per wave, where a deal sits on the launch's critical path).  `keys`: 64 x 8 bytes of the calling wave.
 __device__ inline void deal_wave_lds(uint64_t gid, uint32_t episode, uint32_t k0, uint32_t k1, int lane, uint64_t* keys,
                                      uint64_t& o0, uint64_t& o1, uint64_t& o2) {
-  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (1u << 16) | (uint32_t)(lane >> 2)), k0, k1);
+  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (RNG_DEAL << 16) | (uint32_t)(lane >> 2)), k0, k1);
   const int w = lane & 3;
   const uint32_t key = w == 0 ? d.x : w == 1 ? d.y : w == 2 ? d.z : d.w;
   const uint64_t kk = ((uint64_t)key << 6) | (uint32_t)lane;
@@ -735,10 +737,9 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
     if (i + 1 < ntab && lane < DDZ_NFIELDS) Rnext = ((const uint4*)(a.state + (t + 1) * STATE_ROW_BYTES))[lane];
     uint64_t P = pack_row(R);
     const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META), mz = rl(R.z, DDZ_F_META);
-    int role = mx & 0xFF;
-    if (role > 2) role = 0;  // never index outside the table on a corrupted import
-    bool is_done = (mx >> 8) & 0xFF, dealt = (my >> 16) & 0xFF;
-    uint32_t ply = my & 0xFFFF, episode = mz;
+    int role = meta_role(mx);
+    bool is_done = meta_done(mx), dealt = meta_dealt(my);
+    uint32_t ply = meta_ply(my), episode = mz;
     const uint64_t gid = a.gid_base + (uint64_t)t;
     const bool active = dealt && !is_done;
     const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
@@ -756,13 +757,13 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
       cnt = (int)rl((uint32_t)cnt_l, i);
       if (lane == 0) a.offsets[t] = (int32_t)base;
       if (PICK && active && cnt > 0) {  // random.choice(actions), envi.py:83
-        const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (2u << 16) | ply), a.k0, a.k1);
+        const uint4 d = rng_draw(gid, episode, RNG_STEP, ply, a.k0, a.k1);
         pk.want = (int)__umulhi(rfl(d.x), (uint32_t)cnt);
       }
       const Out o{a.rows, a.ids, base, a.cap, nullptr, nullptr, nullptr};
       const int n = plan_scan<PICK ? EM_PICK : EM_WRITE, IDS>(hand, active ? info : QF_FROZEN, hot, lane, o, pk);
       if (lane == 0) {
-        const int bits = (n != cnt ? 1 : 0) | (base + cnt > a.cap ? 2 : 0);
+        const int bits = (n != cnt ? DDZ_ST_MISMATCH : 0) | (base + cnt > a.cap ? DDZ_ST_CAPACITY : 0);
         if (bits) atomicOr(a.status, bits);
       }
     }
@@ -785,7 +786,7 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
           if (PICK) {
             idx = pk.want; c0 = pk.r0; c1 = pk.r1; c2 = pk.r2; c3 = pk.r3;
           } else {
-            const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (2u << 16) | ply), a.k0, a.k1);
+            const uint4 d = rng_draw(gid, episode, RNG_STEP, ply, a.k0, a.k1);
             idx = (int)__umulhi(rfl(d.x), (uint32_t)A);
           }
         } else if (MODE == DDZ_STEP_CHOICE) {
@@ -811,13 +812,13 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
         }
       }
       uint4 tr0 = make_uint4(0, 0, 0, 0);
-      uint4 tr1 = make_uint4((uint32_t)role, ((uint32_t)A & 0xFFFF) | (ply << 16), episode, 0xFFFFFFFFu);
+      uint4 tr1 = make_uint4((uint32_t)role, ((uint32_t)A & TRAJ_LEGAL_MASK) | (ply << TRAJ_PLY_SHIFT), episode, TRAJ_NO_INDEX);
       uint32_t o_done = is_done, o_illegal = 0, o_reward = 0;
       if (frozen) {
-        tr1.x |= (uint32_t)is_done << 8 | 2u << 24;
+        tr1.x |= (uint32_t)is_done << TRAJ_WON_SHIFT | TRAJ_FROZEN;
       } else if (idx < 0) {
         o_done = 0; o_illegal = 1;
-        tr1.x |= 1u << 24;
+        tr1.x |= TRAJ_ILLEGAL;
       } else {
         changed = true;
         const uint32_t cw3 = c3 & 0x00FFFFFFu;
@@ -834,11 +835,11 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
           R = make_uint4(c0, c1, c2, c3);
         }
         const bool won = (rl(R.w, DDZ_F_HAND0 + role) >> 24) == 0;
-        o_reward = won ? (role == 1 ? 0xFFu : 1u) : 0u;  // rule_play.py:14: -1 lord won, +1 farmers
+        o_reward = won ? (role == 1 ? REWARD_LORD : REWARD_FARMERS) : 0u;
         o_done = won;
         s_ply += 1; s_eps += won; s_lord += (won && role == 1); s_up += (won && role == 0);
         tr0 = make_uint4(c0, c1, c2, c3);
-        tr1.x |= (uint32_t)won << 8 | o_reward << 16;
+        tr1.x |= (uint32_t)won << TRAJ_WON_SHIFT | o_reward << TRAJ_REWARD_SHIFT;
         tr1.w = (uint32_t)idx;
         const int nrole = rp1;  // lord -> down -> up, game.py:173-181
         ply += 1;
@@ -847,13 +848,14 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
           uint64_t h0, h1, h2;
           deal_wave(gid, episode, a.k0, a.k1, lane, h0, h1, h2);
           R = lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-              : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, episode, 0) : make_uint4(0, 0, 0, 0);
+              : lane == DDZ_F_META ? meta_fresh(episode) : make_uint4(0, 0, 0, 0);
           role = 1; is_done = false;
           qhand = h1; qinfo = mk_info(EMPTY, 0, 1);  // the lord leads
         } else {
           if (lane == DDZ_F_META)
-            R = make_uint4((uint32_t)nrole | (won ? 1u << 8 : 0u) | ((won ? (uint32_t)role : 0xFFu) << 16) | (o_reward << 24),
-                           (my & 0xFFFF0000u) | (ply & 0xFFFF), mz, R.w);
+            R = make_uint4((uint32_t)nrole | (won ? 1u << META_DONE_SHIFT : 0u) |
+                               ((won ? (uint32_t)role : META_NO_WINNER) << META_WINNER_SHIFT) | (o_reward << META_REWARD_SHIFT),
+                           (my & ~META_PLY_MASK) | (ply & META_PLY_MASK), mz, R.w);
           role = nrole; is_done = won;
         }
       }
@@ -871,8 +873,7 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
         episode = dealt ? episode + 1 : 0;
         uint64_t h0, h1, h2;
         deal_wave(gid, episode, a.k0, a.k1, lane, h0, h1, h2);
-        R = lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-            : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, episode, 0) : make_uint4(0, 0, 0, 0);
+        R = fresh_deal_row(lane, h0, h1, h2, episode);
         role = 1; is_done = false; dealt = true;
         qhand = h1; qinfo = mk_info(EMPTY, 0, 1);
       }
@@ -896,7 +897,7 @@ __global__ __launch_bounds__(TB, 4) void k_table(TableArgs a) {
       Pick nopk{-1, 0, 0, 0, 0};
       int n = (dealt && !is_done) ? plan_scan<EM_WRITE, IDS>(hand, info, hot, lane, o, nopk) : 0;
       if (n > a.stride) {  // cannot happen for a <= 20-card hand with the default stride
-        if (lane == 0) atomicOr(a.status, 2);
+        if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
         n = 0;
       }
       if (lane == 0) a.slab_counts[t] = n;
@@ -1124,10 +1125,9 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META), mz = rl(R.z, DDZ_F_META);
     const uint32_t my_hi = my & 0xFFFF0000u;
     uint32_t mw = rl(R.w, DDZ_F_META);
-    int role = mx & 0xFF;
-    if (role > 2) role = 0;
-    const bool active = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF);  // dealt and not done
-    uint32_t ply = my & 0xFFFF, episode = mz;
+    int role = meta_role(mx);
+    const bool active = meta_dealt(my) && !meta_done(mx);
+    uint32_t ply = meta_ply(my), episode = mz;
     // hands in turn order: hc = the actor's, hn = the next player's, hp = the previous player's; a ply
     // rotates the three names (register moves) instead of selecting by role twice
     uint64_t hc = rl64(P, DDZ_F_HAND0 + role), hn = rl64(P, DDZ_F_HAND0 + (role == 2 ? 0 : role + 1)),
@@ -1152,7 +1152,8 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       }
       if (TRAJ) {
         const uint4 f0 = make_uint4(0, 0, 0, 0);
-        const uint4 f1 = make_uint4((uint32_t)role | ((mx >> 8) & 0xFF) << 8 | 2u << 24, ply << 16, episode, 0xFFFFFFFFu);
+        // (the done byte as imported; k_table and k_slab record 0 / 1)
+        const uint4 f1 = make_uint4((uint32_t)role | meta_done(mx) << TRAJ_WON_SHIFT | TRAJ_FROZEN, ply << TRAJ_PLY_SHIFT, episode, TRAJ_NO_INDEX);
         for (int it = (int)a.n_iters; it > 0; --it) {
           if (lane < 2) tj[lane] = sel4(lane == 0, f0, f1);
           tj += 2 * a.T;
@@ -1163,14 +1164,14 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
     int idle = 0;  // iterations that applied no ply (n <= 0: an empty imported hand, or behind the STAGE_CAP guard)
     for (int it = (int)a.n_iters; it > 0; --it) {
       uint4 tr0 = make_uint4(0, 0, 0, 0);
-      uint4 tr1 = make_uint4((uint32_t)role, ply << 16, episode, 0xFFFFFFFFu);
+      uint4 tr1 = make_uint4((uint32_t)role, ply << TRAJ_PLY_SHIFT, episode, TRAJ_NO_INDEX);
       uint32_t dn = rfl(dnext);  // the same value in every lane: a scalar branch, and the lane of the draw below
       if (dn >= 64u) {
         dn = 0;
         dnext = 0;
         uint32_t qk0 = a.k0, qk1 = a.k1;  // opaque: round keys are computed here, not hoisted and spilled
         asm volatile("" : "+s"(qk0), "+s"(qk1));
-        draws = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (2u << 16) | (ply + (uint32_t)lane)), qk0, qk1).x;
+        draws = rng_draw(gid, episode, RNG_STEP, ply + (uint32_t)lane, qk0, qk1).x;
       }
       const uint64_t hand = hc;
       // rfl: the combo to beat stays wave-uniform for the compiler, so the category dispatch below is
@@ -1275,7 +1276,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           __builtin_amdgcn_wave_barrier();
           n = (int)rfl((uint32_t)(n0 + n1));  // wave-uniform: the guard, the pick's two tests are scalar branches
           if (n > STAGE_CAP || n > a.stride) {  // cannot happen for a <= 20-card hand; never index past the slab
-            if (lane == 0) atomicOr(a.status, 2);
+            if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
             n = 0;
           }
           stamps.mark(2);  // hybrid: closed-form round + planner + scan rounds + staging
@@ -1308,11 +1309,11 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           stamps.mark(10);  // hybrid: pick
         }
       }
-      tr1.y |= (uint32_t)n & 0xFFFF;
+      tr1.y |= (uint32_t)n & TRAJ_LEGAL_MASK;
       // (this test stays a lane-mask branch: read through rfl or a ballot it costs the record-writing 12-wave variants
       // 4..28 B of scratch and the headline 1.4 %, profiles/r10_notes.md)
       if (n <= 0) {
-        tr1.x |= 2u << 24;
+        tr1.x |= TRAJ_FROZEN;
         idle += 1;
       } else {
         {  // envi.py:39-43 on the packed rows, as lane masks (a pass adds zeros; no nibble carries: counts <= 4, jokers <= 1)
@@ -1330,9 +1331,9 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         // form none
         constexpr bool WON_SCALAR = !(STAGED && RW != WPB && DDZ_NATIVE_JOKER_KICKERS);
         const bool won = WON_SCALAR ? rfl((uint32_t)hnew | (uint32_t)(hnew >> 32)) == 0u : hnew == 0;
-        const uint32_t o_reward = won ? (role == 1 ? 0xFFu : 1u) : 0u;  // rule_play.py:14
+        const uint32_t o_reward = reward_code(won, role);
         tr0 = c;
-        tr1.x |= (uint32_t)won << 8 | o_reward << 16;
+        tr1.x |= traj_outcome(won, o_reward);
         tr1.w = (uint32_t)idx;
         ply += 1;
         dnext += 1;
@@ -1374,7 +1375,10 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
       uint4 Rf = unpack_row(Pf, aux);
       // a deal leaves ply = 0 and the fresh bytes 6..7; every other ply keeps the table's own (my_hi)
-      if (lane == DDZ_F_META) Rf = make_uint4((uint32_t)role | (0xFFu << 16), ply == 0 ? 1u << 16 : my_hi | (ply & 0xFFFF), episode, mw);
+      if (lane == DDZ_F_META) {
+        Rf = meta_after_ply(role, false, 0, 0u, my_hi, ply, episode, mw);
+        if (ply == 0) Rf.y = meta_fresh(episode).y;
+      }
       if (lane < DDZ_NFIELDS) trow[lane] = Rf;  // one coalesced 176-byte store per table and launch
     }
     stamps.mark(9);  // state store
@@ -1474,7 +1478,7 @@ __device__ __forceinline__ int slab_list(uint64_t hand, uint32_t info, int64_t b
     Pick pk{-1, 0, 0, 0, 0};
     n = plan_scan<EM_SLAB, IDS>(hand, info, hot, lane, o, pk);
     if (n > stride) {  // cannot happen for a <= 20-card hand (tools/max_legal_bound.c); rows past the slab were dropped
-      if (lane == 0 && status) atomicOr(status, 2);
+      if (lane == 0 && status) atomicOr(status, DDZ_ST_CAPACITY);
       n = 0;
     }
   }
@@ -1729,7 +1733,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
       if (a.thr && valid && cnt_l > 0) {
         const uint4 meta = *(const uint4*)(a.state + t * STATE_ROW_BYTES + DDZ_F_META * 16);
         const uint64_t g_ = a.gid_base + (uint64_t)t;
-        const uint4 dr = philox4x32_10(make_uint4((uint32_t)g_, (uint32_t)(g_ >> 32), meta.z, (3u << 16) | (meta.y & 0xFFFF)), a.k0, a.k1);
+        const uint4 dr = rng_draw(g_, meta.z, RNG_EPSILON, meta_ply(meta.y), a.k0, a.k1);
         if ((uint64_t)dr.x < a.thr) sel_l = (int)__umulhi(dr.y, (uint32_t)cnt_l);
       }
       if (a.choice_out && valid) a.choice_out[t] = sel_l;
@@ -1750,11 +1754,11 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
     // ---- decode, one table per lane
     uint4* tr = srow + (valid ? lane : 0) * DDZ_NFIELDS;
     const uint4 M = tr[DDZ_F_META];
-    int role = M.x & 0xFF;
+    int role = M.x & META_BYTE;
     if (role > 2) role = 0;  // never index outside the table on a corrupted import
-    const bool is_done = (M.x >> 8) & 0xFF;
-    const bool dealt = (M.y >> 16) & 0xFF;
-    const uint32_t ply = M.y & 0xFFFF, episode = M.z;
+    const bool is_done = (M.x >> META_DONE_SHIFT) & META_BYTE;
+    const bool dealt = (M.y >> META_DEALT_SHIFT) & META_BYTE;
+    const uint32_t ply = M.y & META_PLY_MASK, episode = M.z;
     const uint64_t gid = a.gid_base + (uint64_t)t;
     const bool active = valid && dealt && !is_done;
     const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
@@ -1772,7 +1776,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
       bool draw = MODE == DDZ_STEP_RANDOM;
       if (MODE == DDZ_STEP_IDS) draw = sel_l == -1;
       if (DRAWS && draw && !frozen) {  // random.choice(actions), envi.py:83
-        const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), episode, (2u << 16) | ply), a.k0, a.k1);
+        const uint4 d = rng_draw(gid, episode, RNG_STEP, ply, a.k0, a.k1);
         idx = (int)__umulhi(d.x, (uint32_t)A);
       }
       if (SEARCH) {  // wave-parallel search of a table's list for the wanted counts, table after table
@@ -1820,27 +1824,27 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
     stamps.mark(2);
     // ---- apply (envi.py:38-43 _update + native step), outputs, trajectory record
     uint4 tr0 = make_uint4(0, 0, 0, 0);
-    uint4 tr1 = make_uint4((uint32_t)role, ((uint32_t)A & 0xFFFF) | (ply << 16), episode, 0xFFFFFFFFu);
+    uint4 tr1 = make_uint4((uint32_t)role, ((uint32_t)A & TRAJ_LEGAL_MASK) | (ply << TRAJ_PLY_SHIFT), episode, TRAJ_NO_INDEX);
     o_done = is_done;
     live = active;
     qinfo = cur_info;
     bool changed = false, won = false;
     if (frozen) {
-      tr1.x |= (uint32_t)is_done << 8 | 2u << 24;
+      tr1.x |= traj_outcome(is_done, 0) | TRAJ_FROZEN;
       if (active) qhand = pack_row(Hr);  // a live table whose list was reported empty: write it afresh
     } else if (idx < 0) {  // not in the list: table untouched, flagged; its list is written again as it was
       o_done = 0; o_illegal = 1;
-      tr1.x |= 1u << 24;
+      tr1.x |= TRAJ_ILLEGAL;
       qhand = pack_row(Hr);
     } else {
       changed = true;
       const uint32_t ncards = cinfo >> 24;
       const uint32_t cw3 = c.w & 0x00FFFFFFu;
       won = (Hr.w >> 24) == ncards;
-      o_reward = won ? (role == 1 ? 0xFFu : 1u) : 0u;  // rule_play.py:14: -1 lord won, +1 farmers
+      o_reward = reward_code(won, role);
       o_done = won;
       tr0 = c;
-      tr1.x |= (uint32_t)won << 8 | o_reward << 16;
+      tr1.x |= traj_outcome(won, o_reward);
       tr1.w = (uint32_t)idx;
       if (!(won && a.auto_reset)) {
         // byte-wise: every byte of the hand >= the row's byte, so no borrow/carry crosses a byte
@@ -1849,8 +1853,9 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
         tr[DDZ_F_HIST0 + role] = make_uint4(Hi.x + c.x, Hi.y + c.y, Hi.z + c.z, Hi.w + cw3);
         tr[DDZ_F_TAKEN] = make_uint4(Tk.x + c.x, Tk.y + c.y, Tk.z + c.z, Tk.w + cw3);
         tr[DDZ_F_RECENT0 + role] = c;
-        tr[DDZ_F_META] = make_uint4((uint32_t)rp1 | (won ? 1u << 8 : 0u) | ((won ? (uint32_t)role : 0xFFu) << 16) | (o_reward << 24),
-                                    (M.y & 0xFFFF0000u) | ((ply + 1) & 0xFFFF), M.z, M.w);
+        tr[DDZ_F_META] = make_uint4((uint32_t)rp1 | (won ? 1u << META_DONE_SHIFT : 0u) |
+                                        ((won ? (uint32_t)role : META_NO_WINNER) << META_WINNER_SHIFT) | (o_reward << META_REWARD_SHIFT),
+                                    (M.y & ~META_PLY_MASK) | ((ply + 1) & META_PLY_MASK), M.z, M.w);
         live = !won;
         // the next actor (lord -> down -> up, game.py:173-181) has to beat this ply's combo, or -- after a pass -- the
         // previous player's: its hand is untouched by this ply
@@ -1885,7 +1890,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
         deal_wave(a.gid_base + (uint64_t)(t0 + i), ep, a.k0, a.k1, lane, h0, h1, h2);
         if (lane < DDZ_NFIELDS)
           srow[i * DDZ_NFIELDS + lane] = lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-                                         : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, ep, 0) : make_uint4(0, 0, 0, 0);
+                                         : lane == DDZ_F_META ? meta_fresh(ep) : make_uint4(0, 0, 0, 0);
         if (lane == i) { qhand = h1; qinfo = LEAD; }
       }
       // the rows of the tables that moved, back to the state: coalesced 16-byte stores
@@ -1941,7 +1946,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
             if (lane < DDZ_NFIELDS)
               ((uint4*)(a.state + tt * STATE_ROW_BYTES))[lane] =
                   lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-                  : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, ep, 0) : make_uint4(0, 0, 0, 0);
+                  : lane == DDZ_F_META ? meta_fresh(ep) : make_uint4(0, 0, 0, 0);
             hand = h1;
             stamps.mark(7);
           }
@@ -1963,7 +1968,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
             const int R = pk.rc;
             stamps.mark(8);
             if (R > TEAM_ROUNDS) {  // cannot happen (see team_round): flagged, an empty list
-              if (lane == 0 && a.status) atomicOr(a.status, 2);
+              if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_CAPACITY);
             } else if (R >= thr) {
               heavy = true;
               if (lane == 0) s_item[atomicAdd(&s_nheavy, 1)] = make_uint4((uint32_t)hand, (uint32_t)(hand >> 32), (uint32_t)R, (uint32_t)wv);
@@ -1972,7 +1977,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
               for (int r = 0; r < R; ++r)
                 n += team_round<true, IDS>(s_desc[wv][r], hand8, hot, lane, o.base + n, o.cap, a.rows, a.ids);
               if (n > a.stride) {
-                if (lane == 0 && a.status) atomicOr(a.status, 2);
+                if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_CAPACITY);
                 n = 0;
               }
               stamps.mark(9);
@@ -2014,7 +2019,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
             run += (int)rl((uint32_t)inc, 63);
           }
           if (run > a.stride) {  // cannot happen for a <= 20-card hand (tools/max_legal_bound.c)
-            if (lane == 0 && a.status) atomicOr(a.status, 2);
+            if (lane == 0 && a.status) atomicOr(a.status, DDZ_ST_CAPACITY);
             run = 0;
           }
           if (lane == 0) a.counts[tb0 + ow] = run;
@@ -2060,7 +2065,7 @@ __global__ __launch_bounds__(TB, DDZ_SLAB_WAVES) void k_slab(SlabArgs a) {
           if (lane < DDZ_NFIELDS)
             ((uint4*)(a.state + tt * STATE_ROW_BYTES))[lane] =
                 lane == 0 ? unpack_row(h0, 17) : lane == 1 ? unpack_row(h1, 20) : lane == 2 ? unpack_row(h2, 17)
-                : lane == DDZ_F_META ? make_uint4(1u | (0xFFu << 16), 1u << 16, ep, 0) : make_uint4(0, 0, 0, 0);
+                : lane == DDZ_F_META ? meta_fresh(ep) : make_uint4(0, 0, 0, 0);
           hand = h1;
         }
         const int n = slab_list<IDS>(hand, rfl(e.z), tt * a.stride, a.stride, a.rows, a.ids, hot, lane, fl, a.status);
@@ -2134,7 +2139,7 @@ __global__ __launch_bounds__(TB, 4) void k_moves_slab(const uint4* __restrict__ 
     if (lane == i) n_l = m;
   }
   if (lane < ntab) counts[t0 + lane] = n_l;
-  if (bad && lane == 0 && status) atomicOr(status, 4);
+  if (bad && lane == 0 && status) atomicOr(status, DDZ_ST_BAD_LAST);
 }
 
 // slab -> CSR: the fixed-stride lists packed into offsets[n+1] / rows[sum A] / ids[sum A] (what a ragged NN forward
@@ -2200,7 +2205,7 @@ __global__ __launch_bounds__(CSR_BT) void k_csr_copy(const int32_t* __restrict__
   if (t < n) offsets[t] = (int32_t)(off < cap ? off : cap);
   if (t == n - 1) {
     offsets[n] = (int32_t)(off + c < cap ? off + c : cap);
-    if (off + c > cap && status) atomicOr(status, 2);
+    if (off + c > cap && status) atomicOr(status, DDZ_ST_CAPACITY);
   }
   // every wave copies the lists of its 64 tables flat: output row r of the wave belongs to the last table whose
   // exclusive offset is <= r (binary search over 64 LDS words), so the loads of one trip are independent
@@ -2255,9 +2260,8 @@ __global__ __launch_bounds__(TB, 4) void k_mask(const uint8_t* __restrict__ stat
     __builtin_amdgcn_wave_barrier();
     const uint64_t P = pack_row(R);
     const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
-    int role = mx & 0xFF;
-    if (role > 2) role = 0;
-    const bool active = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF);  // dealt and not done
+    const int role = meta_role(mx);
+    const bool active = ((my >> META_DEALT_SHIFT) & META_BYTE) && !((mx >> META_DONE_SHIFT) & META_BYTE);  // dealt and not done
     const int rm1 = role == 0 ? 2 : role - 1, rp1 = role == 2 ? 0 : role + 1;
     const uint64_t hand = rl64(P, DDZ_F_HAND0 + role);
     const uint32_t info = last_info(rl64(P, DDZ_F_RECENT0 + rm1), (int)(rl(R.w, DDZ_F_RECENT0 + rm1) >> 24),
@@ -2316,7 +2320,7 @@ __global__ __launch_bounds__(BLOCK) void k_moves(const uint4* __restrict__ hands
       const Out o{rows, ids, base, cap, nullptr, nullptr, nullptr};
       const int m = plan_scan<EM_WRITE, IDS>(hand, info, hot, lane, o, pk);
       if (lane == 0) {
-        const int bits = (m != cnt ? 1 : 0) | (base + cnt > cap ? 2 : 0) | ((info & QF_BADLAST) ? 4 : 0);
+        const int bits = (m != cnt ? DDZ_ST_MISMATCH : 0) | (base + cnt > cap ? DDZ_ST_CAPACITY : 0) | ((info & QF_BADLAST) ? DDZ_ST_BAD_LAST : 0);
         if (bits) atomicOr(status, bits);
       }
       base += cnt;
@@ -2395,7 +2399,7 @@ __global__ __launch_bounds__(BLOCK) void k_select(const uint8_t* __restrict__ st
   if (thr) {
     const uint4 meta = *(const uint4*)(state + t * STATE_ROW_BYTES + DDZ_F_META * 16);
     const uint64_t gid = gid_base + (uint64_t)t;
-    const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), meta.z, (3u << 16) | (meta.y & 0xFFFF)), k0, k1);
+    const uint4 d = rng_draw(gid, meta.z, RNG_EPSILON, meta_ply(meta.y), k0, k1);
     if ((uint64_t)d.x < thr) best = (int)__umulhi(d.y, (uint32_t)A);
   }
   choice[t] = best;
@@ -2638,17 +2642,18 @@ __global__ __launch_bounds__(BLOCK) void k_pack_traj(const uint4* __restrict__ t
   const uint64_t nib = pack_row(row);
   // 0x3FFF: not an action -- a row outside the action space, or a record of a frozen table / an illegal selection
   // (flags != 0: its all-zero row is NOT the pass)
-  int lo = 0, hi = ((m.x >> 24) & 3) ? -1 : NUM_ACTIONS_X - 1, id = 0x3FFF;
+  int lo = 0, hi = ((m.x >> TRAJ_FLAGS_SHIFT) & 3) ? -1 : NUM_ACTIONS_X - 1, id = 0x3FFF;
   while (lo <= hi) {
     const int mid = (lo + hi) >> 1;
     const uint64_t v = g_sorted_nib[mid];
     if (v == nib) { id = g_sorted_id[mid]; break; }
     if (v < nib) lo = mid + 1; else hi = mid - 1;
   }
-  const uint32_t role = m.x & 0xFF, done = (m.x >> 8) & 1, rew = (m.x >> 16) & 0xFF, flags = (m.x >> 24) & 3;
-  const uint32_t rc = rew == 0 ? 0u : rew == 1 ? 1u : 2u;
+  const uint32_t role = m.x & TRAJ_BYTE, done = (m.x >> TRAJ_WON_SHIFT) & 1, rew = (m.x >> TRAJ_REWARD_SHIFT) & TRAJ_BYTE,
+                 flags = (m.x >> TRAJ_FLAGS_SHIFT) & 3;
+  const uint32_t rc = rew == 0 ? 0u : rew == REWARD_FARMERS ? 1u : 2u;
   const uint32_t w0 = (uint32_t)id | ((m.y & 0x1FF) << 14) | ((role & 3) << 23) | (done << 25) | (rc << 26) | (flags << 28);
-  const uint32_t w1 = (((uint32_t)((int32_t)m.w + 1)) & 0x3FF) | (((m.y >> 16) & 0xFF) << 10) | ((m.z & 0x3FFF) << 18);
+  const uint32_t w1 = (((uint32_t)((int32_t)m.w + 1)) & 0x3FF) | (((m.y >> TRAJ_PLY_SHIFT) & 0xFF) << 10) | ((m.z & 0x3FFF) << 18);
   out[i] = make_uint2(w0, w1);
 }
 

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
   uint8_t* const nodes = g.nodes;
   uint64_t* const tab = g.tab;
   const uint32_t hlog = a.hash_log;
-  if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, 64);   // outside the domain: nothing runs
+  if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, DDZ_ST_DOMAIN);   // outside the domain: nothing runs
   if (rh.kind == ROOT_INSIDE && a.phase == GUIDED_OPEN) {
     // ---- OPEN: the root actor's list is the same in every world
     const bool live = guided_open(g, a, root, hot, lane, stage, svl) > 0;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
         const int n = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
         __builtin_amdgcn_wave_barrier();
         if (n > STAGE_CAP) {
-          if (lane == 0) atomicOr(a.status, 2);
+          if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
           break;
         }
         if (n <= 0) break;   // outside the domain: unfinished
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_gismcts(GuidedArgs a) 
                                                           a.c, own, sides, best, at, bchild);
         if (untried > 0) {
           // ---- expansion: spec v2's draw and pick
-          const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
+          const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, RNG_EXPAND << 16), a.k0, a.k1).x;
           const int idx = ismcts_untried(nodes, tab, hlog, nnodes, node, trips, okm, n0, n, info, stage, lane, untried,
                                          rfl(__umulhi(de, untried)));
           if (idx < 0 || idx >= n) break;   // (cannot happen: `untried` entries without a child exist)

@@ -71,7 +71,7 @@ __device__ __forceinline__ int guided_open(const GuidedTree& g, const GuidedArgs
   int n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
   __builtin_amdgcn_wave_barrier();
   if (n_root > STAGE_CAP || n_root > a.stride) {
-    if (lane == 0) atomicOr(a.status, 2);
+    if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
     n_root = 0;
   }
   if (n_root > 0)
@@ -129,7 +129,7 @@ struct DescentRows {
     const int rp1 = role_next(role), rm1 = role_prev(role);
     const uint64_t Pf = lane == role ? hc : lane == rp1 ? hn : lane == rm1 ? hp : P;
     uint4 r = unpack_row(Pf, aux);
-    if (lane == DDZ_F_META) r = make_uint4((uint32_t)role | (0xFFu << 16), (my & 0xFFFF0000u) | (ply & 0xFFFFu), mz, mw);
+    if (lane == DDZ_F_META) r = meta_after_ply(role, false, 0, 0u, my, ply, mz, mw);
     return r;
   }
 };
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
   uint8_t* const nodes = g.nodes;
   uint64_t* const tab = g.tab;
   const uint32_t hlog = a.hash_log;
-  if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, 64);   // outside the domain: nothing runs
+  if (rh.kind == ROOT_OUTSIDE && lane == 0 && tree == 0) atomicOr(a.status, DDZ_ST_DOMAIN);   // outside the domain: nothing runs
   if (rh.kind == ROOT_INSIDE && a.phase == GUIDED_OPEN) {
     // ---- OPEN: the root's list is node 0's n
     const int n_root = guided_open(g, a, root, hot, lane, stage, svl);
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
           const int nn = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
           if (nn != n) break;   // (cannot happen: the state of a node is a function of its path)
           const uint32_t u = (uint32_t)n - nchild;
-          const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
+          const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, RNG_EXPAND << 16), a.k0, a.k1).x;
           const int idx = search_untried(tab, hlog, node, n, nchild, rfl(__umulhi(de, u)), lane);
           if (idx < 0 || idx >= n) break;   // (cannot happen: u untried indices exist)
           uint64_t snib; uint32_t scat, svlv;
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_guided(GuidedArgs a) {
           int pn = ply_list(hc, ply_info(trick, passes), hot, lane, stage, svl, pokm, pn0);
           __builtin_amdgcn_wave_barrier();
           if (pn > STAGE_CAP) {
-            if (lane == 0) atomicOr(a.status, 2);
+            if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
             pn = 0;
           }
           made_meta |= (uint32_t)pn << 16;

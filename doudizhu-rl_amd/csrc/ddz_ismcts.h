@@ -231,7 +231,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
   const RootHands rh = root_hands<true>(R, a.roles, lane);
   if (rh.kind == ROOT_IDLE) return;   // not dealt, done, or not this call's seat: nothing runs
   if (rh.kind == ROOT_OUTSIDE) {      // outside the domain: nothing runs, the workspace is not touched
-    if (lane == 0 && tree == 0) atomicOr(a.status, 64);
+    if (lane == 0 && tree == 0) atomicOr(a.status, DDZ_ST_DOMAIN);
     return;
   }
   const PlayRoot& root = rh.root;
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
     n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
     __builtin_amdgcn_wave_barrier();
     if (n_root > STAGE_CAP || n_root > a.stride) {
-      if (lane == 0) atomicOr(a.status, 2);
+      if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
       return;
     }
     if (n_root <= 0) return;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
       const int n = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
       __builtin_amdgcn_wave_barrier();
       if (n > STAGE_CAP) {
-        if (lane == 0) atomicOr(a.status, 2);
+        if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
         break;
       }
       if (n <= 0) break;   // outside the domain: unfinished
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
                                             best, at, bchild);
       if (untried > 0) {
         // ---- expansion: the (draw_e * |U|) >> 32-th entry without a child, ascending
-        const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
+        const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, RNG_EXPAND << 16), a.k0, a.k1).x;
         const int idx = ismcts_untried(nodes, tab, hlog, nnodes, node, trips, okm, n0, n, info, stage, lane, untried,
                                        rfl(__umulhi(de, untried)));
         if (idx < 0 || idx >= n) break;   // (cannot happen: `untried` entries without a child exist)
@@ -316,14 +316,14 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_ismcts(SearchArgs a) {
           if (dn >= 64u) {
             dn = 0;
             dnext = 0;
-            draws = ply_draw(gid, (tree << 16) | it, 7u << 16, ply, lane, a.k0, a.k1);
+            draws = ply_draw(gid, (tree << 16) | it, RNG_TREE_PLAYOUT, ply, lane, a.k0, a.k1);
           }
           const uint32_t draw = rl(draws, (int)dn);
           const uint32_t pinfo = ply_info(trick, passes);
           uint64_t pokm; int pn0;
           int pn = ply_list(hc, pinfo, hot, lane, stage, svl, pokm, pn0);
           if (pn > STAGE_CAP) {
-            if (lane == 0) atomicOr(a.status, 2);
+            if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
             pn = 0;
           }
           if (pn <= 0) break;   // stopped unfinished

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
   if constexpr (HIDDEN) {   // the pool of unseen cards and the opponents' hand sizes, the domain checked once -- called here, not
     uint64_t unseen;        // through root_hands<true>: so built, the hidden rows ran 0.3 .. 0.6 % slower (profiles/r18_notes.md 3)
     if (!unseen_pool(root, lane, n_next, n_prev, unseen, pool)) {   // outside the domain: nothing runs, wins stay as they are
-      if (lane == 0 && chunk == 0) atomicOr(a.status, 64);
+      if (lane == 0 && chunk == 0) atomicOr(a.status, DDZ_ST_DOMAIN);
       return;
     }
     if (a.worlds) {   // ddz_playout_worlds: row 0 = the next player's counts and size, row 1 = the previous player's
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
           dnext = 0;
           uint32_t qk0 = a.k0, qk1 = a.k1;
           asm volatile("" : "+s"(qk0), "+s"(qk1));   // the key stays in SGPRs (profiles/r15_notes.md: 21 more spills without)
-          draws = ply_draw(gid, (k << 9) | j, 4u << 16, ply, lane, qk0, qk1);
+          draws = ply_draw(gid, (k << 9) | j, RNG_PLAYOUT, ply, lane, qk0, qk1);
         }
         draw = rl(draws, (int)dn);
       }
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(PLAYOUT_WAVES * 64, 6) void k_playout(PlayoutArgs a
       int n0;
       int n = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
       if (n > STAGE_CAP || n > a.stride) {  // cannot happen for a <= 20-card hand: the table (or this playout) runs nothing
-        if (lane == 0) atomicOr(a.status, 2);
+        if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
         n = 0;
       }
       if (probe) {

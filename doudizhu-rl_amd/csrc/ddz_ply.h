@@ -77,9 +77,8 @@ __device__ __forceinline__ PlayRoot play_root_decode(const uint4& R) {
   r.P = pack_row(R);
   r.aux = R.w >> 24;
   const uint32_t mx = rl(R.x, DDZ_F_META), my = rl(R.y, DDZ_F_META);
-  r.role0 = mx & 0xFF;
-  if (r.role0 > 2) r.role0 = 0;
-  r.running = ((my >> 16) & 0xFF) && !((mx >> 8) & 0xFF);
+  r.role0 = meta_role(mx);
+  r.running = meta_dealt(my) && !meta_done(mx);
   if (!r.running) return r;   // (the caller leaves: nothing else is read)
   r.ply0 = my & 0xFFFF;
   r.hc0 = rl64(r.P, DDZ_F_HAND0 + r.role0);
@@ -149,7 +148,7 @@ __device__ __forceinline__ RootHands root_hands(const uint4& R, uint32_t roles, 
 // and two ballots give the hands.  `pool`: unseen_pool's; keys: 64 x 8 bytes of the calling wave; 1 <= n_next.
 __device__ inline void redeal_wave(uint64_t gid, uint32_t k, uint32_t k0, uint32_t k1, int lane, bool pool, int n_next,
                                    uint64_t* keys, uint64_t& o_next, uint64_t& o_prev) {
-  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), k, (5u << 16) | (uint32_t)(lane >> 2)), k0, k1);
+  const uint4 d = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), k, (RNG_WORLD << 16) | (uint32_t)(lane >> 2)), k0, k1);
   const int w = lane & 3;
   const uint32_t key = w == 0 ? d.x : w == 1 ? d.y : w == 2 ? d.z : d.w;
   const uint64_t kk = pool ? ((uint64_t)key << 6) | (uint32_t)lane : ~0ull;  // a card outside the pool ranks behind every pool card
@@ -276,6 +275,6 @@ __device__ __forceinline__ bool ply_apply(uint64_t snib, uint32_t scat, uint32_t
 // the Philox call of a playout loop's 64-draw refill: lane l gets the draw of the ply l behind this one, on the counter
 // (gid, c2, c3 | ply + lane) -- c2 and c3 say whose playout and which RNG domain.  The refill's bookkeeping (the draws, the
 // plies since: dnext, 64 = refill) stays in each loop: k_playout pins the key inside its refill branch.
-__device__ __forceinline__ uint32_t ply_draw(uint64_t gid, uint32_t c2, uint32_t c3, uint32_t ply, int lane, uint32_t k0, uint32_t k1) {
-  return philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), c2, c3 | ((ply + (uint32_t)lane) & 0xFFFFu)), k0, k1).x;
+__device__ __forceinline__ uint32_t ply_draw(uint64_t gid, uint32_t c2, RngDomain domain, uint32_t ply, int lane, uint32_t k0, uint32_t k1) {
+  return rng_draw(gid, c2, domain, (ply + (uint32_t)lane) & 0xFFFFu, k0, k1).x;
 }

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_q_need_assign(const uint64_t* __restric
   int4* dst = (int4*)(row_index + t * QP_COLS + 16 * q);
 #pragma unroll
   for (int i = 0; i < 4; ++i) dst[i] = make_int4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
-  if (dropped) atomicOr(status, 2);   // row capacity overflow (cannot happen with capacity >= 20 T + 15 * FC_M)
+  if (dropped) atomicOr(status, DDZ_ST_CAPACITY);   // row capacity overflow (cannot happen with capacity >= 20 T + 15 * FC_M)
 }
 
 // ---- 2. first layer for the needed rows ----------------------------------------------------------------------------------
@@ -482,7 +482,7 @@ __device__ __forceinline__ void q_slab_moves(const float4* __restrict__ D, const
         const bool ok = (needm >> col) & 1ull;
         const int slot = __popcll(needm & ((1ull << col) - 1ull));
         if (!ok) {
-          if (l16 == 0) atomicOr(status, 32);
+          if (l16 == 0) atomicOr(status, DDZ_ST_Q_NO_ROW);
         } else if (slot < ncache) {
           const float4* cr = cache[slot] + l16;
 #pragma unroll
@@ -983,7 +983,7 @@ __global__ __launch_bounds__(64) void k_qd_seg(const int32_t* __restrict__ cnt, 
       need += s_tot[q];
     }
     const int over = start > row_capacity ? 1 : 0;   // (cannot happen: distinct (row, count) pairs <= needed (t, r, c) triples)
-    if (over) { start = row_capacity / FC_M * FC_M; atomicOr(status, 2); }
+    if (over) { start = row_capacity / FC_M * FC_M; atomicOr(status, DDZ_ST_CAPACITY); }
     dseg[15] = start; dseg[31] = start / FC_M; dseg[32] = need; dseg[33] = over;
   }
   __syncthreads();

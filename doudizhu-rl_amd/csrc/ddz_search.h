@@ -193,7 +193,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
   const RootHands rh = root_hands<HIDDEN>(R, a.roles, lane);
   if (rh.kind == ROOT_IDLE) return;   // not dealt, done, or not this call's seat: nothing runs
   if (rh.kind == ROOT_OUTSIDE) {      // outside the domain: nothing runs, the workspace is not touched
-    if (lane == 0 && tree == 0) atomicOr(a.status, 64);
+    if (lane == 0 && tree == 0) atomicOr(a.status, DDZ_ST_DOMAIN);
     return;
   }
   const PlayRoot& root = rh.root;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
     n_root = ply_list(root.hc0, ply_info(root.trick0, root.passes0), hot, lane, stage, svl, okm, n0);
     __builtin_amdgcn_wave_barrier();
     if (n_root > STAGE_CAP || n_root > a.stride) {
-      if (lane == 0) atomicOr(a.status, 2);
+      if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
       return;
     }
     if (n_root <= 0) return;
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
         const int nn = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
         if (nn != n) break;   // (cannot happen: the state of a node is a function of its path)
         const uint32_t u = (uint32_t)n - nchild;
-        const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, 6u << 16), a.k0, a.k1).x;
+        const uint32_t de = philox4x32_10(make_uint4((uint32_t)gid, (uint32_t)(gid >> 32), (tree << 16) | it, RNG_EXPAND << 16), a.k0, a.k1).x;
         const int idx = search_untried(tab, hlog, node, n, nchild, rfl(__umulhi(de, u)), lane);
         if (idx < 0 || idx >= n) break;   // (cannot happen: u untried indices exist)
         uint64_t snib; uint32_t scat, svlv;
@@ -282,14 +282,14 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64, 6) void k_search(SearchArgs a) {
           if (dn >= 64u) {
             dn = 0;
             dnext = 0;
-            draws = ply_draw(gid, (tree << 16) | it, 7u << 16, ply, lane, a.k0, a.k1);
+            draws = ply_draw(gid, (tree << 16) | it, RNG_TREE_PLAYOUT, ply, lane, a.k0, a.k1);
           }
           const uint32_t draw = rl(draws, (int)dn);
           const uint32_t pinfo = ply_info(trick, passes);
           uint64_t pokm; int pn0;
           int pn = ply_list(hc, pinfo, hot, lane, stage, svl, pokm, pn0);
           if (pn > STAGE_CAP) {
-            if (lane == 0) atomicOr(a.status, 2);
+            if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
             pn = 0;
           }
           if (s == 0) made_meta |= (uint32_t)pn << 16;   // the child's n

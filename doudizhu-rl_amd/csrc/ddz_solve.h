@@ -103,7 +103,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
     return;
   }
   if (HIDDEN && (rh.kind == ROOT_OUTSIDE || rh.n_me < 1)) {
-    if (first) { a.n[t] = -1; atomicOr(a.status, 64); }
+    if (first) { a.n[t] = -1; atomicOr(a.status, DDZ_ST_DOMAIN); }
     return;
   }
   if constexpr (HIDDEN) redeal_wave(a.gid_base + (uint64_t)t, world, a.k0, a.k1, lane, rh.pool, rh.n_next, stage, hn0, hp0);
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
     __builtin_amdgcn_wave_barrier();
   }
   if (n_root > STAGE_CAP || n_root > a.stride) {   // cannot happen for a <= 20-card hand: the table runs nothing
-    if (first) { a.n[t] = 0; atomicOr(a.status, 2); }
+    if (first) { a.n[t] = 0; atomicOr(a.status, DDZ_ST_CAPACITY); }
     return;
   }
   if (first) a.n[t] = n_root;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
             n = ply_list(hc, info, hot, lane, stage, svl, okm, n0);
             __builtin_amdgcn_wave_barrier();
             if (n > STAGE_CAP) {   // cannot happen for a <= 20-card hand
-              if (lane == 0) atomicOr(a.status, 2);
+              if (lane == 0) atomicOr(a.status, DDZ_ST_CAPACITY);
               n = 0;
             }
             idx = 0;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(SOLVE_WAVES * 64, 4) void k_solve(SolveArgs a) {
           __builtin_amdgcn_wave_barrier();
           phase = CHILD;
         }
-        if (over && lane == 0) atomicOr(a.status, 256);
+        if (over && lane == 0) atomicOr(a.status, DDZ_ST_SOLVE_DEPTH);
         if (!unk) won = same_side(role, role0) ? ret : !ret;   // (depth 0: `role` moves behind move j)
         s_nodes += nodes;
       }

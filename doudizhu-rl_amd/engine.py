@@ -20,6 +20,12 @@ NUM_ACTIONS = 13527
 STEP_RANDOM, STEP_CHOICE, STEP_ROWS, STEP_IDS = 0, 1, 2, 3
 FACE_PLANES = (4, 7, 9, 6)  # Env, EnvComplicated, EnvCooperation, EnvCooperationSimplify
 F_HAND0, F_HIST0, F_RECENT0, F_TAKEN, F_META = 0, 3, 6, 9, 10
+# bytes of the meta row (include/ddz_env.h): role to move, done, winner's role (META_NO_WINNER: none), dealt
+META_ROLE, META_DONE, META_WINNER, META_DEALT = 0, 1, 2, 6
+META_NO_WINNER = 0xFF
+# the bits of the status word (include/ddz_env.h, DDZ_ST_*)
+(STATUS_MISMATCH, STATUS_CAPACITY, STATUS_BAD_LAST, STATUS_AUTO_WAIT, STATUS_AUTO_DEPTH, STATUS_Q_NO_ROW, STATUS_DOMAIN,
+ STATUS_CFR_CAPACITY, STATUS_SOLVE_DEPTH) = (1 << k for k in range(9))
 # a 20-card hand never has more than this many legal moves (tests/test_rules_bounds.py);
 # the default row capacity is T * MAX_LEGAL_PER_TABLE so the CSR list cannot overflow.
 MAX_LEGAL_PER_TABLE = 512

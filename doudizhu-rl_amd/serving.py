@@ -13,7 +13,8 @@ ddz_get_moves), so a served observation is bit-identical to the one of a live ta
 import numpy as np
 import torch
 
-from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, NFIELDS, ROW, action_table, auto_choose, get_moves)
+from .engine import (BatchedEnv, F_HAND0, F_HIST0, F_META, F_RECENT0, F_TAKEN, META_DEALT, META_NO_WINNER, META_ROLE, META_WINNER,
+                     NFIELDS, ROW, STATUS_CFR_CAPACITY, STATUS_DOMAIN, action_table, auto_choose, get_moves)
 
 
 def _counts(cards):
@@ -39,9 +40,9 @@ def payloads_to_state(payloads):
             st[i, F_HIST0 + r, :15] = _counts(_get(p["history"], r))
             st[i, F_RECENT0 + r, :15] = _counts(_get(p["last_taken"], r))
         st[i, F_TAKEN, :15] = st[i, F_HIST0:F_HIST0 + 3, :15].sum(0)   # server/core.py:41 taken = h0 + h1 + h2
-        st[i, F_META, 0] = role
-        st[i, F_META, 2] = 0xFF
-        st[i, F_META, 6] = 1
+        st[i, F_META, META_ROLE] = role
+        st[i, F_META, META_WINNER] = META_NO_WINNER
+        st[i, F_META, META_DEALT] = 1
     return st
 
 
@@ -63,7 +64,7 @@ def state_to_payloads(state):
 
     out = []
     for s in st:
-        role = int(s[F_META, 0])
+        role = int(s[F_META, META_ROLE])
         out.append({"role_id": role, "cur_cards": cards(s[F_HAND0 + role]),
                     "history": {r: cards(s[F_HIST0 + r]) for r in range(3)},
                     "left": {r: int(s[F_HAND0 + r, 15]) for r in range(3)},
@@ -164,7 +165,7 @@ def _payload_env(payloads, hidden, device, seed):
 def _check_domain(env, what):
     """ValueError where a table raised status bit 6 (what: the domain's name; None: nothing is asked); -> the status word"""
     status = env.status() if what else 0
-    if status & 64:
+    if status & STATUS_DOMAIN:
         raise ValueError(f"a payload is outside the {what} domain: cur_cards, history and left do not add up to a deck")
     return status
 
@@ -255,7 +256,7 @@ def cfr_act(payloads, iterations=8, device="cuda:0", salt=0, seed=0, greedy=Fals
         return []
     moves, status, (ids,) = _act(payloads, True, device, seed, "endgame", lambda env: env.cfr_choose(
         salt=salt, greedy=greedy, solved=env.cfr(iterations, slots=len(payloads))))
-    if status & 128:
+    if status & STATUS_CFR_CAPACITY:
         raise ValueError("an endgame exceeds the solver's capacities")
     if (ids < 0).any():
         raise ValueError("a payload is no endgame: more than 6 cards are left, or the game is over")

@@ -61,7 +61,7 @@ def main():
         used += torch.stack([(is_lord & by_rule).sum(), (is_lord & by_cfr).sum(), (is_lord & ~by_rule & ~by_cfr).sum()])
         env.step_slab(torch.where(env.role == 1, lord, rule), pkg.STEP_IDS, auto_reset=True)
     status = env.status()
-    assert status & ~128 == 0, status            # (bit 7: more endgames in one iteration than workspace slots)
+    assert status & ~pkg.STATUS_CFR_CAPACITY == 0, status   # (more endgames in one iteration than workspace slots)
     s = env.stats()
     e = max(1, s["episodes"])
     u = used.tolist()

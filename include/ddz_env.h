@@ -1028,18 +1028,35 @@ int ddz_debug_set_geometry(ddz_env_t* env, int tables_per_wave, int slab_coop, i
  * and stats in every mode (tests compare them).                                                                    */
 int ddz_debug_set_auto_teams(ddz_env_t* env, int on);
 
-/* device status word: bit0 enumerator/count mismatch, bit1 row capacity overflow,
- * bit2 invalid `last` combo, bit3 a wait of ddz_auto_choose_state's cooperating wavefronts hit its
- * hang guard (never in a working launch; the ids of that launch are not to be trusted), bit4 the sequential
- * cross-check kernel's depth guard (cannot happen: at most 20 actions), bit5 a move of ddz_q_slab_needed (or of a network table of
- * ddz_q_roles_slab) whose (rank, count)
- * has no row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing), bit6 a running
- * table of ddz_playout_hidden / ddz_playout_worlds outside the hidden-hand domain (its hand, taken row and hand sizes do not
- * add up to a deck): that table ran nothing -- and a running table of ddz_cfr with at most DDZ_CFR_MAX_CARDS cards whose rows
- * do not add up, or of the hidden form of ddz_solve with at most max_cards cards whose rows do not add up; bit7 a table of
- * ddz_cfr that found no workspace slot or whose forest exceeds a capacity (n = -2); bit8 a search of ddz_solve deeper than
- * DDZ_SOLVE_MAX_DEPTH (impossible inside its domain: that root move is left unknown).
- * Copies 4 bytes D2H on `stream` and synchronises it.                                   */
+/* the bits of the device status word ("status bit k" in the comments above is bitk here, the name with the value 1 << k;
+ * a continuation line belongs to the name above it):
+ *   DDZ_ST_MISMATCH      bit0  enumerator/count mismatch
+ *   DDZ_ST_CAPACITY      bit1  row capacity overflow
+ *   DDZ_ST_BAD_LAST      bit2  invalid `last` combo
+ *   DDZ_ST_AUTO_WAIT     bit3  a wait of ddz_auto_choose_state's cooperating wavefronts hit its hang guard (never in a working
+ *                        launch; the ids of that launch are not to be trusted)
+ *   DDZ_ST_AUTO_DEPTH    bit4  the sequential cross-check kernel's depth guard (cannot happen: at most 20 actions)
+ *   DDZ_ST_Q_NO_ROW      bit5  a move of ddz_q_slab_needed (or of a network table of ddz_q_roles_slab) whose (rank, count) has no
+ *                        row in row_index (-1, or at or beyond row_capacity: not dereferenced, that rank contributed nothing)
+ *   DDZ_ST_DOMAIN        bit6  a running table of ddz_playout_hidden / ddz_playout_worlds outside the hidden-hand domain (its hand,
+ *                        taken row and hand sizes do not add up to a deck): that table ran nothing -- and a running table of
+ *                        ddz_cfr with at most DDZ_CFR_MAX_CARDS cards whose rows do not add up, or of the hidden form of
+ *                        ddz_solve with at most max_cards cards whose rows do not add up
+ *   DDZ_ST_CFR_CAPACITY  bit7  a table of ddz_cfr that found no workspace slot or whose forest exceeds a capacity (n = -2)
+ *   DDZ_ST_SOLVE_DEPTH   bit8  a search of ddz_solve deeper than DDZ_SOLVE_MAX_DEPTH (impossible inside its domain: that root
+ *                        move is left unknown)                                                                        */
+enum {
+  DDZ_ST_MISMATCH = 1,
+  DDZ_ST_CAPACITY = 2,
+  DDZ_ST_BAD_LAST = 4,
+  DDZ_ST_AUTO_WAIT = 8,
+  DDZ_ST_AUTO_DEPTH = 16,
+  DDZ_ST_Q_NO_ROW = 32,
+  DDZ_ST_DOMAIN = 64,
+  DDZ_ST_CFR_CAPACITY = 128,
+  DDZ_ST_SOLVE_DEPTH = 256
+};
+/* the status word of a handle.  Copies 4 bytes D2H on `stream` and synchronises it.    */
 int ddz_status(ddz_env_t* env, int32_t* status_out, void* stream);
 /* the same word for the STATELESS rule-agent entry point (ddz_auto_choose has no handle): one per device, bits as above
  * (bit 3: a cooperating wait hit its hang guard -- the ids of launches since the last call are not to be trusted).
