@@ -1050,6 +1050,22 @@ __device__ __forceinline__ void round_pick(M okm, int pre, const uint4& row, int
   if (TRAJ) c = make_uint4(rl(row.x, src), rl(row.y, src), rl(row.z, src), rl(row.w, src));
   round_entry<WIDE>(src, gsz, snib, scat, svlv, ncards);
 }
+// k_rollout's round.  A ply that does not emit (`emit`: wave-uniform, a constant in each copy of the peeled loop)
+// needs the round's SIZE and the lanes' positions only: nothing is stored, and no row is built -- except for a record
+// (TRAJ), which reads the chosen row out of the lanes' rows as the emitting ply does (round_emit's row, restated here so that
+// round_emit stays as its other callers compile it; measured against unpack_row of the entry: profiles/r30_notes.md 4).
+template <bool IDS, bool TRAJ, class L, class M>
+__device__ __forceinline__ int rollout_round(bool emit, M okm, const L& ln, uint32_t copies, int id, uint4* rows, int32_t* ids,
+                                             int64_t pos0, uint4& row, int& pre) {
+  if (emit) return round_emit<IDS>(okm, ln, copies, id, rows, ids, pos0, row, pre);
+  if (TRAJ) {
+    const uint32_t dv = copies << ln.sh;
+    row = make_uint4(dv & ln.w0, dv & ln.w1, dv & ln.w2, (dv & ln.w3) | (copies << 24) | ln.rk);
+  }
+  pre = round_pre(okm);
+  if constexpr (L::WIDE) return __builtin_popcountll(okm);
+  else return __builtin_popcount(okm);
+}
 
 // ------------------------------------------------------------------------------------
 // k_rollout: the random-policy lock-step iteration (game.py:169-181 with envi.py:79-85) with
@@ -1062,7 +1078,8 @@ __device__ __forceinline__ void round_pick(M okm, int pre, const uint4& row, int
 //   nib|category of the tail in the wave's LDS list (the list size is known before the pick) -> flush of the tail as
 //   coalesced 16-byte rows behind the round's -> pick by engine RNG from the round or the staged tail -> apply / terminal /
 //   deal, all on the PACKED table (nibble rows);
-//   the state rows are rebuilt and stored once per table and launch, after its last iteration.
+//   the state rows are rebuilt and stored once per table and launch, after its last iteration; the lists likewise, unless
+//   staged: only the launch's last iteration stores rows, ids and counts[t] (slab rows at and beyond counts[t] stay unwritten).
 struct RolloutArgs {
   uint8_t* state;
   int64_t T;
@@ -1162,7 +1179,20 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       continue;
     }
     int idle = 0;  // iterations that applied no ply (n <= 0: an empty imported hand, or behind the STAGE_CAP guard)
-    for (int it = (int)a.n_iters; it > 0; --it) {
+    // Does an iteration write its list (rows, ids, counts)?  The staged form writes every iteration's into a slab of its own.
+    // Otherwise every iteration of the launch would overwrite the same slab and nothing can read it in between, so only the
+    // LAST one writes; the iterations before it take the list's size and its idx-th entry: no row, no store.  PEELED: the
+    // iteration is stated once, in a loop over the two phases that is unrolled, so that `emit` is a constant in each copy
+    // and the hot loop (phase 0) holds no emission code (-DDDZ_ROLLOUT_GATED: one copy, `emit` a scalar branch around the
+    // stores; profiles/r30_notes.md).
+    int it = (int)a.n_iters;
+#ifdef DDZ_ROLLOUT_GATED
+#pragma unroll 1
+#else
+#pragma unroll
+#endif
+    for (int phase = STAGED ? 1 : 0; phase < 2; ++phase)
+    for (const bool emit = phase == 1; it > (emit ? 0 : 1); --it) {
       uint4 tr0 = make_uint4(0, 0, 0, 0);
       uint4 tr1 = make_uint4((uint32_t)role, ply << TRAJ_PLY_SHIFT, episode, TRAJ_NO_INDEX);
       uint32_t dn = rfl(dnext);  // the same value in every lane: a scalar branch, and the lane of the draw below
@@ -1196,7 +1226,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
       // no tail (nine plies in ten): the round is the list, the pick comes from the round (n0 >= 1)
       auto whole = [&](int n0) {
         n = n0;
-        *cnt_p = n;  // every lane stores the same word: no exec-mask change
+        if (emit) *cnt_p = n;  // every lane stores the same word: no exec-mask change
         s_rows += n;
         idx = (int)__umulhi(draw, (uint32_t)n);  // random.choice(actions), envi.py:83
       };
@@ -1214,7 +1244,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
         // the candidate mask is scalar: bit 0 pass | 1..15 groups | 16..28 bombs | 29 rocket
         const uint32_t okm = 1u | ((mlc & gt_mask(lv0)) << 1) | (mq << 16) | (rocket ? 1u << 29 : 0u);
         const uint32_t copies = ((uint32_t)lc0 & fl.grp) | fl.c4;  // category == group size here
-        whole(round_emit<IDS>(okm, fl, copies, fid, a.rows, a.ids, base, row, pre));
+        whole(rollout_round<IDS, TRAJ>(emit, okm, fl, copies, fid, a.rows, a.ids, base, row, pre));
         round_pick<TRAJ, false>(okm, pre, row, idx, (uint32_t)lc0, c, snib, scat, svlv, ncards);
         stamps.mark(5);  // follow of a single / pair / triple: list + pick
       } else {
@@ -1236,7 +1266,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           int ln = lane;
           asm volatile("" : "+v"(ln));  // opaque: the lane constants are computed here, not hoisted and held
           const LeadLanes ll = lead_lanes(ln);
-          n0 = round_emit<IDS>(okm, ll, ll.copies, ln < 54 ? 1 + ln : ID_BIGBANG, a.rows, a.ids, base, row, pre);
+          n0 = rollout_round<IDS, TRAJ>(emit, okm, ll, ll.copies, ln < 54 ? 1 + ln : ID_BIGBANG, a.rows, a.ids, base, row, pre);
         } else {
           // A follow of any other category: pass + bombs + rocket, unless the hand may hold a higher combination of the
           // category itself (value above lv; chains and planes: a run of the led length).  A bomb is followed by the higher
@@ -1256,7 +1286,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
           // with a tail only pass and the bombs (ids 0, 42..54) come direct: the rocket's id lies inside the planner's part
           const uint32_t okf = m1 == 0 ? 0u : 1u | (cand << 1) | (bombs << 16) | (rocket && !tail ? 1u << 29 : 0u);
           const uint32_t copies = ((uint32_t)lc0 & fl.grp) | fl.c4;  // (group lanes: only legal after a bomb, lc0 == 4)
-          n0 = round_emit<IDS>(okf, fl, copies, fid, a.rows, a.ids, base, row, pre);
+          n0 = rollout_round<IDS, TRAJ>(emit, okf, fl, copies, fid, a.rows, a.ids, base, row, pre);
           okm = okf;
         }
         if (!tail) {
@@ -1280,10 +1310,10 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
             n = 0;
           }
           stamps.mark(2);  // hybrid: closed-form round + planner + scan rounds + staging
-          *cnt_p = n;
+          if (emit) *cnt_p = n;
           s_rows += n;
           const int64_t tbase = base + n0;
-          for (int j = lane; j < n - n0; j += 64) {  // flush: coalesced 16-byte rows
+          for (int j = lane; emit && j < n - n0; j += 64) {  // flush: coalesced 16-byte rows
             const uint64_t e = stage[j];
             a.rows[tbase + j] = unpack_row(e & 0x0FFFFFFFFFFFFFFFull, (uint32_t)(e >> 60));
             if (IDS) a.ids[tbase + j] = sid[j];

@@ -335,10 +335,14 @@ int ddz_get_moves_slab(int device_id, const int8_t* hands, const int8_t* lasts, 
  * launch.  The lists are written in the SLAB layout: table t owns
  * rows[t * stride .. t * stride + counts[t]) (ascending canonical id, same rows as
  * ddz_legal), so no table depends on another: a wavefront keeps its table in registers
- * across the iterations and stores the list and the trajectory record of EVERY iteration
- * (each iteration overwrites the table's slab; after the call counts/rows hold the lists
- * of the last pre-step states).  The state is stored ONCE, after the last iteration:
- * nothing can read it between the iterations of a launch.
+ * across the iterations and stores the trajectory record of EVERY iteration.  A launch
+ * leaves the lists of its LAST iteration's pre-step states in counts / rows / ids: every
+ * iteration would overwrite the table's slab and nothing can read it in between, so the
+ * earlier iterations store no list, and slab rows at and beyond counts[t] are not written
+ * (who needs every iteration's lists calls ddz_rollout_random_csr_staged, or this with
+ * n_iters = 1).  A call of more than 2^20 iterations is several launches; what it leaves
+ * is the same.  The state is stored ONCE, after the last iteration: nothing can read it
+ * between the iterations of a launch.
  *   counts int32[T]; rows int8[T * stride][16]; ids int32[T * stride] or NULL;
  *   stride >= 512 covers every list of a <= 20-card hand (497 is the maximum);
  *   stats (device, int64[8], may be NULL) accumulates {plies, finished episodes, total legal

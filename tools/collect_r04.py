@@ -129,11 +129,12 @@ def rollout_entry(prefix, T, it_hbm, it_mix, old_mix):
         "hbm_bytes_per_env_step": (2 * fk + wk) * 1024 / steps,
         "fetch_bytes_per_env_step": 2 * fk * 1024 / steps, "write_bytes_per_env_step": wk * 1024 / steps,
         "FETCH_SIZE_KB": fk, "WRITE_SIZE_KB": wk, "env_steps": steps,
-        "workload": f"tools/run_rollout.py {T} {it_hbm} ({T} tables, {it_hbm} in-launch iterations, seed 0), kernel of profiles/r10_notes.md (packed table, closed-form rounds, scalar refill / win tests)",
+        "workload": f"tools/run_rollout.py {T} {it_hbm} ({T} tables, {it_hbm} in-launch iterations, seed 0), kernel of profiles/r30_notes.md (only the last iteration of a launch stores its lists)",
         "method": "tools/profile.sh rollout: rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes; "
                   "bytes = KB*1024, FETCH doubled (gfx950 counts 128-B requests at 64 B, MI355X_MICROARCH.md HBM section); "
-                  "WRITE_SIZE taken as is (16-B-per-lane stores).  Every iteration overwrites the same list slab "
-                  "of its table, so the write-back L2 merges them: HBM sees far fewer bytes than the kernel stores",
+                  "WRITE_SIZE taken as is (16-B-per-lane stores).  Only the last iteration of a launch stores its "
+                  "lists; what is written per step is the 32-B record where one is asked for, and per table and launch "
+                  "the 176-B state and the last lists",
         "valu": {
             "SQ_INSTS_VALU_per_env_step": mix["SQ_INSTS_VALU"] / steps_mix,
             "SQ_INSTS_SALU_per_env_step": mix["SQ_INSTS_SALU"] / steps_mix,
@@ -143,7 +144,7 @@ def rollout_entry(prefix, T, it_hbm, it_mix, old_mix):
             "GRBM_GUI_ACTIVE": mix["GRBM_GUI_ACTIVE"], "xcds": 8, "launch_ns": ns,
             "clock_GHz": mix["GRBM_GUI_ACTIVE"] / 8 / ns,
             "env_steps_per_s_in_this_launch": steps_mix / (ns * 1e-9),
-            "workload": f"tools/run_rollout.py {T} {it_mix} (one launch, {steps_mix / 1e6:.2f} M env steps), kernel of profiles/r10_notes.md (packed table, closed-form rounds, scalar refill / win tests)"},
+            "workload": f"tools/run_rollout.py {T} {it_mix} (one launch, {steps_mix / 1e6:.2f} M env steps), kernel of profiles/r30_notes.md (only the last iteration of a launch stores its lists)"},
         "valu_mix": old_mix}
 
 
