@@ -88,6 +88,16 @@ SYMBOLS = {
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ddz_guided_values": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_void_p]),
+    "ddz_puct_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "ddz_puct_open": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
+                                C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_puct_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int64,
+                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ddz_puct_close": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p]),
+    "ddz_puct_priors": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                  C.c_float, C.c_void_p, C.c_void_p]),
     "ddz_gismcts_work_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "ddz_gismcts_open": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int64,
                                    C.c_void_p, C.c_int64, C.c_void_p]),

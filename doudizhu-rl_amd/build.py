@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libddz_hip.so")
 LIB_JK = os.path.join(CSRC, "libddz_hip_jk.so")
 SOURCES = ["ddz_engine.hip"]
-DEPS = ["ddz_device.h", "ddz_build_table.h", "ddz_auto.h", "ddz_auto2.h", "ddz_qnet.h", "ddz_qtrain.h", "ddz_replay.h", "ddz_returns.h", "ddz_teach.h", "ddz_ply.h", "ddz_playout.h", "ddz_search.h", "ddz_guided.h", "ddz_ismcts.h", "ddz_gismcts.h", "ddz_cfr.h", "ddz_solve.h", os.path.join("..", "..", "include", "ddz_env.h")]
+DEPS = ["ddz_device.h", "ddz_build_table.h", "ddz_auto.h", "ddz_auto2.h", "ddz_qnet.h", "ddz_qtrain.h", "ddz_replay.h", "ddz_returns.h", "ddz_teach.h", "ddz_ply.h", "ddz_playout.h", "ddz_search.h", "ddz_guided.h", "ddz_puct.h", "ddz_ismcts.h", "ddz_gismcts.h", "ddz_cfr.h", "ddz_solve.h", os.path.join("..", "..", "include", "ddz_env.h")]
 
 
 def hipcc():

@@ -12,6 +12,9 @@
 //             caller-provided workspace, the descent re-applies stored moves.
 //   k_guided  (ddz_guided.h; ddz_guided_open / _step / _close) k_search's tree with leaf values from outside the kernel: one
 //             iteration of every (table, tree) per launch, the new leaf's state row out, its value in with the next launch.
+//   k_puct    (ddz_puct.h; ddz_puct_open / _step / _close) k_guided's phases with a prior weight per move of every evaluated node:
+//             selection over all moves of a node by the PUCT rule, nothing expanded at random; k_puct_priors makes the weights
+//             from a q slab.
 //   k_ismcts  (ddz_ismcts.h; ddz_ismcts) information-set MCTS: one wavefront per (table, tree), ONE tree over a fresh world per
 //             iteration, a list at every level of the descent, children keyed by (parent, count word).
 //   k_gismcts (ddz_gismcts.h; ddz_gismcts_open / _step / _close) k_ismcts's tree and descent in k_guided's phases: one iteration
@@ -1424,6 +1427,7 @@ __global__ __launch_bounds__(RW * 64, RW == WPB ? 4 : 6) void k_rollout(RolloutA
 #include "ddz_playout.h"  // k_playout / k_playout_choose: playouts of every legal move
 #include "ddz_search.h"   // k_search / k_search_choose: UCT tree search around the playouts, one wavefront per (table, tree)
 #include "ddz_guided.h"   // k_guided / k_guided_value: UCT with leaf values from outside the kernel, one iteration per launch
+#include "ddz_puct.h"     // k_puct / k_puct_priors: guided UCT with move priors, selection over all moves of a node
 #include "ddz_ismcts.h"   // k_ismcts: information-set MCTS, one tree per (table, tree) over all its sampled worlds
 #include "ddz_gismcts.h"  // k_gismcts: k_ismcts's tree with leaf values from outside the kernel, one iteration per launch
 #include "ddz_cfr.h"      // k_cfr / k_cfr_choose: the CFR endgame solver, one wavefront per table, the forest in a workspace slot
@@ -2956,11 +2960,11 @@ int launch_hidden(bool hidden, int64_t blocks, void* stream, const A& a) {
 }
 // what ddz_search, ddz_ismcts and the three ddz_guided_* / ddz_gismcts_* launches do alike: the argument checks in their order, SearchArgs,
 // the launch of one wavefront per (table, tree).  tree_bytes: the workspace of one tree at this budget (asked only once the
-// budget is known to be in range).  A: the kernels' argument struct, SearchArgs or one derived from it whose own fields
+// budget is known to be in range; k_puct's also depends on its pool, so it is any callable).  A: the kernels' argument struct, SearchArgs or one derived from it whose own fields
 // `fill` sets; outs: the call writes visits / wins (they must be there)
 struct SearchNoFill { void operator()(SearchArgs&) const {} };
-template <auto OPEN, auto HIDDEN, typename A = SearchArgs, typename Fill = SearchNoFill>
-int search_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int64_t budget, int64_t trees, int mode, float c, uint64_t salt,
+template <auto OPEN, auto HIDDEN, typename A = SearchArgs, typename Fill = SearchNoFill, typename TreeBytes = uint64_t (*)(int64_t)>
+int search_launch(ddz_env* e, TreeBytes tree_bytes, int64_t budget, int64_t trees, int mode, float c, uint64_t salt,
                   bool hidden, int roles, int64_t stride, int32_t* visits, int32_t* wins, int64_t* totals, void* work,
                   int64_t work_bytes, void* stream, bool outs = true, Fill fill = {}) {
   if (!good(e)) return DDZ_EHANDLE;
@@ -3001,6 +3005,23 @@ int guided_launch(ddz_env* e, uint64_t (*tree_bytes)(int64_t), int phase, int64_
   const auto fill = [=](GuidedArgs& a) { a.phase = phase; a.values = values; a.leaf_rows = leaf_rows; a.need = need; };
   return search_launch<OPEN, HIDDEN, GuidedArgs>(e, tree_bytes, budget, trees, mode, c, salt, hidden, roles, stride, visits, wins, totals,
                                                  work, work_bytes, stream, phase == GUIDED_CLOSE, fill);
+}
+// a launch of k_puct in `phase`: guided_launch's checks in their order, then the mode (sides only), the pool and priors
+int puct_launch(ddz_env* e, int phase, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, bool hidden, int roles,
+                int64_t stride, int64_t pool, const int32_t* values, const uint8_t* priors, uint8_t* leaf_rows, int32_t* need,
+                int32_t* visits, int32_t* wins, int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+  if (!good(e)) return DDZ_EHANDLE;
+  if (!al(values, 4) || !al(leaf_rows, 16) || !al(need, 4) || !al(priors, 16)) return DDZ_EINVAL;
+  if (phase == GUIDED_STEP && (!leaf_rows || !need)) return DDZ_EINVAL;
+  if (budget >= 1 && trees >= 1 && budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return DDZ_EINVAL;   // the int32 root sums
+  if (mode != DDZ_SEARCH_SIDES) return DDZ_EINVAL;
+  if (pool < 16 || pool % 16 != 0 || pool > PUCT_POOL_MAX) return DDZ_EINVAL;
+  const auto fill = [=](PuctArgs& a) {
+    a.phase = phase; a.values = values; a.leaf_rows = leaf_rows; a.need = need; a.priors = priors; a.pool = (uint32_t)pool;
+  };
+  const auto tree_bytes = [pool](int64_t b) { return puct_tree_bytes(b, pool); };
+  return search_launch<k_puct<false>, k_puct<true>, PuctArgs>(e, tree_bytes, budget, trees, mode, c, salt, hidden, roles, stride, visits,
+                                                              wins, totals, work, work_bytes, stream, phase == GUIDED_CLOSE, fill);
 }
 // a *_choose kernel over the env's tables, `per` tables to a block of BLOCK threads
 template <auto K, typename... Q>
@@ -3805,6 +3826,52 @@ int ddz_guided_values(int device, const uint8_t* rows, const int32_t* counts, co
   a.net_roles = (uint32_t)net_roles; a.values = values;
   constexpr int per = BLOCK / 64;
   hipLaunchKernelGGL(k_guided_value, dim3((unsigned)((n + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+// ddz_puct_*: k_puct<hidden> in its three phases; ddz_guided_*'s checks and codes, then the mode, the pool and priors
+int64_t ddz_puct_work_bytes(int64_t n_tables, int64_t budget, int64_t trees, int64_t pool) {
+  if (n_tables < 0 || budget < 1 || budget > DDZ_SEARCH_MAX_BUDGET || trees < 1 || trees > 65536) return -1;
+  if (budget * trees * (int64_t)DDZ_GUIDED_ONE >= (1ll << 31)) return -1;
+  if (pool < 16 || pool % 16 != 0 || pool > PUCT_POOL_MAX) return -1;
+  return (int64_t)puct_tree_bytes(budget, pool) * n_tables * trees;
+}
+
+int ddz_puct_open(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                  int64_t stride, int64_t pool, void* work, int64_t work_bytes, void* stream) {
+  return puct_launch(e, GUIDED_OPEN, budget, trees, mode, c, salt, hidden != 0, roles, stride, pool, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_puct_step(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                  int64_t stride, int64_t pool, const int32_t* values, const uint8_t* priors, uint8_t* leaf_rows, int32_t* need,
+                  void* work, int64_t work_bytes, void* stream) {
+  return puct_launch(e, GUIDED_STEP, budget, trees, mode, c, salt, hidden != 0, roles, stride, pool, values, priors, leaf_rows, need,
+                     nullptr, nullptr, nullptr, work, work_bytes, stream);
+}
+
+int ddz_puct_close(ddz_env_t* e, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                   const int32_t* values, const uint8_t* priors, int64_t stride, int64_t pool, int32_t* visits, int32_t* wins,
+                   int64_t* totals, void* work, int64_t work_bytes, void* stream) {
+  return puct_launch(e, GUIDED_CLOSE, budget, trees, mode, c, salt, hidden != 0, roles, stride, pool, values, priors, nullptr, nullptr,
+                     visits, wins, totals, work, work_bytes, stream);
+}
+
+int ddz_puct_priors(int device, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
+                    const float* inv_reward, int net_roles, float inv_tau, uint8_t* priors, void* stream) {
+  if (!al(rows, 16) || !al(counts, 4) || !al(q, 4)) return DDZ_EINVAL;
+  if (n < 0 || stride < 1 || net_roles < 0 || net_roles > 7 || !inv_reward || !(inv_tau >= 0.0f) || !(inv_tau <= 3.0e38f)) return DDZ_EINVAL;
+  if (n > 0 && (!rows || !counts || !q || !priors)) return DDZ_EINVAL;
+  if (n == 0) return DDZ_OK;
+  if (n > 0x7FFFFFFF || n * stride > ((int64_t)1 << 40)) return DDZ_ECAP;
+  DeviceGuard g(device);
+  if (!g.ok) return DDZ_ENODEV;
+  PuctPriorsArgs a;
+  a.rows = rows; a.counts = counts; a.q = q; a.stride = stride; a.n_leaves = n;
+  for (int r = 0; r < 3; ++r) a.inv_reward[r] = inv_reward[r];
+  a.net_roles = (uint32_t)net_roles; a.values = nullptr; a.inv_tau = inv_tau; a.priors = priors;
+  constexpr int per = BLOCK / 64;
+  hipLaunchKernelGGL(k_puct_priors, dim3((unsigned)((n + per - 1) / per)), dim3(BLOCK), 0, (hipStream_t)stream, a);
   return check_launch();
 }
 

@@ -1345,9 +1345,14 @@ class QLeaf:
     that pass is at its best), and ddz_guided_values turns the maximum into 1024ths: p = qmax / reward[role] is the expected
     outcome in [-1, 1] for the actor's side, value = rint((p + 1) * 512) clamped.  nets: {"lord" | "down" | "up": QNet | None};
     leaves whose actor has no network are left to `fallback` (another evaluator, e.g. engine.PlayoutLeaf), which is called
-    first; without one every role needs a network."""
+    first; without one every role needs a network.  A search with a `priors` field (BatchedEnv.guided_puct, search spec v5)
+    also gets the weight of every move of a leaf from the same q slab (ddz_puct_priors): w_j = rint(255 * exp((q_j - qmax) /
+    (reward[role] * tau))), the best move 255; tau: the temperature, in units of the role's reward."""
 
-    def __init__(self, nets, face_variant, reward_dict=None, fallback=None):
+    def __init__(self, nets, face_variant, reward_dict=None, fallback=None, tau=1.0):
+        if not float(tau) > 0.0:
+            raise ValueError("tau must be positive")
+        self.inv_tau = 1.0 / float(tau)
         _, self.net_of_role = role_slots(nets, face_variant)
         if fallback is None and min(self.net_of_role) < 0:
             missing = [r for r, s in zip(ROLE_ORDER, self.net_of_role) if s < 0]
@@ -1382,10 +1387,12 @@ class QLeaf:
         return loop.q_values(), env
 
     def __call__(self, search):
-        from .engine import guided_values
+        from .engine import guided_values, puct_priors
         if self.fallback is not None:
             self.fallback(search)
         q, env = self.q_values(search)
+        if getattr(search, "priors", None) is not None:
+            puct_priors(search.leaves, env.counts, q, self.inv_reward, inv_tau=self.inv_tau, net_roles=self.net_roles, out=search.priors)
         return guided_values(search.leaves, env.counts, q, self.inv_reward, net_roles=self.net_roles, out=search.values)
 
 

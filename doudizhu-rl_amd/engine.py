@@ -916,6 +916,31 @@ class BatchedEnv:
             raise RuntimeError("a guided search is open on this environment's workspace: close() it first")
         return GuidedSearch(self, budget, trees, mode, c, salt, hidden, roles)
 
+    # ---- guided UCT with move priors (search spec v5) ----
+    def guided_puct(self, budget, trees=None, c=1.25, salt=0, hidden=False, roles=0b111, pool=None, mode="sides"):
+        """Opens a guided PUCT search on every running table (search spec v5): guided()'s phases and unit, but
+        every evaluated node also keeps a prior weight for each of its moves, selection runs over ALL moves of a node by
+        mean + c * p * sqrt(N) / (1 + V), and nothing is expanded at random.  -> a GuidedSearch with the extra field .priors
+        (uint8 [T * trees, stride]): the evaluator fills .values AND .priors[k, :n] (the weights of the leaf's moves in the
+        order of legal_slab() on the imported leaf row) between the steps; PlayoutLeaf and dqn_glue.QLeaf do.  The first step
+        evaluates the root.  Only the "sides" rule (mode is there to say so: anything else is a ValueError).  pool: bytes of
+        prior weights a tree can keep, a multiple of 16 (default 64 * budget rounded up); a node it has no room for is
+        uniform and counted in totals[4].  close(totals) takes int64 [5].  budget * trees * 1024 must stay below 2^31; the
+        same one-open-search-per-environment rule, shared with guided()."""
+        if mode != "sides":
+            raise ValueError('guided_puct has the "sides" rule only')
+        if getattr(self, "_guided_pending", None) is not None:
+            raise RuntimeError("a guided search is open on this environment's workspace: close() it first")
+        return GuidedSearch(self, budget, trees, "sides", c, salt, hidden, roles, puct=True, pool=pool)
+
+    def guided_puct_choose(self, evaluator, budget, trees=None, c=1.25, salt=0, hidden=False, roles=0b111, pool=None, out=None):
+        """The guided-PUCT move of every table: int32 [T] canonical action ids, the move with the most visits of
+        guided_puct(...).run(evaluator), ties to the lowest index (ddz_playout_choose's rule on the visits); an idle table
+        gets what playout_choose gives it.  Feed them to step_slab(mode=STEP_IDS)."""
+        out = self._choose_out("guided_puct_choose", out)
+        visits, _ = self.guided_puct(budget, trees=trees, c=c, salt=salt, hidden=hidden, roles=roles, pool=pool).run(evaluator)
+        return self._choose_wins(visits, out)
+
     def guided_choose(self, evaluator, budget, trees=None, mode="reference", c=0.7, salt=0, hidden=False, roles=0b111, out=None):
         """The guided-UCT move of every table: int32 [T] canonical action ids, search_choose()'s rule (ddz_search_choose: the
         first maximum of wins / visits, compared exactly) on guided(...).run(evaluator)'s root statistics; -1 where nothing
@@ -1144,23 +1169,28 @@ class BatchedEnv:
 class GuidedSearch:
     """One open guided search of a BatchedEnv: guided UCT (search spec v3; BatchedEnv.guided makes it) or guided
     ISMCTS (search spec v4; BatchedEnv.guided_ismcts makes it: the same fields and calls, ddz_gismcts_*'s entry points and
-    workspace).  Item k = t * trees + c is tree c of table t.
+    workspace), or guided PUCT (search spec v5; BatchedEnv.guided_puct makes it: ddz_puct_*'s entry points, the extra field
+    `priors`, totals of five).  Item k = t * trees + c is tree c of table t.
       leaves  uint8 [T * trees, 11, 16]: after step(), the state row of every item's pending leaf (an all-zero row, dealt = 0,
               where the item waits for nothing: a leaf environment that imports them freezes those)
       need    int32 [T * trees]: 1 where the item waits for a value
       values  int32 [T * trees], CALLER-FILLED between the steps: the chance in 1024ths that the side of the leaf's ACTOR
               wins (clamped into [0, 1024] by the kernel; entries with need = 0 are not read)
+      priors  (guided_puct only) uint8 [T * trees, stride], CALLER-FILLED beside values: priors[k, j] is the weight of move j
+              of item k's leaf, in the order of legal_slab() on the imported leaf row; entries at or beyond the leaf's list
+              size are not read
     step() backs up the previous step's leaves with `values` and runs one iteration; close() backs up the last ones and
     returns (visits, wins) int32 [T, stride], wins in 1024ths.  Every call is one launch on the current stream, nothing on
     the host: a whole run can be captured in a graph.  The environment must not change between guided() and close().
     step() after close(), or a second close(), raises RuntimeError without touching the device."""
 
-    def __init__(self, env, budget, trees, mode, c, salt, hidden, roles, ismcts=False):
+    def __init__(self, env, budget, trees, mode, c, salt, hidden, roles, ismcts=False, puct=False, pool=None):
         self.env = env
         self.ismcts = bool(ismcts)
+        self.puct = bool(puct)
         self.hidden = bool(hidden) or self.ismcts
         self.roles = _roles_mask(roles, self.hidden)
-        self._verb = "ddz_gismcts" if self.ismcts else "ddz_guided"
+        self._verb = "ddz_gismcts" if self.ismcts else "ddz_puct" if self.puct else "ddz_guided"
         self.budget, self.trees, self.c, self._visits, self._wins = env._search_args("guided needs", budget, trees, mode, c, None, None,
                                                                                     None)
         if self.budget * self.trees * env.GUIDED_ONE >= 1 << 31:
@@ -1173,9 +1203,17 @@ class GuidedSearch:
         self.values = torch.zeros(n, dtype=torch.int32, device=env.device)
         self.steps = 0
         self.closed = False
-        self._work = env._workspace("_gismcts_work" if self.ismcts else "_guided_work",
-                                    int(self._fn("work_bytes")(env.T, self.budget, self.trees)))
-        check(self._fn("open")(env._h, *self._common(), env.slab_stride, _p(self._work), self._work.numel(), _stream(env.device)))
+        self._pool = ()
+        if self.puct:
+            pool = (64 * self.budget + 15) & ~15 if pool is None else int(pool)
+            if pool < 16 or pool % 16 or pool > 1 << 24:
+                raise ValueError("pool must be a multiple of 16 in [16, 2^24]")
+            self.pool, self._pool = pool, (pool,)
+            self.priors = torch.zeros((n, env.slab_stride), dtype=torch.uint8, device=env.device)
+        self._work = env._workspace("_gismcts_work" if self.ismcts else "_puct_work" if self.puct else "_guided_work",
+                                    int(self._fn("work_bytes")(env.T, self.budget, self.trees, *self._pool)))
+        check(self._fn("open")(env._h, *self._common(), env.slab_stride, *self._pool, _p(self._work), self._work.numel(),
+                               _stream(env.device)))
         env._guided_pending = self
 
     def _fn(self, phase):
@@ -1187,7 +1225,11 @@ class GuidedSearch:
         return head + (self.roles,) if self.ismcts else head + (int(self.hidden), self.roles)
 
     def _values(self):
-        return self.env._arg(self.values, "values", torch.int32, numel=self.n_items)
+        """(values,), or (values, priors) of a PUCT search: checked, as they go to a step or a close (None before the first step)"""
+        got = (self.env._arg(self.values, "values", torch.int32, numel=self.n_items),)
+        if self.puct:
+            got += (self.env._arg(self.priors, "priors", torch.uint8, numel=self.n_items * self.env.slab_stride),)
+        return tuple(_p(x) if self.steps else None for x in got)
 
     def step(self):
         """back up the pending leaves with .values, then one iteration of every item -> (leaves, need)"""
@@ -1197,22 +1239,26 @@ class GuidedSearch:
         values = self._values()
         env._arg(self.leaves, "leaves", torch.uint8, numel=self.n_items * NFIELDS * ROW)
         env._arg(self.need, "need", torch.int32, numel=self.n_items)
-        check(self._fn("step")(env._h, *self._common(), env.slab_stride, _p(values) if self.steps else None,
+        check(self._fn("step")(env._h, *self._common(), env.slab_stride, *self._pool, *values,
                                _p(self.leaves), _p(self.need), _p(self._work), self._work.numel(), _stream(env.device)))
         self.steps += 1
         return self.leaves, self.need
 
     def close(self, totals=None):
         """back up the last pending leaves -> (visits, wins) int32 [T, stride]; totals: int64 [4] on the device, +=
-        {moves applied, iterations run, iterations scored unfinished, nodes created}"""
+        {moves applied, iterations run, iterations scored unfinished, nodes created}; a PUCT search: int64 [5], then the nodes
+        that fell back to uniform priors"""
         if self.closed:
             raise RuntimeError("close() on a closed guided search")
         env = self.env
         values = self._values()
-        env._totals(totals)
+        if self.puct:
+            env._arg(totals, "totals", torch.int64, at_least=5, none_ok=True)
+        else:
+            env._totals(totals)
         self._visits.zero_()
         self._wins.zero_()
-        check(self._fn("close")(env._h, *self._common(), _p(values) if self.steps else None, env.slab_stride,
+        check(self._fn("close")(env._h, *self._common(), *values, env.slab_stride, *self._pool,
                                 _p(self._visits), _p(self._wins), _p(totals), _p(self._work), self._work.numel(),
                                 _stream(env.device)))
         self.closed = True
@@ -1231,7 +1277,9 @@ class PlayoutLeaf:
     """A leaf evaluator for GuidedSearch.run: flat Monte Carlo from the leaf.  The leaf rows are imported into a scratch
     BatchedEnv of one table per item (made once, with the searched environment's seed, rule set and table_id_base 0; made anew
     when a later search has another item count, device or rule set), playout(K) runs
-    there, and value = (max_j wins_j * 1024) // K: the best move's win rate for the leaf's actor, in integers.  No network."""
+    there, and value = (max_j wins_j * 1024) // K: the best move's win rate for the leaf's actor, in integers.  A search with
+    a `priors` field (guided_puct) also gets the weight of every move j of a leaf's list, w_j = 1 + (254 * wins_j) // K: the
+    scratch environment's slab lists are in the order the search reads them.  No network."""
 
     def __init__(self, n_playouts, salt=0, chunks=None):
         self.K, self.salt, self.chunks = int(n_playouts), salt, chunks
@@ -1248,7 +1296,13 @@ class PlayoutLeaf:
         env = self.scratch(search)
         env.state_import(search.leaves)
         wins, = env._run_kept("playout", self.K, salt=self.salt, chunks=self.chunks)
-        search.values.copy_(torch.div(wins.view(env.T, -1).amax(dim=1) * BatchedEnv.GUIDED_ONE, self.K, rounding_mode="floor"))
+        wins = wins.view(env.T, -1)
+        search.values.copy_(torch.div(wins.amax(dim=1) * BatchedEnv.GUIDED_ONE, self.K, rounding_mode="floor"))
+        priors = getattr(search, "priors", None)
+        if priors is not None:
+            w = (1 + torch.div(254 * wins, self.K, rounding_mode="floor")).to(torch.uint8)
+            inside = torch.arange(wins.shape[1], device=wins.device)[None, :] < env.counts.view(-1, 1)
+            priors.copy_(torch.where(inside, w, priors.view(env.T, -1)).view_as(priors))
         return search.values
 
 
@@ -1271,6 +1325,32 @@ def guided_values(rows, counts, q, inv_reward, net_roles=0b111, out=None):
     if n:
         check(_lib.lib().ddz_guided_values(dev.index, _p(rows), _p(counts), _p(q), stride, n, inv, _roles_mask(net_roles, name="net_roles"),
                                            _p(out), _stream(dev)))
+    return out
+
+
+def puct_priors(rows, counts, q, inv_reward, inv_tau=1.0, net_roles=0b111, out=None):
+    """ddz_puct_priors: prior weights from a q slab, beside guided_values.  rows uint8 [n, 176] leaf rows, counts int32 [n] list
+    sizes, q f32 [n, stride]; for every running row whose actor's role is in net_roles, out[i, j] = clamp((int)rintf(255 *
+    expf((q[i, j] - max q[i, :counts[i]]) * inv_reward[role] * inv_tau)), 0, 255) for j < counts[i] -- the maximum gets 255,
+    a NaN in the row gives all ones -- and every other entry of `out` (uint8 [n, stride], made zero-filled if None) stays as
+    it is.  No host sync."""
+    dev = _require_gpu(rows.device)
+    n = counts.numel()
+    _chk(rows, "rows", torch.uint8, dev, numel=n * NFIELDS * ROW, why=" (176-byte rows)")
+    _chk(counts, "counts", torch.int32, dev, shape=(n,))
+    stride = q.numel() // n if n else 1
+    _chk(q, "q", torch.float32, dev, numel=n * stride, why=" ([n, stride])")
+    inv_tau = float(inv_tau)
+    if not 0.0 <= inv_tau < 3.0e38:
+        raise ValueError("inv_tau must be finite and not negative")
+    if out is None:
+        out = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
+    else:
+        _chk(out, "out", torch.uint8, dev, numel=n * stride)
+    inv = (C.c_float * 3)(*[float(x) for x in inv_reward])
+    if n:
+        check(_lib.lib().ddz_puct_priors(dev.index, _p(rows), _p(counts), _p(q), stride, n, inv, _roles_mask(net_roles, name="net_roles"),
+                                         inv_tau, _p(out), _stream(dev)))
     return out
 
 
@@ -1400,16 +1480,18 @@ cached on the env: the next evaluate() overwrites them."""
 
 class Teacher:
     """One of the evaluators as a source of training targets and of moves (teacher spec v1): kind "playout"
-    (BatchedEnv.playout), "search", "ismcts", "guided" / "guided_ismcts" (BatchedEnv.guided(...) / guided_ismcts(...)
-    .run(evaluator); they need evaluator=, e.g. PlayoutLeaf or dqn_glue.QLeaf; "guided_ismcts" is always hidden) or "solve";
+    (BatchedEnv.playout), "search", "ismcts", "guided" / "guided_ismcts" / "guided_puct" (BatchedEnv.guided(...) /
+    guided_ismcts(...) / guided_puct(...) .run(evaluator); they need evaluator=, e.g. PlayoutLeaf or dqn_glue.QLeaf;
+    "guided_ismcts" is always hidden; "guided_puct" has guided's root statistics and unit, and chooses by visits) or "solve";
     the keyword arguments are the evaluator's own (n_playouts, budget, trees, hidden, roles, salt, ...) and are passed through.  evaluate(env) runs the evaluator once on env's current states and
     returns TeacherStats; choose(env, stats) turns THE SAME statistics into moves with the evaluator's own rule
-    (ddz_playout_choose / ddz_search_choose / ddz_solve_choose): no second search.  Nothing here touches the host, so both
+    (ddz_playout_choose / ddz_search_choose / ddz_solve_choose; "guided_puct": ddz_playout_choose on the visits): no second search.  Nothing here touches the host, so both
     can be captured.  hidden is the caller's choice: labels from open hands (hidden=False, what playout / search / solve
     default to) are legitimate for training a network that only sees its own face, not for serving moves to a seat."""
     KINDS = {"playout": ("playout", ("n_playouts",)), "search": ("search", ("budget",)), "ismcts": ("ismcts", ("budget",)),
-             "guided": ("guided", ("budget",)), "guided_ismcts": ("guided_ismcts", ("budget",)), "solve": ("solve", ())}
-    GUIDED = ("guided", "guided_ismcts")     # the kinds that take a leaf evaluator
+             "guided": ("guided", ("budget",)), "guided_ismcts": ("guided_ismcts", ("budget",)),
+             "guided_puct": ("guided_puct", ("budget",)), "solve": ("solve", ())}
+    GUIDED = ("guided", "guided_ismcts", "guided_puct")     # the kinds that take a leaf evaluator
     _BUFFERS = ("self", "wins", "visits", "totals", "out")
 
     def __init__(self, kind, evaluator=None, **kwargs):
@@ -1425,7 +1507,7 @@ class Teacher:
         if missing:
             raise ValueError(f"{kind} needs {', '.join(missing)}")
         if (kind in self.GUIDED) != (evaluator is not None):
-            raise ValueError("evaluator= is the leaf evaluator of the kinds \"guided\" and \"guided_ismcts\", and of no other kind")
+            raise ValueError("evaluator= is the leaf evaluator of the kinds " + ", ".join(f'"{k}"' for k in self.GUIDED) + ", and of no other kind")
         self.kind, self.evaluator, self.kwargs = kind, evaluator, dict(kwargs)
         hidden = kind in ("ismcts", "guided_ismcts") or bool(kwargs.get("hidden", False))
         self.roles = _roles_mask(kwargs.get("roles", 0b111), hidden)
@@ -1436,6 +1518,7 @@ class Teacher:
               "ismcts": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, 1),
               "guided": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
               "guided_ismcts": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
+              "guided_puct": lambda env, kw, visits, wins: (env.counts, wins, visits, None, None, BatchedEnv.GUIDED_ONE),
               # its own n as the list sizes: a table that is no endgame (n <= 0) emits nothing
               "solve": lambda env, kw, n, wins, unknown: (n, wins, None, int(kw.get("worlds", 1)), unknown, 1)}
 
@@ -1455,6 +1538,8 @@ class Teacher:
         out = env._choose_out("Teacher.choose", out)
         if self.kind == "playout":
             env._choose_wins(stats.num, out)
+        elif self.kind == "guided_puct":
+            env._choose_wins(stats.den, out)
         elif self.kind == "solve":
             value = env._kept("teach value", lambda: torch.empty(env.T, dtype=torch.int32, device=env.device))
             env._choose_solved(int(stats.den_const), stats.num, stats.unknown, out, value)

@@ -232,6 +232,17 @@ def guided_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, tre
                 lambda env: env.guided_choose(evaluator, budget, trees=trees, mode=mode, c=c, salt=salt, hidden=True))[0]
 
 
+def guided_puct_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, trees=None, c=1.25, pool=None):
+    """Guided PUCT for a batch of PLAIN serving payloads (no hand_card; one that is there is not read): every request is packed
+    by payloads_to_playout_state and searched by BatchedEnv.guided_puct_choose in the hidden form (search spec v5: tree c on
+    world c of the cards the requester has not seen, `budget` iterations of one launch each, every new node judged by
+    `evaluator` -- engine.PlayoutLeaf, dqn_glue.QLeaf or any callable that fills search.values and search.priors), and the
+    root move with the most visits is returned -- per request a list of rank values 3..17 ([] = pass), or None where the
+    request has no move (a finished game).  ValueError where cur_cards, history and left do not add up to a deck."""
+    return _act(payloads, True, device, seed, "hidden-hand",
+                lambda env: env.guided_puct_choose(evaluator, budget, trees=trees, c=c, salt=salt, hidden=True, pool=pool))[0]
+
+
 def guided_ismcts_act(payloads, evaluator, budget, device="cuda:0", salt=0, seed=0, trees=None, mode="reference", c=0.7):
     """Guided ISMCTS for a batch of PLAIN serving payloads (no hand_card; one that is there is not read): every request is
     packed by payloads_to_playout_state and searched by BatchedEnv.guided_ismcts_choose (search spec v4: `trees` trees of

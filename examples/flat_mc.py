@@ -9,6 +9,7 @@ them.  Prints both win rates from env.stats().
   python examples/flat_mc.py --ismcts BUDGET [--trees 1] [--uct-trees 16] [--mode reference] [--tables 256] [--iterations 200]
   python examples/flat_mc.py --guided BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 4] [--tables 256] [--iterations 200]
   python examples/flat_mc.py --guided-ismcts BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 1] [--uct-trees 4] [--tables 256]
+  python examples/flat_mc.py --guided-puct BUDGET [--leaf playout|q] [--leaf-playouts 4] [--trees 4] [--c 1.25] [--tables 256]
 
 --hidden: the playouts do not read the farmers' hands; they run on hands dealt anew, per playout number, from the cards the
 lord has not seen (playout spec v2, BatchedEnv.playout_choose(hidden=True, roles=0b010): only the lord's tables are
@@ -38,6 +39,12 @@ iterations, every iteration on a fresh deal of the cards the lord has not seen, 
 by --leaf as above) against the RULE farmers -- beside a guided-UCT lord with the same evaluator and the same total iterations
 per move split over --uct-trees worlds, and an ISMCTS lord (random playouts) at the same trees and budget, for example 1 x 256
 against 4 x 64 and 1 x 256.  Printed with their game counts; one run is an observation, not a measurement.
+
+--guided-puct BUDGET: a guided-PUCT lord (BatchedEnv.guided_puct_choose, search spec v5: --trees trees of BUDGET iterations on
+sampled hands, one launch per iteration, every new node judged by --leaf, which also hands back a prior weight for each of
+the node's moves; selection over all moves by mean + c * prior * sqrt(N) / (1 + visits), the move with the most visits is
+played) against the RULE farmers -- beside a guided-UCT lord (mode "sides") with the same evaluator, budget and trees.  Printed
+with their game counts; one run is an observation, not a measurement (tools/puct_probe.py measures).
 
 The playouts are computed for every table on every iteration and used where the lord is to move (the other tables take -1 =
 the engine's random move): simple, and three times the work a loop that asks only for the lord's tables would do.
@@ -127,6 +134,24 @@ def guided_ismcts_match(pkg, a, dev, lord_kind):
     return env.stats()
 
 
+def guided_puct_match(pkg, a, dev, puct):
+    """the lord by guided PUCT (puct=True) or by guided UCT with the "sides" rule at the same budget and trees, the same
+    evaluator, both on sampled hands; the farmers by the rule agent"""
+    env = pkg.BatchedEnv(a.tables, seed=a.seed, device=dev)
+    env.reset()
+    lord = torch.empty(a.tables, dtype=torch.int32, device=dev)
+    leaf = make_leaf(pkg, a, dev)
+    for it in range(a.iterations):
+        leaf.salt = it
+        if puct:
+            env.guided_puct_choose(leaf, a.guided_puct, trees=a.trees, c=a.c, salt=it, hidden=True, roles=0b010, out=lord)
+        else:
+            env.guided_choose(leaf, a.guided_puct, trees=a.trees, mode="sides", salt=it, hidden=True, roles=0b010, out=lord)
+        env.step_slab(torch.where(env.role == 1, lord, env.auto_choose(0b101)), pkg.STEP_IDS, auto_reset=True)
+    assert env.status() == 0
+    return env.stats()
+
+
 def guided_match(pkg, a, dev, guided):
     """the lord by guided UCT (guided=True) or by determinized UCT at the same budget and trees, both on sampled hands; the
     farmers by the rule agent"""
@@ -157,7 +182,9 @@ def main():
     ap.add_argument("--ismcts", type=int, default=0, metavar="BUDGET", help="an ISMCTS lord against the rule farmers")
     ap.add_argument("--guided", type=int, default=0, metavar="BUDGET", help="a guided-UCT lord against the rule farmers")
     ap.add_argument("--guided-ismcts", type=int, default=0, metavar="BUDGET", help="a guided-ISMCTS lord against the rule farmers")
-    ap.add_argument("--leaf", default="playout", choices=("playout", "q"), help="--guided / --guided-ismcts: the leaf evaluator")
+    ap.add_argument("--guided-puct", type=int, default=0, metavar="BUDGET", help="a guided-PUCT lord against the rule farmers")
+    ap.add_argument("--c", type=float, default=1.25, help="--guided-puct: the exploration constant")
+    ap.add_argument("--leaf", default="playout", choices=("playout", "q"), help="--guided / --guided-ismcts / --guided-puct: the leaf evaluator")
     ap.add_argument("--leaf-playouts", type=int, default=4, help="--guided --leaf playout: playouts per move of a leaf")
     ap.add_argument("--trees", type=int, default=1, help="--search / --ismcts / --guided: trees per table")
     ap.add_argument("--uct-trees", type=int, default=None,
@@ -168,6 +195,14 @@ def main():
     dev = torch.device("cuda:0")
     if a.uct_trees is None:
         a.uct_trees = 4 if a.guided_ismcts else 16
+    if a.guided_puct:
+        for puct, name in ((True, f"guided-PUCT lord ({a.trees} x {a.guided_puct} iterations, leaf {a.leaf}, c {a.c})"),
+                           (False, f"guided-UCT lord ({a.trees} x {a.guided_puct} iterations, leaf {a.leaf}, mode sides)")):
+            t0 = time.perf_counter()
+            st = guided_puct_match(pkg, a, dev, puct)
+            dt = time.perf_counter() - t0
+            print(f"{name} vs rule farmers: {rates(st)}  [{dt / a.iterations * 1e3:.2f} ms per iteration at {a.tables} tables]")
+        return
     if a.guided_ismcts:
         uct_budget = max(1, a.guided_ismcts * a.trees // a.uct_trees)
         for kind, name in (("v4", f"guided-ISMCTS lord ({a.trees} x {a.guided_ismcts} iterations, leaf {a.leaf}, mode {a.mode})"),

@@ -541,6 +541,54 @@ int ddz_guided_close(ddz_env_t* env, int64_t budget, int64_t trees, int mode, fl
 int ddz_guided_values(int device_id, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
                       const float* inv_reward, int net_roles, int32_t* values, void* stream);
 
+/* Guided UCT with move priors: "search spec v5 (guided PUCT)" (DESIGN.md 4).  ddz_guided_*'s launches (open / step / close, W in
+ * 1024ths, budget * trees * 1024 < 2^31, the clamped value scored v or 1024 - v by the leaf actor's side, the leaf row, need, the
+ * backup at the start of the next launch or in close, the hidden form on world c with status bit 6, status bit 1) with a PRIOR
+ * WEIGHT for every move of every evaluated node: selection runs over all list indices of a node, visited or not, and nothing
+ * is expanded at random (no expansion draw).  mode must be DDZ_SEARCH_SIDES (else DDZ_EINVAL): a node's actor maximises its own
+ * side's mean.
+ *   priors: uint8 [T * trees][stride], 16-byte aligned, CALLER-FILLED between the steps beside values: priors[item * stride + j]
+ *     is the weight of index j of the pending node's list, in the order of ddz_legal_slab on the imported leaf row, j < n;
+ *     entries at or beyond n are never read.  values and priors may be NULL on the first step only.
+ *   Node: 32 bytes: ddz_search's 24 | prior-pool offset u32 (0xFFFFFFFF: none stored) | weight sum S u32.  Prior pool: `pool` bytes
+ *     per tree behind the hash table, pool a multiple of 16 in [16, 2^24] (else DDZ_EINVAL); the run of a node with list size n is
+ *     n bytes at the next multiple of 4, in the order the nodes are backed up (= created).  A run that does not fit is not stored:
+ *     the node is UNIFORM and counted in totals[4].  A run whose weights are all zero is uniform too (not counted).  A terminal
+ *     node and a node with n = 0 take no run.
+ *   Iteration 0 (the first step of a live item) descends nowhere: node 0 is left pending with the root's row (hidden: on the
+ *     tree's world) and need = 1; its backup stores the root's priors and adds the root's value to node 0.  So `budget`
+ *     iterations grow at most budget - 1 nodes below the root.
+ *   Descent: at a non-terminal node with n > 0, N = its V, for every list index j, single fp32 operations, nothing fused:
+ *       mean_j = ((float)Wside_j / (float)V_j) * 2^-10 where child j exists, else the node's own ((float)Wside / (float)N) * 2^-10
+ *                (Wside = W where the node's actor is on the root actor's side, else V * 1024 - W)
+ *       p_j = (float)w_j / (float)S, or 1.0f / (float)n at a uniform node
+ *       value_j = mean_j + ((c * p_j) * sqrtf((float)N)) / (float)(1 + V_j);   the maximum, ties to the lowest index.
+ *     The selected index has a child: go to it (a terminal one is scored at once).  Otherwise the child is created: a move that
+ *     empties a hand makes it terminal (1024 or 0, backed up in the same launch), any other leaves it pending with its row as
+ *     ddz_guided_step leaves a leaf.  n = 0 or DDZ_SEARCH_MAX_DEPTH below the root: score 0, unfinished.
+ *   ddz_puct_close: backs up the last pending node, then visits / wins as ddz_guided_close; totals int64 [5] += {moves applied,
+ *     iterations run, unfinished, nodes created, nodes that fell back to uniform priors}.  The move with the most visits is
+ *     ddz_playout_choose on visits.
+ *   work: >= ddz_puct_work_bytes(T, budget, trees, pool) bytes (a function of these alone; -1 for arguments out of range),
+ *     16-byte aligned.  A launch that finds a header open did not write, or one out of range, runs nothing on that tree.
+ *     Argument checks and codes are ddz_guided_*'s, in their order; then the mode, the pool.
+ * ddz_puct_priors: prior weights from a q slab, one wavefront per leaf: for every row of rows [n][176] that is running and whose
+ *   actor's role is in net_roles, priors[i * stride + j] = clamp((int)rintf(255 * expf(((q_j - qmax) * inv_reward[role]) *
+ *   inv_tau)), 0, 255) for j < counts[i], qmax = the row's maximum (an entry equal to it gets 255), single fp32 operations; a
+ *   NaN in the row gives all ones.  Other rows and the entries at or beyond counts[i] are left as they are.  inv_tau finite,
+ *   >= 0; inv_reward: HOST float[3] in role order. */
+int64_t ddz_puct_work_bytes(int64_t n_tables, int64_t budget, int64_t trees, int64_t pool);
+int ddz_puct_open(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                  int64_t stride, int64_t pool, void* work, int64_t work_bytes, void* stream);
+int ddz_puct_step(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                  int64_t stride, int64_t pool, const int32_t* values, const uint8_t* priors, uint8_t* leaf_rows, int32_t* need,
+                  void* work, int64_t work_bytes, void* stream);
+int ddz_puct_close(ddz_env_t* env, int64_t budget, int64_t trees, int mode, float c, uint64_t salt, int hidden, int roles,
+                   const int32_t* values, const uint8_t* priors, int64_t stride, int64_t pool, int32_t* visits, int32_t* wins,
+                   int64_t* totals, void* work, int64_t work_bytes, void* stream);
+int ddz_puct_priors(int device_id, const uint8_t* rows, const int32_t* counts, const float* q, int64_t stride, int64_t n,
+                    const float* inv_reward, int net_roles, float inv_tau, uint8_t* priors, void* stream);
+
 /* Information-set MCTS with leaf values from outside the kernel: "search spec v4 (guided ISMCTS)" (DESIGN.md 4).  ddz_ismcts's
  * tree and descent in ddz_guided_*'s phases, unit and leaf value: no tree is built with full knowledge of one deal, and a
  * network (or anything else) judges the leaves.  Everything not named here is ddz_ismcts's for the tree (always the hidden
